@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — SESPH dam-break throughput on MI355X (BASELINE.json metric: particle-steps/s + ms/step).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NS|C2|C4|...]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NS|C2|C4|...] [--dump-outputs DIR]
 
 A "step" is one update() of the solver (hash → radix sort → cell ranges + reorder → density/pressure →
 forces → integrate) over every particle of the scene, with the particle state already resident in HBM when
@@ -36,6 +36,23 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0  # spec, /opt/skills/guides/MI355X_MICROARCH.md (6290 measured-achievable)
 TRAFFIC_PROFILE = "r03b_ns10M_flowing_hbm_traffic.json"  # committed rocprofv3 PMC summary (of the same window) the `traffic` field is read from
 DEFAULT_SPIN_UP, DEFAULT_DT = 3000, 2.5e-4
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs: data bytes of all arrays together (under 64 MB with room for the .npy headers)
+DUMP_SEED = 0x5EED0D0       # --dump-outputs: the row sample of a state larger than DUMP_BYTES
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """Write each array of `arrays` ({name: float32/float64 array, one row per particle, all with the same rows}) as
+    directory/<name>.npy.  If they hold more than `budget` bytes together, every array is cut to the same fixed, seeded
+    sample of rows (kept in ascending row order), so that two runs with the same arguments write the same rows."""
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.itemsize * (a.size // max(1, len(a))) for a in arrays.values())
+    rows = None
+    if n * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(seed).choice(n, budget // row_bytes, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and len(a) == n, (name, a.dtype, a.shape)
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a if rows is None else a[rows]))
 
 
 
@@ -223,7 +240,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--reference-order", action="store_true", help="bench the reference-order kernels instead")
     ap.add_argument("--full-sort", action="store_true", help="sort all pairs from scratch every step (NRS_FLAG_FULL_SORT)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returns to the caller (update()'s pos and vel, and pressure "
+                         "for IISPH) as DIR/<name>.npy; a state over %d MB is cut to a fixed, seeded sample of its rows (N=1 only)"
+                         % (DUMP_BYTES // 10 ** 6))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -247,6 +270,8 @@ def main():
     lattice = scene.CONFIGS[args.config] if args.config in scene.CONFIGS else tuple(int(v) for v in args.config.split(","))
 
     if world > 1 or os.environ.get("NEREUS_BENCH_FORCE_SLAB"):
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is implemented for the single-GPU path only")
         from nereus_amd import slab
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -346,6 +371,11 @@ def main():
     gp, gv = s.download()
     if not (np.isfinite(gp).all() and np.isfinite(gv).all()):
         raise SystemExit("non-finite state after the run")
+    if args.dump_outputs:
+        outputs = {"pos": gp, "vel": gv}
+        if iisph:
+            outputs["pressure"] = s.download(pressure=True)[2]
+        dump_outputs(args.dump_outputs, outputs)
 
     ms_per_step = 1e3 * dt / args.steps
     value = n * args.steps / dt

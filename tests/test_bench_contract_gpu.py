@@ -59,3 +59,41 @@ def test_bench_line_two_ranks_one_gpu_gloo(hip_lib):
     assert d["config"]["particles"] == 2 * 48 * 40 * 40
     # the same window rule as the one-GPU line: spin-up (with count-balanced re-cuts every 50 steps) under the CFL-stable dt
     assert d["config"]["spin_up_steps"] == 120 and d["config"]["rebalance_every"] == 50 and d["cfl_ok"] is True
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("solver", ["sesph", "iisph"])
+def test_bench_dump_outputs_is_the_state_after_the_timed_steps(tmp_path, hip_lib, solver):
+    """--dump-outputs writes what the last timed step returned (pos, vel; pressure for IISPH), and that is the state after exactly
+    spin-up + warm-up + --steps steps: an in-process solver stepped that many times on the same scene gives the same bits."""
+    import numpy as np
+
+    from nereus_amd import capi, scene
+    from nereus_amd.params import default_params
+
+    spin, warm, steps = 30, 2, 3
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--solver", solver, "--config", "40,40,40", "--steps", str(steps),
+                        "--warmup", str(warm), "--spin-up", str(spin), "--resting-steps", "0", "--no-cpu-baseline",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _one_line(r.stdout)
+    assert d["steps"] == steps and d["config"]["first_timed_step"] == spin + warm
+    iisph = solver == "iisph"
+    names = ["pos", "vel"] + (["pressure"] if iisph else [])
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(os.path.join(tmp_path, n + ".npy")) for n in names}
+
+    p = default_params(1 if iisph else 0, False)
+    sc = scene.dam_break((40, 40, 40), h=float(p["interactionRadius"][0]), kpoly=float(p["kpoly"][0]))
+    s = capi.Solver(p, len(sc["pos"]), solver=capi.IISPH if iisph else capi.SESPH)
+    s.set_particles(sc["pos"], sc["vel"])
+    s.set_boundaries(sc["bi"], sc["vbi"], update_grid=True)
+    if not iisph:
+        P = s.params
+        P["timestep"][0] = 2.5e-4   # (bench.py's DEFAULT_DT)
+        s.set_params(P)
+    s.step(spin + warm + steps)
+    want = dict(zip(names, s.download(pressure=iisph)))
+    for n in names:
+        assert got[n].dtype == np.float32 and got[n].shape == want[n].shape, (n, got[n].dtype, got[n].shape)
+        assert np.array_equal(got[n].view(np.uint32), want[n].view(np.uint32)), n
