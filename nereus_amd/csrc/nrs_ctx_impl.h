@@ -83,7 +83,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // compact scan candidates (nrs_math.h): quanta per metre, threshold of the superset test, and whether the geometry allows
         // it at all (a pair inside the interaction radius must be less than two cells apart on every axis)
         float hq = 0.0f;
-        qOk = NRS_COMPACT_SCAN != 0 && P.gridSize[0] >= 4u; // (narrower grids alias the row's three cells: tags by position fail)
+        qOk = P.gridSize[0] >= 4u; // (narrower grids alias the row's three cells: tags by position fail)
         for (int a = 0; a < 3; ++a) {
             qc.o[a] = (double)P.worldOrigin[a];
             qc.s[a] = QP_PER_CELL / (float)P.cellSize[a];
@@ -97,10 +97,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     QuantCfg qc;
     uint32_t qT = 0;
     bool qOk = false;
-    DevBuf gatherPos, gatherVel; // (x, y, z, p / rho^2) and (vx, vy, vz, m / rho) per sorted slot: density kernel -> force kernel of the same step (HitBuffer)
-    DevBuf qpos; // two words per sorted slot (+ 4 slots of padding), written by the reorder kernels
+    DevBuf gatherPos; // (x, y, z, p / rho^2), (vx, vy, vz, m / rho) side by side per sorted slot: density kernel -> force kernel of the same step (HitBuffer)
+    DevBuf qpos; // one word per sorted slot (+ 4 slots of padding), written by the reorder kernels
     // hit lists are built (and the kernels that consume them used) only when the scan that builds them can run
-    bool lists_ok() const { return hitBuf.p != nullptr && (NRS_COMPACT_SCAN == 0 || (qOk && qpos.p != nullptr)); }
+    bool lists_ok() const { return hitBuf.p != nullptr && qOk && qpos.p != nullptr; }
     nrs_config cfg;
     uint64_t cap = 0, n = 0, nb = 0;
     bool midStep = false; // a partial step left the state mid-update
@@ -286,7 +286,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         DevBuf *all[] = {&posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
                          &inv, &sortTmp, &cellStart, &cellEnd, &bCellStart, &bCellEnd, &bSorted, &bHash, &bIndex,
                          &bHashAlt, &bIndexAlt, &densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP,
-                         &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &gatherVel, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
+                         &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
                          &rsMovers, &rsMoversAlt, &rsStayers, &rsMerged, &rsTileMovers, &rsTileOffset, &rsGroupTotal, &rsGroupPrefix, &rsScalars, &rsPrevPacked,
                          &rsTileDead, &rsTileDeadOffset, &rsGroupDeadTotal, &rsGroupDeadPrefix, &slabFlags};
         for (DevBuf *b : all) b->release();
@@ -345,11 +345,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if ((!iisph() || KSET == KS_MULLER) && !(cfg.flags & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_SHARED_LISTS))) {
             NRSCHK(hitBuf.alloc((size_t)HIT_CAP * cap * 4));
             NRSCHK(hitCounts.alloc((size_t)cap * 4));
-            if (NRS_COMPACT_SCAN) NRSCHK(qpos.alloc(((size_t)cap + 4) * QP_BYTES));
-            if (NRS_FORCE_PAIRS && !iisph()) {
-                if (NRS_GATHER_INTERLEAVED) NRSCHK(gatherPos.alloc((size_t)cap * 2 * sizeof(T4)));
-                else { NRSCHK(gatherPos.alloc((size_t)cap * sizeof(T4))); NRSCHK(gatherVel.alloc((size_t)cap * sizeof(T4))); }
-            }
+            NRSCHK(qpos.alloc(((size_t)cap + 4) * sizeof(qword_t)));
+            if (!iisph()) NRSCHK(gatherPos.alloc((size_t)cap * 2 * sizeof(T4)));
             if ((cfg.flags & NRS_FLAG_FAST_ARITH) && !iisph() && std::is_same<R, float>::value && KSET == KS_MULLER)
                 NRSCHK(fastQ.alloc((size_t)cap * sizeof(FastPair)));
         }
@@ -816,7 +813,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (slabOn) { G.actLo = slab.lo - 1; G.actHi = slab.hi + 1; } // density is also needed one cell beyond the cuts
         // the density kernel's hit lists are handed to the force kernel when both run in this call
         HitBuffer hb = {hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap};
-        if (NRS_FORCE_PAIRS) { hb.gpos = gatherPos.p; hb.gvel = NRS_GATHER_INTERLEAVED ? (void *)(gatherPos.as<T4>() + 1) : gatherVel.p; hb.svel = velB.p; }
+        hb.gpos = gatherPos.p; hb.gvel = gatherPos.as<T4>() + 1; hb.svel = velB.p; // (the two records of a slot side by side: GATHER_STRIDE)
         if constexpr (std::is_same<R, float>::value) { if (fastArith() && fastQ.p && !stagedScan()) hb.fast = fastQ.as<FastPair>(); }
         const bool share = !refOrder() && lists_ok() && stop != NRS_STAGE_DENSITY;
         const bool fast = fastArith() && share && fastQ.p;
@@ -953,6 +950,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     //      every solver iteration, on the sum over ALL ranks: nrs_iisph_predict / _iterate / _finish) -----------------------------
     uint32_t iisphIter = 0;  // solver iterations done in the current step
     int iisphPhase = 0;      // 0 idle, 1 predicted (iterations may follow)
+    // (the list kernels use the Muller gradient: they are instantiated, under `if constexpr`, for the Muller kernels only)
     bool iisph_lists() const { return !refOrder() && lists_ok() && KSET == KS_MULLER; }
 
     // predictAdvection (sph_cuda.cu:513-697)
@@ -974,34 +972,38 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         NRSCHK(ev_begin(NRS_STAGE_I_DENSITY));
         const WallList wv = wall_view();
-        if (lists) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hb, posB.as<T4>(), dens.as<R>(), N, walls ? &wv : (const WallList *)nullptr);
-        else hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
+        if (!lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
+        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hb, posB.as<T4>(), dens.as<R>(), N, walls ? &wv : (const WallList *)nullptr);
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_I_DENSITY) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_I_DISPLACEMENT));
         const WallList noWalls = {nullptr, nullptr, nullptr, nullptr, nullptr};
         const uint32_t wb = wall_blocks(g.x);
-        if (lists && walls) // (wall workgroups + interior workgroups without the boundary code, as the scan: k_pressure_lists)
-            hipLaunchKernelGGL((k_displacement_lists<R, KSET, SURF, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
-                               dens.as<R>(), presB.as<R>(), N, wv, wb);
-        else if (lists)
-            hipLaunchKernelGGL((k_displacement_lists<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
-                               dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
-        else
+        if (!lists)
             hipLaunchKernelGGL((k_displacement_ref<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), velB.as<T4>(),
                                dens.as<R>(), presB.as<R>(), N);
+        else if constexpr (KSET == KS_MULLER) {
+            if (walls) // (wall workgroups + interior workgroups without the boundary code, as the scan: k_pressure_lists)
+                hipLaunchKernelGGL((k_displacement_lists<R, KSET, SURF, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
+                                   dens.as<R>(), presB.as<R>(), N, wv, wb);
+            else
+                hipLaunchKernelGGL((k_displacement_lists<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
+                                   dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
+        }
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_I_DISPLACEMENT) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_I_ADVECTION));
-        if (lists && walls)
-            hipLaunchKernelGGL((k_advection_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
-                               dens.as<R>(), presB.as<R>(), N, wv, wb);
-        else if (lists)
-            hipLaunchKernelGGL((k_advection_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
-                               dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
-        else
+        if (!lists)
             hipLaunchKernelGGL((k_advection_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), velB.as<T4>(),
                                dens.as<R>(), presB.as<R>(), N);
+        else if constexpr (KSET == KS_MULLER) {
+            if (walls)
+                hipLaunchKernelGGL((k_advection_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
+                                   dens.as<R>(), presB.as<R>(), N, wv, wb);
+            else
+                hipLaunchKernelGGL((k_advection_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
+                                   dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
+        }
         NRSCHK(ev_end());
         iisphIter = 0;
         return NRS_OK;
@@ -1015,18 +1017,20 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         IisphArrays<R> I = iisph_view();
         const bool lists = iisph_lists();
         const HitBuffer hb = {hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap};
-        if (lists) hipLaunchKernelGGL((k_sumdij_lists<R, KSET>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), N);
-        else hipLaunchKernelGGL((k_sumdij_ref<R, KSET>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), N);
+        if (!lists) hipLaunchKernelGGL((k_sumdij_ref<R, KSET>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), N);
+        else if constexpr (KSET == KS_MULLER) hipLaunchKernelGGL((k_sumdij_lists<R, KSET>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), N);
         const bool walls = HAS_B && lists && wallListed; // (this step's wall list: built for the scan, iisph_predict)
         const WallList wv = wall_view(), noWalls = {nullptr, nullptr, nullptr, nullptr, nullptr};
         const uint32_t wb = wall_blocks(g.x);
-        if (lists && walls)
-            hipLaunchKernelGGL((k_pressure_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, wv, wb);
-        else if (lists)
-            hipLaunchKernelGGL((k_pressure_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
-        else
+        if (!lists)
             hipLaunchKernelGGL((k_pressure_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(),
                                presB.as<R>(), N);
+        else if constexpr (KSET == KS_MULLER) {
+            if (walls)
+                hipLaunchKernelGGL((k_pressure_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, wv, wb);
+            else
+                hipLaunchKernelGGL((k_pressure_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
+        }
         std::swap(P_l.p, P_l2.p);
         ++iisphIter;
         return NRS_OK;
@@ -1044,12 +1048,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const bool walls = HAS_B && lists && wallListed;
         const WallList wv = wall_view(), noWalls = {nullptr, nullptr, nullptr, nullptr, nullptr};
         const uint32_t wb = wall_blocks(g.x);
-        if (lists && walls)
-            hipLaunchKernelGGL((k_pforce_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, wv, wb);
-        else if (lists)
-            hipLaunchKernelGGL((k_pforce_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
-        else
+        if (!lists)
             hipLaunchKernelGGL((k_pforce_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
+        else if constexpr (KSET == KS_MULLER) {
+            if (walls)
+                hipLaunchKernelGGL((k_pforce_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, wv, wb);
+            else
+                hipLaunchKernelGGL((k_pforce_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
+        }
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_I_PFORCE) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_I_INTEGRATE));

@@ -72,12 +72,6 @@ NRS_DEV double bcast_lane(double v, int srcLane)
     const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), srcLane), hi = __builtin_amdgcn_readlane((int)(b >> 32), srcLane);
     return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned int)lo);
 }
-#ifndef NRS_COMPACT_SCAN
-#define NRS_COMPACT_SCAN 1 // interior workgroups scan the 4-byte quantised candidates (Sweep::scan_compact); 0: the exact positions
-#endif
-#ifndef NRS_FORCE_PAIRS
-#define NRS_FORCE_PAIRS 1 // the list-driven force kernel gathers (p / rho^2, m / rho) pairs written by the density kernel (HitBuffer::pairs)
-#endif
 #ifndef NRS_DBG_LDS_PAD
 #define NRS_DBG_LDS_PAD 0 // bytes of dynamic LDS added to every density workgroup (occupancy experiments only)
 #endif
@@ -88,7 +82,7 @@ NRS_DEV double bcast_lane(double v, int srcLane)
 #define QP_WALK 4 // list entries whose exact positions are gathered together in density_from_superset
 #endif
 #ifndef QP_PRE
-#define QP_PRE 2 // (4: 104 VGPRs unbounded, 5 dwords spilled at the 80-VGPR bound, 0.649 vs 0.583 ms) dwordx4 candidate loads (two candidates each) per row issued before the first test (x 3 rows of a z-plane)
+#define QP_PRE 2 // (4: 104 VGPRs unbounded, 5 dwords spilled at the 80-VGPR bound, 0.649 vs 0.583 ms) dwordx4 candidate loads (four candidates each) per row issued before the first test (x 3 rows of a z-plane)
 #endif
 constexpr int SCAN_CAP = 21; // list entries the compact scan can hold: HIT_CAP + the particle itself (+ 3 spill rows behind them)
 // a * b + c on 24-bit signed operands in ONE instruction (the compiler prefers three multiplies and a three-operand add)
@@ -104,11 +98,8 @@ constexpr int SCAN_BATCH = 4; // candidate positions fetched per thread per memo
 // lst[HIT_CAP-1 .. HIT_CAP-nb] (descending slots, ascending visiting order); both lists are ordered by cell
 // number, so the process phase restores the reference's order (cell by cell: fluid, then boundary) by merging.
 struct HitCounts { int nf, nb; bool over; bool anyB; }; // anyB: some of the 27 cells holds boundary particles
-// NRS_GATHER_INTERLEAVED (the gather records of HitBuffer): the two records of a slot side by side (slot j at 32 j bytes: both loads of a hit fall into one 128-byte line)
-#ifndef NRS_GATHER_INTERLEAVED
-#define NRS_GATHER_INTERLEAVED 1
-#endif
-constexpr uint32_t GATHER_STRIDE = NRS_GATHER_INTERLEAVED ? 2u : 1u;
+// the gather records of HitBuffer: the two records of a slot side by side (slot j at 32 j bytes: both loads of a hit fall into one 128-byte line)
+constexpr uint32_t GATHER_STRIDE = 2u;
 template <typename R> struct PrePair { R prq, mrho; }; // (p / rho^2, m / rho) of one sorted slot, see HitBuffer::pairs
 
 template <typename R> struct Sweep {
@@ -209,9 +200,6 @@ template <typename R> struct Sweep {
                 }
             }
             if (HAS_B) {
-#if defined(NRS_ABL_NOBSWEEP) // timing ablation: boundary cells are not swept
-                bmask = 0u;
-#endif
                 anyB = anyB || bmask != 0u;
                 // BFILT 2 (Monaghan, shared lists): EVERY boundary particle of the 27 cells contributes to the force loop, so a list of
                 // them is the boundary cell table itself — density_from_hits / forces_from_hits walk it (BOUNDARY_BY_CELL)
@@ -256,11 +244,11 @@ template <typename R> struct Sweep {
     }
 
     // ---- compact scan (interior code: no boundary particles) ---------------------------------------------------------------
-    // Same walk as scan() — z-plane by z-plane, the three x-cells of a row as one run — but the candidates are the 8-byte words
-    // of G.qpos (nrs_math.h, quantize_pos) and the test is an integer squared distance against G.qT (two v_pk_sub_i16 + two
-    // v_dot2_i32_i16): the list is a SUPERSET of the exact hits (< 1 % more entries), in the visiting order.  Two candidates
-    // travel per global_load_dwordx4, and the first QP_PRE loads of all three rows of a plane are issued together before the
-    // first test; a load may run one slot past the end of its row (masked by q < nT; the array is padded).
+    // Same walk as scan() — z-plane by z-plane, the three x-cells of a row as one run — but the candidates are the 4-byte words
+    // of G.qpos (nrs_math.h, quantize_pos) and the test is an integer squared distance against G.qT (one subtraction, three sign
+    // extensions, three 24-bit multiplies): the list is a SUPERSET of the exact hits (about 3 % more entries), in the visiting
+    // order.  Four candidates travel per global_load_dwordx4, and the first QP_PRE loads of all three rows of a plane are issued
+    // together before the first test; a load may run past the end of its row (masked by q < nT; the array is padded).
     // The append is BRANCH-FREE: every slot stores its entry at the thread's write cursor and the cursor advances only on a hit,
     // so a miss is overwritten by the next slot (rows SCAN_CAP .. SCAN_CAP + 2 of the LDS array are the spill rows of a full
     // list).  In a wavefront some lane hits at almost every slot, so a branchy append ran its body ~70 times per wave anyway,
@@ -270,12 +258,11 @@ template <typename R> struct Sweep {
     // SCAN_CAP = HIT_CAP + 1).
     // (Measured and dropped: skipping the corner rows the owner cannot reach geometrically — the lanes of a wave rarely agree, 0.538
     // vs 0.546 ms at rest, 0.915 vs 0.910 developed.)
-    typedef short qs2 __attribute__((ext_vector_type(2)));
-    static constexpr int QSLOTS = 16 / QP_BYTES; // candidates per global_load_dwordx4
-    struct __attribute__((packed, aligned(QP_BYTES))) Q2 { uint32_t v[4]; };
+    static constexpr int QSLOTS = 16 / sizeof(qword_t); // candidates per global_load_dwordx4
+    struct __attribute__((packed, aligned(sizeof(qword_t)))) Q2 { uint32_t v[4]; };
     static NRS_DEV Q2 ldq(const qword_t *__restrict__ qpos, uint32_t idx)
     {
-        return *reinterpret_cast<const Q2 *>(reinterpret_cast<const char *>(qpos) + idx * (uint32_t)QP_BYTES);
+        return *reinterpret_cast<const Q2 *>(reinterpret_cast<const char *>(qpos) + idx * (uint32_t)sizeof(qword_t));
     }
     template <int W>
     static NRS_DEV HitCounts scan_compact(const Params<R> &P, const GridView<R> &G, V3<R> p, uint32_t (*lst)[W])
@@ -290,12 +277,7 @@ template <typename R> struct Sweep {
         // an owner too far from the grid origin for the error budget of the quanta (or with a NaN coordinate) is served by the
         // reference-order walk, like a list overflow
         const bool far = !((fabsf(tx) < QP_FAR) & (fabsf(ty) < QP_FAR) & (fabsf(tz) < QP_FAR));
-        const qword_t Qw = pack_quanta(tx, ty, tz);
-#if QP_BYTES == 8
-        const qs2 Qxy = __builtin_bit_cast(qs2, Qw.x), Qz = __builtin_bit_cast(qs2, Qw.y);
-#else
-        const uint32_t Qi = Qw | QP_GUARD;
-#endif
+        const uint32_t Qi = pack_quanta(tx, ty, tz) | QP_GUARD;
         const uint32_t qT = G.qT;
         const qword_t *__restrict__ qpos = G.qpos;
         // write cursor: byte offset of lst[nf][tid] from lst[0][0]
@@ -309,19 +291,12 @@ template <typename R> struct Sweep {
 #pragma unroll
             for (int u = 0; u < QSLOTS; ++u) {
                 if ((u & 1) == 0) cur = min(cur, capOff);
-#if QP_BYTES == 8
-                const qs2 dxy = Qxy - __builtin_bit_cast(qs2, c.v[2 * u]), dz = Qz - __builtin_bit_cast(qs2, c.v[2 * u + 1]);
-                const uint32_t d2 = (uint32_t)__builtin_amdgcn_sdot2(dz, dz, __builtin_amdgcn_sdot2(dxy, dxy, 0, false), false);
-#else
                 const uint32_t t = Qi - c.v[u];
                 const int dx = ((int)(t << 22)) >> 22, dy = ((int)(t << 11)) >> 22, dz = ((int)t) >> 22;
                 const uint32_t d2 = (uint32_t)mad24(dz, dz, mad24(dy, dy, __mul24(dx, dx)));
-#endif
                 const uint32_t q = base + (uint32_t)u;
                 const bool hit = (d2 < qT) & (q < nT);
-#if !defined(NRS_ABL_NOAPPEND)
                 *reinterpret_cast<uint32_t *>(lbase + cur) = aTag + q;
-#endif
                 cur += hit ? rowBytes : 0u;
             }
         };
@@ -544,14 +519,10 @@ NRS_DEV R density_from_superset(const Params<R> &P, const typename Vec4T<R>::typ
             const uint32_t j = e[u] & HIT_INDEX;
             const float d2 = dot(r, r);
             if ((k0 + u < nf) && (d2 < tKeep) && (STRICT || j != self)) { // (STRICT: the wide IISPH list keeps the particle itself)
-#if defined(NRS_ABL_NODIV) // timing ablation: row tags only (summation order within a row is then not the reference's)
-                const uint32_t tag = (e[u] >> HIT_TAG_SHIFT);
-#else
                 int gxj;
                 if constexpr (INRANGE) gxj = (int)floor(div_steps((float)(q[u].x - P.worldOrigin[0]), (float)P.cellSize[0], yCell));
                 else gxj = (int)floor((q[u].x - P.worldOrigin[0]) / P.cellSize[0]);
                 const uint32_t tag = (e[u] >> HIT_TAG_SHIFT) + (((uint32_t)(gxj - gxi) + 1u) & mx);
-#endif
                 lst[min(w, HIT_CAP - 1)][tid] = j | (tag << HIT_TAG_SHIFT);
                 ++w;
                 if (tag != prevTag) { d += part; part = (R)0.0; prevTag = tag; }
@@ -577,14 +548,10 @@ template <typename R> NRS_DEV bool density_inrange_ok(const Params<R> &P, V3<R> 
 {
     if constexpr (!std::is_same<R, float>::value) return false;
     else {
-#if NRS_INRANGE_DIV
         const float cs = P.cellSize[0], wo = fabsf(P.worldOrigin[0]);
         if (!(cs >= 0x1p-20f && cs <= 0x1p10f && wo <= 0x1p60f)) return false;
         if (wo >= 0x1p-60f) return true;
         return __all(fabsf(p.x - P.worldOrigin[0]) >= 4.0f * cs) != 0;
-#else
-        return false;
-#endif
     }
 }
 
@@ -632,41 +599,9 @@ NRS_DEV BoundaryTerms<R, KSET> boundary_terms(const Params<R> &P, V3<R> pos1, V3
 // Measured on the bench's own state (NS scene after 3000 steps at dt = 2.5e-4 s, tools/ab_flowing.sh): force stage 1.078 -> 0.887 ms
 // (-18 %) with 94 VGPRs / 5 waves per SIMD; bounded to 80 / 72 VGPRs it spills into the loop and loses (1.11 / 1.45 ms); at rest (six
 // hits per particle) 0.386 ms either way.  368 -> 272 vector instructions per two hits.
-#ifndef NRS_PACKED_HITS
-#define NRS_PACKED_HITS 1
-#endif
 // (f2, V3x2, splat2, pair2, dot2 and the packed forms of the in-range steps: nrs_math.h)
-// Two IEEE divisions a.x / b.x, a.y / b.y.  The compiler expands a correctly rounded fp32 division into v_div_scale (x2), v_rcp, five
-// fused multiply-adds and a multiply, v_div_fmas, v_div_fixup (AMDGPU LowerFDIV32); here the six arithmetic steps of the two
-// divisions run as v_pk_fma_f32 / v_pk_mul_f32 on both at once — the same operations on the same operands, 16 instructions instead
-// of 22, the quotients are the correctly rounded ones either way (tools/check_div2.hip: all 2^32 numerators for twelve denominators and
-// 2^32 random operand pairs incl. zeros, denormals, infinities, NaNs: 0 differing quotients).  Bit-identical — and SLOWER: the force stage
-// 1.053 ms against 0.887 ms with the compiler's own expansion (two more registers tip the 96-VGPR bound into spills; at 4 waves, no
-// spills: 0.912 ms — the hand-ordered chain leaves the scheduler less to interleave).  Kept behind the macro, off.
-#ifndef NRS_PACKED_DIV
-#define NRS_PACKED_DIV 0
-#endif
-NRS_DEV f2 div2(f2 a, f2 b)
-{
-#if NRS_PACKED_DIV
-    bool da, db, na, nb;
-    const f2 den = pair2(__builtin_amdgcn_div_scalef(a.x, b.x, false, &da), __builtin_amdgcn_div_scalef(a.y, b.y, false, &db));
-    const f2 num = pair2(__builtin_amdgcn_div_scalef(a.x, b.x, true, &na), __builtin_amdgcn_div_scalef(a.y, b.y, true, &nb));
-    const f2 rcp = pair2(__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y));
-    const f2 nden = -den;
-    const f2 e0 = __builtin_elementwise_fma(nden, rcp, splat2(1.0f));
-    const f2 y = __builtin_elementwise_fma(e0, rcp, rcp);
-    const f2 q0 = num * y;
-    const f2 e1 = __builtin_elementwise_fma(nden, q0, num);
-    const f2 q1 = __builtin_elementwise_fma(e1, y, q0);
-    const f2 e2 = __builtin_elementwise_fma(nden, q1, num);
-    const float qa = __builtin_amdgcn_div_fmasf(e2.x, y.x, q1.x, na);
-    const float qb = __builtin_amdgcn_div_fmasf(e2.y, y.y, q1.y, nb);
-    return pair2(__builtin_amdgcn_div_fixupf(qa, b.x, a.x), __builtin_amdgcn_div_fixupf(qb, b.y, a.y));
-#else
-    return pair2(a.x / b.x, a.y / b.y);
-#endif
-}
+// two IEEE divisions a.x / b.x, a.y / b.y (a hand-packed form of their arithmetic steps was measured slower)
+NRS_DEV f2 div2(f2 a, f2 b) { return pair2(a.x / b.x, a.y / b.y); }
 // ---- the force walk's divisions and square roots for operands in range (nrs_math.h "operands in range") ----------------------------------
 // Five of the six divisions of a hit and its square root run as the bare arithmetic steps of the compiler's own expansions, two hits at a
 // time on packed fp32, behind three guards:
@@ -885,7 +820,6 @@ NRS_DEV ForceAcc<R> forces_from_hits(const Params<R> &P, const GridView<R> &G,
                 }
         return A;
     }
-#if NRS_PACKED_HITS
     if constexpr (!HAS_B && !STRICT && PAIRS && KSET == KS_MULLER && std::is_same<R, float>::value) {
         // interior code, fluid hits only: two consecutive hits per iteration on packed fp32 (fluid_terms2_muller); the list heads of
         // the NEXT iteration are requested before this iteration's gathers are used
@@ -899,19 +833,11 @@ NRS_DEV ForceAcc<R> forces_from_hits(const Params<R> &P, const GridView<R> &G,
             auto entry = [&](int k) { return lroot[(size_t)k * lstride + lcol]; };
             uint32_t e0 = nf > 0 ? entry(0) : 0u, e1 = nf > 1 ? entry(1) : e0;
             for (int k = 0; k < nf; k += 2) {
-#if defined(NRS_ABL_FORCE_COALESCED) // timing ablation: the gathers of a wave hit consecutive slots (what a staged walk could reach at best)
-                const uint32_t j0 = (blockIdx.x * BLOCK + threadIdx.x + (uint32_t)k * 3u) % G.nSorted, j1 = (j0 + 1u) % G.nSorted;
-#else
                 const uint32_t j0 = e0 & HIT_INDEX, j1 = e1 & HIT_INDEX;
-#endif
                 const bool two = k + 1 < nf;
                 const uint32_t n0 = k + 2 < nf ? entry(k + 2) : 0u;
                 const uint32_t n1 = k + 3 < nf ? entry(k + 3) : n0;
-#if defined(NRS_ABL_FORCE_NOVEL) // timing ablation: one gather per hit
-                const float4 pa = gpos[GATHER_STRIDE * j0], pb = gpos[GATHER_STRIDE * j1], va = pa, vb = pb;
-#else
                 const float4 pa = gpos[GATHER_STRIDE * j0], pb = gpos[GATHER_STRIDE * j1], va = gvel[GATHER_STRIDE * j0], vb = gvel[GATHER_STRIDE * j1];
-#endif
                 const PairTerms2 T = fluid_terms2_muller<SURF, decltype(inRange)::value>(P, pos1, vel1, own, c0, wAtDiameter, diameter2, pa, pb, va, vb,
                                                                                         PrePair<float>{pa.w, va.w}, PrePair<float>{pb.w, vb.w}, IG, bad);
                 S.fpres = S.fpres + mk3<R>(T.pres.x.x, T.pres.y.x, T.pres.z.x);
@@ -926,7 +852,6 @@ NRS_DEV ForceAcc<R> forces_from_hits(const Params<R> &P, const GridView<R> &G,
             }
             return S;
         };
-#if NRS_INRANGE_DIV
         const InRange IG = in_range_setup(P);
         const bool ownerOk = fminf(fminf(fabsf(pos1.x), fabsf(pos1.y)), fabsf(pos1.z)) >= 0x1p-66f;
         bool again = true;
@@ -935,13 +860,8 @@ NRS_DEV ForceAcc<R> forces_from_hits(const Params<R> &P, const GridView<R> &G,
             A = walk(std::true_type{}, IG, again);
         }
         if (again) A = walk(std::false_type{}, IG, again);
-#else
-        bool unused = false;
-        A = walk(std::false_type{}, InRange{}, unused);
-#endif
         return A;
     }
-#endif
     HitMerge it(lbase, lstride, hc);
     uint32_t j, key;
     bool isB;
@@ -1097,19 +1017,11 @@ NRS_DEV void density_tiled_particle(const Params<R> &P, const GridView<R> &G, co
 {
     const uint32_t tid = threadIdx.x;
     constexpr int BF = SHARE ? (KSET == KS_MULLER ? 1 : 2) : 0;
-    constexpr bool COMPACT = NRS_COMPACT_SCAN && !HAS_B && SHARE; // (the context publishes lists only when its qpos array is valid)
+    constexpr bool COMPACT = !HAS_B && SHARE; // (the context publishes lists only when its qpos array is valid)
     HitCounts hc;
     R d;
     if constexpr (COMPACT) {
-#if defined(NRS_ABL_NOSCAN) // timing ablations (tools/density_ablate2.py): results are wrong by design
-        hc.nf = 0; hc.nb = 0; hc.over = false; hc.anyB = false;
-#else
         hc = Sweep<R>::template scan_compact<BLOCK>(P, G, p, lst);
-#endif
-#if defined(NRS_ABL_NOPROCESS) || defined(NRS_ABL_NOAPPEND) // (NOAPPEND: the scan left its entries unwritten — nobody may read them)
-        d = (R)hc.nf;
-        hc.nf = 0; hc.over = false; // (publish empty lists: the entries carry row tags only)
-#else
         if (hc.over) d = density_of<R, KSET, HAS_B>(P, G, sPos, i); // list overflow / far owner: reference-order path
         else {
             constexpr bool CAN = KSET == KS_MULLER && std::is_same<R, float>::value;
@@ -1118,7 +1030,6 @@ NRS_DEV void density_tiled_particle(const Params<R> &P, const GridView<R> &G, co
             else d = density_from_superset<R, KSET, WIDE>(P, sPos, p, lst, hc.nf, tKeep, i);
             if (hc.nf > HIT_CAP) { hc.over = true; d = density_of<R, KSET, HAS_B>(P, G, sPos, i); } // (only when the list held HIT_CAP + 1 exact hits)
         }
-#endif
     } else {
         hc = Sweep<R>::template scan<HAS_B, BF, BLOCK, WIDE>(P, G, thr, sPos, WIDE ? 0xffffffffu : i, p, lst);
         if (hc.over) d = density_of<R, KSET, HAS_B>(P, G, sPos, i); // list overflow: reference-order path
@@ -1152,14 +1063,14 @@ NRS_DEV void density_tiled_particle(const Params<R> &P, const GridView<R> &G, co
 #define DENSITY_DEFER_MIN_WAVES 6 // waves/SIMD the two-kinds-of-workgroups kernel is register-bounded for: unbounded 84 VGPRs (5 waves) 0.677 ms, 6 (80 VGPRs, 3 dwords spilled) 0.650, 7 (72, 11 spilled) 0.651
 #endif
 template <typename R, int KSET, bool HAS_B, bool SHARE, bool WIDE = false, bool DEFER = false>
-__global__ __launch_bounds__(BLOCK, (((DEFER || (NRS_COMPACT_SCAN && !HAS_B && SHARE)) && sizeof(R) == 4) ? DENSITY_DEFER_MIN_WAVES : 1)) void k_density_tiled(Params<R> P, GridView<R> G, CutThresholds thr,
+__global__ __launch_bounds__(BLOCK, (((DEFER || (!HAS_B && SHARE)) && sizeof(R) == 4) ? DENSITY_DEFER_MIN_WAVES : 1)) void k_density_tiled(Params<R> P, GridView<R> G, CutThresholds thr,
                                                          const typename Vec4T<R>::type *__restrict__ sPos,
                                                          R *__restrict__ dens, R *__restrict__ pres, HitBuffer hb,
                                                          uint32_t n, WallList wl, uint32_t wallBlocks)
 {
     // (rows SCAN_CAP .. SCAN_CAP + 2: spill rows of the branch-free append, Sweep::scan_compact; kernels without the quantised scan
     // keep the 20 KiB that let 8 workgroups share a CU)
-    constexpr int LIST_ROWS = (NRS_COMPACT_SCAN && SHARE && (DEFER || !HAS_B)) ? SCAN_CAP + 3 : HIT_CAP;
+    constexpr int LIST_ROWS = (SHARE && (DEFER || !HAS_B)) ? SCAN_CAP + 3 : HIT_CAP;
     __shared__ uint32_t lst[LIST_ROWS][BLOCK];
     uint32_t block = blockIdx.x, blocks = gridDim.x;
     if (DEFER) {
@@ -1168,11 +1079,7 @@ __global__ __launch_bounds__(BLOCK, (((DEFER || (NRS_COMPACT_SCAN && !HAS_B && S
             for (uint32_t t = block * BLOCK + threadIdx.x; t < count; t += wallBlocks * BLOCK) {
                 const uint32_t i = wl.list[t];
                 const V3<R> p = xyz<R>(sPos[i]);
-#if defined(NRS_ABL_NOWALL) // timing ablation: wall particles get no work at all
-                if (true) {
-#else
                 if (!slab_active<R>(P, G, p.x)) {
-#endif
                     dens[i] = (R)0;
                     if (pres) pres[i] = (R)0;
                     hb.counts[i] = COUNTS_DEFERRED;
@@ -1300,7 +1207,7 @@ NRS_DEV void forces_lists_particle(const Params<R> &P, const GridView<R> &G, con
         ForceAcc<R> A;
         if (hc.over) A = gather_forces<R, KSET, SURF, HAS_B>(P, G, i, pos1, vel1, dens, pres, sPos, sVel, sDens, sPres);
         else // (the context hands out lists only together with the pairs array of the same density launch)
-            A = forces_from_hits<R, KSET, SURF, HAS_B, false, NRS_FORCE_PAIRS != 0, (HAS_B && KSET == KS_MONAGHAN)>(P, G, sPos, sVel, sDens, sPres, pos1, vel1, dens, pres, hb.hits + i, hb.stride,
+            A = forces_from_hits<R, KSET, SURF, HAS_B, false, true, (HAS_B && KSET == KS_MONAGHAN)>(P, G, sPos, sVel, sDens, sPres, pos1, vel1, dens, pres, hb.hits + i, hb.stride,
                                                                                      hc, 0xffffffffu, nullptr, reinterpret_cast<const typename Vec4T<R>::type *>(hb.gpos),
                                                                                      reinterpret_cast<const typename Vec4T<R>::type *>(hb.gvel), hb.hits, i);
         f = sesph_total_force<R>(P, A, dens);
@@ -1312,7 +1219,7 @@ NRS_DEV void forces_lists_particle(const Params<R> &P, const GridView<R> &G, con
 // false for the interior code
 // (the packed two-hit walk of the interior code needs 94 VGPRs: 5 waves per SIMD; the scalar walk is bounded for 7)
 template <typename R, int KSET, bool SURF, bool HAS_B, bool FUSE, bool DEFER = false>
-__global__ __launch_bounds__(BLOCK, (sizeof(R) == 4 ? ((NRS_PACKED_HITS && NRS_FORCE_PAIRS && KSET == KS_MULLER && !HAS_B) ? (FUSE ? FORCES_PACKED_MIN_WAVES : FORCES_PACKED_MIN_WAVES_UNFUSED) : FORCES_LISTS_MIN_WAVES) : 1)) void k_forces_lists(Params<R> P, GridView<R> G, HitBuffer hb,
+__global__ __launch_bounds__(BLOCK, (sizeof(R) == 4 ? ((KSET == KS_MULLER && !HAS_B) ? (FUSE ? FORCES_PACKED_MIN_WAVES : FORCES_PACKED_MIN_WAVES_UNFUSED) : FORCES_LISTS_MIN_WAVES) : 1)) void k_forces_lists(Params<R> P, GridView<R> G, HitBuffer hb,
                                                         const typename Vec4T<R>::type *__restrict__ sPos,
                                                         const typename Vec4T<R>::type *__restrict__ sVel,
                                                         const R *__restrict__ sDens, const R *__restrict__ sPres,
@@ -1323,9 +1230,6 @@ __global__ __launch_bounds__(BLOCK, (sizeof(R) == 4 ? ((NRS_PACKED_HITS && NRS_F
     uint32_t block = blockIdx.x, blocks = gridDim.x;
     if (DEFER) {
         if (block < wallBlocks) {
-#if defined(NRS_ABL_NOWALL_F) // timing ablation: the wall particles get no force evaluation (and are not integrated)
-            return;
-#endif
             const uint32_t count = *wl.count;
             for (uint32_t t = block * BLOCK + threadIdx.x; t < count; t += wallBlocks * BLOCK) {
                 const uint32_t i = wl.list[t];

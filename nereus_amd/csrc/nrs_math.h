@@ -57,9 +57,6 @@ template <typename R> NRS_DEV float length(V3<R> v) { return sqrt_rn(dot(v, v));
 // the numerators +-1.34756e-31 (biased exponent 24) are a last-bit tie that the bare steps round the other way.  The same tool compares the
 // forms with `/` and sqrtf on the device over the region: all 2^32 numerator patterns for twelve denominators, 2^32 random pairs, and every
 // float in [2^-96, inf) for the square root — 0 differences.
-#ifndef NRS_INRANGE_DIV
-#define NRS_INRANGE_DIV 1 // 0: every division and square root as the compiler expands it
-#endif
 NRS_DEV float rcp_refined(float d) // steps 1-3: the reciprocal every quotient by d is built from
 {
     const float r = __builtin_amdgcn_rcpf(d);
@@ -213,11 +210,7 @@ template <typename R, int KSET> NRS_DEV V3<R> W_grad(V3<R> r, R ir, R kpg)
 // length() are float in both precisions, Wdefault_grad squares that float length.
 NRS_DEV float length_listed(float d2)
 {
-#if NRS_INRANGE_DIV
     return d2 >= 0x1p-96f ? sqrt_inrange(d2) : sqrt_rn(d2);
-#else
-    return sqrt_rn(d2);
-#endif
 }
 template <typename R> NRS_DEV V3<R> Wdefault_grad_len(V3<R> r, float rlen, R h, R kpoly_grad) // Wdefault_grad with length(r) handed in
 {
@@ -284,17 +277,6 @@ static constexpr uint32_t CELL_EMPTY = 0xffffffffu;
 // the wrapped difference IS the coordinate difference in quanta, whatever cells the two sit in.  The scan keeps a candidate when
 // the integer squared distance is below (h / quantum + QP_MARGIN)^2: a SUPERSET of the exact hits; the process phase applies the
 // exact float test to the exact position, which it has to gather anyway, and compacts the list before it is published.
-// Two forms, chosen at compile time (both pass the parity suite):
-//   QP_BYTES 8: 16 bits per axis in units of cellSize/16384, words (x | y << 16, z): two v_pk_sub_i16 (wrap per 16-bit lane) and
-//               two v_dot2_i32_i16 give the squared distance (< 3 * 2^30: no overflow as an unsigned number) — 4 VALU
-//               instructions, 8 bytes and two VGPRs per candidate in flight;
-//   QP_BYTES 4: 10 bits per axis in units of cellSize/256 in one word — 8 VALU instructions, 4 bytes, one VGPR (details below).
-// Measured at 10 M particles the 4-byte form wins (density stage 0.536 vs 0.602 ms at rest, 0.904 vs 1.021 ms in the developed
-// flow; exact positions: 0.646 / 1.091): what a candidate costs is its bytes through the L1 path and its register, not the
-// distance arithmetic.
-#ifndef QP_BYTES
-#define QP_BYTES 4 // 4 (default, measured faster: 0.536 vs 0.602 ms at rest, 0.904 vs 1.021 developed): one word, 10 bits per axis, see below.  8: the 16-bit form described above
-#endif
 struct QuantCfg { double o[3]; float s[3]; }; // grid origin, quanta per metre (host: QP_PER_CELL / cellSize)
 template <typename R> NRS_DEV void quantize_t(const QuantCfg &q, V3<R> p, float &tx, float &ty, float &tz)
 {
@@ -302,26 +284,11 @@ template <typename R> NRS_DEV void quantize_t(const QuantCfg &q, V3<R> p, float 
     ty = (float)(p.y - (R)q.o[1]) * q.s[1];
     tz = (float)(p.z - (R)q.o[2]) * q.s[2];
 }
-#if QP_BYTES == 8
-typedef uint2 qword_t;
-constexpr float QP_PER_CELL = 16384.0f;
-// error budget, per axis, in quanta: t = fl(fl(x - o) * s) with s = fl(16384 / cs) carries a relative error <= 3 * 2^-24, i.e.
-// up to 6 quanta at |t| = 2^25 (2048 cells from the grid origin; an fp32 position itself is no finer there); two floors add < 1:
-// |dk - dt| < 13 per axis, 13 * sqrt(3) = 22.6 on the distance; 32 leaves room for the float rounding of the exact test.
-// 32 / 16384 = 0.2 % of h: about 0.6 % more list entries than exact hits.
-constexpr float QP_MARGIN = 32.0f;
-constexpr float QP_FAR = 33554432.0f; // 2^25 quanta: an owner beyond that (or with a NaN coordinate) takes the exact path
-constexpr float QP_HALF = 32767.0f;   // a difference must stay below half the period (4 cells)
-NRS_DEV qword_t pack_quanta(float tx, float ty, float tz)
-{
-    const uint32_t kx = (uint32_t)(int)floorf(tx) & 0xffffu, ky = (uint32_t)(int)floorf(ty) & 0xffffu, kz = (uint32_t)(int)floorf(tz) & 0xffffu;
-    return make_uint2(kx | (ky << 16), kz);
-}
-#else
-// 4-byte form: 10 bits per axis at bits 0 / 11 / 22 (units of cellSize/256, modulo 4 cells); bits 10 and 21 are guard bits, left
-// 0.  With the guard bits SET in the owner's word, ONE 32-bit subtraction gives the three differences modulo 1024 (each guard
-// absorbs its field's borrow); three sign extensions, three 24-bit multiplies and an add give the squared distance.  Half the
-// bytes of the 16-bit form, 8 VALU instructions per distance instead of 4, about 3 % false positives instead of 0.6 %.
+// 4-byte quantised candidates: measured faster than a 16-bit-per-axis form and than exact positions, DESIGN.md §4 (what a candidate
+// costs is its bytes through the L1 path and its register, not the distance arithmetic).
+// 10 bits per axis at bits 0 / 11 / 22 (units of cellSize/256, modulo 4 cells); bits 10 and 21 are guard bits, left 0.  With the
+// guard bits SET in the owner's word, ONE 32-bit subtraction gives the three differences modulo 1024 (each guard absorbs its
+// field's borrow); three sign extensions, three 24-bit multiplies and an add give the squared distance (about 3 % false positives).
 typedef uint32_t qword_t;
 constexpr uint32_t QP_GUARD = (1u << 10) | (1u << 21);
 constexpr float QP_PER_CELL = 256.0f;
@@ -335,7 +302,6 @@ NRS_DEV qword_t pack_quanta(float tx, float ty, float tz)
     const uint32_t kx = (uint32_t)(int)floorf(tx) & 1023u, ky = (uint32_t)(int)floorf(ty) & 1023u, kz = (uint32_t)(int)floorf(tz) & 1023u;
     return kx | (ky << 11) | (kz << 22);
 }
-#endif
 // an owner too far from the grid origin for the error budget of the quanta, or with a NaN coordinate
 template <typename R> NRS_DEV bool quant_far(const QuantCfg &q, V3<R> p)
 {
