@@ -99,8 +99,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool qOk = false;
     DevBuf gatherPos; // (x, y, z, p / rho^2), (vx, vy, vz, m / rho) side by side per sorted slot: density kernel -> force kernel of the same step (HitBuffer)
     DevBuf qpos; // one word per sorted slot (+ 4 slots of padding), written by the reorder kernels
-    // hit lists are built (and the kernels that consume them used) only when the scan that builds them can run
-    bool lists_ok() const { return hitBuf.p != nullptr && qOk && qpos.p != nullptr; }
     nrs_config cfg;
     uint64_t cap = 0, n = 0, nb = 0;
     bool midStep = false; // a partial step left the state mid-update
@@ -110,6 +108,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint32_t *hashCur = nullptr, *indexCur = nullptr; // sorted keys/values after the sort stage
     bool hashReady = false;                           // the fused force kernel already wrote the next step's keys/values
     uint32_t *hashNext = nullptr, *indexNext = nullptr;
+    // the buffer of the pair (a, b) that cur is not: where a sort or the next step's keys / values go
+    static uint32_t *other(const DevBuf &a, const DevBuf &b, const uint32_t *cur) { return cur == a.as<uint32_t>() ? b.as<uint32_t>() : a.as<uint32_t>(); }
     DevBuf cellStart, cellEnd, bCellStart, bCellEnd;
     uint32_t cellsAllocated = 0;
     // boundaries
@@ -120,14 +120,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     DevBuf redPartial, redOut;
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
+    HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
     // wall-particle deferral (nrs_kernels_tiled.h): static near-boundary bit per cell, this step's wall list
     DevBuf nearBits, wallList, wallTile, wallTileOffset, wallGroupTotal, wallGroupPrefix, wallScalars, wallMask;
-    bool nearBitsValid = false;
-    bool wallListed = false; // this step's gathers run with wall workgroups
-    bool deferWalls() const
-    {
-        return !(cfg.flags & NRS_FLAG_NO_WALL_WORKGROUPS) && nearBitsValid && nb != 0 && (!iisph() || iisph_lists()) && !refOrder() && lists_ok();
-    }
+    bool nearBitsValid = false; // the wall buffers exist and nearBits describes the current grid (rebuild_boundary_tables)
     WallList wall_view() const { return WallList{nearBits.as<uint32_t>(), hashCur, wallList.as<uint32_t>(), wallScalars.as<uint32_t>() + 1, wallMask.as<unsigned long long>()}; }
     // this step's wall list: tile counts (reorder kernel) -> two-level scan (the re-sort's scan kernel) -> stable compaction
     int build_wall_list(uint32_t N)
@@ -136,29 +132,13 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const WallList wl = wall_view(); // (the tile counts were left by the reorder kernel of this step)
         uint32_t *sc = wallScalars.as<uint32_t>();
         const ResortScan a = {wallTile.as<uint32_t>(), wallTileOffset.as<uint32_t>(), wallGroupTotal.as<uint32_t>(), wallGroupPrefix.as<uint32_t>(), sc + 1};
-        const ResortScan none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, a, none, sc, (volatile uint64_t *)nullptr, 0u, nTiles);
+        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, a, ResortScan{}, sc, (volatile uint64_t *)nullptr, 0u, nTiles);
         hipLaunchKernelGGL(k_wall_compact, dim3(nTiles), dim3(BLOCK), 0, stream, wl, wallTileOffset.as<uint32_t>(), wallGroupPrefix.as<uint32_t>(),
                            (uint32_t)RESORT_GROUP, wallList.as<uint32_t>(), N);
         HIPCHK(hipGetLastError());
         return NRS_OK;
     }
     DevBuf fastQ;             // NRS_FLAG_FAST_ARITH: (p/rho^2, 1/rho) per sorted slot, density kernel -> force kernel
-    // LDS-staged density scan (nrs_kernels_staged.h): fp32 SESPH on power-of-two grids.  Measured at 10 M particles it is
-    // SLOWER than the global-memory scan in the exact arithmetic (0.84 vs 0.71 ms: the kernel is bound by vector-instruction
-    // issue, not by the latency the staging removes), and since the quantised scan (0.52 ms) also slower than the
-    // exact path in its own fast arithmetic (0.70-0.88 ms): it runs only when NRS_FLAG_STAGED_SCAN asks for it.
-    bool stagedScan() const
-    {
-        if (!(cfg.flags & NRS_FLAG_STAGED_SCAN) || !std::is_same<R, float>::value || iisph() || refOrder() || P.numCells > (1u << 30)) return false;
-        return KSET == KS_MULLER && lists_ok();
-    }
-    // fast arithmetic (reciprocals, rsq, fused multiply-adds) in the FORCE walk: fp32 Muller SESPH on the production kernels with
-    // shared lists; the density kernel (exact) leaves the (p/rho^2, 1/rho) pairs it needs; everything else keeps IEEE arithmetic
-    bool fastArith() const
-    {
-        return (cfg.flags & NRS_FLAG_FAST_ARITH) && std::is_same<R, float>::value && KSET == KS_MULLER && !iisph() && !refOrder() && lists_ok();
-    }
     // coherent re-sort (nrs_kernels_resort.h)
     DevBuf rsMovers, rsMoversAlt, rsStayers, rsMerged, rsTileMovers, rsTileOffset, rsGroupTotal, rsGroupPrefix, rsScalars, rsPrevPacked;
     bool slotOrderValid = false; // posA/velA are in the slot order of hashCur (a full fused step was the last thing that happened)
@@ -269,14 +249,82 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return fail(NRS_E_STATE, buf);
     }
 
-    // the tiled kernels assume the power-of-two grids the reference's hash assumes (sph_kernel_impl.cuh:120)
-    bool refOverride = false; // this IISPH step is being repeated with the reference-order kernels (iisph_tail)
-    bool refOrder() const
-    {
-        return refOverride || (cfg.flags & NRS_FLAG_REFERENCE_ORDER) != 0 || !is_pow2(P.gridSize[0]) || !is_pow2(P.gridSize[1]) ||
-               !is_pow2(P.gridSize[2]);
-    }
     bool iisph() const { return cfg.solver == NRS_SOLVER_IISPH; }
+    bool pow2_grid() const { return is_pow2(P.gridSize[0]) && is_pow2(P.gridSize[1]) && is_pow2(P.gridSize[2]); }
+
+    // ---- which kernels a step launches ------------------------------------------------------------------------------------
+    // The flag- and type-derived half of the choice is fixed at init() and decides which optional buffers exist (init(),
+    // rebuild_boundary_tables()); plan_step() adds the grid facts of the step.  The launch sites read the plan, nothing else.
+    struct Features {
+        bool listKernels; // the solver has list-driven kernels for this kernel set (IISPH: Muller only, the Monaghan support is 2h)
+        bool lists;       // hitBuf, hitCounts, qpos (+ gatherPos for SESPH)
+        bool fast;        // fastQ
+        bool resort;      // the coherent re-sort buffers
+    };
+    Features features() const
+    {
+        const uint32_t f = cfg.flags;
+        Features ft;
+        ft.listKernels = !iisph() || KSET == KS_MULLER;
+        ft.lists = ft.listKernels && !(f & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_SHARED_LISTS));
+        ft.fast = ft.lists && (f & NRS_FLAG_FAST_ARITH) && !iisph() && std::is_same<R, float>::value && KSET == KS_MULLER;
+        ft.resort = !(f & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_FUSION | NRS_FLAG_FULL_SORT)) && cap >= RESORT_MIN_PARTICLES;
+        return ft;
+    }
+    struct StepPlan {
+        bool ref = true;        // reference-order kernels; none of the fields below except quant
+        bool quant = false;     // the reorder writes qpos and the grid view hands it to the scans
+        bool lists = false;     // the density scan builds hit lists and the gathers after it consume them
+        bool wallTiles = false; // the reorder counts the wall slots per tile ...
+        bool walls = false;     // ... and the wall list is built: the gathers run wall workgroups + interior workgroups
+        bool staged = false;    // SESPH: the LDS-staged density launch
+        bool fast = false;      // SESPH: fast arithmetic in the force walk
+        bool keys = false;      // the step's last launch writes the next step's sort keys (SESPH: the fused force launch)
+        bool resort = false;    // ... and counts the movers: the split of the coherent re-sort is queued behind it
+        bool classify = false;  // ... and classifies for the next slab partition
+        bool watch = false;     // IISPH: the list-driven chain flags non-finite gathers (IisphArrays::nonFinite, iisph_tail)
+    };
+    // Chosen at the start of every step (step(), nrs_iisph_predict) and held until its end: a host-driven IISPH step spans three calls.
+    // iisph_tail replaces it with plan_step(stop, true) for the reference-order repeat of a diverged step.
+    StepPlan plan;
+    StepPlan plan_step(int stop, bool ref = false) const
+    {
+        const Features ft = features();
+        StepPlan s;
+        // the tiled kernels assume the power-of-two grids the reference's hash assumes (sph_kernel_impl.cuh:120)
+        s.ref = ref || (cfg.flags & NRS_FLAG_REFERENCE_ORDER) || !pow2_grid();
+        // hit lists are built (and the kernels that consume them used) only when the scan that builds them can run
+        s.quant = ft.lists && qOk;
+        if (s.ref) return s;
+        // SESPH: density -> forces, shared only when the step goes on past the density; IISPH: one scan feeds the chain
+        // (nrs_kernels_iisph.h)
+        s.lists = s.quant && (iisph() || stop != NRS_STAGE_DENSITY);
+        // LDS-staged density scan (nrs_kernels_staged.h): fp32 SESPH on power-of-two grids.  Measured at 10 M particles it is
+        // SLOWER than the global-memory scan in the exact arithmetic (0.84 vs 0.71 ms: the kernel is bound by vector-instruction
+        // issue, not by the latency the staging removes), and since the quantised scan (0.52 ms) also slower than the
+        // exact path in its own fast arithmetic (0.70-0.88 ms): it runs only when NRS_FLAG_STAGED_SCAN asks for it.
+        s.staged = (cfg.flags & NRS_FLAG_STAGED_SCAN) && std::is_same<R, float>::value && KSET == KS_MULLER && !iisph() && s.quant &&
+                   P.numCells <= (1u << 30);
+        // fast arithmetic (reciprocals, rsq, fused multiply-adds) in the FORCE walk: fp32 Muller SESPH with shared lists; the density
+        // kernel (exact) leaves the (p/rho^2, 1/rho) pairs it needs; everything else keeps IEEE arithmetic
+        s.fast = ft.fast && s.lists;
+        // wall workgroups (nrs_kernels_tiled.h): the scan and the gathers over its lists (SESPH forces; IISPH displacement, advection,
+        // pressure, pressure force).  The reorder counts the tiles even when the step stops after the density; the staged launch
+        // has no wall workgroups.
+        s.wallTiles = !(cfg.flags & NRS_FLAG_NO_WALL_WORKGROUPS) && nearBitsValid && nb != 0 && s.quant && !s.staged;
+        s.walls = s.wallTiles && s.lists;
+        // a full step also leaves the next step's sort keys (and the split of the coherent re-sort) — IISPH not in slab runs, whose
+        // arrays are re-partitioned first
+        s.keys = stop == 0 && !(cfg.flags & NRS_FLAG_NO_FUSION) && !(iisph() && slabOn);
+        const bool resort = s.keys && ft.resort && n >= RESORT_MIN_PARTICLES;
+        s.resort = resort && !slabOn;
+        // slab runs: the next partition's classification rides in the same launch (k_slab_count and most of k_slab_scatter then have
+        // nothing left to do)
+        s.classify = resort && slabOn;
+        // (not in slab runs, whose loop the host drives)
+        s.watch = iisph() && s.lists && !slabOn;
+        return s;
+    }
 
     ~Ctx() override
     {
@@ -341,15 +389,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             DevBuf *z[] = {&densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP, &diiF, &diiB, &sumDij};
             for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
         }
-        // SESPH: density → forces; IISPH (Muller kernels only: the Monaghan support is 2h): one scan feeds the chain
-        if ((!iisph() || KSET == KS_MULLER) && !(cfg.flags & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_SHARED_LISTS))) {
+        const Features ft = features();
+        if (ft.lists) {
             NRSCHK(hitBuf.alloc((size_t)HIT_CAP * cap * 4));
             NRSCHK(hitCounts.alloc((size_t)cap * 4));
             NRSCHK(qpos.alloc(((size_t)cap + 4) * sizeof(qword_t)));
             if (!iisph()) NRSCHK(gatherPos.alloc((size_t)cap * 2 * sizeof(T4)));
-            if ((cfg.flags & NRS_FLAG_FAST_ARITH) && !iisph() && std::is_same<R, float>::value && KSET == KS_MULLER)
-                NRSCHK(fastQ.alloc((size_t)cap * sizeof(FastPair)));
         }
+        if (ft.fast) NRSCHK(fastQ.alloc((size_t)cap * sizeof(FastPair)));
         NRSCHK(errWord.alloc(8)); // [0] run guard of the scans, [1] IISPH: a gathered value went non-finite (IisphArrays::nonFinite)
         HIPCHK(hipMemsetAsync(errWord.p, 0, 8, stream));
         NRSCHK(redPartial.alloc(sizeof(double) * 1024));
@@ -365,7 +412,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         HIPCHK(rocprim::radix_sort_pairs<SortCfg10>(nullptr, tmp10, k, vv, (size_t)cap, 0u, 30u, stream));
         size_t tmpAll = std::max(tmp, std::max(tmp9, tmp10));
         // coherent re-sort: SESPH steps on the production kernels re-use the previous step's order
-        if (!(cfg.flags & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_FUSION | NRS_FLAG_FULL_SORT)) && cap >= RESORT_MIN_PARTICLES) {
+        if (ft.resort) {
             const size_t nTiles = (cap + BLOCK - 1) / BLOCK, nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
             const size_t mcap = cap; // any share of the particles may be movers (see rsMaxPct)
             NRSCHK(rsMovers.alloc(8 * cap)); NRSCHK(rsMoversAlt.alloc(8 * mcap)); NRSCHK(rsStayers.alloc(8 * cap)); NRSCHK(rsMerged.alloc(8 * cap));
@@ -516,7 +563,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                            dBi.as<T4>(), dVbi.as<R>(), bSorted.as<T4>(), bCellStart.as<uint32_t>(),
                            bCellEnd.as<uint32_t>(), (uint32_t)nb);
         nearBitsValid = false;
-        if ((!iisph() || KSET == KS_MULLER) && is_pow2(P.gridSize[0]) && is_pow2(P.gridSize[1]) && is_pow2(P.gridSize[2])) {
+        if (features().listKernels && pow2_grid()) {
             const size_t words = ((size_t)P.numCells + 31) / 32;
             NRSCHK(nearBits.alloc(words * 4));
             const size_t nTiles = (cap + BLOCK - 1) / BLOCK, nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
@@ -636,7 +683,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         G.actHi = INT_MAX;
         G.nSorted = (uint32_t)n;
         G.err = errWord.as<uint32_t>();
-        G.qpos = lists_ok() ? qpos.as<qword_t>() : (const qword_t *)nullptr;
+        G.qpos = plan.quant ? qpos.as<qword_t>() : (const qword_t *)nullptr;
         G.qT = qT;
         G.qc = qc;
         return G;
@@ -649,7 +696,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         I.velAdv = velAdv.as<T4>(); I.forcesAdv = forcesAdv.as<T4>(); I.forcesP = forcesP.as<T4>();
         I.diiF = diiF.as<T4>(); I.diiB = diiB.as<T4>(); I.sumDij = sumDij.as<T4>(); I.diiSum = diiSum.as<T4>();
         I.inv = inv.as<uint32_t>();
-        I.nonFinite = (iisph_lists() && !slabOn) ? errWord.as<uint32_t>() + 1 : (uint32_t *)nullptr; // (second word of the error buffer)
+        I.nonFinite = plan.watch ? errWord.as<uint32_t>() + 1 : (uint32_t *)nullptr; // (second word of the error buffer)
         return I;
     }
 
@@ -670,8 +717,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         uint32_t *vIn = indexA.as<uint32_t>(), *vAlt = indexB.as<uint32_t>();
         if (hashReady) { // keys/values of this step were produced by the previous step's fused force kernel
             kIn = hashNext; vIn = indexNext;
-            kAlt = (kIn == hashA.as<uint32_t>()) ? hashB.as<uint32_t>() : hashA.as<uint32_t>();
-            vAlt = (vIn == indexA.as<uint32_t>()) ? indexB.as<uint32_t>() : indexA.as<uint32_t>();
+            kAlt = other(hashA, hashB, kIn); vAlt = other(indexA, indexB, vIn);
         } else {
             NRSCHK(ev_begin(NRS_STAGE_HASH));
             hipLaunchKernelGGL((k_hash<R>), g, b, 0, stream, P, posA.as<T4>(), kIn, vIn, N);
@@ -726,19 +772,18 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!cellsClean) HIPCHK(hipMemsetAsync(cellStart.p, 0xff, (size_t)P.numCells * 4, stream));
         cellsClean = false;
         holesPending = false; // the gather below reads only live slots
-        wallListed = deferWalls() && !stagedScan(); // (wall workgroups read the sorted keys this stage leaves in hashCur)
+        const uint32_t *nearB = plan.wallTiles ? nearBits.as<uint32_t>() : (const uint32_t *)nullptr;
+        qword_t *qp = plan.quant ? qpos.as<qword_t>() : (qword_t *)nullptr;
         if (merged)
             hipLaunchKernelGGL((k_reorder_merged<R>), g, b, 0, stream, merged, hashCur, indexCur, posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
                                cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
-                               wallListed ? nearBits.as<uint32_t>() : (const uint32_t *)nullptr, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc,
-                               lists_ok() ? qpos.as<qword_t>() : (qword_t *)nullptr);
+                               nearB, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc, qp);
         else
             hipLaunchKernelGGL((k_reorder<R>), g, b, 0, stream, hashCur, indexCur, posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
                                cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
-                               wallListed ? nearBits.as<uint32_t>() : (const uint32_t *)nullptr, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc,
-                               lists_ok() ? qpos.as<qword_t>() : (qword_t *)nullptr);
+                               nearB, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc, qp);
         if (iisph() && (cfg.flags & NRS_FLAG_IISPH_SELF_BY_SLOT)) // Q5 off: the pressure kernels skip j == own slot
             hipLaunchKernelGGL(k_identity, g, b, 0, stream, inv.as<uint32_t>(), N);
         NRSCHK(ev_end());
@@ -760,8 +805,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int launch_resort_scan(uint32_t nTiles, bool withDead)
     {
         const uint32_t nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
-        ResortScan none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, scan_movers(), withDead ? scan_dead() : none,
+        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, scan_movers(), withDead ? scan_dead() : ResortScan{},
                            rsScalars.as<uint32_t>(), (volatile uint64_t *)rsHostTotalDev, ++rsSeq, nTiles);
         HIPCHK(hipEventRecord(rsEvent, stream));
         return NRS_OK;
@@ -778,8 +822,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(clean_tile_counts());
         hipLaunchKernelGGL(k_holes_count, dim3(nTiles), dim3(BLOCK), 0, stream, hashNext, rsTileDead.as<uint32_t>(), NP);
         const uint32_t nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
-        ResortScan none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, scan_dead(), none, rsScalars.as<uint32_t>(),
+        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, scan_dead(), ResortScan{}, rsScalars.as<uint32_t>(),
                            (volatile uint64_t *)nullptr, 0u, nTiles);
         hipLaunchKernelGGL((k_holes_compact<R>), dim3(nTiles), dim3(BLOCK), 0, stream, hashNext, offsets_dead(), posA.as<T4>(), velA.as<T4>(),
                            posB.as<T4>(), velB.as<T4>(), NP);
@@ -812,58 +855,45 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         GridView<R> G = grid_view();
         if (slabOn) { G.actLo = slab.lo - 1; G.actHi = slab.hi + 1; } // density is also needed one cell beyond the cuts
         // the density kernel's hit lists are handed to the force kernel when both run in this call
-        HitBuffer hb = {hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap};
+        HitBuffer hb = hit_buffer();
         hb.gpos = gatherPos.p; hb.gvel = gatherPos.as<T4>() + 1; hb.svel = velB.p; // (the two records of a slot side by side: GATHER_STRIDE)
-        if constexpr (std::is_same<R, float>::value) { if (fastArith() && fastQ.p && !stagedScan()) hb.fast = fastQ.as<FastPair>(); }
-        const bool share = !refOrder() && lists_ok() && stop != NRS_STAGE_DENSITY;
-        const bool fast = fastArith() && share && fastQ.p;
-        if (HAS_B && share && wallListed && !refOrder()) { // (timed with the reorder stage, whose tile counts it finishes: the density stage is its one launch)
+        if (plan.fast && !plan.staged) hb.fast = fastQ.as<FastPair>(); // (the staged kernel writes fastQ through its own argument)
+        const HitBuffer *share = plan.lists ? &hb : nullptr;
+        const WallList wv = wall_view();
+        const WallList *walls = plan.walls ? &wv : nullptr;
+        if (plan.walls) { // (timed with the reorder stage, whose tile counts it finishes: the density stage is its one launch)
             NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
             NRSCHK(build_wall_list(N));
             NRSCHK(ev_end());
         }
         NRSCHK(ev_begin(NRS_STAGE_DENSITY));
-        const WallList wv = wall_view();
-        bool didStaged = false;
-        if constexpr (std::is_same<R, float>::value) {
-            if (stagedScan()) {
-                launch_density_staged<KSET, HAS_B>(stream, P, G, share ? &hb : (const HitBuffer *)nullptr, fast, posB.as<T4>(), dens.as<R>(),
-                                                   presB.as<R>(), fast ? fastQ.as<FastPair>() : (FastPair *)nullptr, N);
-                didStaged = true;
-            }
-        }
-        const bool wallsDeferred = !didStaged && !refOrder() && HAS_B && share && wallListed;
-        if (didStaged) {
-        } else if (refOrder())
+        if (plan.ref) {
             hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
-        else
-            launch_density_tiled<R, KSET, HAS_B>(stream, P, G, share ? &hb : (const HitBuffer *)nullptr, posB.as<T4>(), dens.as<R>(),
-                                                 presB.as<R>(), N, (HAS_B && share && wallListed) ? &wv : (const WallList *)nullptr);
+        } else if (plan.staged) {
+            if constexpr (std::is_same<R, float>::value)
+                launch_density_staged<KSET, HAS_B>(stream, P, G, share, plan.fast, posB.as<T4>(), dens.as<R>(), presB.as<R>(),
+                                                   plan.fast ? fastQ.as<FastPair>() : (FastPair *)nullptr, N);
+        } else {
+            launch_density_tiled<R, KSET, HAS_B>(stream, P, G, share, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, walls);
+        }
         if (slabOn) { G.actLo = slab.lo; G.actHi = slab.hi; }
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_DENSITY) return NRS_OK;
         // A full step on the production kernels fuses forces + integrate + next-step hash into one launch that
         // writes the new state straight into the A ("current") arrays, which reorder has finished reading.
-        const bool fuse = !refOrder() && stop == 0 && !(cfg.flags & NRS_FLAG_NO_FUSION);
         NRSCHK(ev_begin(NRS_STAGE_FORCES));
-        if (refOrder()) {
-            hipLaunchKernelGGL((k_forces_ref<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), velB.as<T4>(),
-                               dens.as<R>(), presB.as<R>(), forces.as<T4>(), N);
-        } else if (fuse) {
-            FusedOut<R> fo;
+        FusedOut<R> fo{};
+        if (plan.keys) {
             fo.newPos = posA.as<T4>(); fo.newVel = velA.as<T4>();
-            fo.hash = (hashCur == hashA.as<uint32_t>()) ? hashB.as<uint32_t>() : hashA.as<uint32_t>();
-            fo.index = (indexCur == indexA.as<uint32_t>()) ? indexB.as<uint32_t>() : indexA.as<uint32_t>();
-            const bool resort = rsMovers.p && !slabOn && (uint64_t)N >= RESORT_MIN_PARTICLES;
-            // slab runs: the next partition's classification rides in the same launch (k_slab_count and most of
-            // k_slab_scatter then have nothing left to do)
-            const bool classify = rsMovers.p && slabOn && (uint64_t)N >= RESORT_MIN_PARTICLES;
-            if (resort || classify) NRSCHK(clean_tile_counts());
-            fo.prevHash = (resort || classify) ? hashCur : nullptr;
-            fo.tileMovers = (resort || classify) ? rsTileMovers.as<uint32_t>() : nullptr;
-            fo.slabFlags = nullptr; fo.slabBlockCounts = nullptr; fo.slabBlocks = 0; fo.tileDead = nullptr; fo.slab = slab;
+            fo.hash = other(hashA, hashB, hashCur); fo.index = other(indexA, indexB, indexCur);
+            fo.slab = slab;
+            if (plan.resort || plan.classify) {
+                NRSCHK(clean_tile_counts());
+                fo.prevHash = hashCur;
+                fo.tileMovers = rsTileMovers.as<uint32_t>();
+            }
             classifiedValid = false;
-            if (classify) {
+            if (plan.classify) {
                 const uint32_t nbk = std::max<uint32_t>(1u, (N + SLAB_TILE - 1) / SLAB_TILE);
                 NRSCHK(slabFlags.alloc(cap));
                 NRSCHK(slabCounts.alloc((size_t)ST_TOTALS * ((cap_blocks() > nbk) ? cap_blocks() : nbk) * 4));
@@ -876,42 +906,28 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                 classifiedN = N;
                 rsTilesDirty = true; // until a pack's scan consumes the tile counts
             }
-            bool didFast = false;
-            if constexpr (std::is_same<R, float>::value && KSET == KS_MULLER) {
-                if (fast) {
-                    launch_forces_fast<SURF, HAS_B>(stream, P, G, hb, posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(),
-                                                    fastQ.as<FastPair>(), (T4 *)nullptr, &fo, N);
-                    didFast = true;
-                }
-            }
-            if (!didFast)
-                launch_forces_tiled<R, KSET, SURF, HAS_B>(stream, P, G, share ? &hb : (const HitBuffer *)nullptr, posB.as<T4>(),
-                                                          velB.as<T4>(), dens.as<R>(), presB.as<R>(), (T4 *)nullptr, &fo, N,
-                                                          (HAS_B && share && wallsDeferred) ? &wv : (const WallList *)nullptr);
+        }
+        const FusedOut<R> *fused = plan.keys ? &fo : nullptr;
+        T4 *out = plan.keys ? (T4 *)nullptr : forces.as<T4>();
+        if (plan.ref) {
+            hipLaunchKernelGGL((k_forces_ref<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), velB.as<T4>(),
+                               dens.as<R>(), presB.as<R>(), out, N);
+        } else if (plan.fast) {
+            if constexpr (std::is_same<R, float>::value && KSET == KS_MULLER)
+                launch_forces_fast<SURF, HAS_B>(stream, P, G, hb, posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(),
+                                                fastQ.as<FastPair>(), out, fused, N);
+        } else {
+            launch_forces_tiled<R, KSET, SURF, HAS_B>(stream, P, G, share, posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), out,
+                                                      fused, N, walls);
+        }
+        if (plan.keys) {
             if (!slabOn) keys_ready(fo.hash, fo.index);
             else { hashNext = fo.hash; indexNext = fo.index; } // a slab run re-partitions the arrays before the next step (AS_SLOT_ORDER)
             fusedThisStep = true;
-            if (resort) {
-                NRSCHK(ev_end());
-                NRSCHK(queue_resort_split(N));
-            }
-        } else {
-            bool didFast = false;
-            if constexpr (std::is_same<R, float>::value && KSET == KS_MULLER) {
-                if (fast) {
-                    launch_forces_fast<SURF, HAS_B>(stream, P, G, hb, posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(),
-                                                    fastQ.as<FastPair>(), forces.as<T4>(), (const FusedOut<float> *)nullptr, N);
-                    didFast = true;
-                }
-            }
-            if (!didFast)
-                launch_forces_tiled<R, KSET, SURF, HAS_B>(stream, P, G, share ? &hb : (const HitBuffer *)nullptr, posB.as<T4>(),
-                                                          velB.as<T4>(), dens.as<R>(), presB.as<R>(), forces.as<T4>(),
-                                                          (const FusedOut<R> *)nullptr, N,
-                                                          (HAS_B && share && wallsDeferred) ? &wv : (const WallList *)nullptr);
         }
         NRSCHK(ev_end());
-        if (stop == NRS_STAGE_FORCES || fuse) return NRS_OK;
+        if (plan.resort) NRSCHK(queue_resort_split(N));
+        if (stop == NRS_STAGE_FORCES || plan.keys) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_INTEGRATE));
         hipLaunchKernelGGL((k_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), forces.as<T4>(), N);
         NRSCHK(ev_end());
@@ -950,8 +966,18 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     //      every solver iteration, on the sum over ALL ranks: nrs_iisph_predict / _iterate / _finish) -----------------------------
     uint32_t iisphIter = 0;  // solver iterations done in the current step
     int iisphPhase = 0;      // 0 idle, 1 predicted (iterations may follow)
-    // (the list kernels use the Muller gradient: they are instantiated, under `if constexpr`, for the Muller kernels only)
-    bool iisph_lists() const { return !refOrder() && lists_ok() && KSET == KS_MULLER; }
+    // An IISPH list kernel with wall workgroups over this step's wall list + interior workgroups without the boundary code, as the
+    // scan (grid + wall_blocks), or interior workgroups only.  The list kernels use the Muller gradient: they are instantiated, under
+    // `if constexpr`, for the Muller kernels only (plan.lists is never set for Monaghan IISPH, Features::listKernels).
+    template <typename... K, typename... A> void launch_listed(void (*walled)(K...), void (*plain)(K...), uint32_t blocks, A... args)
+    {
+        if (plan.walls) {
+            const uint32_t wb = wall_blocks(blocks);
+            hipLaunchKernelGGL(walled, dim3(blocks + wb), dim3(BLOCK), 0, stream, args..., wall_view(), wb);
+        } else {
+            hipLaunchKernelGGL(plain, dim3(blocks), dim3(BLOCK), 0, stream, args..., WallList{}, 0u);
+        }
+    }
 
     // predictAdvection (sph_cuda.cu:513-697)
     template <bool HAS_B> int iisph_predict(int stop)
@@ -961,49 +987,34 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const GridView<R> G = grid_view();
         IisphArrays<R> I = iisph_view();
         // one neighbourhood scan per step: its hit lists drive the rest of the chain (nrs_kernels_iisph.h)
-        const bool lists = iisph_lists();
-        const HitBuffer hb = {hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap};
-        // (wall workgroups: for the scan and, round 3, for the list kernels with boundary loops — displacement, advection, pressure, pressure force)
-        const bool walls = HAS_B && lists && wallListed;
-        if (walls) {
+        const HitBuffer hb = hit_buffer();
+        if (plan.walls) {
             NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
             NRSCHK(build_wall_list(N));
             NRSCHK(ev_end());
         }
         NRSCHK(ev_begin(NRS_STAGE_I_DENSITY));
         const WallList wv = wall_view();
-        if (!lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
-        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hb, posB.as<T4>(), dens.as<R>(), N, walls ? &wv : (const WallList *)nullptr);
+        if (!plan.lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
+        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hb, posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_I_DENSITY) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_I_DISPLACEMENT));
-        const WallList noWalls = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        const uint32_t wb = wall_blocks(g.x);
-        if (!lists)
+        if (!plan.lists)
             hipLaunchKernelGGL((k_displacement_ref<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), velB.as<T4>(),
                                dens.as<R>(), presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER) {
-            if (walls) // (wall workgroups + interior workgroups without the boundary code, as the scan: k_pressure_lists)
-                hipLaunchKernelGGL((k_displacement_lists<R, KSET, SURF, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
-                                   dens.as<R>(), presB.as<R>(), N, wv, wb);
-            else
-                hipLaunchKernelGGL((k_displacement_lists<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
-                                   dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
-        }
+        else if constexpr (KSET == KS_MULLER)
+            launch_listed(k_displacement_lists<R, KSET, SURF, HAS_B, true>, k_displacement_lists<R, KSET, SURF, HAS_B>, g.x, P, G, I, hb,
+                          posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_I_DISPLACEMENT) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_I_ADVECTION));
-        if (!lists)
+        if (!plan.lists)
             hipLaunchKernelGGL((k_advection_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), velB.as<T4>(),
                                dens.as<R>(), presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER) {
-            if (walls)
-                hipLaunchKernelGGL((k_advection_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
-                                   dens.as<R>(), presB.as<R>(), N, wv, wb);
-            else
-                hipLaunchKernelGGL((k_advection_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), velB.as<T4>(),
-                                   dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
-        }
+        else if constexpr (KSET == KS_MULLER)
+            launch_listed(k_advection_lists<R, KSET, HAS_B, true>, k_advection_lists<R, KSET, HAS_B>, g.x, P, G, I, hb, posB.as<T4>(),
+                          velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
         NRSCHK(ev_end());
         iisphIter = 0;
         return NRS_OK;
@@ -1015,21 +1026,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const dim3 g(nblocks(N)), b(BLOCK);
         const GridView<R> G = grid_view();
         IisphArrays<R> I = iisph_view();
-        const bool lists = iisph_lists();
-        const HitBuffer hb = {hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap};
-        if (!lists) hipLaunchKernelGGL((k_sumdij_ref<R, KSET>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER) hipLaunchKernelGGL((k_sumdij_lists<R, KSET>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), N);
-        const bool walls = HAS_B && lists && wallListed; // (this step's wall list: built for the scan, iisph_predict)
-        const WallList wv = wall_view(), noWalls = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        const uint32_t wb = wall_blocks(g.x);
-        if (!lists)
-            hipLaunchKernelGGL((k_pressure_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(),
-                               presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER) {
-            if (walls)
-                hipLaunchKernelGGL((k_pressure_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, wv, wb);
-            else
-                hipLaunchKernelGGL((k_pressure_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
+        const HitBuffer hb = hit_buffer();
+        if (!plan.lists) {
+            hipLaunchKernelGGL((k_sumdij_ref<R, KSET>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), N);
+            hipLaunchKernelGGL((k_pressure_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
+        } else if constexpr (KSET == KS_MULLER) {
+            hipLaunchKernelGGL((k_sumdij_lists<R, KSET>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), N);
+            launch_listed(k_pressure_lists<R, KSET, HAS_B, true>, k_pressure_lists<R, KSET, HAS_B>, g.x, P, G, I, hb, posB.as<T4>(),
+                          dens.as<R>(), presB.as<R>(), N);
         }
         std::swap(P_l.p, P_l2.p);
         ++iisphIter;
@@ -1042,66 +1046,49 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const dim3 g(nblocks(N)), b(BLOCK);
         const GridView<R> G = grid_view();
         IisphArrays<R> I = iisph_view();
-        const bool lists = iisph_lists();
-        const HitBuffer hb = {hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap};
         NRSCHK(ev_begin(NRS_STAGE_I_PFORCE));
-        const bool walls = HAS_B && lists && wallListed;
-        const WallList wv = wall_view(), noWalls = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        const uint32_t wb = wall_blocks(g.x);
-        if (!lists)
+        if (!plan.lists)
             hipLaunchKernelGGL((k_pforce_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER) {
-            if (walls)
-                hipLaunchKernelGGL((k_pforce_lists<R, KSET, HAS_B, true>), dim3(g.x + wb), b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, wv, wb);
-            else
-                hipLaunchKernelGGL((k_pforce_lists<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, noWalls, 0u);
-        }
+        else if constexpr (KSET == KS_MULLER)
+            launch_listed(k_pforce_lists<R, KSET, HAS_B, true>, k_pforce_lists<R, KSET, HAS_B>, g.x, P, G, I, hit_buffer(), posB.as<T4>(),
+                          dens.as<R>(), presB.as<R>(), N);
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_I_PFORCE) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_I_INTEGRATE));
-        // a full step on the production kernels also leaves the next step's sort keys (and the split of the coherent
-        // re-sort), as the fused SESPH force kernel does — not in slab runs, whose arrays are re-partitioned first
-        const bool keys = !refOrder() && stop == 0 && !(cfg.flags & NRS_FLAG_NO_FUSION) && !slabOn;
-        const bool resort = keys && rsMovers.p && (uint64_t)N >= RESORT_MIN_PARTICLES;
-        uint32_t *nh = nullptr, *ni = nullptr;
-        if (keys) {
-            nh = (hashCur == hashA.as<uint32_t>()) ? hashB.as<uint32_t>() : hashA.as<uint32_t>();
-            ni = (indexCur == indexA.as<uint32_t>()) ? indexB.as<uint32_t>() : indexA.as<uint32_t>();
-        }
-        if (resort) NRSCHK(clean_tile_counts());
+        // (as the fused SESPH force kernel does)
+        uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
+        if (plan.resort) NRSCHK(clean_tile_counts());
         hipLaunchKernelGGL((k_iisph_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), velAdv.as<T4>(), forcesP.as<T4>(), N,
-                           nh, ni, resort ? (const uint32_t *)hashCur : (const uint32_t *)nullptr,
-                           resort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr, slabOn ? 1 : 0);
+                           nh, ni, plan.resort ? (const uint32_t *)hashCur : (const uint32_t *)nullptr,
+                           plan.resort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr, slabOn ? 1 : 0);
         NRSCHK(ev_end());
-        if (keys) {
-            keys_ready(nh, ni);
-            if (resort) NRSCHK(queue_resort_split(N));
-        }
+        if (plan.keys) keys_ready(nh, ni);
+        if (plan.resort) NRSCHK(queue_resort_split(N));
         return NRS_OK;
     }
 
     // The list-driven chain is the reference-order chain only while every value a neighbour gathers is finite (IisphArrays::nonFinite).
     // A solve that overflows raises the flag; the step is then repeated from the sorted input with the reference-order kernels,
-    // so that even a diverging run produces what the reference's loops produce.  (Not in slab runs, whose loop the host drives.)
+    // so that even a diverging run produces what the reference's loops produce (plan.watch).
     template <bool HAS_B> int iisph_tail(int stop)
     {
-        const bool watch = iisph_lists() && !slabOn;
-        uint32_t *flag = errWord.as<uint32_t>() + 1;
-        if (watch) HIPCHK(hipMemsetAsync(flag, 0, 4, stream));
-        NRSCHK(iisph_tail_once<HAS_B>(stop, watch));
-        if (!watch || !iisphDiverged) return NRS_OK;
-        refOverride = true;
+        if (plan.watch) HIPCHK(hipMemsetAsync(errWord.as<uint32_t>() + 1, 0, 4, stream));
+        NRSCHK(iisph_tail_once<HAS_B>(stop));
+        if (!plan.watch || !iisphDiverged) return NRS_OK;
+        const StepPlan chosen = plan;
+        plan = plan_step(stop, true);
         ++iisphRestarts;
         hipLaunchKernelGGL((k_gather_scalar<R>), dim3(nblocks((uint32_t)n)), dim3(BLOCK), 0, stream, presA.as<R>(), indexCur, presB.as<R>(), (uint32_t)n);
-        const int rc = iisph_tail_once<HAS_B>(stop, false);
-        refOverride = false;
+        const int rc = iisph_tail_once<HAS_B>(stop);
+        plan = chosen;
         return rc;
     }
     bool iisphDiverged = false;
     uint64_t iisphRestarts = 0;
-    template <bool HAS_B> int iisph_tail_once(int stop, bool watch)
+    template <bool HAS_B> int iisph_tail_once(int stop)
     {
         const uint32_t N = (uint32_t)n;
+        const bool watch = plan.watch;
         iisphDiverged = false;
         uint32_t hflag = 0u;
         uint32_t *flag = errWord.as<uint32_t>() + 1;
@@ -1158,6 +1145,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (midStep || iisphPhase) return fail(NRS_E_STATE, "a step is already in progress");
             if (n == 0) return NRS_OK;
             fusedThisStep = false; splitClearedCells = false;
+            plan = plan_step(0);
             NRSCHK(stage_prefix(0));
             if (nb) NRSCHK(iisph_predict<true>(0)); else NRSCHK(iisph_predict<false>(0));
             iisphPhase = 1;
@@ -1332,8 +1320,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                 SlabOut<R> out;
                 out.stayPos = posB.as<T4>(); out.stayVel = velB.as<T4>();
                 // the hash pass of the next step, done here (into the key buffers the last sort did not end in)
-                packKeys = (hashCur == hashA.as<uint32_t>()) ? hashB.as<uint32_t>() : hashA.as<uint32_t>();
-                packVals = (indexCur == indexA.as<uint32_t>()) ? indexB.as<uint32_t>() : indexA.as<uint32_t>();
+                packKeys = other(hashA, hashB, hashCur);
+                packVals = other(indexA, indexB, indexCur);
                 if (inplace) { packKeys = hashNext; packVals = indexNext; } // the fused kernel's keys / slot numbers stay where they are
                 out.hash = packKeys; out.index = packVals;
                 out.prevHash = resort ? hashCur : nullptr;
@@ -1579,6 +1567,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         for (int s = 0; s < nsteps; ++s) {
             fusedThisStep = false;
             splitClearedCells = false;
+            plan = plan_step(stop);
             NRSCHK(stage_prefix(stop));
             if (stop && stop <= NRS_STAGE_REORDER) { midStep = true; break; }
             if (iisph()) { if (nb) NRSCHK(iisph_tail<true>(stop)); else NRSCHK(iisph_tail<false>(stop)); }

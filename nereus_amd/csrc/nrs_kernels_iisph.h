@@ -50,7 +50,7 @@ NRS_DEV void displacement_lists_particle(const Params<R> &P, const GridView<R> &
                                          const typename Vec4T<R>::type *__restrict__ sPos, const typename Vec4T<R>::type *__restrict__ sVel,
                                          const R *__restrict__ sDens, const R *__restrict__ sPres, uint32_t i)
 {
-    static_assert(KSET == KS_MULLER, "list-driven IISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::iisph_lists)");
+    static_assert(KSET == KS_MULLER, "list-driven IISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::Features::listKernels)");
     const V3<R> pos1 = xyz<R>(sPos[i]);
     const V3<R> vel1 = xyz<R>(sVel[i]);
     const R pres = (R)0.0;
@@ -182,7 +182,7 @@ NRS_DEV void advection_lists_particle(const Params<R> &P, const GridView<R> &G, 
                                       const typename Vec4T<R>::type *__restrict__ sPos, const typename Vec4T<R>::type *__restrict__ sVel,
                                       const R *__restrict__ sDens, const R *__restrict__ sPres, uint32_t i)
 {
-    static_assert(KSET == KS_MULLER, "list-driven IISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::iisph_lists)");
+    static_assert(KSET == KS_MULLER, "list-driven IISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::Features::listKernels)");
     const V3<R> pos1 = xyz<R>(sPos[i]);
     const V3<R> vel1 = xyz<R>(sVel[i]);
     const V3<R> velAdv1 = xyz<R>(I.velAdv[i]);
@@ -394,7 +394,7 @@ NRS_DEV void pressure_lists_particle(const Params<R> &P, const GridView<R> &G, c
                                      const typename Vec4T<R>::type *__restrict__ sPos, const R *__restrict__ sDens, R *__restrict__ sPres,
                                      uint32_t i)
 {
-    static_assert(KSET == KS_MULLER, "list-driven IISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::iisph_lists)");
+    static_assert(KSET == KS_MULLER, "list-driven IISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::Features::listKernels)");
     const uint32_t skip = I.inv[i];
     const V3<R> pos1 = xyz<R>(sPos[i]);
     const R dens = sDens[i];
@@ -514,7 +514,7 @@ NRS_DEV void pforce_lists_particle(const Params<R> &P, const GridView<R> &G, con
                                    const typename Vec4T<R>::type *__restrict__ sPos, const R *__restrict__ sDens, const R *__restrict__ sPres,
                                    uint32_t i)
 {
-    static_assert(KSET == KS_MULLER, "list-driven IISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::iisph_lists)");
+    static_assert(KSET == KS_MULLER, "list-driven IISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::Features::listKernels)");
     const uint32_t skip = I.inv[i];
     const V3<R> pos1 = xyz<R>(sPos[i]);
     const R p = sPres[i];

@@ -579,8 +579,7 @@ static inline void launch_density_staged(hipStream_t stream, const Params<float>
 {
     const CutThresholds thr = make_thresholds<float>(P);
     const dim3 g((n + STG_WAVE - 1) / STG_WAVE), b(STG_WAVE);
-    HitBuffer hb = {nullptr, nullptr, 0};
-    if (share) hb = *share;
+    const HitBuffer hb = share ? *share : HitBuffer{};
     constexpr unsigned pad = NRS_DBG_LDS_PAD; // occupancy experiment (compile-time, see nrs_kernels_tiled.h)
     if (fast && KSET == KS_MULLER) {
         if (share) hipLaunchKernelGGL((k_density_staged<KS_MULLER, HAS_B, true, true>), g, b, pad, stream, P, G, thr, sPos, dens, pres, fq, hb, n);
@@ -596,17 +595,7 @@ static inline void launch_forces_fast(hipStream_t stream, const Params<float> &P
                                       const float4 *sPos, const float4 *sVel, const float *dens, const float *pres, const FastPair *fq,
                                       float4 *forces, const FusedOut<float> *fused, uint32_t n)
 {
-    FusedOut<float> fo;
-    fo.newPos = fo.newVel = nullptr;
-    fo.hash = fo.index = nullptr;
-    fo.prevHash = nullptr;
-    fo.tileMovers = nullptr;
-    fo.slabFlags = nullptr;
-    fo.slabBlockCounts = nullptr;
-    fo.slabBlocks = 0;
-    fo.tileDead = nullptr;
-    fo.slab = SlabCfg{0, 0, 0};
-    if (fused) fo = *fused;
+    const FusedOut<float> fo = fused ? *fused : FusedOut<float>{};
     const dim3 g((n + BLOCK - 1) / BLOCK), b(BLOCK);
     if (fused) hipLaunchKernelGGL((k_forces_fast<SURF, HAS_B, true>), g, b, 0, stream, P, G, lists, sPos, sVel, dens, pres, fq, forces, fo, n);
     else hipLaunchKernelGGL((k_forces_fast<SURF, HAS_B, false>), g, b, 0, stream, P, G, lists, sPos, sVel, dens, pres, fq, forces, fo, n);

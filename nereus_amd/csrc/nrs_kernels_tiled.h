@@ -1305,22 +1305,20 @@ static inline void launch_density_tiled(hipStream_t stream, const Params<R> &P, 
 {
     const CutThresholds thr = make_thresholds<R>(P);
     const dim3 g((n + BLOCK - 1) / BLOCK), b(BLOCK);
-    HitBuffer hb = {nullptr, nullptr, 0};
-    const WallList none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const HitBuffer hb = share ? *share : HitBuffer{};
     // occupancy experiment (tools/occupancy_sweep.sh builds variants with -DNRS_DBG_LDS_PAD=bytes): extra dynamic LDS per
     // workgroup lowers the workgroups per CU
     constexpr unsigned pad = NRS_DBG_LDS_PAD;
     if (share) {
-        hb = *share;
         if (HAS_B && wall) {
             const uint32_t wb = wall_blocks(g.x);
             hipLaunchKernelGGL((k_density_tiled<R, KSET, false, true, false, true>), dim3(g.x + wb), b, pad, stream, P, G, thr, sPos, dens, pres, hb, n,
                                *wall, wb);
         } else {
-            hipLaunchKernelGGL((k_density_tiled<R, KSET, HAS_B, true>), g, b, pad, stream, P, G, thr, sPos, dens, pres, hb, n, none, 0u);
+            hipLaunchKernelGGL((k_density_tiled<R, KSET, HAS_B, true>), g, b, pad, stream, P, G, thr, sPos, dens, pres, hb, n, WallList{}, 0u);
         }
     } else {
-        hipLaunchKernelGGL((k_density_tiled<R, KSET, HAS_B, false>), g, b, 0, stream, P, G, thr, sPos, dens, pres, hb, n, none, 0u);
+        hipLaunchKernelGGL((k_density_tiled<R, KSET, HAS_B, false>), g, b, 0, stream, P, G, thr, sPos, dens, pres, hb, n, WallList{}, 0u);
     }
 }
 template <typename R, int KSET, bool HAS_B>
@@ -1328,7 +1326,6 @@ static inline void launch_density_wide(hipStream_t stream, const Params<R> &P, c
                                        const typename Vec4T<R>::type *sPos, R *dens, uint32_t n, const WallList *wall = nullptr)
 {
     const CutThresholds thr = make_thresholds<R>(P);
-    const WallList none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     const uint32_t g = (n + BLOCK - 1) / BLOCK;
     if (HAS_B && wall) { // wall workgroups (boundary code, exact positions) + interior workgroups (quantised scan), see k_density_tiled
         const uint32_t wb = wall_blocks(g);
@@ -1337,7 +1334,7 @@ static inline void launch_density_wide(hipStream_t stream, const Params<R> &P, c
         return;
     }
     hipLaunchKernelGGL((k_density_tiled<R, KSET, HAS_B, true, true>), dim3(g), dim3(BLOCK), 0, stream, P, G, thr,
-                       sPos, dens, (R *)nullptr, hb, n, none, 0u);
+                       sPos, dens, (R *)nullptr, hb, n, WallList{}, 0u);
 }
 // `lists`: hit lists published by launch_density_tiled of the same step (then no scan), or nullptr
 template <typename R, int KSET, bool SURF, bool HAS_B>
@@ -1346,28 +1343,17 @@ static inline void launch_forces_tiled(hipStream_t stream, const Params<R> &P, c
                                        const R *pres, typename Vec4T<R>::type *forces, const FusedOut<R> *fused, uint32_t n,
                                        const WallList *wall = nullptr)
 {
-    FusedOut<R> fo;
-    fo.newPos = fo.newVel = nullptr;
-    fo.hash = fo.index = nullptr;
-    fo.prevHash = nullptr;
-    fo.tileMovers = nullptr;
-    fo.slabFlags = nullptr;
-    fo.slabBlockCounts = nullptr;
-    fo.slabBlocks = 0;
-    fo.tileDead = nullptr;
-    fo.slab = SlabCfg{0, 0, 0};
-    if (fused) fo = *fused;
+    const FusedOut<R> fo = fused ? *fused : FusedOut<R>{};
     const dim3 g((n + BLOCK - 1) / BLOCK), b(BLOCK);
     constexpr unsigned padF = NRS_DBG_LDS_PAD_F; // occupancy experiment
-    const WallList none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     if (lists && HAS_B && wall) { // wall workgroups + interior workgroups without the boundary code (see k_density_tiled)
         const uint32_t wb = wall_blocks(g.x);
         const dim3 gd(g.x + wb);
         if (fused) hipLaunchKernelGGL((k_forces_lists<R, KSET, SURF, false, true, true>), gd, b, padF, stream, P, G, *lists, sPos, sVel, dens, pres, forces, fo, n, *wall, wb);
         else hipLaunchKernelGGL((k_forces_lists<R, KSET, SURF, false, false, true>), gd, b, 0, stream, P, G, *lists, sPos, sVel, dens, pres, forces, fo, n, *wall, wb);
     } else if (lists) {
-        if (fused) hipLaunchKernelGGL((k_forces_lists<R, KSET, SURF, HAS_B, true>), g, b, padF, stream, P, G, *lists, sPos, sVel, dens, pres, forces, fo, n, none, 0u);
-        else hipLaunchKernelGGL((k_forces_lists<R, KSET, SURF, HAS_B, false>), g, b, 0, stream, P, G, *lists, sPos, sVel, dens, pres, forces, fo, n, none, 0u);
+        if (fused) hipLaunchKernelGGL((k_forces_lists<R, KSET, SURF, HAS_B, true>), g, b, padF, stream, P, G, *lists, sPos, sVel, dens, pres, forces, fo, n, WallList{}, 0u);
+        else hipLaunchKernelGGL((k_forces_lists<R, KSET, SURF, HAS_B, false>), g, b, 0, stream, P, G, *lists, sPos, sVel, dens, pres, forces, fo, n, WallList{}, 0u);
     } else {
         const CutThresholds thr = make_thresholds<R>(P);
         if (fused) hipLaunchKernelGGL((k_forces_tiled<R, KSET, SURF, HAS_B, true>), g, b, 0, stream, P, G, thr, sPos, sVel, dens, pres, forces, fo, n);
