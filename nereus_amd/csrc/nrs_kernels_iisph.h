@@ -9,9 +9,11 @@
 // reference-order kernels of nrs_kernels_ref.h.  No LDS, no cell-table traffic.
 //
 // The boundary loops of computePressure / computePressureForce run over an index range that mixes fluid and boundary
-// indices; they are kept as cell walks with the reference's bounds, next to the list-driven fluid part.
-// Not list-driven: Monaghan kernels (support 2h: no list cut-off is exact) and particles whose list overflowed
-// (per-particle flag: the reference-order cell walk is used for that particle).
+// indices; they are kept as cell walks with the reference's bounds (pressure_walk / pforce_walk), next to the
+// list-driven fluid part.
+// Not list-driven: Monaghan kernels (support 2h: no list cut-off is exact) and particles whose list overflowed (per-particle
+// flag): such a particle takes the reference-order walk of its phase, displacement_walk ... pforce_walk in nrs_kernels_ref.h —
+// the same functions the k_*_ref kernels call.
 #pragma once
 #include "nrs_kernels_tiled.h"
 
@@ -41,6 +43,34 @@ template <typename F> NRS_DEV void for_each_hit(const uint32_t *lbase, uint32_t 
         const bool fresh = key != prevKey;
         prevKey = key;
         f(j, isB, fresh);
+    }
+}
+
+// The launch of a walled gather: one sorted slot per thread, f(std::bool_constant<HAS_B>{}, i) — or, with WALLS (the step's wall
+// list exists: the scan of this step ran with wall workgroups, k_density_tiled), the first `wallBlocks` workgroups walk the wall list
+// with the boundary code, f(std::true_type{}, i) — every lane a particle with boundary cells in its neighbourhood —, and the others
+// take one sorted slot each, skip the slots flagged COUNTS_DEFERRED and are compiled WITHOUT the boundary code, f(std::false_type{}, i)
+// (the Q6 bounds of the pressure loops make a lane with boundary cells run 27 cell walks while the other 63 lanes of its wave wait).
+// Every particle is evaluated once, by the same operations.
+template <bool HAS_B, bool WALLS, typename F>
+NRS_DEV void wall_split(const HitBuffer &hb, const WallList &wl, uint32_t wallBlocks, uint32_t n, F &&f)
+{
+    uint32_t block = blockIdx.x, blocks = gridDim.x;
+    if constexpr (WALLS) {
+        if (block < wallBlocks) {
+            const uint32_t count = *wl.count;
+            for (uint32_t t = block * BLOCK + threadIdx.x; t < count; t += wallBlocks * BLOCK) f(std::true_type{}, wl.list[t]);
+            return;
+        }
+        block -= wallBlocks; blocks -= wallBlocks;
+    }
+    const uint32_t i = xcd_tile(block, blocks) * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (WALLS) {
+        if (hb.counts[i] & COUNTS_DEFERRED) return;
+        f(std::false_type{}, i);
+    } else {
+        f(std::bool_constant<HAS_B>{}, i);
     }
 }
 
@@ -75,37 +105,8 @@ NRS_DEV void displacement_lists_particle(const Params<R> &P, const GridView<R> &
     // a particle with a NaN / inf / absurd coordinate (a caller's bug) is in nobody's hit list, while the reference's loops without
     // a cut-off multiply its NaN distance into their sums: such a step is repeated in reference order as well
     watch_finite<R>(I.nonFinite, pos1);
-    if (hc.over) { // per-cell walk of the reference-order kernel for this particle
-        const I3 gp = calcGridPos<R>(P, pos1);
-        for (int z = -1; z <= 1; z++)
-            for (int y = -1; y <= 1; y++)
-                for (int x = -1; x <= 1; x++) {
-                    const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                    V3<R> res = mk3<R>(0, 0, 0);
-                    const uint32_t s = G.cellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.cellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            if (j == i) continue;
-                            const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                            if (length(d) < ir) res = res - ((pm / (dens * dens)) * W_grad<R, KSET>(d, ir, kpg));
-                        }
-                    }
-                    df = df + res;
-                    if (HAS_B) {
-                        V3<R> rb = mk3<R>(0, 0, 0);
-                        const uint32_t sb = G.bCellStart[h];
-                        if (sb != CELL_EMPTY) {
-                            const uint32_t e = G.bCellEnd[h];
-                            for (uint32_t j = sb; j < e; ++j) {
-                                const typename Vec4T<R>::type b = G.sB[j];
-                                const V3<R> d = pos1 - xyz<R>(b);
-                                if (length(d) < ir) rb = rb - (((rd * b.w) / (dens * dens)) * W_grad<R, KSET>(d, ir, kpg));
-                            }
-                        }
-                        db = db + rb;
-                    }
-                }
+    if (hc.over) { // the reference-order walk for this particle
+        displacement_walk<R, KSET, HAS_B>(P, G, sPos, i, pos1, dens, df, db);
     } else if (!HAS_B || hc.nb == 0) { // no boundary hits: the fluid entries alone, batched
         V3<R> part = mk3<R>(0, 0, 0);
         uint32_t prevTag = 0xffffffffu;
@@ -144,26 +145,6 @@ NRS_DEV void displacement_lists_particle(const Params<R> &P, const GridView<R> &
     I.diiSum[i] = mk4<R>(df + db, (R)0.0); // the same sum computePressure forms per neighbour (sph_kernel_impl.cuh:1420)
     watch_finite<R>(I.nonFinite, df + db);
 }
-// one sorted slot per thread — or, with WALLS (see k_pressure_lists), wall workgroups over the step's wall list + interior workgroups
-// compiled without the boundary code
-#define NRS_IISPH_WALL_SPLIT(PARTICLE_CALL_B, PARTICLE_CALL_NOB, PARTICLE_CALL_ANY)                                                    \
-    uint32_t block = blockIdx.x, blocks = gridDim.x;                                                                                  \
-    if (WALLS) {                                                                                                                      \
-        if (block < wallBlocks) {                                                                                                     \
-            const uint32_t count = *wl.count;                                                                                         \
-            for (uint32_t t = block * BLOCK + threadIdx.x; t < count; t += wallBlocks * BLOCK) { const uint32_t i = wl.list[t]; PARTICLE_CALL_B; } \
-            return;                                                                                                                   \
-        }                                                                                                                             \
-        block -= wallBlocks; blocks -= wallBlocks;                                                                                    \
-    }                                                                                                                                 \
-    const uint32_t i = xcd_tile(block, blocks) * BLOCK + threadIdx.x;                                                                 \
-    if (i >= n) return;                                                                                                               \
-    if (WALLS) {                                                                                                                      \
-        if (hb.counts[i] & COUNTS_DEFERRED) return;                                                                                   \
-        PARTICLE_CALL_NOB;                                                                                                            \
-    } else {                                                                                                                          \
-        PARTICLE_CALL_ANY;                                                                                                            \
-    }
 template <typename R, int KSET, bool SURF, bool HAS_B, bool WALLS = false>
 __global__ __launch_bounds__(BLOCK, (sizeof(R) == 4 ? IISPH_DISP_WAVES : 1)) void k_displacement_lists(Params<R> P, GridView<R> G, IisphArrays<R> I, HitBuffer hb,
                                                               const typename Vec4T<R>::type *__restrict__ sPos,
@@ -171,9 +152,9 @@ __global__ __launch_bounds__(BLOCK, (sizeof(R) == 4 ? IISPH_DISP_WAVES : 1)) voi
                                                               const R *__restrict__ sDens, const R *__restrict__ sPres,
                                                               uint32_t n, WallList wl, uint32_t wallBlocks)
 {
-    NRS_IISPH_WALL_SPLIT((displacement_lists_particle<R, KSET, SURF, true>(P, G, I, hb, sPos, sVel, sDens, sPres, i)),
-                         (displacement_lists_particle<R, KSET, SURF, false>(P, G, I, hb, sPos, sVel, sDens, sPres, i)),
-                         (displacement_lists_particle<R, KSET, SURF, HAS_B>(P, G, I, hb, sPos, sVel, sDens, sPres, i)))
+    wall_split<HAS_B, WALLS>(hb, wl, wallBlocks, n, [&](auto hasB, uint32_t i) {
+        displacement_lists_particle<R, KSET, SURF, decltype(hasB)::value>(P, G, I, hb, sPos, sVel, sDens, sPres, i);
+    });
 }
 
 // ---- computeAdvectionFactor (sph_kernel_impl.cuh:1114-1218) --------------------------------------------------
@@ -193,73 +174,7 @@ NRS_DEV void advection_lists_particle(const Params<R> &P, const GridView<R> &G, 
     const HitCounts hc = unpack_counts(hb.counts[i]);
     R rho_advf = (R)0.0, rho_advb = (R)0.0, aii = (R)0.0;
     if (hc.over) {
-        const I3 gp = calcGridPos<R>(P, pos1);
-        for (int z = -1; z <= 1; z++)
-            for (int y = -1; y <= 1; y++)
-                for (int x = -1; x <= 1; x++) {
-                    const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                    R res = (R)0.0;
-                    const uint32_t s = G.cellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.cellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            if (j == i) continue;
-                            const V3<R> vij = velAdv1 - xyz<R>(I.velAdv[j]);
-                            const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                            if (length(d) < ir) res += (dt * pm * dot(vij, W_grad<R, KSET>(d, ir, kpg)));
-                        }
-                    }
-                    rho_advf += res;
-                    if (HAS_B) {
-                        R rb = (R)0.0;
-                        const uint32_t sb = G.bCellStart[h];
-                        if (sb != CELL_EMPTY) {
-                            const uint32_t e = G.bCellEnd[h];
-                            for (uint32_t j = sb; j < e; ++j) {
-                                const typename Vec4T<R>::type b = G.sB[j];
-                                const V3<R> d = pos1 - xyz<R>(b);
-                                rb += (dt * (rd * b.w) * dot(vel1, W_grad<R, KSET>(d, ir, kpg)));
-                            }
-                        }
-                        rho_advb += rb;
-                    }
-                }
-        for (int z = -1; z <= 1; z++)
-            for (int y = -1; y <= 1; y++)
-                for (int x = -1; x <= 1; x++) {
-                    const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                    R res = (R)0.0;
-                    const uint32_t s = G.cellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.cellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            if (j == i) continue;
-                            const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                            const R dpi = (pm) / (dens * dens);
-                            const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                            const V3<R> dji = dpi * grad;
-                            res += (pm * dot((diif + diib) - dji, grad));
-                        }
-                    }
-                    aii += res;
-                    if (HAS_B) {
-                        R rb = (R)0.0;
-                        const uint32_t sb = G.bCellStart[h];
-                        if (sb != CELL_EMPTY) {
-                            const uint32_t e = G.bCellEnd[h];
-                            for (uint32_t j = sb; j < e; ++j) {
-                                const typename Vec4T<R>::type b = G.sB[j];
-                                const V3<R> d = pos1 - xyz<R>(b);
-                                const R psi = rd * b.w;
-                                const R dpi = (pm) / (dens * dens);
-                                const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                                const V3<R> dji = dpi * grad;
-                                rb += psi * dot((diif + diib) - dji, grad);
-                            }
-                        }
-                        aii += rb;
-                    }
-                }
+        advection_walk<R, KSET, HAS_B>(P, G, I, sPos, i, pos1, vel1, velAdv1, dens, diif, diib, rho_advf, rho_advb, aii);
     } else if (!HAS_B || hc.nb == 0) {
         // no boundary hits (all but the particles next to a wall): both sums in ONE batched walk of the fluid entries — the same entries in
         // the same order feed rho_adv (one partial per cell, `length < h` as its loop tests) and a_ii (one partial per cell, no test), and
@@ -335,9 +250,9 @@ __global__ __launch_bounds__(BLOCK, (sizeof(R) == 4 ? IISPH_ADV_WAVES : 1)) void
                                                            const R *__restrict__ sDens, const R *__restrict__ sPres,
                                                            uint32_t n, WallList wl, uint32_t wallBlocks)
 {
-    NRS_IISPH_WALL_SPLIT((advection_lists_particle<R, KSET, true>(P, G, I, hb, sPos, sVel, sDens, sPres, i)),
-                         (advection_lists_particle<R, KSET, false>(P, G, I, hb, sPos, sVel, sDens, sPres, i)),
-                         (advection_lists_particle<R, KSET, HAS_B>(P, G, I, hb, sPos, sVel, sDens, sPres, i)))
+    wall_split<HAS_B, WALLS>(hb, wl, wallBlocks, n, [&](auto hasB, uint32_t i) {
+        advection_lists_particle<R, KSET, decltype(hasB)::value>(P, G, I, hb, sPos, sVel, sDens, sPres, i);
+    });
 }
 
 // ---- computeSumDijPj (sph_kernel_impl.cuh:1259-1325): fluid neighbours only -----------------------------------
@@ -353,24 +268,7 @@ __global__ __launch_bounds__(BLOCK) void k_sumdij_lists(Params<R> P, GridView<R>
     HitCounts hc = unpack_counts(hb.counts[i]);
     V3<R> dijpj = mk3<R>(0, 0, 0);
     if (hc.over) {
-        const I3 gp = calcGridPos<R>(P, pos1);
-        for (int z = -1; z <= 1; z++)
-            for (int y = -1; y <= 1; y++)
-                for (int x = -1; x <= 1; x++) {
-                    const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                    V3<R> res = mk3<R>(0, 0, 0);
-                    const uint32_t s = G.cellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.cellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            if (j == i) continue;
-                            const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                            const R densj = sDens[j];
-                            res = res - ((pm / (densj * densj)) * I.P_l[j] * W_grad<R, KSET>(d, ir, kpg));
-                        }
-                    }
-                    dijpj = dijpj + res;
-                }
+        sumdij_walk<R, KSET>(P, G, I, sPos, sDens, i, pos1, dijpj);
     } else {
         // boundary hits play no part here: the fluid entries alone, one partial sum per cell tag (the list is in cell order)
         V3<R> part = mk3<R>(0, 0, 0);
@@ -408,48 +306,12 @@ NRS_DEV void pressure_lists_particle(const Params<R> &P, const GridView<R> &G, c
     R bsum = (R)0.0;
     const R dpi = pm / (dens * dens);
     HitCounts hc = unpack_counts(hb.counts[i]);
-    if (HAS_B && hc.anyB) { // (anyB: the scan saw boundary particles in at least one of the 27 cells; none: nothing to add)
-        // boundary part: its own accumulator, so it can run apart from the fluid part.  The loop bounds are the
-        // reference's: from the FLUID cell start to the BOUNDARY cell end, over the boundary array.
-        const I3 gp = calcGridPos<R>(P, pos1);
-        for (int z = -1; z <= 1; z++)
-            for (int y = -1; y <= 1; y++)
-                for (int x = -1; x <= 1; x++) {
-                    const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                    if (G.bCellStart[h] != CELL_EMPTY) {
-                        const uint32_t s = G.cellStart[h], eB = G.bCellEnd[h];
-                        for (uint32_t j = s; j < eB; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            const V3<R> d = pos1 - xyz<R>(b);
-                            const R psi = rd * b.w;
-                            bsum += psi * dot(dijpj, W_grad<R, KSET>(d, ir, kpg));
-                        }
-                    }
-                }
-    }
-    auto term = [&](uint32_t j) {
-        const V3<R> d = pos1 - xyz<R>(sPos[j]);
-        const R p_lj = I.P_l[j];
-        const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-        const V3<R> dji = dpi * (grad);
-        const V3<R> d_ji_pi = dji * p_lj;
-        const V3<R> diij = xyz<R>(I.diiSum[j]); // = diiF[j] + diiB[j]
-        const V3<R> sum_dijj = xyz<R>(I.sumDij[j]);
-        fsum += pm * dot(dijpj - diij * p_lj - (sum_dijj - d_ji_pi), grad);
-    };
+    // the boundary part has its own accumulator, so it runs apart from the fluid part (anyB: the scan saw boundary particles in at least
+    // one of the 27 cells; none: nothing to add)
+    const auto diiSum = [&](uint32_t j) { return xyz<R>(I.diiSum[j]); }; // = diiF[j] + diiB[j]
+    if (HAS_B && hc.anyB) pressure_walk<R, KSET, false, true>(P, G, I, sPos, skip, pos1, dens, dijpj, diiSum, fsum, bsum);
     if (hc.over) {
-        const I3 gp = calcGridPos<R>(P, pos1);
-        for (int z = -1; z <= 1; z++)
-            for (int y = -1; y <= 1; y++)
-                for (int x = -1; x <= 1; x++) {
-                    const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                    const uint32_t s = G.cellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.cellEnd[h];
-                        for (uint32_t j = s; j < e; ++j)
-                            if (j != skip) term(j);
-                    }
-                }
+        pressure_walk<R, KSET, true, false>(P, G, I, sPos, skip, pos1, dens, dijpj, diiSum, fsum, bsum);
     } else {
         struct Nb { typename Vec4T<R>::type q, dii, sdj; R pl; };
         walk_fluid_batched(hb.hits + i, hb.stride, hc.nf, [&](uint32_t j) { return Nb{sPos[j], I.diiSum[j], I.sumDij[j], I.P_l[j]}; },
@@ -477,34 +339,15 @@ NRS_DEV void pressure_lists_particle(const Params<R> &P, const GridView<R> &G, c
     sPres[i] = p_l;
     I.densCorr[i] = rho_corr;
 }
-// WALLS (the step's wall list exists: the scan of this step ran with wall workgroups, k_density_tiled): the first `wallBlocks` workgroups
-// walk the wall list with the boundary code — every lane a particle with boundary cells in its neighbourhood —, the others take one sorted
-// slot each, skip the slots flagged COUNTS_DEFERRED and are compiled WITHOUT the boundary loops (whose Q6 bounds make a lane with boundary
-// cells run 27 cell walks while the other 63 lanes of its wave wait).  Every particle is evaluated once, by the same operations.
 template <typename R, int KSET, bool HAS_B, bool WALLS = false>
 __global__ __launch_bounds__(BLOCK, (sizeof(R) == 4 ? IISPH_PRES_WAVES : 1)) void k_pressure_lists(Params<R> P, GridView<R> G, IisphArrays<R> I, HitBuffer hb,
                                                           const typename Vec4T<R>::type *__restrict__ sPos,
                                                           const R *__restrict__ sDens, R *__restrict__ sPres, uint32_t n,
                                                           WallList wl, uint32_t wallBlocks)
 {
-    uint32_t block = blockIdx.x, blocks = gridDim.x;
-    if (WALLS) {
-        if (block < wallBlocks) {
-            const uint32_t count = *wl.count;
-            for (uint32_t t = block * BLOCK + threadIdx.x; t < count; t += wallBlocks * BLOCK)
-                pressure_lists_particle<R, KSET, true>(P, G, I, hb, sPos, sDens, sPres, wl.list[t]);
-            return;
-        }
-        block -= wallBlocks; blocks -= wallBlocks;
-    }
-    const uint32_t i = xcd_tile(block, blocks) * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (WALLS) {
-        if (hb.counts[i] & COUNTS_DEFERRED) return;
-        pressure_lists_particle<R, KSET, false>(P, G, I, hb, sPos, sDens, sPres, i);
-    } else {
-        pressure_lists_particle<R, KSET, HAS_B>(P, G, I, hb, sPos, sDens, sPres, i);
-    }
+    wall_split<HAS_B, WALLS>(hb, wl, wallBlocks, n, [&](auto hasB, uint32_t i) {
+        pressure_lists_particle<R, KSET, decltype(hasB)::value>(P, G, I, hb, sPos, sDens, sPres, i);
+    });
 }
 
 // ---- computePressureForce (sph_kernel_impl.cuh:1497-1620, same Q5/Q6).  One accumulator takes the fluid terms of a
@@ -522,14 +365,6 @@ NRS_DEV void pforce_lists_particle(const Params<R> &P, const GridView<R> &G, con
     const R ir = P.interactionRadius, pm = P.particleMass, kpg = P.kpoly_grad, rd = P.restDensity;
     V3<R> fp = mk3<R>(0, 0, 0);
     HitCounts hc = unpack_counts(hb.counts[i]);
-    auto term = [&](uint32_t j) {
-        const V3<R> d = pos1 - xyz<R>(sPos[j]);
-        const R pj = sPres[j];
-        const R densj = sDens[j];
-        const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-        const V3<R> contrib = -pm * pm * (p / (dens * dens) + pj / (densj * densj)) * grad;
-        fp = fp + contrib;
-    };
     if ((!HAS_B || !hc.anyB) && !hc.over) { // no boundary particles in any of the 27 cells: only the fluid list contributes
         struct Nb { typename Vec4T<R>::type q; R pj, dn; };
         walk_fluid_batched(hb.hits + i, hb.stride, hc.nf, [&](uint32_t j) { return Nb{sPos[j], sPres[j], sDens[j]}; },
@@ -539,18 +374,10 @@ NRS_DEV void pforce_lists_particle(const Params<R> &P, const GridView<R> &G, con
                                fp = fp + (-pm * pm * (p / (dens * dens) + nb.pj / (nb.dn * nb.dn)) * grad);
                            });
     } else {
-        const I3 gp = calcGridPos<R>(P, pos1);
         int kf = 0; // cursor into the fluid list (ascending cell number)
-        for (int c = 0; c < 27; ++c) {
-            const int z = c / 9 - 1, y = (c / 3) % 3 - 1, x = c % 3 - 1;
-            const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+        fp = pforce_walk<R, KSET, HAS_B>(P, G, sPos, sDens, sPres, pos1, p, dens, [&](int c, uint32_t h, auto &term) {
             if (hc.over) {
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j)
-                        if (j != skip) term(j);
-                }
+                pforce_fluid_cell<R>(G, h, skip, term);
             } else {
                 while (kf < hc.nf) {
                     const uint32_t ent = hb.hits[(size_t)kf * hb.stride + i];
@@ -560,45 +387,19 @@ NRS_DEV void pforce_lists_particle(const Params<R> &P, const GridView<R> &G, con
                     ++kf;
                 }
             }
-            if (HAS_B && G.bCellStart[h] != CELL_EMPTY) {
-                const uint32_t s = G.cellStart[h], eB = G.bCellEnd[h];
-                for (uint32_t j = s; j < eB; ++j) { // Q6 bounds
-                    const typename Vec4T<R>::type b = G.sB[j];
-                    const V3<R> d = pos1 - xyz<R>(b);
-                    const R psi = rd * b.w;
-                    const V3<R> contrib = (pm * psi * (p / (dens * dens)) * W_grad<R, KSET>(d, ir, kpg));
-                    fp = fp + contrib;
-                }
-            }
-        }
+        });
     }
     I.forcesP[i] = mk4<R>(fp, (R)0.0);
 }
-// WALLS: as k_pressure_lists
 template <typename R, int KSET, bool HAS_B, bool WALLS = false>
 __global__ __launch_bounds__(BLOCK) void k_pforce_lists(Params<R> P, GridView<R> G, IisphArrays<R> I, HitBuffer hb,
                                                         const typename Vec4T<R>::type *__restrict__ sPos,
                                                         const R *__restrict__ sDens, const R *__restrict__ sPres, uint32_t n,
                                                         WallList wl, uint32_t wallBlocks)
 {
-    uint32_t block = blockIdx.x, blocks = gridDim.x;
-    if (WALLS) {
-        if (block < wallBlocks) {
-            const uint32_t count = *wl.count;
-            for (uint32_t t = block * BLOCK + threadIdx.x; t < count; t += wallBlocks * BLOCK)
-                pforce_lists_particle<R, KSET, true>(P, G, I, hb, sPos, sDens, sPres, wl.list[t]);
-            return;
-        }
-        block -= wallBlocks; blocks -= wallBlocks;
-    }
-    const uint32_t i = xcd_tile(block, blocks) * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (WALLS) {
-        if (hb.counts[i] & COUNTS_DEFERRED) return;
-        pforce_lists_particle<R, KSET, false>(P, G, I, hb, sPos, sDens, sPres, i);
-    } else {
-        pforce_lists_particle<R, KSET, HAS_B>(P, G, I, hb, sPos, sDens, sPres, i);
-    }
+    wall_split<HAS_B, WALLS>(hb, wl, wallBlocks, n, [&](auto hasB, uint32_t i) {
+        pforce_lists_particle<R, KSET, decltype(hasB)::value>(P, G, I, hb, sPos, sDens, sPres, i);
+    });
 }
 
 } // namespace nrs

@@ -444,191 +444,17 @@ static __global__ __launch_bounds__(BLOCK) void k_gather_scalar(const R *__restr
 
 // computeIisphDensity (:770-846) is k_density_ref with pres == nullptr.
 
-// computeDisplacementFactor (sph_kernel_impl.cuh:851-963) + its two cell helpers (:689-765)
-template <typename R, int KSET, bool SURF, bool HAS_B>
-__global__ __launch_bounds__(BLOCK) void k_displacement_ref(Params<R> P, GridView<R> G, IisphArrays<R> I,
-                                                            const typename Vec4T<R>::type *__restrict__ sPos,
-                                                            const typename Vec4T<R>::type *__restrict__ sVel,
-                                                            const R *__restrict__ sDens, const R *__restrict__ sPres,
-                                                            uint32_t n)
-{
-    uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> pos1 = xyz<R>(sPos[i]);
-    const V3<R> vel1 = xyz<R>(sVel[i]);
-    const R pres = (R)0.0;
-    const R dens = sDens[i];
-    const R kpg = P.kpoly_grad, pm = P.particleMass, ir = P.interactionRadius, rd = P.restDensity, dt = P.timestep;
-    ForceAcc<R> A = gather_forces<R, KSET, SURF, HAS_B>(P, G, i, pos1, vel1, dens, pres, sPos, sVel, sDens, sPres);
-    V3<R> fvisc = 2.0 * A.fvisc;
-    fvisc = (pm * P.viscosity) * fvisc;
-    const V3<R> fgrav = pm * mk3<R>(P.gravity[0], P.gravity[1], P.gravity[2]);
-    const V3<R> force_adv = fvisc + A.fsurf + A.fbound + fgrav;
-    const V3<R> vel_adv = vel1 + dt * (force_adv / pm);
-    I.forcesAdv[i] = mk4<R>(force_adv, (R)0.0);
-    I.velAdv[i] = mk4<R>(vel_adv, (R)0.0);
+// The per-particle walks of the IISPH loops below are shared with the list-driven kernels (nrs_kernels_iisph.h), which take them
+// for a particle whose hit list overflowed: one statement of each reference loop for both kernel paths.
 
-    const I3 gp = calcGridPos<R>(P, pos1);
-    V3<R> df = mk3<R>(0, 0, 0), db = mk3<R>(0, 0, 0);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                {
-                    V3<R> res = mk3<R>(0, 0, 0);
-                    const uint32_t s = G.cellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.cellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            if (j == i) continue;
-                            const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                            if (length(d) < ir) {
-                                const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                                res = res - ((pm / (dens * dens)) * grad);
-                            }
-                        }
-                    }
-                    df = df + res;
-                }
-                if (HAS_B) {
-                    V3<R> res = mk3<R>(0, 0, 0);
-                    const uint32_t s = G.bCellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.bCellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            const V3<R> d = pos1 - xyz<R>(b);
-                            const R psi = rd * b.w;
-                            if (length(d) < ir) {
-                                const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                                res = res - ((psi / (dens * dens)) * grad);
-                            }
-                        }
-                    }
-                    db = db + res;
-                }
-            }
-    I.diiF[i] = mk4<R>(df, (R)0.0);
-    I.diiB[i] = mk4<R>(db, (R)0.0);
-}
-
-// computeAdvectionFactor (sph_kernel_impl.cuh:1114-1218) + helpers (:968-1108)
+// the dii sums of computeDisplacementFactor (sph_kernel_impl.cuh:851-963) + its two cell helpers (:689-765): df over the fluid,
+// db over the boundary particles, one partial per cell; both added to the caller's values
 template <typename R, int KSET, bool HAS_B>
-__global__ __launch_bounds__(BLOCK) void k_advection_ref(Params<R> P, GridView<R> G, IisphArrays<R> I,
-                                                         const typename Vec4T<R>::type *__restrict__ sPos,
-                                                         const typename Vec4T<R>::type *__restrict__ sVel,
-                                                         const R *__restrict__ sDens, const R *__restrict__ sPres,
-                                                         uint32_t n)
+NRS_DEV void displacement_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                               uint32_t i, V3<R> pos1, R dens, V3<R> &df, V3<R> &db)
 {
-    uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> pos1 = xyz<R>(sPos[i]);
-    const V3<R> vel1 = xyz<R>(sVel[i]);
-    const V3<R> velAdv1 = xyz<R>(I.velAdv[i]);
-    const R dens = sDens[i];
-    const V3<R> diif = xyz<R>(I.diiF[i]);
-    const V3<R> diib = xyz<R>(I.diiB[i]);
+    const R kpg = P.kpoly_grad, pm = P.particleMass, ir = P.interactionRadius, rd = P.restDensity;
     const I3 gp = calcGridPos<R>(P, pos1);
-    const R kpg = P.kpoly_grad, pm = P.particleMass, ir = P.interactionRadius, rd = P.restDensity, dt = P.timestep;
-
-    R rho_advf = (R)0.0, rho_advb = (R)0.0;
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                {
-                    R res = (R)0.0;
-                    const uint32_t s = G.cellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.cellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            if (j == i) continue;
-                            const V3<R> velAdv2 = xyz<R>(I.velAdv[j]);
-                            const V3<R> vij = velAdv1 - velAdv2;
-                            const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                            if (length(d) < ir) {
-                                const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                                res += (dt * pm * dot(vij, grad));
-                            }
-                        }
-                    }
-                    rho_advf += res;
-                }
-                if (HAS_B) {
-                    R res = (R)0.0;
-                    const uint32_t s = G.bCellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.bCellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) { // no cut-off: relies on W_grad == 0 beyond h (Q8)
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            const V3<R> d = pos1 - xyz<R>(b);
-                            const V3<R> vij = vel1;
-                            const R psi = (rd * b.w);
-                            const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                            res += (dt * psi * dot(vij, grad));
-                        }
-                    }
-                    rho_advb += res;
-                }
-            }
-    const R rho_adv = dens + (rho_advf + rho_advb);
-    I.densAdv[i] = rho_adv;
-    I.P_l[i] = (R)(0.5 * sPres[i]);
-
-    R aii = (R)0.0;
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                {
-                    R res = (R)0.0;
-                    const uint32_t s = G.cellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.cellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            if (j == i) continue;
-                            const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                            const R dpi = (pm) / (dens * dens);
-                            const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                            const V3<R> dji = dpi * grad;
-                            res += (pm * dot((diif + diib) - dji, grad));
-                        }
-                    }
-                    aii += res;
-                }
-                if (HAS_B) {
-                    R res = (R)0.0;
-                    const uint32_t s = G.bCellStart[h];
-                    if (s != CELL_EMPTY) {
-                        const uint32_t e = G.bCellEnd[h];
-                        for (uint32_t j = s; j < e; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            const V3<R> d = pos1 - xyz<R>(b);
-                            const R psi = rd * b.w;
-                            const R dpi = (pm) / (dens * dens);
-                            const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                            const V3<R> dji = dpi * grad;
-                            res += psi * dot((diif + diib) - dji, grad);
-                        }
-                    }
-                    aii += res;
-                }
-            }
-    I.aii[i] = aii;
-}
-
-// computeSumDijPj (sph_kernel_impl.cuh:1259-1325) + dijpjcell (:1224-1253)
-template <typename R, int KSET>
-__global__ __launch_bounds__(BLOCK) void k_sumdij_ref(Params<R> P, GridView<R> G, IisphArrays<R> I,
-                                                      const typename Vec4T<R>::type *__restrict__ sPos,
-                                                      const R *__restrict__ sDens, uint32_t n)
-{
-    uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> pos1 = xyz<R>(sPos[i]);
-    const I3 gp = calcGridPos<R>(P, pos1);
-    const R ir = P.interactionRadius, pm = P.particleMass, kpg = P.kpoly_grad;
-    V3<R> dijpj = mk3<R>(0, 0, 0);
     for (int z = -1; z <= 1; z++)
         for (int y = -1; y <= 1; y++)
             for (int x = -1; x <= 1; x++) {
@@ -640,15 +466,129 @@ __global__ __launch_bounds__(BLOCK) void k_sumdij_ref(Params<R> P, GridView<R> G
                     for (uint32_t j = s; j < e; ++j) {
                         if (j == i) continue;
                         const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                        const R p_lj = I.P_l[j];
-                        const R densj = sDens[j];
+                        if (length(d) < ir) res = res - ((pm / (dens * dens)) * W_grad<R, KSET>(d, ir, kpg));
+                    }
+                }
+                df = df + res;
+                if (HAS_B) {
+                    V3<R> rb = mk3<R>(0, 0, 0);
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            const V3<R> d = pos1 - xyz<R>(b);
+                            if (length(d) < ir) rb = rb - (((rd * b.w) / (dens * dens)) * W_grad<R, KSET>(d, ir, kpg));
+                        }
+                    }
+                    db = db + rb;
+                }
+            }
+}
+
+// the two sums of computeAdvectionFactor (sph_kernel_impl.cuh:1114-1218) + helpers (:968-1108): rho_adv (fluid partials to
+// rho_advf, boundary partials to rho_advb) and a_ii, one partial per cell; all three added to the caller's values
+template <typename R, int KSET, bool HAS_B>
+NRS_DEV void advection_walk(const Params<R> &P, const GridView<R> &G, const IisphArrays<R> &I,
+                            const typename Vec4T<R>::type *__restrict__ sPos, uint32_t i, V3<R> pos1, V3<R> vel1, V3<R> velAdv1,
+                            R dens, V3<R> diif, V3<R> diib, R &rho_advf, R &rho_advb, R &aii)
+{
+    const R kpg = P.kpoly_grad, pm = P.particleMass, ir = P.interactionRadius, rd = P.restDensity, dt = P.timestep;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                R res = (R)0.0;
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        if (j == i) continue;
+                        const V3<R> vij = velAdv1 - xyz<R>(I.velAdv[j]);
+                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
+                        if (length(d) < ir) res += (dt * pm * dot(vij, W_grad<R, KSET>(d, ir, kpg)));
+                    }
+                }
+                rho_advf += res;
+                if (HAS_B) {
+                    R rb = (R)0.0;
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) { // no cut-off: relies on W_grad == 0 beyond h (Q8)
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            const V3<R> d = pos1 - xyz<R>(b);
+                            rb += (dt * (rd * b.w) * dot(vel1, W_grad<R, KSET>(d, ir, kpg)));
+                        }
+                    }
+                    rho_advb += rb;
+                }
+            }
+    for (int z = -1; z <= 1; z++) // (no cut-off on either loop of a_ii: Q8)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                R res = (R)0.0;
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        if (j == i) continue;
+                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
+                        const R dpi = (pm) / (dens * dens);
                         const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                        res = res - ((pm / (densj * densj)) * p_lj * grad);
+                        const V3<R> dji = dpi * grad;
+                        res += (pm * dot((diif + diib) - dji, grad));
+                    }
+                }
+                aii += res;
+                if (HAS_B) {
+                    R rb = (R)0.0;
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            const V3<R> d = pos1 - xyz<R>(b);
+                            const R psi = rd * b.w;
+                            const R dpi = (pm) / (dens * dens);
+                            const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
+                            const V3<R> dji = dpi * grad;
+                            rb += psi * dot((diif + diib) - dji, grad);
+                        }
+                    }
+                    aii += rb;
+                }
+            }
+}
+
+// computeSumDijPj (sph_kernel_impl.cuh:1259-1325) + dijpjcell (:1224-1253): fluid neighbours only, one partial per cell;
+// added to the caller's dijpj
+template <typename R, int KSET>
+NRS_DEV void sumdij_walk(const Params<R> &P, const GridView<R> &G, const IisphArrays<R> &I,
+                         const typename Vec4T<R>::type *__restrict__ sPos, const R *__restrict__ sDens, uint32_t i, V3<R> pos1,
+                         V3<R> &dijpj)
+{
+    const R ir = P.interactionRadius, pm = P.particleMass, kpg = P.kpoly_grad;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                V3<R> res = mk3<R>(0, 0, 0);
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        if (j == i) continue;
+                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
+                        const R densj = sDens[j];
+                        res = res - ((pm / (densj * densj)) * I.P_l[j] * W_grad<R, KSET>(d, ir, kpg));
                     }
                 }
                 dijpj = dijpj + res;
             }
-    I.sumDij[i] = mk4<R>(dijpj, (R)0.0);
 }
 
 // NRS_FLAG_IISPH_SELF_BY_SLOT: inv[slot] = slot, so that the two kernels below skip the particle itself (SURVEY Q5 off)
@@ -658,9 +598,102 @@ static __global__ __launch_bounds__(BLOCK) void k_identity(uint32_t *__restrict_
     if (i < n) a[i] = i;
 }
 
+// the boundary loops of computePressure / computePressureForce run j from the FLUID cell start to the BOUNDARY cell end,
+// over the boundary array, in every cell that holds boundary particles.  f(b) for each such b (xyz + Vbi in w).
+template <typename R, typename F> NRS_DEV void for_each_boundary_q6(const GridView<R> &G, uint32_t h, F &&f)
+{
+    if (G.bCellStart[h] != CELL_EMPTY) {
+        const uint32_t s = G.cellStart[h], eB = G.bCellEnd[h];
+        for (uint32_t j = s; j < eB; ++j) f(G.sB[j]);
+    }
+}
+
+// the neighbour sums of computePressure (sph_kernel_impl.cuh:1330-1492), one accumulator each, no per-cell partials:
+// FLUID: fsum over the fluid slots but `skip` (Q5: the callers pass inv[i], the reference thread id); dii(j) = diiF[j] + diiB[j]
+// BOUND: bsum over the boundary particles of the Q6 range
+template <typename R, int KSET, bool FLUID, bool BOUND, typename Dii>
+NRS_DEV void pressure_walk(const Params<R> &P, const GridView<R> &G, const IisphArrays<R> &I,
+                           const typename Vec4T<R>::type *__restrict__ sPos, uint32_t skip, V3<R> pos1, R dens, V3<R> dijpj,
+                           Dii &&dii, R &fsum, R &bsum)
+{
+    const R ir = P.interactionRadius, pm = P.particleMass, kpg = P.kpoly_grad, rd = P.restDensity;
+    const R dpi = pm / (dens * dens);
+    auto term = [&](uint32_t j) {
+        const V3<R> d = pos1 - xyz<R>(sPos[j]);
+        const R p_lj = I.P_l[j];
+        const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
+        const V3<R> dji = dpi * (grad);
+        const V3<R> d_ji_pi = dji * p_lj;
+        const V3<R> diij = dii(j);
+        const V3<R> sum_dijj = xyz<R>(I.sumDij[j]);
+        fsum += pm * dot(dijpj - diij * p_lj - (sum_dijj - d_ji_pi), grad);
+    };
+    const I3 gp = calcGridPos<R>(P, pos1);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                if (FLUID) {
+                    const uint32_t s = G.cellStart[h];
+                    if (s != CELL_EMPTY) {
+                        const uint32_t e = G.cellEnd[h];
+                        for (uint32_t j = s; j < e; ++j)
+                            if (j != skip) term(j);
+                    }
+                }
+                if (BOUND)
+                    for_each_boundary_q6<R>(G, h, [&](const typename Vec4T<R>::type &b) {
+                        const V3<R> d = pos1 - xyz<R>(b);
+                        const R psi = rd * b.w;
+                        bsum += psi * dot(dijpj, W_grad<R, KSET>(d, ir, kpg));
+                    });
+            }
+}
+
+// the pressure force of computePressureForce (sph_kernel_impl.cuh:1497-1620): one accumulator takes the fluid terms of a cell and
+// then that cell's boundary terms (Q6 range), cell by cell (c = 0..26, z, y, x).  fluidCell(c, h, term) calls term(j) for the cell's
+// fluid slots but the reference thread id (Q5), ascending.
+template <typename R, int KSET, bool HAS_B, typename FluidCell>
+NRS_DEV V3<R> pforce_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                          const R *__restrict__ sDens, const R *__restrict__ sPres, V3<R> pos1, R p, R dens, FluidCell &&fluidCell)
+{
+    const R ir = P.interactionRadius, pm = P.particleMass, kpg = P.kpoly_grad, rd = P.restDensity;
+    V3<R> fp = mk3<R>(0, 0, 0);
+    auto term = [&](uint32_t j) {
+        const V3<R> d = pos1 - xyz<R>(sPos[j]);
+        const R pj = sPres[j];
+        const R densj = sDens[j];
+        const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
+        const V3<R> contrib = -pm * pm * (p / (dens * dens) + pj / (densj * densj)) * grad;
+        fp = fp + contrib;
+    };
+    const I3 gp = calcGridPos<R>(P, pos1);
+    for (int c = 0; c < 27; ++c) {
+        const int z = c / 9 - 1, y = (c / 3) % 3 - 1, x = c % 3 - 1;
+        const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+        fluidCell(c, h, term);
+        if (HAS_B)
+            for_each_boundary_q6<R>(G, h, [&](const typename Vec4T<R>::type &b) {
+                const V3<R> d = pos1 - xyz<R>(b);
+                const R psi = rd * b.w;
+                const V3<R> contrib = (pm * psi * (p / (dens * dens)) * W_grad<R, KSET>(d, ir, kpg));
+                fp = fp + contrib;
+            });
+    }
+    return fp;
+}
+// the fluid cell walk of both computePressureForce paths: term(j) for the slots of cell h but skip
+template <typename R, typename F> NRS_DEV void pforce_fluid_cell(const GridView<R> &G, uint32_t h, uint32_t skip, F &term)
+{
+    const uint32_t s = G.cellStart[h];
+    if (s != CELL_EMPTY) {
+        const uint32_t e = G.cellEnd[h];
+        for (uint32_t j = s; j < e; ++j)
+            if (j != skip) term(j);
+    }
+}
+
 // computePressure (sph_kernel_impl.cuh:1330-1492): relaxed Jacobi, omega = 0.5.
-// Q5: the fluid loop skips j == inv[i] (the reference thread id), not j == i.
-// Q6: the boundary loop runs j from the FLUID cell start to the boundary cell end.
 // Q7: reads P_l, writes P_l_next (true Jacobi; the reference updates in place and races).
 template <typename R, int KSET, bool HAS_B>
 __global__ __launch_bounds__(BLOCK) void k_pressure_ref(Params<R> P, GridView<R> G, IisphArrays<R> I,
@@ -677,44 +710,10 @@ __global__ __launch_bounds__(BLOCK) void k_pressure_ref(Params<R> P, GridView<R>
     const R rho_adv = I.densAdv[i];
     const R aii = I.aii[i];
     const V3<R> dijpj = xyz<R>(I.sumDij[i]);
-    const I3 gp = calcGridPos<R>(P, pos1);
-    const R ir = P.interactionRadius, pm = P.particleMass, kpg = P.kpoly_grad, dt = P.timestep, rd = P.restDensity;
+    const R dt = P.timestep, rd = P.restDensity;
     R fsum = (R)0.0, bsum = (R)0.0;
-    const R dpi = pm / (dens * dens);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        if (j == skip) continue;
-                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                        const R p_lj = I.P_l[j];
-                        const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                        const V3<R> dji = dpi * (grad);
-                        const V3<R> d_ji_pi = dji * p_lj;
-                        const V3<R> diifj = xyz<R>(I.diiF[j]);
-                        const V3<R> diibj = xyz<R>(I.diiB[j]);
-                        const V3<R> sum_dijj = xyz<R>(I.sumDij[j]);
-                        fsum += pm * dot(dijpj - (diifj + diibj) * p_lj - (sum_dijj - d_ji_pi), grad);
-                    }
-                }
-                if (HAS_B) {
-                    const uint32_t sB = G.bCellStart[h];
-                    if (sB != CELL_EMPTY) {
-                        const uint32_t eB = G.bCellEnd[h];
-                        for (uint32_t j = s; j < eB; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            const V3<R> d = pos1 - xyz<R>(b);
-                            const R psi = rd * b.w;
-                            const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                            bsum += psi * dot(dijpj, grad);
-                        }
-                    }
-                }
-            }
+    pressure_walk<R, KSET, true, HAS_B>(P, G, I, sPos, skip, pos1, dens, dijpj,
+                                        [&](uint32_t j) { return xyz<R>(I.diiF[j]) + xyz<R>(I.diiB[j]); }, fsum, bsum);
     const R omega = (R)0.5;
     R rho_corr = rho_adv + fsum + bsum;
     const R dt2 = dt * dt;
@@ -732,7 +731,69 @@ __global__ __launch_bounds__(BLOCK) void k_pressure_ref(Params<R> P, GridView<R>
     I.densCorr[i] = rho_corr;
 }
 
-// computePressureForce (sph_kernel_impl.cuh:1497-1620), same Q5/Q6
+// computeDisplacementFactor (sph_kernel_impl.cuh:851-963)
+template <typename R, int KSET, bool SURF, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_displacement_ref(Params<R> P, GridView<R> G, IisphArrays<R> I,
+                                                            const typename Vec4T<R>::type *__restrict__ sPos,
+                                                            const typename Vec4T<R>::type *__restrict__ sVel,
+                                                            const R *__restrict__ sDens, const R *__restrict__ sPres,
+                                                            uint32_t n)
+{
+    uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3<R> pos1 = xyz<R>(sPos[i]);
+    const V3<R> vel1 = xyz<R>(sVel[i]);
+    const R pres = (R)0.0;
+    const R dens = sDens[i];
+    const R pm = P.particleMass, dt = P.timestep;
+    ForceAcc<R> A = gather_forces<R, KSET, SURF, HAS_B>(P, G, i, pos1, vel1, dens, pres, sPos, sVel, sDens, sPres);
+    V3<R> fvisc = 2.0 * A.fvisc;
+    fvisc = (pm * P.viscosity) * fvisc;
+    const V3<R> fgrav = pm * mk3<R>(P.gravity[0], P.gravity[1], P.gravity[2]);
+    const V3<R> force_adv = fvisc + A.fsurf + A.fbound + fgrav;
+    const V3<R> vel_adv = vel1 + dt * (force_adv / pm);
+    I.forcesAdv[i] = mk4<R>(force_adv, (R)0.0);
+    I.velAdv[i] = mk4<R>(vel_adv, (R)0.0);
+    V3<R> df = mk3<R>(0, 0, 0), db = mk3<R>(0, 0, 0);
+    displacement_walk<R, KSET, HAS_B>(P, G, sPos, i, pos1, dens, df, db);
+    I.diiF[i] = mk4<R>(df, (R)0.0);
+    I.diiB[i] = mk4<R>(db, (R)0.0);
+}
+
+// computeAdvectionFactor (sph_kernel_impl.cuh:1114-1218)
+template <typename R, int KSET, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_advection_ref(Params<R> P, GridView<R> G, IisphArrays<R> I,
+                                                         const typename Vec4T<R>::type *__restrict__ sPos,
+                                                         const typename Vec4T<R>::type *__restrict__ sVel,
+                                                         const R *__restrict__ sDens, const R *__restrict__ sPres,
+                                                         uint32_t n)
+{
+    uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const R dens = sDens[i];
+    R rho_advf = (R)0.0, rho_advb = (R)0.0, aii = (R)0.0;
+    advection_walk<R, KSET, HAS_B>(P, G, I, sPos, i, xyz<R>(sPos[i]), xyz<R>(sVel[i]), xyz<R>(I.velAdv[i]), dens, xyz<R>(I.diiF[i]),
+                                   xyz<R>(I.diiB[i]), rho_advf, rho_advb, aii);
+    const R rho_adv = dens + (rho_advf + rho_advb);
+    I.densAdv[i] = rho_adv;
+    I.P_l[i] = (R)(0.5 * sPres[i]);
+    I.aii[i] = aii;
+}
+
+// computeSumDijPj (sph_kernel_impl.cuh:1259-1325)
+template <typename R, int KSET>
+__global__ __launch_bounds__(BLOCK) void k_sumdij_ref(Params<R> P, GridView<R> G, IisphArrays<R> I,
+                                                      const typename Vec4T<R>::type *__restrict__ sPos,
+                                                      const R *__restrict__ sDens, uint32_t n)
+{
+    uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    V3<R> dijpj = mk3<R>(0, 0, 0);
+    sumdij_walk<R, KSET>(P, G, I, sPos, sDens, i, xyz<R>(sPos[i]), dijpj);
+    I.sumDij[i] = mk4<R>(dijpj, (R)0.0);
+}
+
+// computePressureForce (sph_kernel_impl.cuh:1497-1620)
 template <typename R, int KSET, bool HAS_B>
 __global__ __launch_bounds__(BLOCK) void k_pforce_ref(Params<R> P, GridView<R> G, IisphArrays<R> I,
                                                       const typename Vec4T<R>::type *__restrict__ sPos,
@@ -742,44 +803,8 @@ __global__ __launch_bounds__(BLOCK) void k_pforce_ref(Params<R> P, GridView<R> G
     uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const uint32_t skip = I.inv[i];
-    const V3<R> pos1 = xyz<R>(sPos[i]);
-    const R p = sPres[i];
-    const R dens = sDens[i];
-    const I3 gp = calcGridPos<R>(P, pos1);
-    const R ir = P.interactionRadius, pm = P.particleMass, kpg = P.kpoly_grad, rd = P.restDensity;
-    V3<R> fp = mk3<R>(0, 0, 0);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        if (j == skip) continue;
-                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                        const R pj = sPres[j];
-                        const R densj = sDens[j];
-                        const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                        const V3<R> contrib = -pm * pm * (p / (dens * dens) + pj / (densj * densj)) * grad;
-                        fp = fp + contrib;
-                    }
-                }
-                if (HAS_B) {
-                    const uint32_t sB = G.bCellStart[h];
-                    if (sB != CELL_EMPTY) {
-                        const uint32_t eB = G.bCellEnd[h];
-                        for (uint32_t j = s; j < eB; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            const V3<R> d = pos1 - xyz<R>(b);
-                            const R psi = rd * b.w;
-                            const V3<R> grad = W_grad<R, KSET>(d, ir, kpg);
-                            const V3<R> contrib = (pm * psi * (p / (dens * dens)) * grad);
-                            fp = fp + contrib;
-                        }
-                    }
-                }
-            }
+    const V3<R> fp = pforce_walk<R, KSET, HAS_B>(P, G, sPos, sDens, sPres, xyz<R>(sPos[i]), sPres[i], sDens[i],
+                                                 [&](int, uint32_t h, auto &term) { pforce_fluid_cell<R>(G, h, skip, term); });
     I.forcesP[i] = mk4<R>(fp, (R)0.0);
 }
 

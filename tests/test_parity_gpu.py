@@ -610,12 +610,12 @@ def test_iisph_stages_and_steps(hip_lib):
 
 def test_iisph_list_kernels_equal_reference_order_bitwise(hip_lib):
     """The list-driven IISPH chain (one scan per step) against the plain reference-order kernels, bit for bit:
-    no boundaries, with boundaries, and a crowded blob whose hit lists overflow (per-particle fallback)."""
+    no boundaries, with boundaries, and crowded blobs whose hit lists overflow (per-particle fallback), without and with boundaries."""
     scenes = []
     p, pos, vel = compressed_block()
-    scenes.append((p, pos, vel, None, None))
+    scenes.append((p, pos, vel, None, None, False))
     p2, sc = small_dam_break(solver=IISPH)
-    scenes.append((p2, sc["pos"], sc["vel"], sc["bi"], sc["vbi"]))
+    scenes.append((p2, sc["pos"], sc["vel"], sc["bi"], sc["vbi"], False))
     rng = np.random.default_rng(5)
     h = float(p["interactionRadius"][0])
     blob = np.ones((120, 4), np.float32)
@@ -623,10 +623,25 @@ def test_iisph_list_kernels_equal_reference_order_bitwise(hip_lib):
     loose = np.ones((200, 4), np.float32)
     loose[:, :3] = (np.array([0.2, 0.1, -0.3]) + rng.uniform(-3 * h, 3 * h, (200, 3))).astype(np.float32)
     crowd = np.concatenate([blob, loose])
-    scenes.append((p, crowd, np.zeros_like(crowd), None, None))
+    scenes.append((p, crowd, np.zeros_like(crowd), None, None, True))
+    # a crowded blob on the floor of the dam-break tank, away from the block: overflowing particles with boundary cells in their
+    # neighbourhood (the HAS_B fallback and the wall workgroups)
+    tank = sc["tank"]
+    h2 = float(p2["interactionRadius"][0])
+    wblob = np.ones((120, 4), np.float32)
+    wblob[:, :3] = (np.array([0.75 * tank[0], 0.6 * h2, 0.5 * tank[2]]) + rng.uniform(-0.45 * h2, 0.45 * h2, (120, 3))).astype(np.float32)
+    walled = np.concatenate([sc["pos"], wblob])
+    scenes.append((p2, walled, np.zeros_like(walled), sc["bi"], sc["vbi"], True))
     names = ["dens", "velAdv", "forcesAdv", "diiFluid", "diiBoundary", "densAdv", "aii", "sumDij", "densCorr", "P_l", "pres",
              "forcesP"]
-    for (pp, pos, vel, bi, vbi) in scenes:
+    for (pp, pos, vel, bi, vbi, overflows) in scenes:
+        if overflows:
+            s = capi.Solver(pp, len(pos), solver=capi.IISPH)
+            s.set_particles(pos, vel)
+            s.set_boundaries(bi, vbi, update_grid=True)
+            s.step(1)
+            assert s.get_stat(capi.STAT_HIT_OVERFLOW) > 0   # the scene really takes the per-particle fallback
+            s.close()
         outs = []
         for ref in (False, True):
             s = capi.Solver(pp, len(pos), solver=capi.IISPH, reference_order=ref)
