@@ -60,7 +60,9 @@ typedef struct nrs_params_f64 {
 
 typedef struct nrs_ctx nrs_ctx;
 
-enum { NRS_SOLVER_SESPH = 0, NRS_SOLVER_IISPH = 1 };     /* Nereus::SPH (sph/sph.h:23) / Nereus::IISPH (iisph.h:8) */
+/* Nereus::SPH (sph/sph.h:23) / Nereus::IISPH (iisph.h:8) / predictive-corrective PCISPH (Solenthaler & Pajarola 2009; the
+ * reference's Nereus::PCISPH stops after the density, its pressure solve is an empty stub: DESIGN.md "PCISPH" defines this one) */
+enum { NRS_SOLVER_SESPH = 0, NRS_SOLVER_IISPH = 1, NRS_SOLVER_PCISPH = 2 };
 enum { NRS_KERNELS_MONAGHAN = 0, NRS_KERNELS_MULLER = 1 }; /* KERNEL_SET, common/common.h:14-15 */
 
 /* nrs_config.flags */
@@ -81,7 +83,7 @@ enum {
                                            (calcGridPos keeps its true division); densities, forces and the integrated state agree
                                            with the default reference-order IEEE arithmetic to ~1e-6 relative per step.  The
                                            reference itself is built with --use_fast_math (CMakeLists.txt:85).  Ignored (exact
-                                           arithmetic) for fp64, Monaghan kernels, IISPH and NRS_FLAG_REFERENCE_ORDER. */
+                                           arithmetic) for fp64, Monaghan kernels, IISPH, PCISPH and NRS_FLAG_REFERENCE_ORDER. */
     NRS_FLAG_IISPH_SELF_BY_SLOT = 1u << 6, /* IISPH: computePressure / computePressureForce exclude the particle ITSELF from their
                                            neighbour sums.  The reference excludes the slot whose number equals the CUDA thread
                                            id instead (sph_kernel_impl.cuh:1412,1568), which makes its result depend
@@ -94,7 +96,8 @@ enum {
     NRS_FLAG_STAGED_SCAN = 1u << 8,     /* SESPH fp32 Muller: the density launch is the LDS-STAGED scan (k_density_staged: one wavefront
                                            per 64 consecutive sorted slots, row hulls by ballot + readlane, one z-plane of candidates
                                            staged in LDS) instead of the quantised global-memory scan.  Same lists, same sums, bit for
-                                           bit; measured slower, kept as the north-star's literal kernel shape */
+                                           bit; measured slower, kept as the north-star's literal kernel shape.
+                                           Ignored by IISPH and PCISPH contexts (their one scan publishes the wide hit lists) */
     NRS_FLAG_IISPH_INPLACE_P = 1u << 1, /* reserved: the reference's racy in-place Jacobi is NOT
                                            offered; P_l is always double-buffered */
 };
@@ -124,7 +127,8 @@ typedef struct nrs_config {
 } nrs_config;
 
 /* Pipeline stages, for nrs_step_partial / nrs_stage_ms.  Order is the order of SPH::update()
- * (sph/sph.cpp:233-284) and IISPH::update() (sph/iisph/iisph.cpp:172-216). */
+ * (sph/sph.cpp:233-284) and IISPH::update() (sph/iisph/iisph.cpp:172-216).  A PCISPH step is HASH, SORT, REORDER, DENSITY
+ * (density only, no Tait pressure), then the P_* stages; nrs_step_partial on a PCISPH context accepts those and refuses the others. */
 enum {
     NRS_STAGE_HASH = 1,      /* calcHash                     sph_cuda.cu:230 */
     NRS_STAGE_SORT = 2,      /* sortParticles                sph_cuda.cu:58 */
@@ -132,6 +136,9 @@ enum {
     NRS_STAGE_DENSITY = 4,   /* computeDensityPressure kernel sph_kernel_impl.cuh:365 */
     NRS_STAGE_FORCES = 5,    /* computeForces kernel          sph_kernel_impl.cuh:609 */
     NRS_STAGE_INTEGRATE = 6, /* integrateSystem              sph_cuda.cu:211 */
+    NRS_STAGE_P_ADVECT = 7,    /* PCISPH: non-pressure forces, vel_adv, first predicted positions, p = 0 */
+    NRS_STAGE_P_SOLVE = 8,     /* PCISPH: the predictive-corrective loop (two launches per iteration) */
+    NRS_STAGE_P_INTEGRATE = 9, /* PCISPH: v = vel_adv + dt Fp / m, x += dt v (iisph_integrate) */
     NRS_STAGE_I_DENSITY = 10,      /* computeIisphDensity        sph_kernel_impl.cuh:770 */
     NRS_STAGE_I_DISPLACEMENT = 11, /* computeDisplacementFactor  :851 */
     NRS_STAGE_I_ADVECTION = 12,    /* computeAdvectionFactor     :1114 */
@@ -171,6 +178,9 @@ enum {
     NRS_ARR_DII_FLUID = 27,
     NRS_ARR_DII_BOUNDARY = 28,
     NRS_ARR_SUM_DIJ = 29,
+    NRS_ARR_POS_PRED = 30,  /* PCISPH: SVec4[N] predicted positions x* of the last iteration.  On a PCISPH context NRS_ARR_VEL_ADV,
+                               _FORCES_ADV, _FORCES_P (the pressure force), _DENS_CORR (the predicted density) and _P_L (the pressure p)
+                               hold the PCISPH quantities; NRS_ARR_PRES and nrs_download(pres) the step's final pressures */
 };
 
 const char *nrs_last_error(void);
@@ -243,10 +253,18 @@ int nrs_get_array(nrs_ctx *ctx, int which, void *dst, uint64_t dst_bytes, uint64
  * i.e. read it after each step).  For zero-copy consumers (renderer VBO upload, halo packing). */
 int nrs_device_ptr(nrs_ctx *ctx, int which, void **dptr, uint64_t *bytes);
 
-/* IISPH: solver iterations of the last step (the `l` of sph_cuda.cu:736). */
+/* IISPH / PCISPH: solver iterations of the last step (the `l` of sph_cuda.cu:736). */
 int nrs_last_iterations(nrs_ctx *ctx, uint32_t *iters);
-/* Cap on IISPH solver iterations per step (0 = none, as the reference). */
+/* Cap on IISPH / PCISPH solver iterations per step.  0 = none for IISPH, as the reference; 0 = 50 for PCISPH (a predictive-corrective
+ * loop need not end). */
 int nrs_set_max_iterations(nrs_ctx *ctx, uint32_t max_iters);
+
+/* PCISPH solver settings (NRS_E_STATE on any other context).  The loop stops after the iteration l with l >= min_iters and
+ * max_i max(rho*_i - rho0, 0) / rho0 <= max_density_error, or at the iteration cap (nrs_set_max_iterations).  delta = 0: the
+ * pressure scale delta is derived from a prototype particle on a cubic lattice of spacing prototype_spacing (0 = cbrt(m / rho0)),
+ * evaluated on the device once per parameter change; delta > 0 is used as given.  Defaults: 0.01, 3, 0, 0.
+ * NRS_E_INVALID for max_density_error <= 0, min_iters == 0 or a negative spacing / delta. */
+int nrs_pcisph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double prototype_spacing, double delta);
 
 /* Per-stage device time, measured with HIP events recorded on the context's stream around the stage's
  * launches.  stage_mask: bit s set = time NRS_STAGE_s (0 = off, 0xffffffff = every stage).  nrs_set_profiling also
@@ -269,7 +287,7 @@ int nrs_stage_ms(nrs_ctx *ctx, int stage, float *ms, uint32_t *launches);
  *   [u32 nMigrants, u32 nHalo, u32 0, u32 0 | vec4 pos[capacity] | vec4 vel[capacity]].
  * Pass NULL for the neighbour that does not exist (ends of the chain).  IISPH contexts: halo_cells >= 8 and the step is driven
  * through nrs_iisph_predict / _iterate / _finish (below). */
-int nrs_slab_configure(nrs_ctx *ctx, int32_t cell_lo, int32_t cell_hi, int32_t halo_cells);
+int nrs_slab_configure(nrs_ctx *ctx, int32_t cell_lo, int32_t cell_hi, int32_t halo_cells); /* NRS_E_INVALID on a PCISPH context */
 /* counts (optional) receives {stay, migrate-left, halo-left, migrate-right, halo-right, ghost}.
  * With counts == NULL nrs_slab_pack does not wait for the device: the two messages are complete in stream order when it returns (the
  * caller enqueues its sends on the same stream right behind it), and the stream populations are read back together with the headers of
@@ -299,7 +317,7 @@ int nrs_slab_histogram(nrs_ctx *ctx, int32_t first_cell, uint32_t ncells, uint32
  * need a halo of at least 2 * iterations + 4 cells — every iteration consumes two cells of halo validity, the predict stages three,
  * the pressure force one — i.e. >= 8; nrs_iisph_iterate fails with NRS_E_STATE when the loop runs longer than the halo supports.
  * The warm-start pressure of every particle travels in vel.w of the slab messages (iisph_integrate zeroes vel.w anyway). */
-int nrs_iisph_predict(nrs_ctx *ctx);
+int nrs_iisph_predict(nrs_ctx *ctx); /* (the three: NRS_E_STATE on any other context) */
 int nrs_iisph_iterate(nrs_ctx *ctx, double *sum_density_corr, uint64_t *count);
 int nrs_iisph_finish(nrs_ctx *ctx);
 
@@ -316,8 +334,12 @@ int nrs_resort_stats(nrs_ctx *ctx, uint64_t *steps, uint64_t *fallbacks);
  *   NRS_STAT_HIT_MEAN/_MAX  neighbours (fluid + boundary hits) per particle kept in the hit lists
  *   NRS_STAT_UNSTAGED       particles whose wavefront could not stage its neighbour rows in LDS (grid-edge cells, or
  *                           hulls longer than the pool) and scanned them from global memory instead
- * The HIT_* / UNSTAGED values need the shared hit lists of the production kernels (NRS_E_STATE otherwise). */
-enum { NRS_STAT_MOVERS = 0, NRS_STAT_HIT_OVERFLOW = 1, NRS_STAT_HIT_MEAN = 2, NRS_STAT_HIT_MAX = 3, NRS_STAT_UNSTAGED = 4 };
+ *   NRS_STAT_DENSITY_ERROR  PCISPH: max_i max(rho*_i - rho0, 0) / rho0 after the last iteration of the last step
+ *   NRS_STAT_PCISPH_DELTA   PCISPH: the pressure scale delta the last step used
+ * The HIT_* / UNSTAGED values need the shared hit lists of the production kernels (NRS_E_STATE otherwise); the PCISPH values a
+ * PCISPH context that has completed a solve. */
+enum { NRS_STAT_MOVERS = 0, NRS_STAT_HIT_OVERFLOW = 1, NRS_STAT_HIT_MEAN = 2, NRS_STAT_HIT_MAX = 3, NRS_STAT_UNSTAGED = 4,
+       NRS_STAT_DENSITY_ERROR = 5, NRS_STAT_PCISPH_DELTA = 6 };
 int nrs_get_stat(nrs_ctx *ctx, int which, double *out);
 
 /* Akinci boundary volumes on the device (no context needed): vbi[i] = 1 / sum_k W_poly6(|x_i - x_k|, h) over the boundary

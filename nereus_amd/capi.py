@@ -14,7 +14,7 @@ from .params import params_dtype
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NEREUS_HIP_LIB") or os.path.join(_HERE, "libnereus_hip.so")  # (override: kernel A/B builds in tools/)
 
-SESPH, IISPH = 0, 1
+SESPH, IISPH, PCISPH = 0, 1, 2
 MONAGHAN, MULLER = 0, 1
 FLAG_REFERENCE_ORDER = 1
 FLAG_NO_FUSION = 4
@@ -26,13 +26,16 @@ FLAG_NO_WALL_WORKGROUPS = 128
 FLAG_STAGED_SCAN = 256
 E_NOTREADY = -6
 STAT_MOVERS, STAT_HIT_OVERFLOW, STAT_HIT_MEAN, STAT_HIT_MAX, STAT_UNSTAGED = 0, 1, 2, 3, 4
+STAT_DENSITY_ERROR, STAT_PCISPH_DELTA = 5, 6
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
 STAGE_I_DENSITY, STAGE_I_DISPLACEMENT, STAGE_I_ADVECTION, STAGE_I_SOLVE, STAGE_I_PFORCE, STAGE_I_INTEGRATE = (
     10, 11, 12, 13, 14, 15)
-STAGE_NAMES = {1: "hash", 2: "sort", 3: "reorder", 4: "density", 5: "forces", 6: "integrate", 10: "i_density",
-               11: "i_displacement", 12: "i_advection", 13: "i_solve", 14: "i_pforce", 15: "i_integrate"}
+STAGE_P_ADVECT, STAGE_P_SOLVE, STAGE_P_INTEGRATE = 7, 8, 9
+STAGE_NAMES = {1: "hash", 2: "sort", 3: "reorder", 4: "density", 5: "forces", 6: "integrate", 7: "p_advect", 8: "p_solve",
+               9: "p_integrate", 10: "i_density", 11: "i_displacement", 12: "i_advection", 13: "i_solve", 14: "i_pforce",
+               15: "i_integrate"}
 
 # NRS_ARR_*: name -> (id, kind) with kind in {"v4", "s", "u"}
 ARRAYS = {
@@ -42,7 +45,7 @@ ARRAYS = {
     "bCellStart": (14, "u"), "bCellEnd": (15, "u"), "bSorted": (16, "v4"),
     "densAdv": (20, "s"), "densCorr": (21, "s"), "P_l": (22, "s"), "aii": (23, "s"), "velAdv": (24, "v4"),
     "forcesAdv": (25, "v4"), "forcesP": (26, "v4"), "diiFluid": (27, "v4"), "diiBoundary": (28, "v4"),
-    "sumDij": (29, "v4"),
+    "sumDij": (29, "v4"), "posPred": (30, "v4"),
 }
 
 # every symbol include/nereus_hip.h declares (checked by tests/test_abi.py)
@@ -54,7 +57,7 @@ EXPORTS = [
     "nrs_max_velocity", "nrs_slab_configure", "nrs_slab_pack", "nrs_slab_unpack", "nrs_num_owned",
     "nrs_slab_message_bytes", "nrs_slab_histogram", "nrs_resort_stats", "nrs_snapshot_begin", "nrs_snapshot_wait",
     "nrs_get_stat", "nrs_boundary_volumes", "nrs_eval_smoothing", "nrs_iisph_predict", "nrs_iisph_iterate", "nrs_iisph_finish",
-    "nrs_slab_last_counts",
+    "nrs_slab_last_counts", "nrs_pcisph_configure",
 ]
 
 
@@ -105,6 +108,7 @@ def load_library(path=None):
     lib.nrs_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u64)]
     lib.nrs_last_iterations.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.nrs_set_max_iterations.argtypes = [vp, C.c_uint32]
+    lib.nrs_pcisph_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_double]
     lib.nrs_set_profiling.argtypes = [vp, C.c_uint32]
     lib.nrs_stage_ms.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     lib.nrs_max_density.argtypes = [vp, C.POINTER(C.c_double)]
@@ -161,7 +165,7 @@ def eval_smoothing(which, r, s, h, c0, c1, double=False):
 
 
 class Solver:
-    """Thin object wrapper over an nrs_ctx (device-resident SESPH / IISPH solver)."""
+    """Thin object wrapper over an nrs_ctx (device-resident SESPH / IISPH / PCISPH solver)."""
 
     def __init__(self, params, capacity, solver=SESPH, double=False, kernel_set=MULLER, surface_tension=True,
                  reference_order=False, device=-1, stream=None, flags=0):
@@ -273,6 +277,11 @@ class Solver:
 
     def set_max_iterations(self, m):
         self._chk(self.lib.nrs_set_max_iterations(self.h, int(m)))
+
+    def pcisph_configure(self, max_density_error=0.01, min_iters=3, prototype_spacing=0.0, delta=0.0):
+        """PCISPH loop settings (nrs_pcisph_configure): exit error, minimum iterations, prototype lattice spacing (0 = cbrt(m / rho0)),
+        pressure scale delta (0 = from the prototype)"""
+        self._chk(self.lib.nrs_pcisph_configure(self.h, float(max_density_error), int(min_iters), float(prototype_spacing), float(delta)))
 
     def set_profiling(self, stages=True):
         """stages: True = all, False = off, or an iterable of stage ids."""

@@ -129,7 +129,7 @@ struct nrs_ctx {
 extern "C" {
 
 const char *nrs_last_error(void) { return g_err.c_str(); }
-uint32_t nrs_version(void) { return (0u << 16) | 2u; } // 0.2: NRS_FLAG_STAGED_SCAN / NO_WALL_WORKGROUPS, nrs_slab_last_counts, asynchronous nrs_step
+uint32_t nrs_version(void) { return (0u << 16) | 3u; } // 0.3: NRS_SOLVER_PCISPH, nrs_pcisph_configure (0.2: NRS_FLAG_STAGED_SCAN / NO_WALL_WORKGROUPS, nrs_slab_last_counts, asynchronous nrs_step)
 int nrs_device_count(void)
 {
     int n = 0;
@@ -143,7 +143,7 @@ int nrs_create(const nrs_config *cfg, const void *params, nrs_ctx **out)
     if (cfg->struct_size != sizeof(nrs_config)) return fail(NRS_E_INVALID, "nrs_config.struct_size mismatch");
     if (cfg->precision != 32 && cfg->precision != 64) return fail(NRS_E_INVALID, "precision must be 32 or 64");
     if (cfg->kernel_set != NRS_KERNELS_MULLER && cfg->kernel_set != NRS_KERNELS_MONAGHAN) return fail(NRS_E_INVALID, "bad kernel_set");
-    if (cfg->solver != NRS_SOLVER_SESPH && cfg->solver != NRS_SOLVER_IISPH) return fail(NRS_E_INVALID, "bad solver");
+    if (cfg->solver != NRS_SOLVER_SESPH && cfg->solver != NRS_SOLVER_IISPH && cfg->solver != NRS_SOLVER_PCISPH) return fail(NRS_E_INVALID, "bad solver");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(NRS_E_NODEVICE, "no HIP device available: libnereus_hip has no CPU fallback");
@@ -289,6 +289,11 @@ int nrs_set_max_iterations(nrs_ctx *ctx, uint32_t max_iters)
     CTX_GUARD(ctx);
     ctx->impl->maxIters = max_iters;
     return NRS_OK;
+}
+int nrs_pcisph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double prototype_spacing, double delta)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->pcisph_configure(max_density_error, min_iters, prototype_spacing, delta);
 }
 int nrs_set_profiling(nrs_ctx *ctx, uint32_t stage_mask)
 {

@@ -15,6 +15,7 @@
 #include "nrs_kernels_staged.h"
 #include <type_traits>
 #include "nrs_kernels_iisph.h"
+#include "nrs_kernels_pcisph.h"
 #include "nrs_kernels_slab.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
@@ -118,6 +119,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // IISPH
     DevBuf densAdv, densCorr, P_l, P_l2, aii, velAdv, forcesAdv, forcesP, diiF, diiB, sumDij, diiSum;
     DevBuf redPartial, redOut;
+    // PCISPH (nrs_kernels_pcisph.h): the two predicted-position buffers (xsCur = the newest) and the density errors the exit test
+    // takes the max of; velAdv, forcesAdv, forcesP, densCorr (rho*) and P_l (p) are shared with the IISPH names
+    DevBuf posPred, posPred2, pciErr;
+    double pciEta = 0.01, pciSpacing = 0.0, pciDeltaGiven = 0.0;
+    uint32_t pciMinIters = 3;
+    bool pciDeltaValid = false; // pciDelta belongs to the current parameters and settings
+    R pciDelta = (R)0;
+    double pciLastErr = -1.0; // max e_i after the last iteration of the last solve (< 0: no solve yet)
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
     HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
@@ -250,13 +259,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
 
     bool iisph() const { return cfg.solver == NRS_SOLVER_IISPH; }
+    bool pcisph() const { return cfg.solver == NRS_SOLVER_PCISPH; }
+    bool sesph() const { return cfg.solver == NRS_SOLVER_SESPH; }
     bool pow2_grid() const { return is_pow2(P.gridSize[0]) && is_pow2(P.gridSize[1]) && is_pow2(P.gridSize[2]); }
 
     // ---- which kernels a step launches ------------------------------------------------------------------------------------
     // The flag- and type-derived half of the choice is fixed at init() and decides which optional buffers exist (init(),
     // rebuild_boundary_tables()); plan_step() adds the grid facts of the step.  The launch sites read the plan, nothing else.
     struct Features {
-        bool listKernels; // the solver has list-driven kernels for this kernel set (IISPH: Muller only, the Monaghan support is 2h)
+        bool listKernels; // the solver has list-driven kernels for this kernel set (IISPH, PCISPH: Muller only, the Monaghan support is 2h)
         bool lists;       // hitBuf, hitCounts, qpos (+ gatherPos for SESPH)
         bool fast;        // fastQ
         bool resort;      // the coherent re-sort buffers
@@ -265,9 +276,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         const uint32_t f = cfg.flags;
         Features ft;
-        ft.listKernels = !iisph() || KSET == KS_MULLER;
+        ft.listKernels = sesph() || KSET == KS_MULLER;
         ft.lists = ft.listKernels && !(f & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_SHARED_LISTS));
-        ft.fast = ft.lists && (f & NRS_FLAG_FAST_ARITH) && !iisph() && std::is_same<R, float>::value && KSET == KS_MULLER;
+        ft.fast = ft.lists && (f & NRS_FLAG_FAST_ARITH) && sesph() && std::is_same<R, float>::value && KSET == KS_MULLER;
         ft.resort = !(f & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_FUSION | NRS_FLAG_FULL_SORT)) && cap >= RESORT_MIN_PARTICLES;
         return ft;
     }
@@ -296,14 +307,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // hit lists are built (and the kernels that consume them used) only when the scan that builds them can run
         s.quant = ft.lists && qOk;
         if (s.ref) return s;
-        // SESPH: density -> forces, shared only when the step goes on past the density; IISPH: one scan feeds the chain
-        // (nrs_kernels_iisph.h)
-        s.lists = s.quant && (iisph() || stop != NRS_STAGE_DENSITY);
+        // SESPH: density -> forces, shared only when the step goes on past the density; IISPH, PCISPH: one scan feeds the chain
+        // (nrs_kernels_iisph.h, nrs_kernels_pcisph.h)
+        s.lists = s.quant && (!sesph() || stop != NRS_STAGE_DENSITY);
         // LDS-staged density scan (nrs_kernels_staged.h): fp32 SESPH on power-of-two grids.  Measured at 10 M particles it is
         // SLOWER than the global-memory scan in the exact arithmetic (0.84 vs 0.71 ms: the kernel is bound by vector-instruction
         // issue, not by the latency the staging removes), and since the quantised scan (0.52 ms) also slower than the
         // exact path in its own fast arithmetic (0.70-0.88 ms): it runs only when NRS_FLAG_STAGED_SCAN asks for it.
-        s.staged = (cfg.flags & NRS_FLAG_STAGED_SCAN) && std::is_same<R, float>::value && KSET == KS_MULLER && !iisph() && s.quant &&
+        s.staged = (cfg.flags & NRS_FLAG_STAGED_SCAN) && std::is_same<R, float>::value && KSET == KS_MULLER && sesph() && s.quant &&
                    P.numCells <= (1u << 30);
         // fast arithmetic (reciprocals, rsq, fused multiply-adds) in the FORCE walk: fp32 Muller SESPH with shared lists; the density
         // kernel (exact) leaves the (p/rho^2, 1/rho) pairs it needs; everything else keeps IEEE arithmetic
@@ -321,7 +332,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // slab runs: the next partition's classification rides in the same launch (k_slab_count and most of k_slab_scatter then have
         // nothing left to do)
         s.classify = resort && slabOn;
-        // (not in slab runs, whose loop the host drives)
+        // (not in slab runs, whose loop the host drives; PCISPH has no reference-order repeat)
         s.watch = iisph() && s.lists && !slabOn;
         return s;
     }
@@ -334,7 +345,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         DevBuf *all[] = {&posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
                          &inv, &sortTmp, &cellStart, &cellEnd, &bCellStart, &bCellEnd, &bSorted, &bHash, &bIndex,
                          &bHashAlt, &bIndexAlt, &densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP,
-                         &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
+                         &posPred, &posPred2, &pciErr, &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
                          &rsMovers, &rsMoversAlt, &rsStayers, &rsMerged, &rsTileMovers, &rsTileOffset, &rsGroupTotal, &rsGroupPrefix, &rsScalars, &rsPrevPacked,
                          &rsTileDead, &rsTileDeadOffset, &rsGroupDeadTotal, &rsGroupDeadPrefix, &slabFlags};
         for (DevBuf *b : all) b->release();
@@ -389,12 +400,19 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             DevBuf *z[] = {&densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP, &diiF, &diiB, &sumDij};
             for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
         }
+        if (pcisph()) { // (no dii / a_ii / sum d_ij p_j, no inverse slot table: the loop skips j == i by sorted slot)
+            NRSCHK(velAdv.alloc(v)); NRSCHK(forcesAdv.alloc(v)); NRSCHK(forcesP.alloc(v));
+            NRSCHK(densCorr.alloc(s)); NRSCHK(P_l.alloc(s));
+            NRSCHK(posPred.alloc(v)); NRSCHK(posPred2.alloc(v)); NRSCHK(pciErr.alloc(s));
+            DevBuf *z[] = {&velAdv, &forcesAdv, &forcesP, &densCorr, &P_l, &posPred, &posPred2, &pciErr};
+            for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
+        }
         const Features ft = features();
         if (ft.lists) {
             NRSCHK(hitBuf.alloc((size_t)HIT_CAP * cap * 4));
             NRSCHK(hitCounts.alloc((size_t)cap * 4));
             NRSCHK(qpos.alloc(((size_t)cap + 4) * sizeof(qword_t)));
-            if (!iisph()) NRSCHK(gatherPos.alloc((size_t)cap * 2 * sizeof(T4)));
+            if (sesph()) NRSCHK(gatherPos.alloc((size_t)cap * 2 * sizeof(T4)));
         }
         if (ft.fast) NRSCHK(fastQ.alloc((size_t)cap * sizeof(FastPair)));
         NRSCHK(errWord.alloc(8)); // [0] run guard of the scans, [1] IISPH: a gathered value went non-finite (IisphArrays::nonFinite)
@@ -467,6 +485,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                               std::memcmp(PU.cellSize, q.cellSize, sizeof(PU.cellSize)) == 0;
         if (!sameGrid) NRSCHK(invalidate_grid_state());
         const uint32_t cellsBefore = P.numCells;
+        // delta (pcisph_prepare) depends on these alone; the host classes set the parameters every step
+        if (q.timestep != PU.timestep || q.particleMass != PU.particleMass || q.restDensity != PU.restDensity ||
+            q.interactionRadius != PU.interactionRadius || q.kpoly_grad != PU.kpoly_grad)
+            pciDeltaValid = false;
         PU = q;
         if (!sameGrid && slabOn) choose_window(slab.lo, slab.hi, slab.halo, true);
         derive_kernel_params();
@@ -947,12 +969,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         if (!n) { *out = 0; return NRS_OK; }
         NRSCHK(compact_holes());
-        const uint32_t N = (uint32_t)n;
+        if (which == 0) return max_of<false>(dens.p, (uint32_t)n, out);
+        return max_of<true>(velA.p, (uint32_t)n, out);
+    }
+    // max over an SReal array (VEC: of |v| over a vec4 array), deterministic: per-block maxima on the device, their max on the host
+    template <bool VEC> int max_of(const void *a, uint32_t N, double *out)
+    {
         const uint32_t nbk = std::min<uint32_t>(1024u, nblocks(N));
-        if (which == 0)
-            hipLaunchKernelGGL((k_max_partial<R, false>), dim3(nbk), dim3(BLOCK), 0, stream, (const void *)dens.p, redPartial.as<double>(), N);
-        else
-            hipLaunchKernelGGL((k_max_partial<R, true>), dim3(nbk), dim3(BLOCK), 0, stream, (const void *)velA.p, redPartial.as<double>(), N);
+        hipLaunchKernelGGL((k_max_partial<R, VEC>), dim3(nbk), dim3(BLOCK), 0, stream, a, redPartial.as<double>(), N);
         std::vector<double> h(nbk);
         HIPCHK(hipMemcpyAsync(h.data(), redPartial.p, sizeof(double) * nbk, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
@@ -1054,7 +1078,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                           dens.as<R>(), presB.as<R>(), N);
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_I_PFORCE) return NRS_OK;
-        NRSCHK(ev_begin(NRS_STAGE_I_INTEGRATE));
+        return integrate_adv(NRS_STAGE_I_INTEGRATE);
+    }
+    // iisph_integrate (sph_cuda.cu:857-867) of velAdv + forcesP, timed as `stage`: the last launch of an IISPH or PCISPH step
+    int integrate_adv(int stage)
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        NRSCHK(ev_begin(stage));
         // (as the fused SESPH force kernel does)
         uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
         if (plan.resort) NRSCHK(clean_tile_counts());
@@ -1136,6 +1167,123 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return iisph_finish<HAS_B>(stop);
     }
 
+    // ---- PCISPH step (nrs_kernels_pcisph.h; DESIGN.md "PCISPH") -------------------------------------------------------------------
+    int pciXs = 0; // which of posPred / posPred2 holds the newest predicted positions
+    void *pci_xs_current() const { return pciXs ? posPred2.p : posPred.p; }
+    PciArrays<R> pci_view(int in, int out) const
+    {
+        PciArrays<R> A;
+        A.velAdv = velAdv.as<T4>(); A.forcesAdv = forcesAdv.as<T4>(); A.forcesP = forcesP.as<T4>();
+        A.densPred = densCorr.as<R>(); A.pres = P_l.as<R>(); A.err = pciErr.as<R>();
+        A.xsIn = (in ? posPred2 : posPred).as<T4>();
+        A.xsOut = (out ? posPred2 : posPred).as<T4>();
+        A.delta = pciDelta;
+        return A;
+    }
+    int pcisph_configure(double eta, uint32_t minIters, double spacing, double delta) override
+    {
+        if (!pcisph()) return fail(NRS_E_STATE, "nrs_pcisph_configure on a context that is not PCISPH");
+        if (!(eta > 0.0) || !std::isfinite(eta)) return fail(NRS_E_INVALID, "max_density_error must be > 0");
+        if (minIters == 0) return fail(NRS_E_INVALID, "min_iters must be >= 1");
+        if (!(spacing >= 0.0) || !std::isfinite(spacing)) return fail(NRS_E_INVALID, "prototype_spacing must be >= 0 (0 = cbrt(m / rho0))");
+        if (!(delta >= 0.0) || !std::isfinite(delta)) return fail(NRS_E_INVALID, "delta must be >= 0 (0 = from the prototype)");
+        pciEta = eta; pciMinIters = minIters; pciSpacing = spacing; pciDeltaGiven = delta;
+        pciDeltaValid = false;
+        return NRS_OK;
+    }
+    // delta = -1 / (beta (-sum g . sum g - sum g . g)), beta = 2 (dt m / rho0)^2, over the prototype's lattice neighbours (k_pci_prototype,
+    // the solver's own W_grad on the device); once per parameter or settings change
+    int pcisph_prepare()
+    {
+        if (pciDeltaValid) return NRS_OK;
+        if (pciDeltaGiven > 0.0) {
+            pciDelta = (R)pciDeltaGiven;
+            pciDeltaValid = true;
+            return NRS_OK;
+        }
+        const double m = (double)PU.particleMass, rd = (double)PU.restDensity, h = (double)PU.interactionRadius, dt = (double)PU.timestep;
+        const R sp = (R)(pciSpacing > 0.0 ? pciSpacing : std::cbrt(m / rd));
+        if (!(sp > (R)0) || !std::isfinite((double)sp) || !(h > 0.0) || h / (double)sp > 64.0)
+            return fail(NRS_E_INVALID, "PCISPH: prototype spacing must be positive and at least h / 64");
+        const int kmax = (int)std::ceil(h / (double)sp) + 1;
+        hipLaunchKernelGGL((k_pci_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
+        HIPCHK(hipGetLastError());
+        double o[5];
+        HIPCHK(hipMemcpyAsync(o, redPartial.p, sizeof(o), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (o[4] == 0.0) {
+            char buf[200];
+            snprintf(buf, sizeof(buf), "PCISPH: the prototype particle (lattice spacing %g, h %g) has no neighbour within h: no pressure scale delta",
+                     (double)sp, h);
+            return fail(NRS_E_INVALID, buf);
+        }
+        const double q = dt * m / rd, beta = 2.0 * q * q;
+        const double d = -1.0 / (beta * (-(o[0] * o[0] + o[1] * o[1] + o[2] * o[2]) - o[3]));
+        if (!std::isfinite(d)) return fail(NRS_E_INVALID, "PCISPH: the prototype gives no finite pressure scale delta");
+        pciDelta = (R)d;
+        pciDeltaValid = true;
+        return NRS_OK;
+    }
+    template <bool HAS_B> int pcisph_tail(int stop)
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        const GridView<R> G = grid_view();
+        const HitBuffer hb = hit_buffer();
+        // one neighbourhood scan per step (the wide lists of the IISPH chain): its hit lists drive the rest of the step
+        if (plan.walls) {
+            NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
+            NRSCHK(build_wall_list(N));
+            NRSCHK(ev_end());
+        }
+        NRSCHK(ev_begin(NRS_STAGE_DENSITY));
+        const WallList wv = wall_view();
+        if (!plan.lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
+        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hb, posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
+        NRSCHK(ev_end());
+        if (stop == NRS_STAGE_DENSITY) return NRS_OK;
+        NRSCHK(ev_begin(NRS_STAGE_P_ADVECT));
+        pciXs = 0;
+        const PciArrays<R> A0 = pci_view(0, 0);
+        if (!plan.lists)
+            hipLaunchKernelGGL((k_pci_advect_ref<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, A0, posB.as<T4>(), velB.as<T4>(), dens.as<R>(),
+                               presB.as<R>(), N);
+        else if constexpr (KSET == KS_MULLER)
+            launch_listed(k_pci_advect_lists<R, KSET, SURF, HAS_B, true>, k_pci_advect_lists<R, KSET, SURF, HAS_B>, g.x, P, G, A0, hb,
+                          posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
+        NRSCHK(ev_end());
+        if (stop == NRS_STAGE_P_ADVECT) return NRS_OK;
+        // the predictive-corrective loop: stop after the iteration l with l >= min_iters and max e <= eta, or at the cap; the max is
+        // not formed (nor read back) before min_iters
+        NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
+        const uint32_t cap = maxIters ? maxIters : 50u;
+        uint32_t l = 0;
+        double err = -1.0;
+        for (;;) {
+            const PciArrays<R> A = pci_view(pciXs, pciXs ^ 1);
+            if (!plan.lists) {
+                hipLaunchKernelGGL((k_pci_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
+                hipLaunchKernelGGL((k_pci_pforce_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
+            } else if constexpr (KSET == KS_MULLER) {
+                launch_listed(k_pci_density_lists<R, KSET, HAS_B, true>, k_pci_density_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
+                launch_listed(k_pci_pforce_lists<R, KSET, HAS_B, true>, k_pci_pforce_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
+            }
+            pciXs ^= 1;
+            ++l;
+            const bool last = l >= cap;
+            if (l >= pciMinIters || last) {
+                NRSCHK(max_of<false>(pciErr.p, N, &err));
+                if (last || err <= pciEta) break;
+            }
+        }
+        lastIters = l;
+        pciLastErr = err;
+        HIPCHK(hipMemcpyAsync(presB.p, P_l.p, sizeof(R) * N, hipMemcpyDeviceToDevice, stream)); // (the step's pressures, NRS_ARR_PRES)
+        NRSCHK(ev_end());
+        if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
+        return integrate_adv(NRS_STAGE_P_INTEGRATE);
+    }
+
     // ---- host-driven IISPH step (multi-GPU: the loop exit needs the average over ALL ranks) ---------------------------------
     int iisph_phase(int phase, double *sum, uint64_t *count) override
     {
@@ -1188,6 +1336,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // IISPH: every solver iteration consumes two cells of halo validity, the predict stages three and the pressure force one
         // (DESIGN.md §5): 2 iterations — the reference's minimum — need 8 cells
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
+        if (pcisph()) return fail(NRS_E_INVALID, "PCISPH contexts have no slab decomposition");
         if (iisph() && halo < 8) return fail(NRS_E_INVALID, "IISPH slabs need a halo of at least 8 cells (2 * iterations + 4)");
         if (halo < 2) return fail(NRS_E_INVALID, "halo must be >= 2 cells (one cell for the density of the ring + one)");
         if ((long long)hi - lo < 2ll * halo) return fail(NRS_E_INVALID, "slab narrower than two halos");
@@ -1527,6 +1676,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int get_stat(int which, double *out) override
     {
         if (which == NRS_STAT_MOVERS) { *out = lastMovers; return NRS_OK; }
+        if (which == NRS_STAT_DENSITY_ERROR || which == NRS_STAT_PCISPH_DELTA) {
+            if (!pcisph()) return fail(NRS_E_STATE, "PCISPH statistic requested from another context");
+            if (pciLastErr < 0.0) return fail(NRS_E_STATE, "no PCISPH solve yet");
+            *out = which == NRS_STAT_DENSITY_ERROR ? pciLastErr : (double)pciDelta;
+            return NRS_OK;
+        }
         if (which != NRS_STAT_HIT_OVERFLOW && which != NRS_STAT_HIT_MEAN && which != NRS_STAT_HIT_MAX && which != NRS_STAT_UNSTAGED)
             return fail(NRS_E_INVALID, "unknown statistic");
         if (!hitCounts.p || !n || midStep) return fail(NRS_E_STATE, "no shared hit lists (reference-order kernels, or no step yet)");
@@ -1555,7 +1710,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             std::swap(posA.p, posB.p);
             std::swap(velA.p, velB.p);
         }
-        if (iisph()) std::swap(presA.p, presB.p);
+        if (iisph() || pcisph()) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB)
         return NRS_OK;
     }
     int step(int nsteps, int stop) override
@@ -1563,7 +1718,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (iisphPhase) return fail(NRS_E_STATE, "a host-driven IISPH step is in progress (nrs_iisph_finish first)");
         NRSCHK(validate("nrs_step"));
         if (midStep) return fail(NRS_E_STATE, "state is mid-update after nrs_step_partial; upload particles first");
+        if (pcisph() && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
+            return fail(NRS_E_INVALID, "stage not part of a PCISPH step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
         if (n == 0) return NRS_OK;
+        if (pcisph()) NRSCHK(pcisph_prepare());
         for (int s = 0; s < nsteps; ++s) {
             fusedThisStep = false;
             splitClearedCells = false;
@@ -1571,6 +1729,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(stage_prefix(stop));
             if (stop && stop <= NRS_STAGE_REORDER) { midStep = true; break; }
             if (iisph()) { if (nb) NRSCHK(iisph_tail<true>(stop)); else NRSCHK(iisph_tail<false>(stop)); }
+            else if (pcisph()) { if (nb) NRSCHK(pcisph_tail<true>(stop)); else NRSCHK(pcisph_tail<false>(stop)); }
             else { if (nb) NRSCHK(sesph_tail<true>(stop)); else NRSCHK(sesph_tail<false>(stop)); }
             HIPCHK(hipGetLastError());
             if (stop) { midStep = true; break; }
@@ -1711,7 +1870,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         case NRS_ARR_SORTED_POS: p = sortedIsCurrent ? posA.p : posB.p; sz = v; break;
         case NRS_ARR_SORTED_VEL: p = sortedIsCurrent ? velA.p : velB.p; sz = v; break;
         case NRS_ARR_DENS: p = dens.p; sz = s; break;
-        case NRS_ARR_PRES: p = (iisph() && sortedIsCurrent) ? presA.p : presB.p; sz = s; break;
+        case NRS_ARR_PRES: p = ((iisph() || pcisph()) && sortedIsCurrent) ? presA.p : presB.p; sz = s; break;
         case NRS_ARR_FORCES: p = forces.p; sz = v; break;
         case NRS_ARR_B_HASH: p = bHashCur; sz = 4 * nb; break;
         case NRS_ARR_B_INDEX: p = bIndexCur; sz = 4 * nb; break;
@@ -1728,9 +1887,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         case NRS_ARR_DII_FLUID: p = diiF.p; sz = v; break;
         case NRS_ARR_DII_BOUNDARY: p = diiB.p; sz = v; break;
         case NRS_ARR_SUM_DIJ: p = sumDij.p; sz = v; break;
+        case NRS_ARR_POS_PRED: p = pci_xs_current(); sz = v; break;
         default: return fail(NRS_E_INVALID, "unknown array id");
         }
-        if (which >= NRS_ARR_DENS_ADV && !iisph()) return fail(NRS_E_STATE, "IISPH array requested from a SESPH context");
+        if (which == NRS_ARR_POS_PRED && !pcisph()) return fail(NRS_E_STATE, "PCISPH array requested from another context");
+        const bool pciArray = which == NRS_ARR_VEL_ADV || which == NRS_ARR_FORCES_ADV || which == NRS_ARR_FORCES_P ||
+                              which == NRS_ARR_DENS_CORR || which == NRS_ARR_P_L || which == NRS_ARR_POS_PRED;
+        if (pcisph() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PCISPH context");
+        if (which >= NRS_ARR_DENS_ADV && sesph()) return fail(NRS_E_STATE, "IISPH array requested from a SESPH context");
         *dptr = p;
         *bytes = p ? sz : 0;
         return NRS_OK;

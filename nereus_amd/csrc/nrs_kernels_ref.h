@@ -842,6 +842,216 @@ __global__ __launch_bounds__(BLOCK) void k_iisph_integrate(Params<R> P, typename
     }
 }
 
+// =========================================== PCISPH ===================================================
+// Predictive-corrective incompressible SPH (Solenthaler & Pajarola 2009).  The reference leaves its PCISPH solve an empty stub
+// (sph_cuda.cu:944-952), so DESIGN.md "PCISPH" defines what is computed here.  Every neighbour sum of the loop runs over the pairs
+// with length(x_i - x_j) < h at the step's START positions (the neighbourhood of the step's density scan) AND length(x*_i - x*_j) < h
+// at the predicted ones; boundary particles are static (x*_b = x_b); the fluid sums skip j == i by sorted slot.  Sums are formed in
+// the order of density_of: cells z, y, x of the start cell, in each a fluid partial (j ascending) and then a boundary partial, each
+// added to the running total — so the list-driven kernels (nrs_kernels_pcisph.h) can be bit-identical to the walks below.
+template <typename R> struct PciArrays {
+    typedef typename Vec4T<R>::type T4;
+    T4 *velAdv, *forcesAdv, *forcesP; // vel_adv, the non-pressure force, the pressure force Fp
+    R *densPred, *pres, *err;         // rho*, p, e = max(rho* - rho0, 0) / rho0 (input of the exit test's max)
+    const T4 *xsIn;                   // predicted positions the launch reads (its own and its neighbours')
+    T4 *xsOut;                        // ... and where the pressure-force launch writes the next ones (double-buffered)
+    R delta;                          // the pressure scale: p += delta (rho* - rho0)
+};
+// (a scalar times a vector in SReal: the vector operators of nrs_math.h take float scalars, SURVEY Q11, which the PCISPH loop's own
+// coefficients need not inherit)
+template <typename R> NRS_DEV V3<R> pci_scale(R s, V3<R> v) { return mk3<R>(s * v.x, s * v.y, s * v.z); }
+// the coefficients of the pressure force: fluid -m^2 (p_i + p_j) / rho0^2, boundary -m psi_b p_i / rho0^2 (psi_b = rho0 V_b)
+template <typename R> NRS_DEV R pci_fluid_coef(const Params<R> &P, R p, R pj)
+{
+    const R pm = P.particleMass, rd = P.restDensity;
+    return -(pm * pm) * ((p + pj) / (rd * rd));
+}
+template <typename R> NRS_DEV R pci_boundary_coef(const Params<R> &P, R psi, R p)
+{
+    const R pm = P.particleMass, rd = P.restDensity;
+    return -(pm * psi) * (p / (rd * rd));
+}
+// x* = x + dt (vel_adv + dt Fp / m): the expression of k_iisph_integrate, so that the positions the last iteration predicts are the
+// positions the step integrates to
+template <typename R> NRS_DEV V3<R> pci_predict(const Params<R> &P, V3<R> pos1, V3<R> velAdv1, V3<R> fp)
+{
+    const R dt = P.timestep, pm = P.particleMass;
+    const V3<R> v = velAdv1 + (dt * fp / pm);
+    return pos1 + (dt * v);
+}
+// rho* -> p (clamped at 0) and e_i; NaN densities give e = inf (the loop then runs to its cap and reports it)
+template <typename R> NRS_DEV void pci_pressure_update(const Params<R> &P, const PciArrays<R> &A, uint32_t i, R rs)
+{
+    const R rd = P.restDensity;
+    const R dr = rs - rd;
+    const R pn = A.pres[i] + A.delta * dr;
+    A.densPred[i] = rs;
+    A.pres[i] = pn > (R)0 ? pn : (R)0;
+    A.err[i] = dr <= (R)0 ? (R)0 : (dr == dr ? dr / rd : (R)INFINITY);
+}
+// vel_adv = v + dt force_adv / m with the non-pressure forces of the IISPH displacement stage (k_displacement_ref's force half,
+// which is also what the reference's never-launched pciComputePosVelAdv computes)
+template <typename R> NRS_DEV V3<R> pci_advect_force(const Params<R> &P, const ForceAcc<R> &A)
+{
+    const R pm = P.particleMass;
+    V3<R> fvisc = 2.0 * A.fvisc;
+    fvisc = (pm * P.viscosity) * fvisc;
+    const V3<R> fgrav = pm * mk3<R>(P.gravity[0], P.gravity[1], P.gravity[2]);
+    return fvisc + A.fsurf + A.fbound + fgrav;
+}
+template <typename R> NRS_DEV void pci_advect_store(const Params<R> &P, const PciArrays<R> &A, uint32_t i, V3<R> pos1, V3<R> vel1,
+                                                    V3<R> force_adv)
+{
+    const R pm = P.particleMass, dt = P.timestep;
+    const V3<R> vel_adv = vel1 + dt * (force_adv / pm);
+    const V3<R> zero = mk3<R>(0, 0, 0);
+    A.forcesAdv[i] = mk4<R>(force_adv, (R)0.0);
+    A.velAdv[i] = mk4<R>(vel_adv, (R)0.0);
+    A.forcesP[i] = mk4<R>(zero, (R)0.0);
+    A.pres[i] = (R)0.0;
+    A.xsOut[i] = mk4<R>(pci_predict<R>(P, pos1, vel_adv, zero), (R)1.0);
+}
+
+// predicted density of particle i (iteration launch A), reference order
+template <typename R, int KSET, bool HAS_B>
+NRS_DEV R pci_density_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                           const typename Vec4T<R>::type *__restrict__ xs, uint32_t i, V3<R> pos1, V3<R> xs1)
+{
+    const R ir = P.interactionRadius, kp = P.kpoly, pm = P.particleMass, rd = P.restDensity;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    R dens = (R)0.0;
+    dens += pm * W_dens<R, KSET>(mk3<R>(0, 0, 0), ir, kp);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                R c = (R)0.0;
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
+                        const V3<R> d = xs1 - xyz<R>(xs[j]);
+                        if (length(d) < ir) c += pm * W_dens<R, KSET>(d, ir, kp);
+                    }
+                }
+                dens += c;
+                if (HAS_B) {
+                    R cb = (R)0.0;
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            if (!(length(pos1 - xyz<R>(b)) < ir)) continue;
+                            const V3<R> d = xs1 - xyz<R>(b);
+                            if (length(d) < ir) cb += (rd * b.w) * W_dens<R, KSET>(d, ir, kp);
+                        }
+                    }
+                    dens += cb;
+                }
+            }
+    return dens;
+}
+// pressure force on particle i (iteration launch B), reference order
+template <typename R, int KSET, bool HAS_B>
+NRS_DEV V3<R> pci_pforce_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                              const typename Vec4T<R>::type *__restrict__ xs, const R *__restrict__ pres, uint32_t i, V3<R> pos1,
+                              V3<R> xs1, R p)
+{
+    const R ir = P.interactionRadius, kpg = P.kpoly_grad, rd = P.restDensity;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    V3<R> fp = mk3<R>(0, 0, 0);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                V3<R> c = mk3<R>(0, 0, 0);
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
+                        const V3<R> d = xs1 - xyz<R>(xs[j]);
+                        if (length(d) < ir) c = c + pci_scale<R>(pci_fluid_coef<R>(P, p, pres[j]), W_grad<R, KSET>(d, ir, kpg));
+                    }
+                }
+                fp = fp + c;
+                if (HAS_B) {
+                    V3<R> cb = mk3<R>(0, 0, 0);
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            if (!(length(pos1 - xyz<R>(b)) < ir)) continue;
+                            const V3<R> d = xs1 - xyz<R>(b);
+                            if (length(d) < ir) cb = cb + pci_scale<R>(pci_boundary_coef<R>(P, rd * b.w, p), W_grad<R, KSET>(d, ir, kpg));
+                        }
+                    }
+                    fp = fp + cb;
+                }
+            }
+    return fp;
+}
+
+// PCISPH advection: non-pressure forces, vel_adv, x*0 = x + dt vel_adv, p = 0, Fp = 0
+template <typename R, int KSET, bool SURF, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_pci_advect_ref(Params<R> P, GridView<R> G, PciArrays<R> A,
+                                                          const typename Vec4T<R>::type *__restrict__ sPos,
+                                                          const typename Vec4T<R>::type *__restrict__ sVel,
+                                                          const R *__restrict__ sDens, const R *__restrict__ sPres, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3<R> pos1 = xyz<R>(sPos[i]), vel1 = xyz<R>(sVel[i]);
+    const ForceAcc<R> F = gather_forces<R, KSET, SURF, HAS_B>(P, G, i, pos1, vel1, sDens[i], (R)0.0, sPos, sVel, sDens, sPres);
+    pci_advect_store<R>(P, A, i, pos1, vel1, pci_advect_force<R>(P, F));
+}
+// iteration launch A: predicted density, pressure update, density error
+template <typename R, int KSET, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_pci_density_ref(Params<R> P, GridView<R> G, PciArrays<R> A,
+                                                           const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const R rs = pci_density_walk<R, KSET, HAS_B>(P, G, sPos, A.xsIn, i, xyz<R>(sPos[i]), xyz<R>(A.xsIn[i]));
+    pci_pressure_update<R>(P, A, i, rs);
+}
+// iteration launch B: pressure force and the next predicted positions
+template <typename R, int KSET, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_pci_pforce_ref(Params<R> P, GridView<R> G, PciArrays<R> A,
+                                                          const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3<R> pos1 = xyz<R>(sPos[i]);
+    const V3<R> fp = pci_pforce_walk<R, KSET, HAS_B>(P, G, sPos, A.xsIn, A.pres, i, pos1, xyz<R>(A.xsIn[i]), A.pres[i]);
+    A.forcesP[i] = mk4<R>(fp, (R)0.0);
+    A.xsOut[i] = mk4<R>(pci_predict<R>(P, pos1, xyz<R>(A.velAdv[i]), fp), (R)1.0);
+}
+// the prototype sums of delta: out[0..2] = sum_k g_k, out[3] = sum_k g_k . g_k, out[4] = neighbours, over the lattice points k s,
+// k in Z^3, 0 < |k s| < h, with g_k = W_grad(-k s) (in double, k_z, k_y, k_x ascending).  One thread.
+template <typename R, int KSET>
+__global__ __launch_bounds__(64) void k_pci_prototype(Params<R> P, R spacing, int kmax, double *__restrict__ out)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const R ir = P.interactionRadius, kpg = P.kpoly_grad;
+    double sx = 0.0, sy = 0.0, sz = 0.0, gg = 0.0, cnt = 0.0;
+    for (int z = -kmax; z <= kmax; ++z)
+        for (int y = -kmax; y <= kmax; ++y)
+            for (int x = -kmax; x <= kmax; ++x) {
+                if (x == 0 && y == 0 && z == 0) continue;
+                const V3<R> d = mk3<R>(-(R)x * spacing, -(R)y * spacing, -(R)z * spacing);
+                if (!(length(d) < ir)) continue;
+                const V3<R> g = W_grad<R, KSET>(d, ir, kpg);
+                sx += (double)g.x; sy += (double)g.y; sz += (double)g.z;
+                gg += (double)g.x * (double)g.x + (double)g.y * (double)g.y + (double)g.z * (double)g.z;
+                cnt += 1.0;
+            }
+    out[0] = sx; out[1] = sy; out[2] = sz; out[3] = gg; out[4] = cnt;
+}
+
 // deterministic two-pass sum of an SReal array in double (replaces thrust::reduce, sph_cuda.cu:816-819)
 template <typename R>
 __global__ __launch_bounds__(BLOCK) void k_sum_partial(const R *__restrict__ a, double *__restrict__ partial, uint32_t n,

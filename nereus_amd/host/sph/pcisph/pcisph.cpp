@@ -4,21 +4,53 @@
 // (pcisph_pressureSolve, sph_cuda.cu:944-952) and copies the SORTED positions / velocities back to the host arrays
 // (:201-202): nothing moves, but the host arrays come back permuted into hash order.  Mirrored here exactly;
 // densities and pressures of the step are additionally readable on the host (getHostDensity / getHostPressure).
+// setPressureSolve(true) replaces the stub with the library's PCISPH step (a context of kind NRS_SOLVER_PCISPH).
 #include "pcisph.h"
 
 #include "nereus_hip.h"
 
+#include <cstdio>
+#include <cstdlib>
+
 NEREUS_NAMESPACE_BEGIN
 
-PCISPH::PCISPH() : SPH() {}
-PCISPH::PCISPH(SphSimParams params) : SPH(params) {}
+PCISPH::PCISPH() : SPH(), m_pressureSolve(false), m_eta(0.01f) {}
+PCISPH::PCISPH(SphSimParams params) : SPH(params), m_pressureSolve(false), m_eta(0.01f) {}
 PCISPH::~PCISPH() {}
 void PCISPH::_initialize() { SPH::_initialize(); }
 void PCISPH::_finalize() { SPH::_finalize(); }
 
+int PCISPH::solverKind() const { return m_pressureSolve ? NRS_SOLVER_PCISPH : NRS_SOLVER_SESPH; }
+
+void PCISPH::setPressureSolve(bool on, SReal eta)
+{
+    if (m_ctx) { // (the context's kind is fixed when it is created)
+        std::fprintf(stderr, "Nereus: PCISPH::setPressureSolve must be called before the first update() / updateGpuBoundaries()\n");
+        std::exit(EXIT_FAILURE);
+    }
+    m_pressureSolve = on;
+    m_eta = eta;
+}
+
+void PCISPH::configureContext()
+{
+    if (m_pressureSolve && nrs_pcisph_configure(m_ctx, (double)m_eta, 3, 0.0, 0.0) != NRS_OK) fatal("nrs_pcisph_configure");
+}
+
+SUint PCISPH::getLastIterations()
+{
+    uint32_t it = 0;
+    if (m_pressureSolve && m_ctx && nrs_last_iterations(m_ctx, &it) != NRS_OK) fatal("nrs_last_iterations");
+    return (SUint)it;
+}
+
 void PCISPH::update()
 {
     if (m_numParticles == 0) return;
+    if (m_pressureSolve) {
+        SPH::update(); // upload if dirty → step → lazy download (pressures included)
+        return;
+    }
     ensureContext();
     m_hostDirty = true; // the reference uploads the host arrays every step (pcisph.cpp:164-165)
     pushHostToDevice();

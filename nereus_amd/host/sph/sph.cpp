@@ -207,6 +207,7 @@ void SPH::ensureContext()
     cfg.capacity = std::max<SUint>(m_hostCapacity, m_numParticles);
     if (nrs_create(&cfg, &m_params, &m_ctx) != NRS_OK) fatal("nrs_create");
     m_ctxCapacity = (SUint)cfg.capacity;
+    configureContext();
     if (m_boundariesPending && m_bi && m_vbi && m_num_boundaries) {
         if (nrs_set_boundaries(m_ctx, m_bi, m_vbi, m_num_boundaries, 0) != NRS_OK) fatal("nrs_set_boundaries");
         m_boundariesPending = false;
@@ -233,7 +234,7 @@ void SPH::pushHostToDevice()
 void SPH::pullDeviceToHost() const
 {
     if (!m_deviceNewer || !m_ctx) return;
-    const bool wantPressure = solverKind() == NRS_SOLVER_IISPH;
+    const bool wantPressure = solverKind() == NRS_SOLVER_IISPH || solverKind() == NRS_SOLVER_PCISPH;
     if (nrs_download(m_ctx, m_pos, m_vel, wantPressure ? m_pressure : nullptr) != NRS_OK) fatal("nrs_download");
     m_deviceNewer = false;
 }

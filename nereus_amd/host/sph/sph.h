@@ -112,6 +112,7 @@ public:
 
 protected:
     virtual int solverKind() const; // NRS_SOLVER_*
+    virtual void configureContext() {} // solver settings of a freshly created device context (ensureContext)
     void ensureContext();
     void releaseContext();
     void growHost(SUint capacity);

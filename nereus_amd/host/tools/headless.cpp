@@ -2,7 +2,8 @@
 // the viewer) and dumps the state for the parity tests.
 //
 //   headless params  <sesph|iisph> <out.bin>                    constructor-default SphSimParams bytes
-//   headless run     <sesph|iisph> <in.bin> <steps> <out.bin>   particles/boundaries from a file
+//   headless run     <sesph|iisph> <in.bin> <steps> <out.bin>   particles/boundaries from a file (also pcisph: the reference's
+//                                                               stub, and pcisph-solve: PCISPH::setPressureSolve(true))
 //   headless resume  <sesph|iisph> <in.bin> <steps_a> <steps_b> <ckpt> <out.bin>   run steps_a, saveState, then a NEW
 //                                                               solver loadState()s and runs steps_b (boundaries re-set)
 //   headless cfl     sesph <in.bin> <steps> <out.bin>           run with setAdaptiveTimestep(true)
@@ -65,8 +66,9 @@ int main(int argc, char **argv)
         std::fclose(o);
         return 0;
     }
-    const bool iisph = kind == "iisph", pcisph = kind == "pcisph";
+    const bool iisph = kind == "iisph", pcisphSolve = kind == "pcisph-solve", pcisph = kind == "pcisph" || pcisphSolve;
     Nereus::SPH *sim = iisph ? (Nereus::SPH *)new Nereus::IISPH() : (pcisph ? (Nereus::SPH *)new Nereus::PCISPH() : new Nereus::SPH());
+    if (pcisphSolve) static_cast<Nereus::PCISPH *>(sim)->setPressureSolve(true);
     sim->_initialize();
     std::vector<SVec4> bi;
     std::vector<SReal> vbi;
@@ -108,6 +110,7 @@ int main(int argc, char **argv)
             for (int s = 0; s < steps; ++s) sim->update();
         }
         if (iisph) iters = static_cast<Nereus::IISPH *>(sim)->getLastIterations();
+        if (pcisphSolve) iters = static_cast<Nereus::PCISPH *>(sim)->getLastIterations();
         dump(argv[5], sim, iters, bi, vbi);
     } else if (mode == "resume" || mode == "cfl") {
         FILE *f = std::fopen(argv[3], "rb");
