@@ -61,8 +61,10 @@ typedef struct nrs_params_f64 {
 typedef struct nrs_ctx nrs_ctx;
 
 /* Nereus::SPH (sph/sph.h:23) / Nereus::IISPH (iisph.h:8) / predictive-corrective PCISPH (Solenthaler & Pajarola 2009; the
- * reference's Nereus::PCISPH stops after the density, its pressure solve is an empty stub: DESIGN.md "PCISPH" defines this one) */
-enum { NRS_SOLVER_SESPH = 0, NRS_SOLVER_IISPH = 1, NRS_SOLVER_PCISPH = 2 };
+ * reference's Nereus::PCISPH stops after the density, its pressure solve is an empty stub: DESIGN.md "PCISPH" defines this one) /
+ * position-based fluids (Macklin & Mueller 2013; DESIGN.md "PBF").  PBF came after nrs_version() 0.3 without a version change: a
+ * library supports it when nrs_create accepts NRS_SOLVER_PBF. */
+enum { NRS_SOLVER_SESPH = 0, NRS_SOLVER_IISPH = 1, NRS_SOLVER_PCISPH = 2, NRS_SOLVER_PBF = 3 };
 enum { NRS_KERNELS_MONAGHAN = 0, NRS_KERNELS_MULLER = 1 }; /* KERNEL_SET, common/common.h:14-15 */
 
 /* nrs_config.flags */
@@ -128,7 +130,8 @@ typedef struct nrs_config {
 
 /* Pipeline stages, for nrs_step_partial / nrs_stage_ms.  Order is the order of SPH::update()
  * (sph/sph.cpp:233-284) and IISPH::update() (sph/iisph/iisph.cpp:172-216).  A PCISPH step is HASH, SORT, REORDER, DENSITY
- * (density only, no Tait pressure), then the P_* stages; nrs_step_partial on a PCISPH context accepts those and refuses the others. */
+ * (density only, no Tait pressure), then the P_* stages; nrs_step_partial on a PCISPH context accepts those and refuses the others.
+ * A PBF step has the same stages (and the same refusals). */
 enum {
     NRS_STAGE_HASH = 1,      /* calcHash                     sph_cuda.cu:230 */
     NRS_STAGE_SORT = 2,      /* sortParticles                sph_cuda.cu:58 */
@@ -136,9 +139,9 @@ enum {
     NRS_STAGE_DENSITY = 4,   /* computeDensityPressure kernel sph_kernel_impl.cuh:365 */
     NRS_STAGE_FORCES = 5,    /* computeForces kernel          sph_kernel_impl.cuh:609 */
     NRS_STAGE_INTEGRATE = 6, /* integrateSystem              sph_cuda.cu:211 */
-    NRS_STAGE_P_ADVECT = 7,    /* PCISPH: non-pressure forces, vel_adv, first predicted positions, p = 0 */
-    NRS_STAGE_P_SOLVE = 8,     /* PCISPH: the predictive-corrective loop (two launches per iteration) */
-    NRS_STAGE_P_INTEGRATE = 9, /* PCISPH: v = vel_adv + dt Fp / m, x += dt v (iisph_integrate) */
+    NRS_STAGE_P_ADVECT = 7,    /* PCISPH, PBF: non-pressure forces, vel_adv, first predicted positions, p (lambda) = 0 */
+    NRS_STAGE_P_SOLVE = 8,     /* PCISPH: the predictive-corrective loop; PBF: the Jacobi projection (two launches per iteration) */
+    NRS_STAGE_P_INTEGRATE = 9, /* PCISPH: v = vel_adv + dt Fp / m, x += dt v (iisph_integrate); PBF: v = (x* - x) / dt (+ XSPH), x = x* */
     NRS_STAGE_I_DENSITY = 10,      /* computeIisphDensity        sph_kernel_impl.cuh:770 */
     NRS_STAGE_I_DISPLACEMENT = 11, /* computeDisplacementFactor  :851 */
     NRS_STAGE_I_ADVECTION = 12,    /* computeAdvectionFactor     :1114 */
@@ -180,7 +183,10 @@ enum {
     NRS_ARR_SUM_DIJ = 29,
     NRS_ARR_POS_PRED = 30,  /* PCISPH: SVec4[N] predicted positions x* of the last iteration.  On a PCISPH context NRS_ARR_VEL_ADV,
                                _FORCES_ADV, _FORCES_P (the pressure force), _DENS_CORR (the predicted density) and _P_L (the pressure p)
-                               hold the PCISPH quantities; NRS_ARR_PRES and nrs_download(pres) the step's final pressures */
+                               hold the PCISPH quantities; NRS_ARR_PRES and nrs_download(pres) the step's final pressures.
+                               On a PBF context the same arrays hold the PBF quantities: _POS_PRED x*, _VEL_ADV, _FORCES_ADV,
+                               _DENS_CORR rho*, _P_L lambda and _FORCES_P the correction dx of the last iteration; NRS_ARR_PRES
+                               and nrs_download(pres) give lambda */
 };
 
 const char *nrs_last_error(void);
@@ -253,10 +259,10 @@ int nrs_get_array(nrs_ctx *ctx, int which, void *dst, uint64_t dst_bytes, uint64
  * i.e. read it after each step).  For zero-copy consumers (renderer VBO upload, halo packing). */
 int nrs_device_ptr(nrs_ctx *ctx, int which, void **dptr, uint64_t *bytes);
 
-/* IISPH / PCISPH: solver iterations of the last step (the `l` of sph_cuda.cu:736). */
+/* IISPH / PCISPH / PBF: solver iterations of the last step (the `l` of sph_cuda.cu:736). */
 int nrs_last_iterations(nrs_ctx *ctx, uint32_t *iters);
-/* Cap on IISPH / PCISPH solver iterations per step.  0 = none for IISPH, as the reference; 0 = 50 for PCISPH (a predictive-corrective
- * loop need not end). */
+/* Cap on IISPH / PCISPH / PBF solver iterations per step.  0 = none for IISPH, as the reference; 0 = 50 for PCISPH and PBF (their
+ * loops need not end; a PBF step in fixed-count mode ignores the cap). */
 int nrs_set_max_iterations(nrs_ctx *ctx, uint32_t max_iters);
 
 /* PCISPH solver settings (NRS_E_STATE on any other context).  The loop stops after the iteration l with l >= min_iters and
@@ -265,6 +271,15 @@ int nrs_set_max_iterations(nrs_ctx *ctx, uint32_t max_iters);
  * evaluated on the device once per parameter change; delta > 0 is used as given.  Defaults: 0.01, 3, 0, 0.
  * NRS_E_INVALID for max_density_error <= 0, min_iters == 0 or a negative spacing / delta. */
 int nrs_pcisph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double prototype_spacing, double delta);
+
+/* PBF solver settings (NRS_E_STATE on any other context).  max_density_error > 0: the loop stops after the iteration l with
+ * l >= min_iters and max_i max(rho*_i - rho0, 0) / rho0 <= max_density_error, or at the iteration cap (nrs_set_max_iterations,
+ * 0 = 50).  max_density_error = 0: exactly min_iters iterations and nothing read back during the step (fixed-count mode).
+ * relaxation: the constraint-force mixing term is eps = relaxation * D_proto, D_proto the constraint's gradient norm for a prototype
+ * particle on the cubic lattice of spacing cbrt(m / rho0), evaluated on the device once per parameter change.  xsph: the XSPH
+ * velocity smoothing factor c (0 = off).  Defaults: 0.01, 2, 0.01, 0.  NRS_E_INVALID for max_density_error < 0, min_iters == 0,
+ * relaxation <= 0 or xsph outside [0, 1]. */
+int nrs_pbf_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double relaxation, double xsph);
 
 /* Per-stage device time, measured with HIP events recorded on the context's stream around the stage's
  * launches.  stage_mask: bit s set = time NRS_STAGE_s (0 = off, 0xffffffff = every stage).  nrs_set_profiling also
@@ -287,7 +302,7 @@ int nrs_stage_ms(nrs_ctx *ctx, int stage, float *ms, uint32_t *launches);
  *   [u32 nMigrants, u32 nHalo, u32 0, u32 0 | vec4 pos[capacity] | vec4 vel[capacity]].
  * Pass NULL for the neighbour that does not exist (ends of the chain).  IISPH contexts: halo_cells >= 8 and the step is driven
  * through nrs_iisph_predict / _iterate / _finish (below). */
-int nrs_slab_configure(nrs_ctx *ctx, int32_t cell_lo, int32_t cell_hi, int32_t halo_cells); /* NRS_E_INVALID on a PCISPH context */
+int nrs_slab_configure(nrs_ctx *ctx, int32_t cell_lo, int32_t cell_hi, int32_t halo_cells); /* NRS_E_INVALID on a PCISPH or PBF context */
 /* counts (optional) receives {stay, migrate-left, halo-left, migrate-right, halo-right, ghost}.
  * With counts == NULL nrs_slab_pack does not wait for the device: the two messages are complete in stream order when it returns (the
  * caller enqueues its sends on the same stream right behind it), and the stream populations are read back together with the headers of
@@ -334,12 +349,14 @@ int nrs_resort_stats(nrs_ctx *ctx, uint64_t *steps, uint64_t *fallbacks);
  *   NRS_STAT_HIT_MEAN/_MAX  neighbours (fluid + boundary hits) per particle kept in the hit lists
  *   NRS_STAT_UNSTAGED       particles whose wavefront could not stage its neighbour rows in LDS (grid-edge cells, or
  *                           hulls longer than the pool) and scanned them from global memory instead
- *   NRS_STAT_DENSITY_ERROR  PCISPH: max_i max(rho*_i - rho0, 0) / rho0 after the last iteration of the last step
+ *   NRS_STAT_DENSITY_ERROR  PCISPH, PBF: max_i max(rho*_i - rho0, 0) / rho0 after the last iteration of the last step (a PBF step
+ *                           in fixed-count mode forms it when it is asked for)
  *   NRS_STAT_PCISPH_DELTA   PCISPH: the pressure scale delta the last step used
- * The HIT_* / UNSTAGED values need the shared hit lists of the production kernels (NRS_E_STATE otherwise); the PCISPH values a
- * PCISPH context that has completed a solve. */
+ *   NRS_STAT_PBF_EPSILON    PBF: the constraint-force mixing term eps the last step used
+ * The HIT_* / UNSTAGED values need the shared hit lists of the production kernels (NRS_E_STATE otherwise); the PCISPH / PBF values a
+ * context of that kind that has completed a solve. */
 enum { NRS_STAT_MOVERS = 0, NRS_STAT_HIT_OVERFLOW = 1, NRS_STAT_HIT_MEAN = 2, NRS_STAT_HIT_MAX = 3, NRS_STAT_UNSTAGED = 4,
-       NRS_STAT_DENSITY_ERROR = 5, NRS_STAT_PCISPH_DELTA = 6 };
+       NRS_STAT_DENSITY_ERROR = 5, NRS_STAT_PCISPH_DELTA = 6, NRS_STAT_PBF_EPSILON = 7 };
 int nrs_get_stat(nrs_ctx *ctx, int which, double *out);
 
 /* Akinci boundary volumes on the device (no context needed): vbi[i] = 1 / sum_k W_poly6(|x_i - x_k|, h) over the boundary

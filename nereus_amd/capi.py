@@ -14,7 +14,7 @@ from .params import params_dtype
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NEREUS_HIP_LIB") or os.path.join(_HERE, "libnereus_hip.so")  # (override: kernel A/B builds in tools/)
 
-SESPH, IISPH, PCISPH = 0, 1, 2
+SESPH, IISPH, PCISPH, PBF = 0, 1, 2, 3
 MONAGHAN, MULLER = 0, 1
 FLAG_REFERENCE_ORDER = 1
 FLAG_NO_FUSION = 4
@@ -26,7 +26,7 @@ FLAG_NO_WALL_WORKGROUPS = 128
 FLAG_STAGED_SCAN = 256
 E_NOTREADY = -6
 STAT_MOVERS, STAT_HIT_OVERFLOW, STAT_HIT_MEAN, STAT_HIT_MAX, STAT_UNSTAGED = 0, 1, 2, 3, 4
-STAT_DENSITY_ERROR, STAT_PCISPH_DELTA = 5, 6
+STAT_DENSITY_ERROR, STAT_PCISPH_DELTA, STAT_PBF_EPSILON = 5, 6, 7
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
@@ -57,7 +57,7 @@ EXPORTS = [
     "nrs_max_velocity", "nrs_slab_configure", "nrs_slab_pack", "nrs_slab_unpack", "nrs_num_owned",
     "nrs_slab_message_bytes", "nrs_slab_histogram", "nrs_resort_stats", "nrs_snapshot_begin", "nrs_snapshot_wait",
     "nrs_get_stat", "nrs_boundary_volumes", "nrs_eval_smoothing", "nrs_iisph_predict", "nrs_iisph_iterate", "nrs_iisph_finish",
-    "nrs_slab_last_counts", "nrs_pcisph_configure",
+    "nrs_slab_last_counts", "nrs_pcisph_configure", "nrs_pbf_configure",
 ]
 
 
@@ -109,6 +109,7 @@ def load_library(path=None):
     lib.nrs_last_iterations.argtypes = [vp, C.POINTER(C.c_uint32)]
     lib.nrs_set_max_iterations.argtypes = [vp, C.c_uint32]
     lib.nrs_pcisph_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_double]
+    lib.nrs_pbf_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_double]
     lib.nrs_set_profiling.argtypes = [vp, C.c_uint32]
     lib.nrs_stage_ms.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     lib.nrs_max_density.argtypes = [vp, C.POINTER(C.c_double)]
@@ -165,7 +166,7 @@ def eval_smoothing(which, r, s, h, c0, c1, double=False):
 
 
 class Solver:
-    """Thin object wrapper over an nrs_ctx (device-resident SESPH / IISPH / PCISPH solver)."""
+    """Thin object wrapper over an nrs_ctx (device-resident SESPH / IISPH / PCISPH / PBF solver)."""
 
     def __init__(self, params, capacity, solver=SESPH, double=False, kernel_set=MULLER, surface_tension=True,
                  reference_order=False, device=-1, stream=None, flags=0):
@@ -282,6 +283,11 @@ class Solver:
         """PCISPH loop settings (nrs_pcisph_configure): exit error, minimum iterations, prototype lattice spacing (0 = cbrt(m / rho0)),
         pressure scale delta (0 = from the prototype)"""
         self._chk(self.lib.nrs_pcisph_configure(self.h, float(max_density_error), int(min_iters), float(prototype_spacing), float(delta)))
+
+    def pbf_configure(self, max_density_error=0.01, min_iters=2, relaxation=0.01, xsph=0.0):
+        """PBF loop settings (nrs_pbf_configure): exit error (0 = exactly min_iters iterations, nothing read back), minimum iterations,
+        eps = relaxation * D_proto, XSPH factor (0 = off)"""
+        self._chk(self.lib.nrs_pbf_configure(self.h, float(max_density_error), int(min_iters), float(relaxation), float(xsph)))
 
     def set_profiling(self, stages=True):
         """stages: True = all, False = off, or an iterable of stage ids."""

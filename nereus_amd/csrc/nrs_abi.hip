@@ -143,7 +143,8 @@ int nrs_create(const nrs_config *cfg, const void *params, nrs_ctx **out)
     if (cfg->struct_size != sizeof(nrs_config)) return fail(NRS_E_INVALID, "nrs_config.struct_size mismatch");
     if (cfg->precision != 32 && cfg->precision != 64) return fail(NRS_E_INVALID, "precision must be 32 or 64");
     if (cfg->kernel_set != NRS_KERNELS_MULLER && cfg->kernel_set != NRS_KERNELS_MONAGHAN) return fail(NRS_E_INVALID, "bad kernel_set");
-    if (cfg->solver != NRS_SOLVER_SESPH && cfg->solver != NRS_SOLVER_IISPH && cfg->solver != NRS_SOLVER_PCISPH) return fail(NRS_E_INVALID, "bad solver");
+    if (cfg->solver != NRS_SOLVER_SESPH && cfg->solver != NRS_SOLVER_IISPH && cfg->solver != NRS_SOLVER_PCISPH && cfg->solver != NRS_SOLVER_PBF)
+        return fail(NRS_E_INVALID, "bad solver");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(NRS_E_NODEVICE, "no HIP device available: libnereus_hip has no CPU fallback");
@@ -294,6 +295,11 @@ int nrs_pcisph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_it
 {
     CTX_GUARD(ctx);
     return ctx->impl->pcisph_configure(max_density_error, min_iters, prototype_spacing, delta);
+}
+int nrs_pbf_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double relaxation, double xsph)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->pbf_configure(max_density_error, min_iters, relaxation, xsph);
 }
 int nrs_set_profiling(nrs_ctx *ctx, uint32_t stage_mask)
 {

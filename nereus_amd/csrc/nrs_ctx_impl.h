@@ -16,6 +16,7 @@
 #include <type_traits>
 #include "nrs_kernels_iisph.h"
 #include "nrs_kernels_pcisph.h"
+#include "nrs_kernels_pbf.h"
 #include "nrs_kernels_slab.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
@@ -127,6 +128,13 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool pciDeltaValid = false; // pciDelta belongs to the current parameters and settings
     R pciDelta = (R)0;
     double pciLastErr = -1.0; // max e_i after the last iteration of the last solve (< 0: no solve yet)
+    // PBF (nrs_kernels_pbf.h) shares all of these: posPred / posPred2, pciErr, velAdv, forcesAdv, densCorr (rho*), P_l (lambda), forcesP
+    // (the last correction dx) and pciLastErr
+    double pbfEta = 0.01, pbfRelax = 0.01, pbfXsph = 0.0;
+    uint32_t pbfMinIters = 2;
+    bool pbfEpsValid = false; // pbfEps belongs to the current parameters and settings
+    R pbfEps = (R)0;
+    uint32_t pbfErrPending = 0; // fixed-count solve: max e over this many particles is formed on request (get_stat), not in the step
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
     HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
@@ -261,6 +269,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool iisph() const { return cfg.solver == NRS_SOLVER_IISPH; }
     bool pcisph() const { return cfg.solver == NRS_SOLVER_PCISPH; }
     bool sesph() const { return cfg.solver == NRS_SOLVER_SESPH; }
+    bool pbf() const { return cfg.solver == NRS_SOLVER_PBF; }
     bool pow2_grid() const { return is_pow2(P.gridSize[0]) && is_pow2(P.gridSize[1]) && is_pow2(P.gridSize[2]); }
 
     // ---- which kernels a step launches ------------------------------------------------------------------------------------
@@ -400,7 +409,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             DevBuf *z[] = {&densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP, &diiF, &diiB, &sumDij};
             for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
         }
-        if (pcisph()) { // (no dii / a_ii / sum d_ij p_j, no inverse slot table: the loop skips j == i by sorted slot)
+        if (pcisph() || pbf()) { // (no dii / a_ii / sum d_ij p_j, no inverse slot table: the loop skips j == i by sorted slot)
             NRSCHK(velAdv.alloc(v)); NRSCHK(forcesAdv.alloc(v)); NRSCHK(forcesP.alloc(v));
             NRSCHK(densCorr.alloc(s)); NRSCHK(P_l.alloc(s));
             NRSCHK(posPred.alloc(v)); NRSCHK(posPred2.alloc(v)); NRSCHK(pciErr.alloc(s));
@@ -489,6 +498,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (q.timestep != PU.timestep || q.particleMass != PU.particleMass || q.restDensity != PU.restDensity ||
             q.interactionRadius != PU.interactionRadius || q.kpoly_grad != PU.kpoly_grad)
             pciDeltaValid = false;
+        // ... and eps (pbf_prepare) on these
+        if (q.particleMass != PU.particleMass || q.restDensity != PU.restDensity || q.interactionRadius != PU.interactionRadius ||
+            q.kpress_grad != PU.kpress_grad)
+            pbfEpsValid = false;
         PU = q;
         if (!sameGrid && slabOn) choose_window(slab.lo, slab.hi, slab.halo, true);
         derive_kernel_params();
@@ -1224,12 +1237,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         pciDeltaValid = true;
         return NRS_OK;
     }
-    template <bool HAS_B> int pcisph_tail(int stop)
+    // the density scan and the advection launch of a PCISPH or PBF step (x*0 into posPred); *more = false when the step stops here
+    template <bool HAS_B> int pci_prefix(int stop, bool *more)
     {
         const uint32_t N = (uint32_t)n;
         const dim3 g(nblocks(N)), b(BLOCK);
         const GridView<R> G = grid_view();
         const HitBuffer hb = hit_buffer();
+        *more = false;
         // one neighbourhood scan per step (the wide lists of the IISPH chain): its hit lists drive the rest of the step
         if (plan.walls) {
             NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
@@ -1252,7 +1267,18 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             launch_listed(k_pci_advect_lists<R, KSET, SURF, HAS_B, true>, k_pci_advect_lists<R, KSET, SURF, HAS_B>, g.x, P, G, A0, hb,
                           posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
         NRSCHK(ev_end());
-        if (stop == NRS_STAGE_P_ADVECT) return NRS_OK;
+        *more = stop != NRS_STAGE_P_ADVECT;
+        return NRS_OK;
+    }
+    template <bool HAS_B> int pcisph_tail(int stop)
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        const GridView<R> G = grid_view();
+        const HitBuffer hb = hit_buffer();
+        bool more;
+        NRSCHK(pci_prefix<HAS_B>(stop, &more));
+        if (!more) return NRS_OK;
         // the predictive-corrective loop: stop after the iteration l with l >= min_iters and max e <= eta, or at the cap; the max is
         // not formed (nor read back) before min_iters
         NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
@@ -1282,6 +1308,117 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
         return integrate_adv(NRS_STAGE_P_INTEGRATE);
+    }
+
+    // ---- PBF step (nrs_kernels_pbf.h; DESIGN.md "PBF") ---------------------------------------------------------------------------------
+    PbfArrays<R> pbf_view(int in, int out) const
+    {
+        PbfArrays<R> A;
+        A.densPred = densCorr.as<R>(); A.lambda = P_l.as<R>(); A.err = pciErr.as<R>();
+        A.dx = forcesP.as<T4>();
+        A.xsIn = (in ? posPred2 : posPred).as<T4>();
+        A.xsOut = (out ? posPred2 : posPred).as<T4>();
+        A.eps = pbfEps;
+        return A;
+    }
+    int pbf_configure(double eta, uint32_t minIters, double relaxation, double xsph) override
+    {
+        if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_configure on a context that is not PBF");
+        if (!(eta >= 0.0) || !std::isfinite(eta)) return fail(NRS_E_INVALID, "max_density_error must be >= 0 (0 = a fixed min_iters iterations)");
+        if (minIters == 0) return fail(NRS_E_INVALID, "min_iters must be >= 1");
+        if (!(relaxation > 0.0) || !std::isfinite(relaxation)) return fail(NRS_E_INVALID, "relaxation must be > 0");
+        if (!(xsph >= 0.0 && xsph <= 1.0)) return fail(NRS_E_INVALID, "xsph must be in [0, 1]");
+        pbfEta = eta; pbfMinIters = minIters; pbfRelax = relaxation; pbfXsph = xsph;
+        pbfEpsValid = false;
+        return NRS_OK;
+    }
+    // eps = relaxation * D_proto, D = |sum g|^2 + sum |g|^2 over the neighbours of a prototype particle on the cubic lattice of spacing
+    // cbrt(m / rho0) (k_pbf_prototype, the solver's own gradient on the device); once per parameter or settings change
+    int pbf_prepare()
+    {
+        if (pbfEpsValid) return NRS_OK;
+        const double m = (double)PU.particleMass, rd = (double)PU.restDensity, h = (double)PU.interactionRadius;
+        const R sp = (R)std::cbrt(m / rd);
+        if (!(sp > (R)0) || !std::isfinite((double)sp) || !(h > 0.0) || h / (double)sp > 64.0)
+            return fail(NRS_E_INVALID, "PBF: the prototype spacing cbrt(m / rho0) must be positive and at least h / 64");
+        const int kmax = (int)std::ceil(h / (double)sp) + 1;
+        hipLaunchKernelGGL((k_pbf_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
+        HIPCHK(hipGetLastError());
+        double o[5];
+        HIPCHK(hipMemcpyAsync(o, redPartial.p, sizeof(o), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (o[4] == 0.0) {
+            char buf[200];
+            snprintf(buf, sizeof(buf), "PBF: the prototype particle (lattice spacing %g, h %g) has no neighbour within h: no eps", (double)sp, h);
+            return fail(NRS_E_INVALID, buf);
+        }
+        const double e = pbfRelax * (o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3]);
+        if (!(e > 0.0) || !std::isfinite(e)) return fail(NRS_E_INVALID, "PBF: the prototype gives no finite positive eps");
+        pbfEps = (R)e;
+        pbfEpsValid = true;
+        return NRS_OK;
+    }
+    template <bool HAS_B> int pbf_tail(int stop)
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        const GridView<R> G = grid_view();
+        const HitBuffer hb = hit_buffer();
+        bool more;
+        NRSCHK(pci_prefix<HAS_B>(stop, &more));
+        if (!more) return NRS_OK;
+        // Jacobi projection: with eta > 0 stop after the iteration l with l >= min_iters and max e <= eta, or at the cap, the max not
+        // formed (nor read back) before min_iters; with eta = 0 exactly min_iters iterations and no read-back at all
+        NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
+        const bool fixed = pbfEta == 0.0;
+        const uint32_t cap = fixed ? pbfMinIters : (maxIters ? maxIters : 50u);
+        uint32_t l = 0;
+        double err = -1.0;
+        for (;;) {
+            const PbfArrays<R> A = pbf_view(pciXs, pciXs ^ 1);
+            if (!plan.lists) {
+                hipLaunchKernelGGL((k_pbf_lambda_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
+                hipLaunchKernelGGL((k_pbf_correct_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
+            } else if constexpr (KSET == KS_MULLER) {
+                launch_listed(k_pbf_lambda_lists<R, KSET, HAS_B, true>, k_pbf_lambda_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
+                launch_listed(k_pbf_correct_lists<R, KSET, HAS_B, true>, k_pbf_correct_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
+            }
+            pciXs ^= 1;
+            ++l;
+            const bool last = l >= cap;
+            if (fixed) {
+                if (last) break;
+            } else if (l >= pbfMinIters || last) {
+                NRSCHK(max_of<false>(pciErr.p, N, &err));
+                if (last || err <= pbfEta) break;
+            }
+        }
+        lastIters = l;
+        pciLastErr = err;
+        pbfErrPending = fixed ? N : 0u;
+        HIPCHK(hipMemcpyAsync(presB.p, P_l.p, sizeof(R) * N, hipMemcpyDeviceToDevice, stream)); // (lambda, NRS_ARR_PRES)
+        NRSCHK(ev_end());
+        if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
+        // v = (x* - x) / dt (+ XSPH), x = x*.  The XSPH launch reads x_j and x*_j of its neighbours, so it leaves the velocities in velB
+        // and k_pbf_integrate, which overwrites x, follows it.
+        NRSCHK(ev_begin(NRS_STAGE_P_INTEGRATE));
+        const T4 *xs = (const T4 *)pci_xs_current();
+        const bool xsph = pbfXsph > 0.0;
+        if (xsph) {
+            if (!plan.lists)
+                hipLaunchKernelGGL((k_pbf_xsph_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), xs, velB.as<T4>(), (R)pbfXsph, N);
+            else if constexpr (KSET == KS_MULLER)
+                hipLaunchKernelGGL((k_pbf_xsph_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), xs, velB.as<T4>(), (R)pbfXsph, N);
+        }
+        uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
+        if (plan.resort) NRSCHK(clean_tile_counts());
+        hipLaunchKernelGGL((k_pbf_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), xs, xsph ? 1 : 0, N, nh, ni,
+                           plan.resort ? (const uint32_t *)hashCur : (const uint32_t *)nullptr,
+                           plan.resort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr);
+        NRSCHK(ev_end());
+        if (plan.keys) keys_ready(nh, ni);
+        if (plan.resort) NRSCHK(queue_resort_split(N));
+        return NRS_OK;
     }
 
     // ---- host-driven IISPH step (multi-GPU: the loop exit needs the average over ALL ranks) ---------------------------------
@@ -1337,6 +1474,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // (DESIGN.md §5): 2 iterations — the reference's minimum — need 8 cells
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
         if (pcisph()) return fail(NRS_E_INVALID, "PCISPH contexts have no slab decomposition");
+        if (pbf()) return fail(NRS_E_INVALID, "PBF contexts have no slab decomposition");
         if (iisph() && halo < 8) return fail(NRS_E_INVALID, "IISPH slabs need a halo of at least 8 cells (2 * iterations + 4)");
         if (halo < 2) return fail(NRS_E_INVALID, "halo must be >= 2 cells (one cell for the density of the ring + one)");
         if ((long long)hi - lo < 2ll * halo) return fail(NRS_E_INVALID, "slab narrower than two halos");
@@ -1676,12 +1814,22 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int get_stat(int which, double *out) override
     {
         if (which == NRS_STAT_MOVERS) { *out = lastMovers; return NRS_OK; }
+        if (pbf() && (which == NRS_STAT_DENSITY_ERROR || which == NRS_STAT_PBF_EPSILON)) {
+            if (pbfErrPending) { // (fixed-count mode: pciErr still holds the e_i of the last iteration)
+                NRSCHK(max_of<false>(pciErr.p, pbfErrPending, &pciLastErr));
+                pbfErrPending = 0;
+            }
+            if (pciLastErr < 0.0) return fail(NRS_E_STATE, "no PBF solve yet");
+            *out = which == NRS_STAT_DENSITY_ERROR ? pciLastErr : (double)pbfEps;
+            return NRS_OK;
+        }
         if (which == NRS_STAT_DENSITY_ERROR || which == NRS_STAT_PCISPH_DELTA) {
             if (!pcisph()) return fail(NRS_E_STATE, "PCISPH statistic requested from another context");
             if (pciLastErr < 0.0) return fail(NRS_E_STATE, "no PCISPH solve yet");
             *out = which == NRS_STAT_DENSITY_ERROR ? pciLastErr : (double)pciDelta;
             return NRS_OK;
         }
+        if (which == NRS_STAT_PBF_EPSILON) return fail(NRS_E_STATE, "PBF statistic requested from another context");
         if (which != NRS_STAT_HIT_OVERFLOW && which != NRS_STAT_HIT_MEAN && which != NRS_STAT_HIT_MAX && which != NRS_STAT_UNSTAGED)
             return fail(NRS_E_INVALID, "unknown statistic");
         if (!hitCounts.p || !n || midStep) return fail(NRS_E_STATE, "no shared hit lists (reference-order kernels, or no step yet)");
@@ -1710,7 +1858,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             std::swap(posA.p, posB.p);
             std::swap(velA.p, velB.p);
         }
-        if (iisph() || pcisph()) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB)
+        if (iisph() || pcisph() || pbf()) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB, PBF its lambda)
         return NRS_OK;
     }
     int step(int nsteps, int stop) override
@@ -1720,8 +1868,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (midStep) return fail(NRS_E_STATE, "state is mid-update after nrs_step_partial; upload particles first");
         if (pcisph() && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
             return fail(NRS_E_INVALID, "stage not part of a PCISPH step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
+        if (pbf() && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
+            return fail(NRS_E_INVALID, "stage not part of a PBF step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
         if (n == 0) return NRS_OK;
         if (pcisph()) NRSCHK(pcisph_prepare());
+        if (pbf()) NRSCHK(pbf_prepare());
         for (int s = 0; s < nsteps; ++s) {
             fusedThisStep = false;
             splitClearedCells = false;
@@ -1730,6 +1881,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (stop && stop <= NRS_STAGE_REORDER) { midStep = true; break; }
             if (iisph()) { if (nb) NRSCHK(iisph_tail<true>(stop)); else NRSCHK(iisph_tail<false>(stop)); }
             else if (pcisph()) { if (nb) NRSCHK(pcisph_tail<true>(stop)); else NRSCHK(pcisph_tail<false>(stop)); }
+            else if (pbf()) { if (nb) NRSCHK(pbf_tail<true>(stop)); else NRSCHK(pbf_tail<false>(stop)); }
             else { if (nb) NRSCHK(sesph_tail<true>(stop)); else NRSCHK(sesph_tail<false>(stop)); }
             HIPCHK(hipGetLastError());
             if (stop) { midStep = true; break; }
@@ -1870,7 +2022,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         case NRS_ARR_SORTED_POS: p = sortedIsCurrent ? posA.p : posB.p; sz = v; break;
         case NRS_ARR_SORTED_VEL: p = sortedIsCurrent ? velA.p : velB.p; sz = v; break;
         case NRS_ARR_DENS: p = dens.p; sz = s; break;
-        case NRS_ARR_PRES: p = ((iisph() || pcisph()) && sortedIsCurrent) ? presA.p : presB.p; sz = s; break;
+        case NRS_ARR_PRES: p = ((iisph() || pcisph() || pbf()) && sortedIsCurrent) ? presA.p : presB.p; sz = s; break;
         case NRS_ARR_FORCES: p = forces.p; sz = v; break;
         case NRS_ARR_B_HASH: p = bHashCur; sz = 4 * nb; break;
         case NRS_ARR_B_INDEX: p = bIndexCur; sz = 4 * nb; break;
@@ -1890,10 +2042,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         case NRS_ARR_POS_PRED: p = pci_xs_current(); sz = v; break;
         default: return fail(NRS_E_INVALID, "unknown array id");
         }
-        if (which == NRS_ARR_POS_PRED && !pcisph()) return fail(NRS_E_STATE, "PCISPH array requested from another context");
+        if (which == NRS_ARR_POS_PRED && !pcisph() && !pbf()) return fail(NRS_E_STATE, "PCISPH / PBF array requested from another context");
         const bool pciArray = which == NRS_ARR_VEL_ADV || which == NRS_ARR_FORCES_ADV || which == NRS_ARR_FORCES_P ||
                               which == NRS_ARR_DENS_CORR || which == NRS_ARR_P_L || which == NRS_ARR_POS_PRED;
         if (pcisph() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PCISPH context");
+        if (pbf() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PBF context");
         if (which >= NRS_ARR_DENS_ADV && sesph()) return fail(NRS_E_STATE, "IISPH array requested from a SESPH context");
         *dptr = p;
         *bytes = p ? sz : 0;

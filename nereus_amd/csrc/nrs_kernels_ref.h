@@ -1052,6 +1052,284 @@ __global__ __launch_bounds__(64) void k_pci_prototype(Params<R> P, R spacing, in
     out[0] = sx; out[1] = sy; out[2] = sz; out[3] = gg; out[4] = cnt;
 }
 
+// =========================================== PBF ===================================================
+// Position-based fluids (Macklin & Mueller 2013): a density constraint solved by Jacobi projection.  The reference names it among
+// its future works only; DESIGN.md "PBF" defines what is computed here.  The neighbour rule and the order of every sum are those of
+// the PCISPH loop above (start-position AND predicted-position cut-off, j != i by sorted slot, static boundary particles, one
+// fluid partial and then one boundary partial per cell in the order of density_of), so the list-driven kernels (nrs_kernels_pbf.h)
+// can be bit-identical to the walks below.  The advection launch is PCISPH's (k_pci_advect_*).
+template <typename R> struct PbfArrays {
+    typedef typename Vec4T<R>::type T4;
+    R *densPred, *lambda, *err; // rho*, lambda, e = max(rho* - rho0, 0) / rho0 (input of the exit test's max)
+    T4 *dx;                     // the correction of the last position launch
+    const T4 *xsIn;             // predicted positions the launch reads (its own and its neighbours')
+    T4 *xsOut;                  // ... and where the position launch writes the corrected ones (double-buffered)
+    R eps;                      // the constraint-force mixing term: relaxation * D_proto
+};
+// grad W_spiky: Wpressure_grad for the Muller set, W_grad for Monaghan (inside the loop's cut-off h).  Defined as 0 at zero separation,
+// where Wpressure_grad divides by |r| = 0.
+template <typename R, int KSET> NRS_DEV V3<R> pbf_grad(const Params<R> &P, V3<R> r)
+{
+    if (!(length(r) > 0.0f)) return mk3<R>(0, 0, 0);
+    if constexpr (KSET == KS_MULLER) return Wpressure_grad<R>(r, P.interactionRadius, P.kpress_grad);
+    else return W_grad<R, KSET>(r, P.interactionRadius, P.kpoly_grad);
+}
+template <typename R> NRS_DEV R pbf_dot(V3<R> a, V3<R> b) { return a.x * b.x + a.y * b.y + a.z * b.z; } // (in SReal, unlike dot())
+// (x* - x) / dt, the velocity a predicted position implies
+template <typename R> NRS_DEV V3<R> pbf_vel(const Params<R> &P, V3<R> xs, V3<R> x)
+{
+    const R dt = P.timestep;
+    return mk3<R>((xs.x - x.x) / dt, (xs.y - x.y) / dt, (xs.z - x.z) / dt);
+}
+// the sums of launch A: rho*, sum g (fluid and boundary), sum |g|^2 (fluid)
+template <typename R> struct PbfSums {
+    R rho, gg;
+    V3<R> g;
+    NRS_DEV void add(const PbfSums &o) { rho += o.rho; g = g + o.g; gg += o.gg; }
+};
+template <typename R> NRS_DEV PbfSums<R> pbf_zero()
+{
+    PbfSums<R> s;
+    s.rho = s.gg = (R)0.0;
+    s.g = mk3<R>(0, 0, 0);
+    return s;
+}
+// one fluid neighbour of launch A at predicted separation d (its start-position test already passed)
+template <typename R, int KSET> NRS_DEV void pbf_lambda_fluid(const Params<R> &P, V3<R> d, PbfSums<R> &s)
+{
+    const R ir = P.interactionRadius, pm = P.particleMass, rd = P.restDensity;
+    if (!(length(d) < ir)) return;
+    s.rho += pm * W_dens<R, KSET>(d, ir, P.kpoly);
+    const V3<R> g = pci_scale<R>(pm / rd, pbf_grad<R, KSET>(P, d));
+    s.g = s.g + g;
+    s.gg += pbf_dot<R>(g, g);
+}
+// one boundary neighbour of launch A: psi_b = rho0 V_b
+template <typename R, int KSET> NRS_DEV void pbf_lambda_boundary(const Params<R> &P, V3<R> d, R psi, PbfSums<R> &s)
+{
+    const R ir = P.interactionRadius, rd = P.restDensity;
+    if (!(length(d) < ir)) return;
+    s.rho += psi * W_dens<R, KSET>(d, ir, P.kpoly);
+    s.g = s.g + pci_scale<R>(psi / rd, pbf_grad<R, KSET>(P, d));
+}
+// rho*, C, D -> lambda and e; NaN densities give e = inf (the loop then runs to its cap and reports it)
+template <typename R> NRS_DEV void pbf_lambda_store(const Params<R> &P, const PbfArrays<R> &A, uint32_t i, const PbfSums<R> &s)
+{
+    const R rd = P.restDensity;
+    const R c = s.rho / rd - (R)1.0;
+    const R C = c > (R)0 ? c : (R)0;
+    const R D = pbf_dot<R>(s.g, s.g) + s.gg;
+    const R dr = s.rho - rd;
+    A.densPred[i] = s.rho;
+    A.lambda[i] = -C / (D + A.eps);
+    A.err[i] = dr <= (R)0 ? (R)0 : (dr == dr ? dr / rd : (R)INFINITY);
+}
+// the terms of launch B: (lambda_i + lambda_j) g_ij and lambda_i g_ib
+template <typename R, int KSET> NRS_DEV V3<R> pbf_correct_fluid(const Params<R> &P, V3<R> d, R li, R lj)
+{
+    if (!(length(d) < P.interactionRadius)) return mk3<R>(0, 0, 0);
+    return pci_scale<R>(li + lj, pci_scale<R>(P.particleMass / P.restDensity, pbf_grad<R, KSET>(P, d)));
+}
+template <typename R, int KSET> NRS_DEV V3<R> pbf_correct_boundary(const Params<R> &P, V3<R> d, R psi, R li)
+{
+    if (!(length(d) < P.interactionRadius)) return mk3<R>(0, 0, 0);
+    return pci_scale<R>(li, pci_scale<R>(psi / P.restDensity, pbf_grad<R, KSET>(P, d)));
+}
+template <typename R> NRS_DEV void pbf_correct_store(const PbfArrays<R> &A, uint32_t i, V3<R> xs1, V3<R> dx)
+{
+    A.dx[i] = mk4<R>(dx, (R)0.0);
+    A.xsOut[i] = mk4<R>(xs1 + dx, (R)1.0);
+}
+// the XSPH term of one fluid neighbour: (m / rho0) W(d) (v_j - v_i)
+template <typename R, int KSET> NRS_DEV V3<R> pbf_xsph_fluid(const Params<R> &P, V3<R> d, V3<R> vj, V3<R> vi)
+{
+    const R ir = P.interactionRadius;
+    if (!(length(d) < ir)) return mk3<R>(0, 0, 0);
+    return pci_scale<R>((P.particleMass / P.restDensity) * W_dens<R, KSET>(d, ir, P.kpoly), vj - vi);
+}
+
+// launch A of particle i, reference order
+template <typename R, int KSET, bool HAS_B>
+NRS_DEV PbfSums<R> pbf_lambda_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                                   const typename Vec4T<R>::type *__restrict__ xs, uint32_t i, V3<R> pos1, V3<R> xs1)
+{
+    const R ir = P.interactionRadius, rd = P.restDensity;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    PbfSums<R> t = pbf_zero<R>();
+    t.rho += P.particleMass * W_dens<R, KSET>(mk3<R>(0, 0, 0), ir, P.kpoly);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                PbfSums<R> c = pbf_zero<R>();
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
+                        pbf_lambda_fluid<R, KSET>(P, xs1 - xyz<R>(xs[j]), c);
+                    }
+                }
+                t.add(c);
+                if (HAS_B) {
+                    PbfSums<R> cb = pbf_zero<R>();
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            if (!(length(pos1 - xyz<R>(b)) < ir)) continue;
+                            pbf_lambda_boundary<R, KSET>(P, xs1 - xyz<R>(b), rd * b.w, cb);
+                        }
+                    }
+                    t.add(cb);
+                }
+            }
+    return t;
+}
+// launch B of particle i (the correction dx_i), reference order
+template <typename R, int KSET, bool HAS_B>
+NRS_DEV V3<R> pbf_correct_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                               const typename Vec4T<R>::type *__restrict__ xs, const R *__restrict__ lambda, uint32_t i, V3<R> pos1,
+                               V3<R> xs1, R li)
+{
+    const R ir = P.interactionRadius, rd = P.restDensity;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    V3<R> dx = mk3<R>(0, 0, 0);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                V3<R> c = mk3<R>(0, 0, 0);
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
+                        c = c + pbf_correct_fluid<R, KSET>(P, xs1 - xyz<R>(xs[j]), li, lambda[j]);
+                    }
+                }
+                dx = dx + c;
+                if (HAS_B) {
+                    V3<R> cb = mk3<R>(0, 0, 0);
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            if (!(length(pos1 - xyz<R>(b)) < ir)) continue;
+                            cb = cb + pbf_correct_boundary<R, KSET>(P, xs1 - xyz<R>(b), rd * b.w, li);
+                        }
+                    }
+                    dx = dx + cb;
+                }
+            }
+    return dx;
+}
+// the XSPH sum of particle i over its fluid neighbours, reference order (v_j formed from x*_j and x_j)
+template <typename R, int KSET>
+NRS_DEV V3<R> pbf_xsph_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                            const typename Vec4T<R>::type *__restrict__ xs, uint32_t i, V3<R> pos1, V3<R> xs1, V3<R> v1)
+{
+    const R ir = P.interactionRadius;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    V3<R> sum = mk3<R>(0, 0, 0);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                V3<R> c = mk3<R>(0, 0, 0);
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        const V3<R> xj = xyz<R>(sPos[j]);
+                        if (j == i || !(length(pos1 - xj) < ir)) continue;
+                        const V3<R> xsj = xyz<R>(xs[j]);
+                        c = c + pbf_xsph_fluid<R, KSET>(P, xs1 - xsj, pbf_vel<R>(P, xsj, xj), v1);
+                    }
+                }
+                sum = sum + c;
+            }
+    return sum;
+}
+
+// launch A: rho*, lambda, e
+template <typename R, int KSET, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_pbf_lambda_ref(Params<R> P, GridView<R> G, PbfArrays<R> A,
+                                                          const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    pbf_lambda_store<R>(P, A, i, pbf_lambda_walk<R, KSET, HAS_B>(P, G, sPos, A.xsIn, i, xyz<R>(sPos[i]), xyz<R>(A.xsIn[i])));
+}
+// launch B: the correction and the next predicted positions
+template <typename R, int KSET, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_pbf_correct_ref(Params<R> P, GridView<R> G, PbfArrays<R> A,
+                                                           const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3<R> xs1 = xyz<R>(A.xsIn[i]);
+    pbf_correct_store<R>(A, i, xs1, pbf_correct_walk<R, KSET, HAS_B>(P, G, sPos, A.xsIn, A.lambda, i, xyz<R>(sPos[i]), xs1, A.lambda[i]));
+}
+// XSPH: vel_i = v_i + c sum_j (m / rho0) W (v_j - v_i), v = (x* - x) / dt (before k_pbf_integrate, which then takes vel as given)
+template <typename R, int KSET>
+__global__ __launch_bounds__(BLOCK) void k_pbf_xsph_ref(Params<R> P, GridView<R> G, const typename Vec4T<R>::type *__restrict__ sPos,
+                                                        const typename Vec4T<R>::type *__restrict__ xs,
+                                                        typename Vec4T<R>::type *__restrict__ vel, R c, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3<R> pos1 = xyz<R>(sPos[i]), xs1 = xyz<R>(xs[i]);
+    const V3<R> v1 = pbf_vel<R>(P, xs1, pos1);
+    vel[i] = mk4<R>(v1 + pci_scale<R>(c, pbf_xsph_walk<R, KSET>(P, G, sPos, xs, i, pos1, xs1, v1)), (R)0.0);
+}
+// PBF integration: v = (x* - x) / dt (or, after the XSPH launch, the velocity it left), x = x* with pos.w kept, vel.w = 0.  The sort
+// keys of the next step and the movers of the coherent re-sort as k_iisph_integrate emits them.
+template <typename R>
+__global__ __launch_bounds__(BLOCK) void k_pbf_integrate(Params<R> P, typename Vec4T<R>::type *__restrict__ pos,
+                                                         typename Vec4T<R>::type *__restrict__ vel,
+                                                         const typename Vec4T<R>::type *__restrict__ xs, int velGiven, uint32_t n,
+                                                         uint32_t *__restrict__ nextHash, uint32_t *__restrict__ nextIndex,
+                                                         const uint32_t *__restrict__ prevHash, uint32_t *__restrict__ tileMovers)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const typename Vec4T<R>::type p0 = pos[i];
+    const V3<R> newPos = xyz<R>(xs[i]);
+    if (!velGiven) vel[i] = mk4<R>(pbf_vel<R>(P, newPos, xyz<R>(p0)), (R)0.0);
+    pos[i] = mk4<R>(newPos, p0.w);
+    if (nextHash) {
+        const I3 g = calcGridPos<R>(P, newPos);
+        const uint32_t h = calcGridHash<R>(P, g.x, g.y, g.z);
+        nextHash[i] = h;
+        nextIndex[i] = i;
+        if (tileMovers && h != prevHash[i]) atomicAdd(&tileMovers[i / BLOCK], 1u);
+    }
+}
+// the prototype sums of D: out[0..2] = sum_k g_k, out[3] = sum_k g_k . g_k, out[4] = neighbours, over the lattice points k s, k in Z^3,
+// 0 < |k s| < h, with g_k = (m / rho0) grad W_spiky(-k s) (in double, k_z, k_y, k_x ascending).  One thread.
+template <typename R, int KSET>
+__global__ __launch_bounds__(64) void k_pbf_prototype(Params<R> P, R spacing, int kmax, double *__restrict__ out)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const R ir = P.interactionRadius;
+    double sx = 0.0, sy = 0.0, sz = 0.0, gg = 0.0, cnt = 0.0;
+    for (int z = -kmax; z <= kmax; ++z)
+        for (int y = -kmax; y <= kmax; ++y)
+            for (int x = -kmax; x <= kmax; ++x) {
+                if (x == 0 && y == 0 && z == 0) continue;
+                const V3<R> d = mk3<R>(-(R)x * spacing, -(R)y * spacing, -(R)z * spacing);
+                if (!(length(d) < ir)) continue;
+                const V3<R> g = pci_scale<R>(P.particleMass / P.restDensity, pbf_grad<R, KSET>(P, d));
+                sx += (double)g.x; sy += (double)g.y; sz += (double)g.z;
+                gg += (double)g.x * (double)g.x + (double)g.y * (double)g.y + (double)g.z * (double)g.z;
+                cnt += 1.0;
+            }
+    out[0] = sx; out[1] = sy; out[2] = sz; out[3] = gg; out[4] = cnt;
+}
+
 // deterministic two-pass sum of an SReal array in double (replaces thrust::reduce, sph_cuda.cu:816-819)
 template <typename R>
 __global__ __launch_bounds__(BLOCK) void k_sum_partial(const R *__restrict__ a, double *__restrict__ partial, uint32_t n,

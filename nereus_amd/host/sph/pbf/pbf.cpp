@@ -1,0 +1,42 @@
+// pbf.cpp — Nereus::PBF: SPH's update() (upload if dirty, one nrs_step, lazy download) on a context of kind NRS_SOLVER_PBF.
+#include "pbf.h"
+
+#include "nereus_hip.h"
+
+#include <cstdio>
+#include <cstdlib>
+
+NEREUS_NAMESPACE_BEGIN
+
+PBF::PBF() : SPH(), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_minIters(2) {}
+PBF::PBF(SphSimParams params) : SPH(params), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_minIters(2) {}
+PBF::~PBF() {}
+
+int PBF::solverKind() const { return NRS_SOLVER_PBF; }
+
+void PBF::setSolverSettings(SReal eta, SUint minIters, SReal relaxation, SReal xsph)
+{
+    if (m_ctx) { // (a context keeps the settings it was created with)
+        std::fprintf(stderr, "Nereus: PBF::setSolverSettings must be called before the first update() / updateGpuBoundaries()\n");
+        std::exit(EXIT_FAILURE);
+    }
+    m_eta = eta;
+    m_minIters = minIters;
+    m_relaxation = relaxation;
+    m_xsph = xsph;
+}
+
+void PBF::configureContext()
+{
+    if (nrs_pbf_configure(m_ctx, (double)m_eta, (uint32_t)m_minIters, (double)m_relaxation, (double)m_xsph) != NRS_OK)
+        fatal("nrs_pbf_configure");
+}
+
+SUint PBF::getLastIterations()
+{
+    uint32_t it = 0;
+    if (m_ctx && nrs_last_iterations(m_ctx, &it) != NRS_OK) fatal("nrs_last_iterations");
+    return (SUint)it;
+}
+
+NEREUS_NAMESPACE_END

@@ -1,0 +1,30 @@
+// pbf.h — Nereus::PBF, position-based fluids (Macklin & Mueller 2013).  Not in the reference, which names PBF among its future works:
+// a device step of the library's NRS_SOLVER_PBF (DESIGN.md "PBF") behind the SPH host surface.  update() is a full step; the
+// pressures read back are the step's lambda.
+#pragma once
+#ifndef PBF_H
+#define PBF_H
+#include "sph.h"
+
+NEREUS_NAMESPACE_BEGIN
+
+class PBF : public SPH {
+public:
+    PBF();
+    PBF(SphSimParams params);
+    virtual ~PBF();
+    // Solver settings (nrs_pbf_configure).  Must be called before the device context exists, i.e. before the first update() or
+    // updateGpuBoundaries().  eta = largest density error max(rho - rho0, 0) / rho0 the loop accepts (0: exactly minIters iterations,
+    // nothing read back), relaxation = eps / D_proto, xsph = the XSPH velocity smoothing factor (0 = off).
+    void setSolverSettings(SReal eta, SUint minIters, SReal relaxation, SReal xsph);
+    SUint getLastIterations(); // solver iterations of the last step
+    int solverKind() const override;
+
+protected:
+    void configureContext() override; // hands the settings to every context ensureContext creates (a capacity change replaces it)
+    SReal m_eta, m_relaxation, m_xsph;
+    SUint m_minIters;
+};
+
+NEREUS_NAMESPACE_END
+#endif // PBF_H

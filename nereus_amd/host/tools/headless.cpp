@@ -3,7 +3,8 @@
 //
 //   headless params  <sesph|iisph> <out.bin>                    constructor-default SphSimParams bytes
 //   headless run     <sesph|iisph> <in.bin> <steps> <out.bin>   particles/boundaries from a file (also pcisph: the reference's
-//                                                               stub, and pcisph-solve: PCISPH::setPressureSolve(true))
+//                                                               stub, pcisph-solve: PCISPH::setPressureSolve(true), and pbf:
+//                                                               Nereus::PBF with its default settings)
 //   headless resume  <sesph|iisph> <in.bin> <steps_a> <steps_b> <ckpt> <out.bin>   run steps_a, saveState, then a NEW
 //                                                               solver loadState()s and runs steps_b (boundaries re-set)
 //   headless cfl     sesph <in.bin> <steps> <out.bin>           run with setAdaptiveTimestep(true)
@@ -19,6 +20,7 @@
 
 #include "common.h"
 #include "iisph/iisph.h"
+#include "pbf/pbf.h"
 #include "pcisph/pcisph.h"
 #include "sph.h"
 #include <sph_boundary_particles/boundary_forces.h>
@@ -67,7 +69,9 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool iisph = kind == "iisph", pcisphSolve = kind == "pcisph-solve", pcisph = kind == "pcisph" || pcisphSolve;
-    Nereus::SPH *sim = iisph ? (Nereus::SPH *)new Nereus::IISPH() : (pcisph ? (Nereus::SPH *)new Nereus::PCISPH() : new Nereus::SPH());
+    const bool pbf = kind == "pbf";
+    Nereus::SPH *sim = iisph ? (Nereus::SPH *)new Nereus::IISPH()
+                             : (pcisph ? (Nereus::SPH *)new Nereus::PCISPH() : (pbf ? (Nereus::SPH *)new Nereus::PBF() : new Nereus::SPH()));
     if (pcisphSolve) static_cast<Nereus::PCISPH *>(sim)->setPressureSolve(true);
     sim->_initialize();
     std::vector<SVec4> bi;
@@ -111,6 +115,7 @@ int main(int argc, char **argv)
         }
         if (iisph) iters = static_cast<Nereus::IISPH *>(sim)->getLastIterations();
         if (pcisphSolve) iters = static_cast<Nereus::PCISPH *>(sim)->getLastIterations();
+        if (pbf) iters = static_cast<Nereus::PBF *>(sim)->getLastIterations();
         dump(argv[5], sim, iters, bi, vbi);
     } else if (mode == "resume" || mode == "cfl") {
         FILE *f = std::fopen(argv[3], "rb");
