@@ -187,6 +187,8 @@ enum {
                                On a PBF context the same arrays hold the PBF quantities: _POS_PRED x*, _VEL_ADV, _FORCES_ADV,
                                _DENS_CORR rho*, _P_L lambda and _FORCES_P the correction dx of the last iteration; NRS_ARR_PRES
                                and nrs_download(pres) give lambda */
+    NRS_ARR_VORTICITY = 31, /* PBF: SVec4[N] sorted (omega, |omega|) of the last step that had vorticity confinement on
+                               (nrs_pbf_set_vorticity); NRS_E_STATE before there is one */
 };
 
 const char *nrs_last_error(void);
@@ -280,6 +282,14 @@ int nrs_pcisph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_it
  * velocity smoothing factor c (0 = off).  Defaults: 0.01, 2, 0.01, 0.  NRS_E_INVALID for max_density_error < 0, min_iters == 0,
  * relaxation <= 0 or xsph outside [0, 1]. */
 int nrs_pbf_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double relaxation, double xsph);
+/* PBF tensile correction (Macklin & Mueller's s_corr; NRS_E_STATE on any other context): on fluid pairs the position correction
+ * uses lambda_i + lambda_j + s_ij, s_ij = -k (W(x*_i - x*_j) / W_q)^4 with W_q = W((dq h, 0, 0)).  Defaults k = 0 (off), dq = 0.2.
+ * NRS_E_INVALID for a NaN or infinite value, k < 0, dq outside (0, 1) or a W_q that is not positive.  Came after nrs_version() 0.3
+ * without a version change, as PBF did. */
+int nrs_pbf_set_tensile(nrs_ctx *ctx, double k, double dq);
+/* PBF vorticity confinement (NRS_E_STATE on any other context): at the end of the step vel_i += dt eps_v (N_i x omega_i),
+ * DESIGN.md "PBF".  Default 0 (off).  NRS_E_INVALID for a NaN, infinite or negative eps_v. */
+int nrs_pbf_set_vorticity(nrs_ctx *ctx, double eps_v);
 
 /* Per-stage device time, measured with HIP events recorded on the context's stream around the stage's
  * launches.  stage_mask: bit s set = time NRS_STAGE_s (0 = off, 0xffffffff = every stage).  nrs_set_profiling also

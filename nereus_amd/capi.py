@@ -45,7 +45,7 @@ ARRAYS = {
     "bCellStart": (14, "u"), "bCellEnd": (15, "u"), "bSorted": (16, "v4"),
     "densAdv": (20, "s"), "densCorr": (21, "s"), "P_l": (22, "s"), "aii": (23, "s"), "velAdv": (24, "v4"),
     "forcesAdv": (25, "v4"), "forcesP": (26, "v4"), "diiFluid": (27, "v4"), "diiBoundary": (28, "v4"),
-    "sumDij": (29, "v4"), "posPred": (30, "v4"),
+    "sumDij": (29, "v4"), "posPred": (30, "v4"), "vorticity": (31, "v4"),
 }
 
 # every symbol include/nereus_hip.h declares (checked by tests/test_abi.py)
@@ -57,7 +57,8 @@ EXPORTS = [
     "nrs_max_velocity", "nrs_slab_configure", "nrs_slab_pack", "nrs_slab_unpack", "nrs_num_owned",
     "nrs_slab_message_bytes", "nrs_slab_histogram", "nrs_resort_stats", "nrs_snapshot_begin", "nrs_snapshot_wait",
     "nrs_get_stat", "nrs_boundary_volumes", "nrs_eval_smoothing", "nrs_iisph_predict", "nrs_iisph_iterate", "nrs_iisph_finish",
-    "nrs_slab_last_counts", "nrs_pcisph_configure", "nrs_pbf_configure",
+    "nrs_slab_last_counts", "nrs_pcisph_configure", "nrs_pbf_configure", "nrs_pbf_set_tensile",
+    "nrs_pbf_set_vorticity",
 ]
 
 
@@ -110,6 +111,8 @@ def load_library(path=None):
     lib.nrs_set_max_iterations.argtypes = [vp, C.c_uint32]
     lib.nrs_pcisph_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_double]
     lib.nrs_pbf_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_double]
+    lib.nrs_pbf_set_tensile.argtypes = [vp, C.c_double, C.c_double]
+    lib.nrs_pbf_set_vorticity.argtypes = [vp, C.c_double]
     lib.nrs_set_profiling.argtypes = [vp, C.c_uint32]
     lib.nrs_stage_ms.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     lib.nrs_max_density.argtypes = [vp, C.POINTER(C.c_double)]
@@ -288,6 +291,14 @@ class Solver:
         """PBF loop settings (nrs_pbf_configure): exit error (0 = exactly min_iters iterations, nothing read back), minimum iterations,
         eps = relaxation * D_proto, XSPH factor (0 = off)"""
         self._chk(self.lib.nrs_pbf_configure(self.h, float(max_density_error), int(min_iters), float(relaxation), float(xsph)))
+
+    def pbf_set_tensile(self, k=0.0, dq=0.2):
+        """PBF tensile correction (nrs_pbf_set_tensile): s_ij = -k (W(x*_ij) / W((dq h, 0, 0)))^4 on fluid pairs (k = 0 = off)"""
+        self._chk(self.lib.nrs_pbf_set_tensile(self.h, float(k), float(dq)))
+
+    def pbf_set_vorticity(self, eps_v=0.0):
+        """PBF vorticity confinement (nrs_pbf_set_vorticity): vel += dt eps_v (N x omega) at the end of the step (0 = off)"""
+        self._chk(self.lib.nrs_pbf_set_vorticity(self.h, float(eps_v)))
 
     def set_profiling(self, stages=True):
         """stages: True = all, False = off, or an iterable of stage ids."""

@@ -301,6 +301,16 @@ int nrs_pbf_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters
     CTX_GUARD(ctx);
     return ctx->impl->pbf_configure(max_density_error, min_iters, relaxation, xsph);
 }
+int nrs_pbf_set_tensile(nrs_ctx *ctx, double k, double dq)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->pbf_set_tensile(k, dq);
+}
+int nrs_pbf_set_vorticity(nrs_ctx *ctx, double eps_v)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->pbf_set_vorticity(eps_v);
+}
 int nrs_set_profiling(nrs_ctx *ctx, uint32_t stage_mask)
 {
     CTX_GUARD(ctx);

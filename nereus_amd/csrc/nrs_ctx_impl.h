@@ -135,6 +135,13 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool pbfEpsValid = false; // pbfEps belongs to the current parameters and settings
     R pbfEps = (R)0;
     uint32_t pbfErrPending = 0; // fixed-count solve: max e over this many particles is formed on request (get_stat), not in the step
+    // PBF tensile correction (k = 0: off) and vorticity confinement (eps_v = 0: off); pbfVort holds (omega, |omega|), allocated when
+    // confinement is first enabled
+    double pbfTensK = 0.0, pbfTensDq = 0.2, pbfVortEps = 0.0;
+    bool pbfWqValid = false; // pbfWq belongs to the current parameters and dq
+    R pbfWq = (R)0;
+    DevBuf pbfVort;
+    bool pbfVortValid = false; // pbfVort holds the omega of a step
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
     HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
@@ -351,7 +358,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         for (auto &e : evPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        DevBuf *all[] = {&posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
+        DevBuf *all[] = {&pbfVort, &posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
                          &inv, &sortTmp, &cellStart, &cellEnd, &bCellStart, &bCellEnd, &bSorted, &bHash, &bIndex,
                          &bHashAlt, &bIndexAlt, &densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP,
                          &posPred, &posPred2, &pciErr, &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
@@ -502,6 +509,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (q.particleMass != PU.particleMass || q.restDensity != PU.restDensity || q.interactionRadius != PU.interactionRadius ||
             q.kpress_grad != PU.kpress_grad)
             pbfEpsValid = false;
+        // ... and W_q of the tensile correction on these
+        if (q.interactionRadius != PU.interactionRadius || q.kpoly != PU.kpoly) pbfWqValid = false;
         PU = q;
         if (!sameGrid && slabOn) choose_window(slab.lo, slab.hi, slab.halo, true);
         derive_kernel_params();
@@ -1332,10 +1341,45 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         pbfEpsValid = false;
         return NRS_OK;
     }
+    // W_q = W((dq h, 0, 0)) on the device (k_pbf_wq), with the current parameters
+    int pbf_eval_wq(double dq, R *wq)
+    {
+        hipLaunchKernelGGL((k_pbf_wq<R, KSET>), dim3(1), dim3(64), 0, stream, P, (R)dq, redPartial.as<double>());
+        HIPCHK(hipGetLastError());
+        double o = 0.0;
+        HIPCHK(hipMemcpyAsync(&o, redPartial.p, sizeof(o), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (!(o > 0.0) || !std::isfinite(o)) return fail(NRS_E_INVALID, "PBF tensile correction: W((dq h, 0, 0)) is not positive");
+        *wq = (R)o;
+        return NRS_OK;
+    }
+    int pbf_set_tensile(double k, double dq) override
+    {
+        if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_set_tensile on a context that is not PBF");
+        if (!(k >= 0.0) || !std::isfinite(k)) return fail(NRS_E_INVALID, "tensile k must be finite and >= 0 (0 = off)");
+        if (!(dq > 0.0 && dq < 1.0)) return fail(NRS_E_INVALID, "tensile dq must be in (0, 1)");
+        R wq;
+        NRSCHK(pbf_eval_wq(dq, &wq));
+        pbfTensK = k; pbfTensDq = dq; pbfWq = wq;
+        pbfWqValid = true;
+        return NRS_OK;
+    }
+    int pbf_set_vorticity(double epsV) override
+    {
+        if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_set_vorticity on a context that is not PBF");
+        if (!(epsV >= 0.0) || !std::isfinite(epsV)) return fail(NRS_E_INVALID, "vorticity eps_v must be finite and >= 0 (0 = off)");
+        if (epsV > 0.0) NRSCHK(pbfVort.alloc(sizeof(T4) * cap));
+        pbfVortEps = epsV;
+        return NRS_OK;
+    }
     // eps = relaxation * D_proto, D = |sum g|^2 + sum |g|^2 over the neighbours of a prototype particle on the cubic lattice of spacing
-    // cbrt(m / rho0) (k_pbf_prototype, the solver's own gradient on the device); once per parameter or settings change
+    // cbrt(m / rho0) (k_pbf_prototype, the solver's own gradient on the device); once per parameter or settings change.  W_q likewise.
     int pbf_prepare()
     {
+        if (pbfTensK > 0.0 && !pbfWqValid) {
+            NRSCHK(pbf_eval_wq(pbfTensDq, &pbfWq));
+            pbfWqValid = true;
+        }
         if (pbfEpsValid) return NRS_OK;
         const double m = (double)PU.particleMass, rd = (double)PU.restDensity, h = (double)PU.interactionRadius;
         const R sp = (R)std::cbrt(m / rd);
@@ -1372,16 +1416,25 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
         const bool fixed = pbfEta == 0.0;
         const uint32_t cap = fixed ? pbfMinIters : (maxIters ? maxIters : 50u);
+        const bool tens = pbfTensK > 0.0;
+        const PbfTensile<R> T{(R)pbfTensK, pbfWq};
         uint32_t l = 0;
         double err = -1.0;
         for (;;) {
             const PbfArrays<R> A = pbf_view(pciXs, pciXs ^ 1);
             if (!plan.lists) {
                 hipLaunchKernelGGL((k_pbf_lambda_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
-                hipLaunchKernelGGL((k_pbf_correct_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
+                if (tens)
+                    hipLaunchKernelGGL((k_pbf_correct_s_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, T, posB.as<T4>(), N);
+                else
+                    hipLaunchKernelGGL((k_pbf_correct_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
             } else if constexpr (KSET == KS_MULLER) {
                 launch_listed(k_pbf_lambda_lists<R, KSET, HAS_B, true>, k_pbf_lambda_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
-                launch_listed(k_pbf_correct_lists<R, KSET, HAS_B, true>, k_pbf_correct_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
+                if (tens)
+                    launch_listed(k_pbf_correct_s_lists<R, KSET, HAS_B, true>, k_pbf_correct_s_lists<R, KSET, HAS_B>, g.x, P, G, A, T, hb,
+                                  posB.as<T4>(), N);
+                else
+                    launch_listed(k_pbf_correct_lists<R, KSET, HAS_B, true>, k_pbf_correct_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
             }
             pciXs ^= 1;
             ++l;
@@ -1403,16 +1456,31 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // and k_pbf_integrate, which overwrites x, follows it.
         NRSCHK(ev_begin(NRS_STAGE_P_INTEGRATE));
         const T4 *xs = (const T4 *)pci_xs_current();
-        const bool xsph = pbfXsph > 0.0;
+        const bool xsph = pbfXsph > 0.0, vort = pbfVortEps > 0.0;
         if (xsph) {
             if (!plan.lists)
                 hipLaunchKernelGGL((k_pbf_xsph_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), xs, velB.as<T4>(), (R)pbfXsph, N);
             else if constexpr (KSET == KS_MULLER)
                 hipLaunchKernelGGL((k_pbf_xsph_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), xs, velB.as<T4>(), (R)pbfXsph, N);
         }
+        // vorticity confinement: omega from u = (x* - x) / dt, then the confinement on the velocity XSPH left (or u); both read x_j
+        if (vort) {
+            T4 *om = pbfVort.as<T4>();
+            const int given = xsph ? 1 : 0;
+            if (!plan.lists) {
+                hipLaunchKernelGGL((k_pbf_vorticity_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), xs, om, N);
+                hipLaunchKernelGGL((k_pbf_confine_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), xs, (const T4 *)om, velB.as<T4>(),
+                                   given, (R)pbfVortEps, N);
+            } else if constexpr (KSET == KS_MULLER) {
+                hipLaunchKernelGGL((k_pbf_vorticity_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), xs, om, N);
+                hipLaunchKernelGGL((k_pbf_confine_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), xs, (const T4 *)om,
+                                   velB.as<T4>(), given, (R)pbfVortEps, N);
+            }
+            pbfVortValid = true;
+        }
         uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
         if (plan.resort) NRSCHK(clean_tile_counts());
-        hipLaunchKernelGGL((k_pbf_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), xs, xsph ? 1 : 0, N, nh, ni,
+        hipLaunchKernelGGL((k_pbf_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), xs, (xsph || vort) ? 1 : 0, N, nh, ni,
                            plan.resort ? (const uint32_t *)hashCur : (const uint32_t *)nullptr,
                            plan.resort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr);
         NRSCHK(ev_end());
@@ -2040,11 +2108,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         case NRS_ARR_DII_BOUNDARY: p = diiB.p; sz = v; break;
         case NRS_ARR_SUM_DIJ: p = sumDij.p; sz = v; break;
         case NRS_ARR_POS_PRED: p = pci_xs_current(); sz = v; break;
+        case NRS_ARR_VORTICITY:
+            if (!pbf()) return fail(NRS_E_STATE, "PBF array requested from another context");
+            if (!pbfVortValid) return fail(NRS_E_STATE, "no PBF step with vorticity confinement yet");
+            p = pbfVort.p; sz = v; break;
         default: return fail(NRS_E_INVALID, "unknown array id");
         }
         if (which == NRS_ARR_POS_PRED && !pcisph() && !pbf()) return fail(NRS_E_STATE, "PCISPH / PBF array requested from another context");
         const bool pciArray = which == NRS_ARR_VEL_ADV || which == NRS_ARR_FORCES_ADV || which == NRS_ARR_FORCES_P ||
-                              which == NRS_ARR_DENS_CORR || which == NRS_ARR_P_L || which == NRS_ARR_POS_PRED;
+                              which == NRS_ARR_DENS_CORR || which == NRS_ARR_P_L || which == NRS_ARR_POS_PRED || which == NRS_ARR_VORTICITY;
         if (pcisph() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PCISPH context");
         if (pbf() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PBF context");
         if (which >= NRS_ARR_DENS_ADV && sesph()) return fail(NRS_E_STATE, "IISPH array requested from a SESPH context");

@@ -1130,6 +1130,27 @@ template <typename R, int KSET> NRS_DEV V3<R> pbf_correct_fluid(const Params<R> 
     if (!(length(d) < P.interactionRadius)) return mk3<R>(0, 0, 0);
     return pci_scale<R>(li + lj, pci_scale<R>(P.particleMass / P.restDensity, pbf_grad<R, KSET>(P, d)));
 }
+// the tensile correction s_corr of launch B: s_ij = -k (W(x*_ij) / W_q)^4, W_q = W((dq h, 0, 0)).  Its instances are kernels of their
+// own (k_pbf_correct_s_*): a template flag on k_pbf_correct_* would rename the instances without it.
+template <typename R> struct PbfTensile {
+    R k, wq;
+};
+template <typename R, int KSET> NRS_DEV V3<R> pbf_correct_fluid_s(const Params<R> &P, V3<R> d, R li, R lj, const PbfTensile<R> &T)
+{
+    const R ir = P.interactionRadius;
+    if (!(length(d) < ir)) return mk3<R>(0, 0, 0);
+    const R r = W_dens<R, KSET>(d, ir, P.kpoly) / T.wq;
+    const R r2 = r * r;
+    const R s = -T.k * (r2 * r2);
+    return pci_scale<R>(li + lj + s, pci_scale<R>(P.particleMass / P.restDensity, pbf_grad<R, KSET>(P, d)));
+}
+// the fluid term of launch B, with or without s_corr
+template <typename R, int KSET, bool TENS>
+NRS_DEV V3<R> pbf_correct_term(const Params<R> &P, V3<R> d, R li, R lj, const PbfTensile<R> &T)
+{
+    if constexpr (TENS) return pbf_correct_fluid_s<R, KSET>(P, d, li, lj, T);
+    else return pbf_correct_fluid<R, KSET>(P, d, li, lj);
+}
 template <typename R, int KSET> NRS_DEV V3<R> pbf_correct_boundary(const Params<R> &P, V3<R> d, R psi, R li)
 {
     if (!(length(d) < P.interactionRadius)) return mk3<R>(0, 0, 0);
@@ -1188,10 +1209,10 @@ NRS_DEV PbfSums<R> pbf_lambda_walk(const Params<R> &P, const GridView<R> &G, con
     return t;
 }
 // launch B of particle i (the correction dx_i), reference order
-template <typename R, int KSET, bool HAS_B>
+template <typename R, int KSET, bool HAS_B, bool TENS = false>
 NRS_DEV V3<R> pbf_correct_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
                                const typename Vec4T<R>::type *__restrict__ xs, const R *__restrict__ lambda, uint32_t i, V3<R> pos1,
-                               V3<R> xs1, R li)
+                               V3<R> xs1, R li, PbfTensile<R> T = PbfTensile<R>{})
 {
     const R ir = P.interactionRadius, rd = P.restDensity;
     const I3 gp = calcGridPos<R>(P, pos1);
@@ -1206,7 +1227,7 @@ NRS_DEV V3<R> pbf_correct_walk(const Params<R> &P, const GridView<R> &G, const t
                     const uint32_t e = G.cellEnd[h];
                     for (uint32_t j = s; j < e; ++j) {
                         if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
-                        c = c + pbf_correct_fluid<R, KSET>(P, xs1 - xyz<R>(xs[j]), li, lambda[j]);
+                        c = c + pbf_correct_term<R, KSET, TENS>(P, xs1 - xyz<R>(xs[j]), li, lambda[j], T);
                     }
                 }
                 dx = dx + c;
@@ -1328,6 +1349,138 @@ __global__ __launch_bounds__(64) void k_pbf_prototype(Params<R> P, R spacing, in
                 cnt += 1.0;
             }
     out[0] = sx; out[1] = sy; out[2] = sz; out[3] = gg; out[4] = cnt;
+}
+
+// launch B with the tensile correction: k_pbf_correct_ref with (lambda_i + lambda_j + s_ij) on fluid pairs
+template <typename R, int KSET, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_pbf_correct_s_ref(Params<R> P, GridView<R> G, PbfArrays<R> A, PbfTensile<R> T,
+                                                             const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3<R> xs1 = xyz<R>(A.xsIn[i]);
+    pbf_correct_store<R>(A, i, xs1,
+                         pbf_correct_walk<R, KSET, HAS_B, true>(P, G, sPos, A.xsIn, A.lambda, i, xyz<R>(sPos[i]), xs1, A.lambda[i], T));
+}
+// W_q = W((dq h, 0, 0)), the reference value of s_corr, with the solver's own W.  One thread.
+template <typename R, int KSET>
+__global__ __launch_bounds__(64) void k_pbf_wq(Params<R> P, R dq, double *__restrict__ out)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    out[0] = (double)W_dens<R, KSET>(mk3<R>(dq * P.interactionRadius, 0, 0), P.interactionRadius, P.kpoly);
+}
+
+// ---- vorticity confinement (integration stage, eps_v > 0) ------------------------------------------------------------------------------
+// u = (x* - x) / dt, the velocity before XSPH.  Two launches ahead of k_pbf_integrate, over fluid neighbours only, with the XSPH walk's
+// neighbour rule:  omega_i = sum_j (m / rho0) (u_i - u_j) x grad W_spiky(x*_ij), stored as (omega, |omega|);  then
+// eta_i = sum_j (m / rho0) (|omega_j| - |omega_i|) grad W_spiky(x*_ij), N_i = eta_i / |eta_i| (0 when |eta_i| <= PBF_VORT_CUT |omega_i| / h,
+// where eta is roundoff of a locally uniform |omega| and has no direction) and vel_i = v_i + dt eps_v (N_i x omega_i), v_i the XSPH
+// velocity if XSPH ran, else u_i.  |omega| and |eta| are SReal norms (pbf_norm), not the float length() of the cut-off tests.
+constexpr double PBF_VORT_CUT = 1e-3;
+template <typename R> NRS_DEV V3<R> pbf_cross(V3<R> a, V3<R> b)
+{
+    return mk3<R>(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+template <typename R> NRS_DEV R pbf_norm(V3<R> a) { return sqrt(pbf_dot<R>(a, a)); }
+// one fluid neighbour of the vorticity sum: (m / rho0) (u_i - u_j) x grad W_spiky(d)
+template <typename R, int KSET> NRS_DEV V3<R> pbf_vort_fluid(const Params<R> &P, V3<R> d, V3<R> uj, V3<R> ui)
+{
+    if (!(length(d) < P.interactionRadius)) return mk3<R>(0, 0, 0);
+    return pbf_cross<R>(ui - uj, pci_scale<R>(P.particleMass / P.restDensity, pbf_grad<R, KSET>(P, d)));
+}
+// one fluid neighbour of the confinement sum: (m / rho0) (|omega_j| - |omega_i|) grad W_spiky(d)
+template <typename R, int KSET> NRS_DEV V3<R> pbf_eta_fluid(const Params<R> &P, V3<R> d, R wj, R wi)
+{
+    if (!(length(d) < P.interactionRadius)) return mk3<R>(0, 0, 0);
+    return pci_scale<R>((P.particleMass / P.restDensity) * (wj - wi), pbf_grad<R, KSET>(P, d));
+}
+template <typename R> NRS_DEV typename Vec4T<R>::type pbf_vort_pack(V3<R> w) { return mk4<R>(w, pbf_norm<R>(w)); }
+// v + dt eps_v (N x omega)
+template <typename R>
+NRS_DEV V3<R> pbf_confine(const Params<R> &P, V3<R> v, V3<R> eta, typename Vec4T<R>::type om, R epsV)
+{
+    const R en = pbf_norm<R>(eta);
+    if (!(en > (R)PBF_VORT_CUT * om.w / P.interactionRadius)) return v;
+    const V3<R> N = pci_scale<R>((R)1.0 / en, eta);
+    return v + pci_scale<R>(P.timestep * epsV, pbf_cross<R>(N, xyz<R>(om)));
+}
+// the vorticity sum of particle i, reference order
+template <typename R, int KSET>
+NRS_DEV V3<R> pbf_vort_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                            const typename Vec4T<R>::type *__restrict__ xs, uint32_t i, V3<R> pos1, V3<R> xs1, V3<R> u1)
+{
+    const R ir = P.interactionRadius;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    V3<R> sum = mk3<R>(0, 0, 0);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                V3<R> c = mk3<R>(0, 0, 0);
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        const V3<R> xj = xyz<R>(sPos[j]);
+                        if (j == i || !(length(pos1 - xj) < ir)) continue;
+                        const V3<R> xsj = xyz<R>(xs[j]);
+                        c = c + pbf_vort_fluid<R, KSET>(P, xs1 - xsj, pbf_vel<R>(P, xsj, xj), u1);
+                    }
+                }
+                sum = sum + c;
+            }
+    return sum;
+}
+// the confinement sum eta of particle i, reference order
+template <typename R, int KSET>
+NRS_DEV V3<R> pbf_eta_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                           const typename Vec4T<R>::type *__restrict__ xs, const typename Vec4T<R>::type *__restrict__ omega,
+                           uint32_t i, V3<R> pos1, V3<R> xs1, R wi)
+{
+    const R ir = P.interactionRadius;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    V3<R> sum = mk3<R>(0, 0, 0);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                V3<R> c = mk3<R>(0, 0, 0);
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
+                        c = c + pbf_eta_fluid<R, KSET>(P, xs1 - xyz<R>(xs[j]), omega[j].w, wi);
+                    }
+                }
+                sum = sum + c;
+            }
+    return sum;
+}
+// vorticity launch: omega[i] = (omega_i, |omega_i|)
+template <typename R, int KSET>
+__global__ __launch_bounds__(BLOCK) void k_pbf_vorticity_ref(Params<R> P, GridView<R> G, const typename Vec4T<R>::type *__restrict__ sPos,
+                                                             const typename Vec4T<R>::type *__restrict__ xs,
+                                                             typename Vec4T<R>::type *__restrict__ omega, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3<R> pos1 = xyz<R>(sPos[i]), xs1 = xyz<R>(xs[i]);
+    omega[i] = pbf_vort_pack<R>(pbf_vort_walk<R, KSET>(P, G, sPos, xs, i, pos1, xs1, pbf_vel<R>(P, xs1, pos1)));
+}
+// confinement launch: vel[i] = v_i + dt eps_v (N_i x omega_i), v_i = vel[i] (velGiven: the XSPH launch ran) or u_i
+template <typename R, int KSET>
+__global__ __launch_bounds__(BLOCK) void k_pbf_confine_ref(Params<R> P, GridView<R> G, const typename Vec4T<R>::type *__restrict__ sPos,
+                                                           const typename Vec4T<R>::type *__restrict__ xs,
+                                                           const typename Vec4T<R>::type *__restrict__ omega,
+                                                           typename Vec4T<R>::type *__restrict__ vel, int velGiven, R epsV, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const V3<R> pos1 = xyz<R>(sPos[i]), xs1 = xyz<R>(xs[i]);
+    const typename Vec4T<R>::type om = omega[i];
+    const V3<R> v = velGiven ? xyz<R>(vel[i]) : pbf_vel<R>(P, xs1, pos1);
+    vel[i] = mk4<R>(pbf_confine<R>(P, v, pbf_eta_walk<R, KSET>(P, G, sPos, xs, omega, i, pos1, xs1, om.w), om, epsV), (R)0.0);
 }
 
 // deterministic two-pass sum of an SReal array in double (replaces thrust::reduce, sph_cuda.cu:816-819)

@@ -8,8 +8,14 @@
 
 NEREUS_NAMESPACE_BEGIN
 
-PBF::PBF() : SPH(), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_minIters(2) {}
-PBF::PBF(SphSimParams params) : SPH(params), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_minIters(2) {}
+PBF::PBF()
+    : SPH(), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_tensileK(0.0f), m_tensileDq(0.2f), m_vorticity(0.0f), m_minIters(2)
+{
+}
+PBF::PBF(SphSimParams params)
+    : SPH(params), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_tensileK(0.0f), m_tensileDq(0.2f), m_vorticity(0.0f), m_minIters(2)
+{
+}
 PBF::~PBF() {}
 
 int PBF::solverKind() const { return NRS_SOLVER_PBF; }
@@ -26,10 +32,31 @@ void PBF::setSolverSettings(SReal eta, SUint minIters, SReal relaxation, SReal x
     m_xsph = xsph;
 }
 
+void PBF::setTensileCorrection(SReal k, SReal dq)
+{
+    if (m_ctx) {
+        std::fprintf(stderr, "Nereus: PBF::setTensileCorrection must be called before the first update() / updateGpuBoundaries()\n");
+        std::exit(EXIT_FAILURE);
+    }
+    m_tensileK = k;
+    m_tensileDq = dq;
+}
+
+void PBF::setVorticityConfinement(SReal eps)
+{
+    if (m_ctx) {
+        std::fprintf(stderr, "Nereus: PBF::setVorticityConfinement must be called before the first update() / updateGpuBoundaries()\n");
+        std::exit(EXIT_FAILURE);
+    }
+    m_vorticity = eps;
+}
+
 void PBF::configureContext()
 {
     if (nrs_pbf_configure(m_ctx, (double)m_eta, (uint32_t)m_minIters, (double)m_relaxation, (double)m_xsph) != NRS_OK)
         fatal("nrs_pbf_configure");
+    if (nrs_pbf_set_tensile(m_ctx, (double)m_tensileK, (double)m_tensileDq) != NRS_OK) fatal("nrs_pbf_set_tensile");
+    if (nrs_pbf_set_vorticity(m_ctx, (double)m_vorticity) != NRS_OK) fatal("nrs_pbf_set_vorticity");
 }
 
 SUint PBF::getLastIterations()

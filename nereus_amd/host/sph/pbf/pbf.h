@@ -17,12 +17,17 @@ public:
     // updateGpuBoundaries().  eta = largest density error max(rho - rho0, 0) / rho0 the loop accepts (0: exactly minIters iterations,
     // nothing read back), relaxation = eps / D_proto, xsph = the XSPH velocity smoothing factor (0 = off).
     void setSolverSettings(SReal eta, SUint minIters, SReal relaxation, SReal xsph);
+    // Tensile correction s_corr = -k (W / W((dq h, 0, 0)))^4 on fluid pairs (nrs_pbf_set_tensile; k = 0: off) and vorticity
+    // confinement with factor eps (nrs_pbf_set_vorticity; 0: off).  Same rule as setSolverSettings: before the context exists.
+    void setTensileCorrection(SReal k, SReal dq);
+    void setVorticityConfinement(SReal eps);
     SUint getLastIterations(); // solver iterations of the last step
     int solverKind() const override;
 
 protected:
     void configureContext() override; // hands the settings to every context ensureContext creates (a capacity change replaces it)
     SReal m_eta, m_relaxation, m_xsph;
+    SReal m_tensileK, m_tensileDq, m_vorticity;
     SUint m_minIters;
 };
 

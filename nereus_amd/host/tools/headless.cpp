@@ -3,8 +3,10 @@
 //
 //   headless params  <sesph|iisph> <out.bin>                    constructor-default SphSimParams bytes
 //   headless run     <sesph|iisph> <in.bin> <steps> <out.bin>   particles/boundaries from a file (also pcisph: the reference's
-//                                                               stub, pcisph-solve: PCISPH::setPressureSolve(true), and pbf:
-//                                                               Nereus::PBF with its default settings)
+//                                                               stub, pcisph-solve: PCISPH::setPressureSolve(true), pbf:
+//                                                               Nereus::PBF with its default settings, and pbf-full: PBF with
+//                                                               XSPH 0.01, the tensile correction k = 1e-4, dq = 0.2 and
+//                                                               vorticity confinement eps_v = 0.01)
 //   headless resume  <sesph|iisph> <in.bin> <steps_a> <steps_b> <ckpt> <out.bin>   run steps_a, saveState, then a NEW
 //                                                               solver loadState()s and runs steps_b (boundaries re-set)
 //   headless cfl     sesph <in.bin> <steps> <out.bin>           run with setAdaptiveTimestep(true)
@@ -69,10 +71,16 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool iisph = kind == "iisph", pcisphSolve = kind == "pcisph-solve", pcisph = kind == "pcisph" || pcisphSolve;
-    const bool pbf = kind == "pbf";
+    const bool pbfFull = kind == "pbf-full", pbf = kind == "pbf" || pbfFull;
     Nereus::SPH *sim = iisph ? (Nereus::SPH *)new Nereus::IISPH()
                              : (pcisph ? (Nereus::SPH *)new Nereus::PCISPH() : (pbf ? (Nereus::SPH *)new Nereus::PBF() : new Nereus::SPH()));
     if (pcisphSolve) static_cast<Nereus::PCISPH *>(sim)->setPressureSolve(true);
+    if (pbfFull) {
+        Nereus::PBF *p = static_cast<Nereus::PBF *>(sim);
+        p->setSolverSettings((SReal)0.01, 2, (SReal)0.01, (SReal)0.01);
+        p->setTensileCorrection((SReal)1e-4, (SReal)0.2);
+        p->setVorticityConfinement((SReal)0.01);
+    }
     sim->_initialize();
     std::vector<SVec4> bi;
     std::vector<SReal> vbi;
