@@ -3,6 +3,7 @@ particle clouds with random grid geometry, wall sheets, precision, kernel set an
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,3 +32,60 @@ def test_random_slab_runs_equal_single_domain(hip_lib):
                        timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     assert "12 seeds, 0 failures" in r.stdout and "'migrants': 0," not in r.stdout
+
+
+def _classes(seeds, solver):
+    from fuzz_parity import make_scene
+    c = dict(fp64=0, narrow_x=0, far=0, nonfinite=0, resort=0, walls=0, monaghan=0)
+    for sd in seeds:
+        sc = make_scene(sd, solver)
+        c["fp64"] += sc["double"]
+        c["narrow_x"] += sc["gs"][0] < 4
+        c["far"] += sd % 17 == 16
+        c["nonfinite"] += not np.all(np.isfinite(sc["pos"]))
+        c["resort"] += sc["n"] >= 40000
+        c["walls"] += sc["bi"] is not None
+        c["monaghan"] += sc["kset"] == 0
+    return c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("solver", ["pcisph", "pbf"])
+def test_random_scenes_pcisph_pbf_production_equals_reference_order(hip_lib, solver):
+    """The soak's scenes with PCISPH / PBF (PBF: random eta, min_iters, relaxation, XSPH, tensile and vorticity settings): production
+    kernels == reference-order kernels bit for bit at STAGE_P_ADVECT, at STAGE_P_SOLVE and after 3 steps (6 on the coherent re-sort
+    seed).  Seeds 9000-9039 cover fp32 and fp64 (6 seeds), 3 narrow-x grids (1-2 cells: no quantised scan, no hit lists), 2 far origins
+    (owners beyond the quanta's budget: wall workgroups' exact scan / far-owner path), 2 scenes with NaN / inf coordinates, 3 coherent
+    re-sort seeds, wall sheets and both kernel sets."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from fuzz_parity import SOLVERS, one
+
+    seeds = range(9000, 9040)
+    c = _classes(seeds, SOLVERS[solver])
+    assert c["fp64"] >= 5 and c["narrow_x"] >= 3 and c["far"] >= 2 and c["nonfinite"] >= 2 and c["resort"] >= 1 and c["walls"] >= 15, c
+    failures = [r for r in (one(sd, SOLVERS[solver]) for sd in seeds) if r]
+    assert not failures, failures[:3]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("solver", ["pcisph", "pbf"])
+def test_random_scenes_pcisph_pbf_device_equals_model(hip_lib, solver):
+    """The device against the float64 models on pieces of the soak's scenes (tools/fuzz_parity.py one_vs_model): one fixed iteration,
+    both paths, fp32 and fp64, Muller and Monaghan, far origins and wall sheets, PBF with random relaxation, XSPH and tensile settings;
+    only geometry where the device's candidate rule is the models' (every cell edge >= h, every grid axis >= 4 cells, see
+    make_model_scene).  A scene whose model result is not finite, or a Monaghan scene with a pair within 1e-5 of the cut-off h (where
+    the truncated Monaghan W jumps, MONAGHAN_CUT_MARGIN), is not comparable: counted, at most 10 % of the slice."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from fuzz_parity import SOLVERS, make_model_scene, one_vs_model
+
+    seeds = range(9100, 9140)
+    scenes = [make_model_scene(sd, SOLVERS[solver]) for sd in seeds]
+    assert sum(sc["double"] for sc in scenes) >= 5 and sum(sc["kset"] == 0 for sc in scenes) >= 10
+    assert sum(sd % 17 == 16 for sd in seeds) >= 2 and sum(sc["bi"] is not None for sc in scenes) >= 15
+    assert 5 <= sum(sc["ref"] for sc in scenes) <= 35
+    assert all(min(sc["gs"]) >= 4 and np.all(sc["cs"] >= sc["h"]) for sc in scenes)
+    results = [one_vs_model(sd, SOLVERS[solver]) for sd in seeds]
+    failures = [r for r in results if r and r not in ("not comparable", "near cut")]
+    assert not failures, failures[:3]
+    skipped = results.count("not comparable") + results.count("near cut")
+    assert skipped <= len(seeds) // 10, (results.count("not comparable"), results.count("near cut"))

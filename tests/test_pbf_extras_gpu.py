@@ -50,17 +50,24 @@ def test_list_kernels_equal_reference_order_bitwise(hip_lib, xsph):
             np.testing.assert_array_equal(a, b, err_msg="scene %d %s" % (k, nm))
 
 
-def _advected_dam(double):
+def _advected_dam(double, kernel_set=capi.MULLER):
     """the small dam break squeezed to 0.87 (as tests/test_pcisph_gpu.py's _scenes: the particles along the floor and the walls are
     compressed) and set swirling about z, after 3 plain PBF steps: a moving state without the symmetry of the lattice that is still
-    compressed enough for lambda to be well above fp32 roundoff (C = rho* / rho0 - 1 cancels)"""
-    p, sc = small_dam_break(double=double)
+    compressed enough for lambda to be well above fp32 roundoff (C = rho* / rho0 - 1 cancels).  Monaghan (tests/test_pcisph_gpu.py
+    _monaghan_scenes): squeezed to 0.65, time step 2e-4, and no plain steps — its loop relaxes the compression within them; the
+    jittered lattice has no exact symmetry either."""
+    p, sc = small_dam_break(double=double, kernel_set=kernel_set)
+    mon = kernel_set == capi.MONAGHAN
+    if mon:
+        p["timestep"] = 2e-4
     pos = sc["pos"].copy()
     lo = pos[:, :3].min(axis=0)
-    pos[:, :3] = (lo + (pos[:, :3] - lo) * 0.87).astype(pos.dtype)
+    pos[:, :3] = (lo + (pos[:, :3] - lo) * (0.65 if mon else 0.87)).astype(pos.dtype)
     vel = np.zeros_like(pos)
     vel[:, :3] = np.cross([0.0, 0.0, 5.0], pos[:, :3] - pos[:, :3].mean(axis=0))
-    s = _pbf(p, pos, vel, sc["bi"], sc["vbi"], double=double)
+    if mon:
+        return p, pos, vel, sc["bi"], sc["vbi"]
+    s = _pbf(p, pos, vel, sc["bi"], sc["vbi"], double=double, kernel_set=kernel_set)
     s.step(3)
     pos, vel = s.download()
     s.close()
@@ -71,10 +78,23 @@ def _advected_dam(double):
 @pytest.mark.parametrize("ref", [False, True])
 @pytest.mark.parametrize("iters", [1, 3])
 def test_device_matches_model(hip_lib, double, tol, ref, iters):
-    eps_v = 2.0   # a kick well above the velocity tolerance
-    p, pos, vel, bi, vbi = _advected_dam(double)
+    _device_matches_model(double, tol, ref, iters, capi.MULLER)
+
+
+@pytest.mark.parametrize("double,tol", [(False, 1e-4), (True, 1e-10)])
+@pytest.mark.parametrize("ref", [False, True])
+@pytest.mark.parametrize("iters", [1, 3])
+def test_monaghan_device_matches_model(hip_lib, double, tol, ref, iters):
+    """test_device_matches_model with the Monaghan kernels: W, W_q and the gradient of lambda, s_corr, omega and eta are the Monaghan
+    branch, against the model's Monaghan restatement; the context builds no hit lists."""
+    _device_matches_model(double, tol, ref, iters, capi.MONAGHAN)
+
+
+def _device_matches_model(double, tol, ref, iters, kernel_set):
+    eps_v = 2.0 if kernel_set == capi.MULLER else 10.0   # a kick well above the velocity tolerance (Monaghan: dt is 1 / 5)
+    p, pos, vel, bi, vbi = _advected_dam(double, kernel_set)
     xsph = 0.1 if iters == 3 else 0.0
-    s = _pbf(p, pos, vel, bi, vbi, double=double, reference_order=ref)
+    s = _pbf(p, pos, vel, bi, vbi, double=double, reference_order=ref, kernel_set=kernel_set)
     s.pbf_configure(0.0, iters, 0.01, xsph)
     s.pbf_set_tensile(K, DQ)
     s.pbf_set_vorticity(eps_v)
@@ -88,9 +108,13 @@ def test_device_matches_model(hip_lib, double, tol, ref, iters):
     s.step(1)
     dev["pos"], dev["vel"] = s.download()
     dev["omega"] = s.get("vorticity")
+    if kernel_set == capi.MONAGHAN:
+        with pytest.raises(capi.NereusError, match="error -4"):
+            s.get_stat(capi.STAT_HIT_MEAN)
     s.close()
-    m = M.run(p, x, va, bs[:, :3], bs[:, 3], eps=eps, min_iters=iters, eta=0.0, xsph=xsph, k=K, dq=DQ, eps_v=eps_v)
-    plain = M.run(p, x, va, bs[:, :3], bs[:, 3], eps=eps, min_iters=iters, eta=0.0, xsph=xsph)
+    np.testing.assert_allclose(eps, 0.01 * M.prototype_d(p, kernel_set)[0], rtol=1e-5)
+    m = M.run(p, x, va, bs[:, :3], bs[:, 3], eps=eps, min_iters=iters, eta=0.0, xsph=xsph, k=K, dq=DQ, eps_v=eps_v, kernel_set=kernel_set)
+    plain = M.run(p, x, va, bs[:, :3], bs[:, 3], eps=eps, min_iters=iters, eta=0.0, xsph=xsph, kernel_set=kernel_set)
     assert rel_err(m["xs"] - plain["xs"], np.zeros_like(m["xs"])) > 0   # s_corr moves x*
     assert m["lam"].min() < 0
     assert rel_err(dev["P_l"], m["lam"]) <= tol

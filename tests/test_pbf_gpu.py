@@ -10,7 +10,7 @@ from nereus_amd import capi, scene
 from tests import pbf_model
 from tests.common import compressed_block, rel_err, small_dam_break
 from tests.oracle_lib import IISPH, SESPH, Oracle
-from tests.test_pcisph_gpu import _bitwise_scenes, _scenes, _solver
+from tests.test_pcisph_gpu import _bitwise_scenes, _monaghan_scenes, _scenes, _solver
 
 pytestmark = pytest.mark.gpu
 
@@ -65,8 +65,8 @@ def test_list_kernels_equal_reference_order_bitwise(hip_lib, xsph):
             np.testing.assert_array_equal(a, b, err_msg="scene %d %s" % (k, nm))
 
 
-def _device_and_model(p, pos, vel, bi, vbi, double, ref, min_iters, cap=50, eta=0.0, xsph=0.0):
-    s = _pbf(p, pos, vel, bi, vbi, double=double, reference_order=ref)
+def _device_and_model(p, pos, vel, bi, vbi, double, ref, min_iters, cap=50, eta=0.0, xsph=0.0, kernel_set=capi.MULLER):
+    s = _pbf(p, pos, vel, bi, vbi, double=double, reference_order=ref, kernel_set=kernel_set)
     s.pbf_configure(eta, min_iters, 0.01, xsph)
     s.set_max_iterations(cap)
     s.step_partial(capi.STAGE_P_ADVECT)
@@ -81,9 +81,12 @@ def _device_and_model(p, pos, vel, bi, vbi, double, ref, min_iters, cap=50, eta=
     s.set_particles(pos, vel)
     s.step(1)
     dev["pos"], dev["vel"], dev["pressure"] = s.download(pressure=True)
+    if kernel_set == capi.MONAGHAN:   # no list kernels for Monaghan (Features::listKernels): the context builds no hit lists
+        with pytest.raises(capi.NereusError, match="error -4"):
+            s.get_stat(capi.STAT_HIT_MEAN)
     s.close()
     m = pbf_model.run(p, x, va, None if bs is None else bs[:, :3], None if bs is None else bs[:, 3], eps=dev["eps"],
-                      min_iters=min_iters, cap=cap, eta=eta, xsph=xsph)
+                      min_iters=min_iters, cap=cap, eta=eta, xsph=xsph, kernel_set=kernel_set)
     return dev, m
 
 
@@ -123,6 +126,46 @@ def test_exit_rule_matches_model(hip_lib, double, ref):
         assert dev["error"] <= 0.01 or dev["iters"] == 50
         if name == "block":
             assert 1 < m["iters"] < 50 and m["errors"][-1] <= 0.01 < m["errors"][0], m["errors"]
+
+
+@pytest.mark.parametrize("double,tol", [(False, 1e-4), (True, 1e-10)])
+@pytest.mark.parametrize("ref", [False, True])
+@pytest.mark.parametrize("iters", [1, 3])
+def test_monaghan_device_matches_model_fixed_iterations(hip_lib, double, tol, ref, iters):
+    """The Monaghan branch of W_dens / pbf_grad and of k_pbf_prototype against the model (tests/test_pcisph_gpu.py's Monaghan scenes:
+    the 0.68 h block and the dam break squeezed to 0.7, time step 2e-4), with the bars of the Muller test.  The Monaghan loop relaxes
+    the layer along the walls faster: after 3 iterations at least 25 particles next to a wall are still compressed (Muller: 50)."""
+    for name, p, pos, vel, bi, vbi in _monaghan_scenes(double):
+        xsph = 0.1 if iters == 3 else 0.0
+        dev, m = _device_and_model(p, pos, vel, bi, vbi, double, ref, iters, cap=1, xsph=xsph, kernel_set=capi.MONAGHAN)
+        assert dev["iters"] == m["iters"] == iters
+        want = 0.01 * pbf_model.prototype_d(p, capi.MONAGHAN)[0]
+        np.testing.assert_allclose(dev["eps"], want, rtol=1e-5)
+        assert abs(want / (0.01 * pbf_model.prototype_d(p)[0]) - 1) > 0.5   # (not the Muller prototype's eps)
+        assert m["lam"].min() < 0, name
+        if bi is not None:
+            near = pbf_model._len(m["xs"][:, None, :] - bi[None, :, :3]).min(axis=1) < float(p["interactionRadius"][0])
+            assert np.count_nonzero(m["lam"][near] < 0) >= (50 if iters == 1 else 25), name
+        for nm, want in (("densCorr", m["rho"]), ("P_l", m["lam"]), ("forcesP", m["dx"]), ("posPred", m["xs"])):
+            got = dev[nm][:, :3] if want.ndim == 2 else dev[nm]
+            assert rel_err(got, want) <= tol, (name, nm, rel_err(got, want))
+        assert rel_err(dev["pos"][:, :3], m["pos"]) <= tol, name
+        assert rel_err(dev["vel"][:, :3], m["vel"]) <= 10 * tol, (name, rel_err(dev["vel"][:, :3], m["vel"]))
+        assert rel_err(dev["pressure"], m["lam"]) <= tol, name
+        assert abs(dev["error"] - m["errors"][-1]) <= 2 * tol, name
+
+
+@pytest.mark.parametrize("double,ref", [(True, True), (False, False)])
+def test_monaghan_exit_rule_matches_model(hip_lib, double, ref):
+    """Monaghan, eta rule with min_iters 1: the 0.68 h block converges after more than min_iters iterations, every error clear of
+    eta (relative margin 1e-3)."""
+    name, p, pos, vel, bi, vbi = _monaghan_scenes(double)[0]
+    dev, m = _device_and_model(p, pos, vel, bi, vbi, double, ref, 1, eta=0.01, kernel_set=capi.MONAGHAN)
+    for e in m["errors"]:
+        assert abs(e - 0.01) >= 1e-3 * 0.01, m["errors"]
+    assert dev["iters"] == m["iters"], (dev["iters"], m["iters"], m["errors"])
+    assert 1 < m["iters"] < 50 and m["errors"][-1] <= 0.01 < m["errors"][0], m["errors"]
+    assert dev["error"] <= 0.01
 
 
 def test_fixed_count_mode_runs_exactly_min_iters(hip_lib):

@@ -102,8 +102,8 @@ def test_list_kernels_equal_reference_order_bitwise(hip_lib):
             np.testing.assert_array_equal(a, b, err_msg="scene %d %s" % (k, nm))
 
 
-def _device_and_model(p, pos, vel, bi, vbi, double, ref, min_iters, cap, eta=0.01):
-    s = _solver(p, pos, vel, bi, vbi, double=double, reference_order=ref)
+def _device_and_model(p, pos, vel, bi, vbi, double, ref, min_iters, cap, eta=0.01, kernel_set=capi.MULLER):
+    s = _solver(p, pos, vel, bi, vbi, double=double, reference_order=ref, kernel_set=kernel_set)
     s.pcisph_configure(eta, min_iters)
     s.set_max_iterations(cap)
     s.step_partial(capi.STAGE_P_ADVECT)
@@ -118,9 +118,12 @@ def _device_and_model(p, pos, vel, bi, vbi, double, ref, min_iters, cap, eta=0.0
     s.set_particles(pos, vel)
     s.step(1)
     dev["pos"], dev["vel"], dev["pressure"] = s.download(pressure=True)
+    if kernel_set == capi.MONAGHAN:   # no list kernels for Monaghan (Features::listKernels): the context builds no hit lists
+        with pytest.raises(capi.NereusError, match="error -4"):
+            s.get_stat(capi.STAT_HIT_MEAN)
     s.close()
     m = pcisph_model.run(p, x, va, None if bs is None else bs[:, :3], None if bs is None else bs[:, 3], delta=dev["delta"],
-                         min_iters=min_iters, cap=cap, eta=eta)
+                         min_iters=min_iters, cap=cap, eta=eta, kernel_set=kernel_set)
     return dev, m
 
 
@@ -162,6 +165,65 @@ def test_default_exit_rule_matches_model(hip_lib, double, ref):
         if min_iters == 1:
             assert 1 < m["iters"] < 50 and m["errors"][-1] <= 0.01 < m["errors"][0], m["errors"]
             assert dev["error"] <= 0.01
+
+
+def _monaghan_scenes(double, squeeze=0.7, ratio=0.68):
+    """Monaghan densities at a given spacing are far below Muller's: the block at spacing 0.68 h (max rho* 1.2 rho0) and the dam-break
+    column squeezed to 0.7 (its floor and wall particles compressed) give the solve something to correct.  The time step is 2e-4: with
+    these parameters the Monaghan advection throws the particles next to the walls more than h off them in a step of 1e-3 (|vel_adv|
+    ~ 66 m/s), after which no boundary term is left to test.  With the prototype's delta the Monaghan loop does not converge on either
+    scene (its error grows over the iterations, DESIGN.md "PCISPH"), so the model comparison runs 3 fixed iterations."""
+    p, pos, vel = compressed_block(double=double, kernel_set=capi.MONAGHAN, ratio=ratio)
+    p2, sc = small_dam_break(double=double, kernel_set=capi.MONAGHAN)
+    for q in (p, p2):
+        q["timestep"] = 2e-4
+    dpos = sc["pos"].copy()
+    lo = dpos[:, :3].min(axis=0)
+    dpos[:, :3] = (lo + (dpos[:, :3] - lo) * squeeze).astype(dpos.dtype)
+    return [("block", p, pos, vel, None, None), ("dam", p2, dpos, sc["vel"], sc["bi"], sc["vbi"])]
+
+
+@pytest.mark.parametrize("double,tol", [(True, 1e-10), (False, 1e-4)])
+@pytest.mark.parametrize("ref", [False, True])
+def test_monaghan_device_matches_model_fixed_iterations(hip_lib, double, tol, ref):
+    """The Monaghan branch of W_dens / W_grad and of k_pci_prototype against the model's independent restatement (pinned to the
+    reference's Wmonaghan / Wmonaghan_grad by tests/test_model_kernels_pin.py), with the bars of the Muller test."""
+    for name, p, pos, vel, bi, vbi in _monaghan_scenes(double):
+        dev, m = _device_and_model(p, pos, vel, bi, vbi, double, ref, 3, 3, kernel_set=capi.MONAGHAN)
+        want, count = pcisph_model.prototype_delta(p, kernel_set=capi.MONAGHAN)
+        assert count == 6
+        np.testing.assert_allclose(dev["delta"], want, rtol=1e-5)
+        assert abs(want / pcisph_model.prototype_delta(p)[0] - 1) > 1   # (not the Muller prototype's delta)
+        assert dev["iters"] == m["iters"] == 3
+        assert m["p"].max() > 0, name
+        if bi is not None:
+            near = m["near_boundary"]
+            assert np.count_nonzero(m["p"][near] > 0) >= 50
+            assert np.abs(m["fp_boundary"][near & (m["p"] > 0)]).max() > 0
+            assert rel_err(m["fp"] - 2 * m["fp_boundary"], m["fp"]) > 100 * tol
+        for nm, want in (("densCorr", m["rho"]), ("P_l", m["p"]), ("forcesP", m["fp"]), ("posPred", m["xs"])):
+            got = dev[nm][:, :3] if want.ndim == 2 else dev[nm]
+            assert rel_err(got, want) <= tol, (name, nm, rel_err(got, want))
+        assert rel_err(dev["pos"][:, :3], m["pos"]) <= tol, name
+        assert rel_err(dev["vel"][:, :3], m["vel"]) <= tol, name
+        assert rel_err(dev["pressure"], m["p"]) <= tol, name
+        assert abs(dev["error"] - m["errors"][-1]) <= 2 * tol, name
+
+
+@pytest.mark.parametrize("double,ref", [(True, True), (False, False)])
+def test_monaghan_exit_rule_matches_model(hip_lib, double, ref):
+    """Monaghan, default exit rule: the 0.68 h block runs to the cap (every error after min_iters well above eta) and the dam break
+    squeezed only to 0.8 has no error from the start (stops at min_iters)."""
+    block = _monaghan_scenes(double)[0]
+    dam = _monaghan_scenes(double, squeeze=0.8)[1]
+    for (name, p, pos, vel, bi, vbi), want in ((block, 50), (dam, 3)):
+        dev, m = _device_and_model(p, pos, vel, bi, vbi, double, ref, 3, 50, kernel_set=capi.MONAGHAN)
+        for l, e in enumerate(m["errors"], 1):
+            if l >= 3:
+                assert abs(e - 0.01) >= 1e-3 * 0.01, (name, l, e)
+        assert dev["iters"] == m["iters"] == want, (name, dev["iters"], m["iters"], m["errors"])
+        if want == 50:
+            assert min(m["errors"][2:]) > 0.05 and dev["error"] > 0.01
 
 
 def test_delta_and_convergence_on_compressed_block(hip_lib):
