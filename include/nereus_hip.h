@@ -62,9 +62,9 @@ typedef struct nrs_ctx nrs_ctx;
 
 /* Nereus::SPH (sph/sph.h:23) / Nereus::IISPH (iisph.h:8) / predictive-corrective PCISPH (Solenthaler & Pajarola 2009; the
  * reference's Nereus::PCISPH stops after the density, its pressure solve is an empty stub: DESIGN.md "PCISPH" defines this one) /
- * position-based fluids (Macklin & Mueller 2013; DESIGN.md "PBF").  PBF came after nrs_version() 0.3 without a version change: a
- * library supports it when nrs_create accepts NRS_SOLVER_PBF. */
-enum { NRS_SOLVER_SESPH = 0, NRS_SOLVER_IISPH = 1, NRS_SOLVER_PCISPH = 2, NRS_SOLVER_PBF = 3 };
+ * position-based fluids (Macklin & Mueller 2013; DESIGN.md "PBF") / divergence-free SPH (Bender & Koschier 2015; DESIGN.md "DFSPH").
+ * PBF and DFSPH came after nrs_version() 0.3 without a version change: a library supports one when nrs_create accepts its id. */
+enum { NRS_SOLVER_SESPH = 0, NRS_SOLVER_IISPH = 1, NRS_SOLVER_PCISPH = 2, NRS_SOLVER_PBF = 3, NRS_SOLVER_DFSPH = 4 };
 enum { NRS_KERNELS_MONAGHAN = 0, NRS_KERNELS_MULLER = 1 }; /* KERNEL_SET, common/common.h:14-15 */
 
 /* nrs_config.flags */
@@ -85,7 +85,7 @@ enum {
                                            (calcGridPos keeps its true division); densities, forces and the integrated state agree
                                            with the default reference-order IEEE arithmetic to ~1e-6 relative per step.  The
                                            reference itself is built with --use_fast_math (CMakeLists.txt:85).  Ignored (exact
-                                           arithmetic) for fp64, Monaghan kernels, IISPH, PCISPH and NRS_FLAG_REFERENCE_ORDER. */
+                                           arithmetic) for fp64, Monaghan kernels, IISPH, PCISPH, PBF, DFSPH and NRS_FLAG_REFERENCE_ORDER. */
     NRS_FLAG_IISPH_SELF_BY_SLOT = 1u << 6, /* IISPH: computePressure / computePressureForce exclude the particle ITSELF from their
                                            neighbour sums.  The reference excludes the slot whose number equals the CUDA thread
                                            id instead (sph_kernel_impl.cuh:1412,1568), which makes its result depend
@@ -99,7 +99,7 @@ enum {
                                            per 64 consecutive sorted slots, row hulls by ballot + readlane, one z-plane of candidates
                                            staged in LDS) instead of the quantised global-memory scan.  Same lists, same sums, bit for
                                            bit; measured slower, kept as the north-star's literal kernel shape.
-                                           Ignored by IISPH and PCISPH contexts (their one scan publishes the wide hit lists) */
+                                           Ignored by IISPH, PCISPH, PBF and DFSPH contexts (their one scan publishes the wide hit lists) */
     NRS_FLAG_IISPH_INPLACE_P = 1u << 1, /* reserved: the reference's racy in-place Jacobi is NOT
                                            offered; P_l is always double-buffered */
 };
@@ -131,7 +131,9 @@ typedef struct nrs_config {
 /* Pipeline stages, for nrs_step_partial / nrs_stage_ms.  Order is the order of SPH::update()
  * (sph/sph.cpp:233-284) and IISPH::update() (sph/iisph/iisph.cpp:172-216).  A PCISPH step is HASH, SORT, REORDER, DENSITY
  * (density only, no Tait pressure), then the P_* stages; nrs_step_partial on a PCISPH context accepts those and refuses the others.
- * A PBF step has the same stages (and the same refusals). */
+ * PBF and DFSPH steps have the same stages (and the same refusals).  DFSPH: DENSITY also holds the factor launch (alpha), P_ADVECT
+ * the divergence solve on the sorted velocities ahead of the advection launch, P_SOLVE the density solve on vel_adv, P_INTEGRATE
+ * v = vel_adv, x += dt v. */
 enum {
     NRS_STAGE_HASH = 1,      /* calcHash                     sph_cuda.cu:230 */
     NRS_STAGE_SORT = 2,      /* sortParticles                sph_cuda.cu:58 */
@@ -189,6 +191,14 @@ enum {
                                and nrs_download(pres) give lambda */
     NRS_ARR_VORTICITY = 31, /* PBF: SVec4[N] sorted (omega, |omega|) of the last step that had vorticity confinement on
                                (nrs_pbf_set_vorticity); NRS_E_STATE before there is one */
+    NRS_ARR_DFSPH_ALPHA = 32,   /* DFSPH: SReal[N] sorted alpha = 1 / D of the last factor launch (NRS_E_STATE on other contexts
+                                   and before a step).  On a DFSPH context NRS_ARR_DENS holds rho, _SORTED_VEL after P_ADVECT the
+                                   divergence-free v, _VEL_ADV v* after the density solve, _FORCES_ADV the non-pressure forces,
+                                   _DENS_CORR rho_adv and _P_L kappa of the last density iteration; NRS_ARR_PRES, NRS_ARR_PRESSURE and
+                                   nrs_download(pres) hold K (m^2, the warm-start total; after a partial step up to P_ADVECT NRS_ARR_PRES
+                                   is the sorted K_prev of the step).  NRS_ARR_POS_PRED is refused. */
+    NRS_ARR_DFSPH_KAPPA_V = 33, /* DFSPH: SReal[N] sorted Kv, the divergence solve's total (after a partial step up to DENSITY the
+                                   sorted Kv_prev of the step); NRS_E_STATE on other contexts and before a step */
 };
 
 const char *nrs_last_error(void);
@@ -261,10 +271,11 @@ int nrs_get_array(nrs_ctx *ctx, int which, void *dst, uint64_t dst_bytes, uint64
  * i.e. read it after each step).  For zero-copy consumers (renderer VBO upload, halo packing). */
 int nrs_device_ptr(nrs_ctx *ctx, int which, void **dptr, uint64_t *bytes);
 
-/* IISPH / PCISPH / PBF: solver iterations of the last step (the `l` of sph_cuda.cu:736). */
+/* IISPH / PCISPH / PBF / DFSPH: solver iterations of the last step (the `l` of sph_cuda.cu:736; DFSPH: the density solve's). */
 int nrs_last_iterations(nrs_ctx *ctx, uint32_t *iters);
-/* Cap on IISPH / PCISPH / PBF solver iterations per step.  0 = none for IISPH, as the reference; 0 = 50 for PCISPH and PBF (their
- * loops need not end; a PBF step in fixed-count mode ignores the cap). */
+/* Cap on IISPH / PCISPH / PBF / DFSPH solver iterations per step.  0 = none for IISPH, as the reference; 0 = 50 for PCISPH and PBF
+ * (their loops need not end; a PBF step in fixed-count mode ignores the cap); 0 = 100 for each of DFSPH's two loops (a loop in
+ * fixed-count mode ignores it). */
 int nrs_set_max_iterations(nrs_ctx *ctx, uint32_t max_iters);
 
 /* PCISPH solver settings (NRS_E_STATE on any other context).  The loop stops after the iteration l with l >= min_iters and
@@ -290,6 +301,15 @@ int nrs_pbf_set_tensile(nrs_ctx *ctx, double k, double dq);
 /* PBF vorticity confinement (NRS_E_STATE on any other context): at the end of the step vel_i += dt eps_v (N_i x omega_i),
  * DESIGN.md "PBF".  Default 0 (off).  NRS_E_INVALID for a NaN, infinite or negative eps_v. */
 int nrs_pbf_set_vorticity(nrs_ctx *ctx, double eps_v);
+/* DFSPH solver settings (NRS_E_STATE on any other context), DESIGN.md "DFSPH".  Each loop (the density solve, and the divergence
+ * solve) stops after the iteration l with l >= its minimum and avg_i e_i <= its error, or at the iteration cap
+ * (nrs_set_max_iterations, 0 = 100); an error of 0 runs exactly the minimum and reads nothing back during the step (fixed-count
+ * mode).  e_i = max(rho_adv_i - rho0, 0) / rho0 in the density solve, max(dt div_i, 0) in the divergence solve.
+ * min_divergence_iters = 0 turns the divergence solve off.  warm_start = 1: each solve starts with one extra pair of launches from
+ * half the previous step's total (K, Kv).  Defaults: 1e-3, 2, 1e-3, 1, 1.  NRS_E_INVALID for a NaN, infinite or negative error,
+ * min_iters == 0 or warm_start outside {0, 1}.  Came after nrs_version() 0.3 without a version change. */
+int nrs_dfsph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double max_divergence_error,
+                        uint32_t min_divergence_iters, int warm_start);
 
 /* Per-stage device time, measured with HIP events recorded on the context's stream around the stage's
  * launches.  stage_mask: bit s set = time NRS_STAGE_s (0 = off, 0xffffffff = every stage).  nrs_set_profiling also
@@ -312,7 +332,7 @@ int nrs_stage_ms(nrs_ctx *ctx, int stage, float *ms, uint32_t *launches);
  *   [u32 nMigrants, u32 nHalo, u32 0, u32 0 | vec4 pos[capacity] | vec4 vel[capacity]].
  * Pass NULL for the neighbour that does not exist (ends of the chain).  IISPH contexts: halo_cells >= 8 and the step is driven
  * through nrs_iisph_predict / _iterate / _finish (below). */
-int nrs_slab_configure(nrs_ctx *ctx, int32_t cell_lo, int32_t cell_hi, int32_t halo_cells); /* NRS_E_INVALID on a PCISPH or PBF context */
+int nrs_slab_configure(nrs_ctx *ctx, int32_t cell_lo, int32_t cell_hi, int32_t halo_cells); /* NRS_E_INVALID on a PCISPH, PBF or DFSPH context */
 /* counts (optional) receives {stay, migrate-left, halo-left, migrate-right, halo-right, ghost}.
  * With counts == NULL nrs_slab_pack does not wait for the device: the two messages are complete in stream order when it returns (the
  * caller enqueues its sends on the same stream right behind it), and the stream populations are read back together with the headers of
@@ -363,10 +383,16 @@ int nrs_resort_stats(nrs_ctx *ctx, uint64_t *steps, uint64_t *fallbacks);
  *                           in fixed-count mode forms it when it is asked for)
  *   NRS_STAT_PCISPH_DELTA   PCISPH: the pressure scale delta the last step used
  *   NRS_STAT_PBF_EPSILON    PBF: the constraint-force mixing term eps the last step used
- * The HIT_* / UNSTAGED values need the shared hit lists of the production kernels (NRS_E_STATE otherwise); the PCISPH / PBF values a
- * context of that kind that has completed a solve. */
+ *   NRS_STAT_DENSITY_ERROR  on DFSPH: max_i e_i of the last density iteration
+ *   NRS_STAT_DFSPH_DENSITY_AVG           DFSPH: avg_i e_i of the last density iteration
+ *   NRS_STAT_DFSPH_DIVERGENCE_AVG        DFSPH: avg_i e_i of the last divergence iteration (NRS_E_STATE when the solve is off)
+ *   NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS DFSPH: divergence iterations of the last step (nrs_last_iterations gives the density solve's)
+ * The DFSPH values are formed on request from the e_i the solve left.
+ * The HIT_* / UNSTAGED values need the shared hit lists of the production kernels (NRS_E_STATE otherwise); the PCISPH / PBF / DFSPH
+ * values a context of that kind that has completed a solve. */
 enum { NRS_STAT_MOVERS = 0, NRS_STAT_HIT_OVERFLOW = 1, NRS_STAT_HIT_MEAN = 2, NRS_STAT_HIT_MAX = 3, NRS_STAT_UNSTAGED = 4,
-       NRS_STAT_DENSITY_ERROR = 5, NRS_STAT_PCISPH_DELTA = 6, NRS_STAT_PBF_EPSILON = 7 };
+       NRS_STAT_DENSITY_ERROR = 5, NRS_STAT_PCISPH_DELTA = 6, NRS_STAT_PBF_EPSILON = 7, NRS_STAT_DFSPH_DENSITY_AVG = 8,
+       NRS_STAT_DFSPH_DIVERGENCE_AVG = 9, NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS = 10 };
 int nrs_get_stat(nrs_ctx *ctx, int which, double *out);
 
 /* Akinci boundary volumes on the device (no context needed): vbi[i] = 1 / sum_k W_poly6(|x_i - x_k|, h) over the boundary

@@ -14,7 +14,7 @@ from .params import params_dtype
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NEREUS_HIP_LIB") or os.path.join(_HERE, "libnereus_hip.so")  # (override: kernel A/B builds in tools/)
 
-SESPH, IISPH, PCISPH, PBF = 0, 1, 2, 3
+SESPH, IISPH, PCISPH, PBF, DFSPH = 0, 1, 2, 3, 4
 MONAGHAN, MULLER = 0, 1
 FLAG_REFERENCE_ORDER = 1
 FLAG_NO_FUSION = 4
@@ -27,6 +27,7 @@ FLAG_STAGED_SCAN = 256
 E_NOTREADY = -6
 STAT_MOVERS, STAT_HIT_OVERFLOW, STAT_HIT_MEAN, STAT_HIT_MAX, STAT_UNSTAGED = 0, 1, 2, 3, 4
 STAT_DENSITY_ERROR, STAT_PCISPH_DELTA, STAT_PBF_EPSILON = 5, 6, 7
+STAT_DFSPH_DENSITY_AVG, STAT_DFSPH_DIVERGENCE_AVG, STAT_DFSPH_DIVERGENCE_ITERATIONS = 8, 9, 10
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
@@ -45,7 +46,7 @@ ARRAYS = {
     "bCellStart": (14, "u"), "bCellEnd": (15, "u"), "bSorted": (16, "v4"),
     "densAdv": (20, "s"), "densCorr": (21, "s"), "P_l": (22, "s"), "aii": (23, "s"), "velAdv": (24, "v4"),
     "forcesAdv": (25, "v4"), "forcesP": (26, "v4"), "diiFluid": (27, "v4"), "diiBoundary": (28, "v4"),
-    "sumDij": (29, "v4"), "posPred": (30, "v4"), "vorticity": (31, "v4"),
+    "sumDij": (29, "v4"), "posPred": (30, "v4"), "vorticity": (31, "v4"), "dfsphAlpha": (32, "s"), "dfsphKappaV": (33, "s"),
 }
 
 # every symbol include/nereus_hip.h declares (checked by tests/test_abi.py)
@@ -58,7 +59,7 @@ EXPORTS = [
     "nrs_slab_message_bytes", "nrs_slab_histogram", "nrs_resort_stats", "nrs_snapshot_begin", "nrs_snapshot_wait",
     "nrs_get_stat", "nrs_boundary_volumes", "nrs_eval_smoothing", "nrs_iisph_predict", "nrs_iisph_iterate", "nrs_iisph_finish",
     "nrs_slab_last_counts", "nrs_pcisph_configure", "nrs_pbf_configure", "nrs_pbf_set_tensile",
-    "nrs_pbf_set_vorticity",
+    "nrs_pbf_set_vorticity", "nrs_dfsph_configure",
 ]
 
 
@@ -113,6 +114,7 @@ def load_library(path=None):
     lib.nrs_pbf_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_double]
     lib.nrs_pbf_set_tensile.argtypes = [vp, C.c_double, C.c_double]
     lib.nrs_pbf_set_vorticity.argtypes = [vp, C.c_double]
+    lib.nrs_dfsph_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_uint32, i32]
     lib.nrs_set_profiling.argtypes = [vp, C.c_uint32]
     lib.nrs_stage_ms.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     lib.nrs_max_density.argtypes = [vp, C.POINTER(C.c_double)]
@@ -169,7 +171,7 @@ def eval_smoothing(which, r, s, h, c0, c1, double=False):
 
 
 class Solver:
-    """Thin object wrapper over an nrs_ctx (device-resident SESPH / IISPH / PCISPH / PBF solver)."""
+    """Thin object wrapper over an nrs_ctx (device-resident SESPH / IISPH / PCISPH / PBF / DFSPH solver)."""
 
     def __init__(self, params, capacity, solver=SESPH, double=False, kernel_set=MULLER, surface_tension=True,
                  reference_order=False, device=-1, stream=None, flags=0):
@@ -299,6 +301,12 @@ class Solver:
     def pbf_set_vorticity(self, eps_v=0.0):
         """PBF vorticity confinement (nrs_pbf_set_vorticity): vel += dt eps_v (N x omega) at the end of the step (0 = off)"""
         self._chk(self.lib.nrs_pbf_set_vorticity(self.h, float(eps_v)))
+
+    def dfsph_configure(self, max_density_error=1e-3, min_iters=2, max_divergence_error=1e-3, min_divergence_iters=1, warm_start=True):
+        """DFSPH settings (nrs_dfsph_configure): per loop the exit average error (0 = exactly the minimum, nothing read back) and the
+        minimum iterations (min_divergence_iters = 0: no divergence solve), and the warm start from the previous step's K / Kv"""
+        self._chk(self.lib.nrs_dfsph_configure(self.h, float(max_density_error), int(min_iters), float(max_divergence_error),
+                                               int(min_divergence_iters), int(warm_start)))
 
     def set_profiling(self, stages=True):
         """stages: True = all, False = off, or an iterable of stage ids."""

@@ -143,7 +143,8 @@ int nrs_create(const nrs_config *cfg, const void *params, nrs_ctx **out)
     if (cfg->struct_size != sizeof(nrs_config)) return fail(NRS_E_INVALID, "nrs_config.struct_size mismatch");
     if (cfg->precision != 32 && cfg->precision != 64) return fail(NRS_E_INVALID, "precision must be 32 or 64");
     if (cfg->kernel_set != NRS_KERNELS_MULLER && cfg->kernel_set != NRS_KERNELS_MONAGHAN) return fail(NRS_E_INVALID, "bad kernel_set");
-    if (cfg->solver != NRS_SOLVER_SESPH && cfg->solver != NRS_SOLVER_IISPH && cfg->solver != NRS_SOLVER_PCISPH && cfg->solver != NRS_SOLVER_PBF)
+    if (cfg->solver != NRS_SOLVER_SESPH && cfg->solver != NRS_SOLVER_IISPH && cfg->solver != NRS_SOLVER_PCISPH && cfg->solver != NRS_SOLVER_PBF &&
+        cfg->solver != NRS_SOLVER_DFSPH)
         return fail(NRS_E_INVALID, "bad solver");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -310,6 +311,12 @@ int nrs_pbf_set_vorticity(nrs_ctx *ctx, double eps_v)
 {
     CTX_GUARD(ctx);
     return ctx->impl->pbf_set_vorticity(eps_v);
+}
+int nrs_dfsph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double max_divergence_error, uint32_t min_divergence_iters,
+                        int warm_start)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->dfsph_configure(max_density_error, min_iters, max_divergence_error, min_divergence_iters, warm_start);
 }
 int nrs_set_profiling(nrs_ctx *ctx, uint32_t stage_mask)
 {

@@ -17,6 +17,7 @@
 #include "nrs_kernels_iisph.h"
 #include "nrs_kernels_pcisph.h"
 #include "nrs_kernels_pbf.h"
+#include "nrs_kernels_dfsph.h"
 #include "nrs_kernels_slab.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
@@ -142,6 +143,19 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     R pbfWq = (R)0;
     DevBuf pbfVort;
     bool pbfVortValid = false; // pbfVort holds the omega of a step
+    // DFSPH (nrs_kernels_dfsph.h; DESIGN.md "DFSPH") shares velAdv, forcesAdv, forcesP (0), densCorr (rho_adv), P_l (kappa), posPred
+    // (the advection launch's x*, unused), pciErr (e of the density solve) and PBF's prototype kernel.  K lives in presA / presB, as
+    // IISPH's warm-start pressure does; Kv in its own pair (dfKvA: slot order of posA, dfKvB: sorted), alpha and the divergence
+    // solve's e in their own buffers.
+    DevBuf dfAlpha, dfKvA, dfKvB, dfErrV;
+    double dfEta = 1e-3, dfEtaV = 1e-3;
+    uint32_t dfMin = 2, dfMinV = 1;
+    bool dfWarm = true;
+    bool dfThrValid = false; // dfThr belongs to the current parameters
+    R dfThr = (R)0;
+    bool dfAlphaValid = false, dfKvValid = false; // NRS_ARR_DFSPH_ALPHA / _KAPPA_V hold a step's values
+    uint32_t dfDenN = 0, dfDivN = 0; // particles whose e of the last density / divergence iteration pciErr / dfErrV hold (0: none)
+    uint32_t dfDivIters = 0;          // divergence iterations of the last step
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
     HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
@@ -277,6 +291,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool pcisph() const { return cfg.solver == NRS_SOLVER_PCISPH; }
     bool sesph() const { return cfg.solver == NRS_SOLVER_SESPH; }
     bool pbf() const { return cfg.solver == NRS_SOLVER_PBF; }
+    bool dfsph() const { return cfg.solver == NRS_SOLVER_DFSPH; }
     bool pow2_grid() const { return is_pow2(P.gridSize[0]) && is_pow2(P.gridSize[1]) && is_pow2(P.gridSize[2]); }
 
     // ---- which kernels a step launches ------------------------------------------------------------------------------------
@@ -358,7 +373,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         for (auto &e : evPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        DevBuf *all[] = {&pbfVort, &posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
+        DevBuf *all[] = {&dfAlpha, &dfKvA, &dfKvB, &dfErrV, &pbfVort, &posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
                          &inv, &sortTmp, &cellStart, &cellEnd, &bCellStart, &bCellEnd, &bSorted, &bHash, &bIndex,
                          &bHashAlt, &bIndexAlt, &densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP,
                          &posPred, &posPred2, &pciErr, &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
@@ -421,6 +436,13 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(densCorr.alloc(s)); NRSCHK(P_l.alloc(s));
             NRSCHK(posPred.alloc(v)); NRSCHK(posPred2.alloc(v)); NRSCHK(pciErr.alloc(s));
             DevBuf *z[] = {&velAdv, &forcesAdv, &forcesP, &densCorr, &P_l, &posPred, &posPred2, &pciErr};
+            for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
+        }
+        if (dfsph()) { // PCISPH's advection buffers (one predicted-position buffer), and DFSPH's own
+            NRSCHK(velAdv.alloc(v)); NRSCHK(forcesAdv.alloc(v)); NRSCHK(forcesP.alloc(v));
+            NRSCHK(densCorr.alloc(s)); NRSCHK(P_l.alloc(s)); NRSCHK(posPred.alloc(v)); NRSCHK(pciErr.alloc(s));
+            NRSCHK(dfAlpha.alloc(s)); NRSCHK(dfKvA.alloc(s)); NRSCHK(dfKvB.alloc(s)); NRSCHK(dfErrV.alloc(s));
+            DevBuf *z[] = {&velAdv, &forcesAdv, &forcesP, &densCorr, &P_l, &posPred, &pciErr, &dfAlpha, &dfKvA, &dfKvB, &dfErrV};
             for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
         }
         const Features ft = features();
@@ -505,10 +527,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (q.timestep != PU.timestep || q.particleMass != PU.particleMass || q.restDensity != PU.restDensity ||
             q.interactionRadius != PU.interactionRadius || q.kpoly_grad != PU.kpoly_grad)
             pciDeltaValid = false;
-        // ... and eps (pbf_prepare) on these
+        // ... and eps (pbf_prepare) and DFSPH's threshold (dfsph_prepare) on these
         if (q.particleMass != PU.particleMass || q.restDensity != PU.restDensity || q.interactionRadius != PU.interactionRadius ||
-            q.kpress_grad != PU.kpress_grad)
+            q.kpress_grad != PU.kpress_grad) {
             pbfEpsValid = false;
+            dfThrValid = false;
+        }
         // ... and W_q of the tensile correction on these
         if (q.interactionRadius != PU.interactionRadius || q.kpoly != PU.kpoly) pbfWqValid = false;
         PU = q;
@@ -547,6 +571,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             else HIPCHK(hipMemsetAsync(velA.as<T4>() + first, 0, sizeof(T4) * count, stream));
             if (pres) HIPCHK(hipMemcpyAsync(presA.as<R>() + first, pres, sizeof(R) * count, hipMemcpyHostToDevice, stream));
             else HIPCHK(hipMemsetAsync(presA.as<R>() + first, 0, sizeof(R) * count, stream));
+            if (dfsph()) HIPCHK(hipMemsetAsync(dfKvA.as<R>() + first, 0, sizeof(R) * count, stream)); // (Kv restarts at zero; K is the pressure)
             HIPCHK(hipStreamSynchronize(stream)); // the caller may reuse its host buffers on return
         }
         if (first + count > n) n = first + count;
@@ -830,6 +855,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                                nearB, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc, qp);
         if (iisph() && (cfg.flags & NRS_FLAG_IISPH_SELF_BY_SLOT)) // Q5 off: the pressure kernels skip j == own slot
             hipLaunchKernelGGL(k_identity, g, b, 0, stream, inv.as<uint32_t>(), N);
+        if (dfsph()) { // the warm-start inputs of the step, K_prev and Kv_prev, into sorted order
+            hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, presA.as<R>(), indexCur, presB.as<R>(), N);
+            hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, dfKvA.as<R>(), indexCur, dfKvB.as<R>(), N);
+            dfKvValid = true;
+        }
         NRSCHK(ev_end());
         return NRS_OK;
     }
@@ -1264,9 +1294,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const WallList wv = wall_view();
         if (!plan.lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
         else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hb, posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
+        if (dfsph()) dfsph_factor<HAS_B>();
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_DENSITY) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_P_ADVECT));
+        if (dfsph()) { // the divergence solve on the sorted velocities: the advection reads divergence-free ones
+            dfDivIters = 0;
+            if (dfMinV) NRSCHK((dfsph_solve<HAS_B, false>(velB.as<T4>(), dfKvB.as<R>(), dfErrV.as<R>(), dfMinV, dfEtaV, &dfDivIters)));
+            dfDivN = dfMinV ? N : 0u;
+        }
         pciXs = 0;
         const PciArrays<R> A0 = pci_view(0, 0);
         if (!plan.lists)
@@ -1374,17 +1410,17 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
     // eps = relaxation * D_proto, D = |sum g|^2 + sum |g|^2 over the neighbours of a prototype particle on the cubic lattice of spacing
     // cbrt(m / rho0) (k_pbf_prototype, the solver's own gradient on the device); once per parameter or settings change.  W_q likewise.
-    int pbf_prepare()
+    // D_proto = |sum g|^2 + sum |g|^2 of the prototype particle (k_pbf_prototype); `who` and `what` name the caller and its result in
+    // the errors
+    int pbf_prototype_d(const char *who, const char *what, double *d)
     {
-        if (pbfTensK > 0.0 && !pbfWqValid) {
-            NRSCHK(pbf_eval_wq(pbfTensDq, &pbfWq));
-            pbfWqValid = true;
-        }
-        if (pbfEpsValid) return NRS_OK;
         const double m = (double)PU.particleMass, rd = (double)PU.restDensity, h = (double)PU.interactionRadius;
         const R sp = (R)std::cbrt(m / rd);
-        if (!(sp > (R)0) || !std::isfinite((double)sp) || !(h > 0.0) || h / (double)sp > 64.0)
-            return fail(NRS_E_INVALID, "PBF: the prototype spacing cbrt(m / rho0) must be positive and at least h / 64");
+        char buf[200];
+        if (!(sp > (R)0) || !std::isfinite((double)sp) || !(h > 0.0) || h / (double)sp > 64.0) {
+            snprintf(buf, sizeof(buf), "%s: the prototype spacing cbrt(m / rho0) must be positive and at least h / 64", who);
+            return fail(NRS_E_INVALID, buf);
+        }
         const int kmax = (int)std::ceil(h / (double)sp) + 1;
         hipLaunchKernelGGL((k_pbf_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
         HIPCHK(hipGetLastError());
@@ -1392,11 +1428,23 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         HIPCHK(hipMemcpyAsync(o, redPartial.p, sizeof(o), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         if (o[4] == 0.0) {
-            char buf[200];
-            snprintf(buf, sizeof(buf), "PBF: the prototype particle (lattice spacing %g, h %g) has no neighbour within h: no eps", (double)sp, h);
+            snprintf(buf, sizeof(buf), "%s: the prototype particle (lattice spacing %g, h %g) has no neighbour within h: no %s", who, (double)sp, h,
+                     what);
             return fail(NRS_E_INVALID, buf);
         }
-        const double e = pbfRelax * (o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3]);
+        *d = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3];
+        return NRS_OK;
+    }
+    int pbf_prepare()
+    {
+        if (pbfTensK > 0.0 && !pbfWqValid) {
+            NRSCHK(pbf_eval_wq(pbfTensDq, &pbfWq));
+            pbfWqValid = true;
+        }
+        if (pbfEpsValid) return NRS_OK;
+        double d;
+        NRSCHK(pbf_prototype_d("PBF", "eps", &d));
+        const double e = pbfRelax * d;
         if (!(e > 0.0) || !std::isfinite(e)) return fail(NRS_E_INVALID, "PBF: the prototype gives no finite positive eps");
         pbfEps = (R)e;
         pbfEpsValid = true;
@@ -1489,6 +1537,108 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return NRS_OK;
     }
 
+    // ---- DFSPH step (nrs_kernels_dfsph.h; DESIGN.md "DFSPH") -------------------------------------------------------------------------
+    // HASH .. DENSITY as PCISPH (then the factor launch), P_ADVECT = the divergence solve + PCISPH's advection launch, P_SOLVE = the
+    // density solve on vel_adv, P_INTEGRATE = integrate_adv (Fp = 0: v = vel_adv, x += dt v)
+    DfsphArrays<R> dfsph_view(T4 *u, R *K, R *err) const
+    {
+        DfsphArrays<R> A;
+        A.u = u; A.dens = dens.as<R>(); A.alpha = dfAlpha.as<R>(); A.kappa = P_l.as<R>(); A.K = K; A.err = err;
+        A.rhoAdv = densCorr.as<R>(); A.thr = dfThr;
+        return A;
+    }
+    int dfsph_configure(double eta, uint32_t minIters, double etaV, uint32_t minItersV, int warm) override
+    {
+        if (!dfsph()) return fail(NRS_E_STATE, "nrs_dfsph_configure on a context that is not DFSPH");
+        if (!std::isfinite(eta) || eta < 0.0 || !std::isfinite(etaV) || etaV < 0.0)
+            return fail(NRS_E_INVALID, "DFSPH: max_density_error and max_divergence_error must be finite and >= 0");
+        if (minIters == 0) return fail(NRS_E_INVALID, "DFSPH: min_iters must be >= 1");
+        if (warm != 0 && warm != 1) return fail(NRS_E_INVALID, "DFSPH: warm_start must be 0 or 1");
+        dfEta = eta; dfMin = minIters; dfEtaV = etaV; dfMinV = minItersV; dfWarm = warm != 0;
+        return NRS_OK;
+    }
+    // thr = 1e-6 D_proto, D_proto = |sum g|^2 + sum |g|^2 of PBF's prototype (k_pbf_prototype); once per parameter change
+    int dfsph_prepare()
+    {
+        if (dfThrValid) return NRS_OK;
+        double d;
+        NRSCHK(pbf_prototype_d("DFSPH", "D_proto", &d));
+        if (!(d > 0.0) || !std::isfinite(d)) return fail(NRS_E_INVALID, "DFSPH: the prototype gives no finite positive D_proto");
+        dfThr = (R)(1e-6 * d);
+        dfThrValid = true;
+        return NRS_OK;
+    }
+    template <bool HAS_B> void dfsph_factor()
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        const GridView<R> G = grid_view();
+        const DfsphArrays<R> A = dfsph_view(nullptr, nullptr, nullptr);
+        if (!plan.lists)
+            hipLaunchKernelGGL((k_dfsph_factor_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
+        else if constexpr (KSET == KS_MULLER)
+            launch_listed(k_dfsph_factor_lists<R, KSET, HAS_B, true>, k_dfsph_factor_lists<R, KSET, HAS_B>, g.x, P, G, A, hit_buffer(),
+                          posB.as<T4>(), N);
+        dfAlphaValid = true;
+    }
+    // one A/B pair on u
+    template <bool HAS_B, bool DENS> void dfsph_pair(const DfsphArrays<R> &A, int phase)
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        const GridView<R> G = grid_view();
+        if (!plan.lists) {
+            hipLaunchKernelGGL((k_dfsph_div_ref<R, KSET, HAS_B, DENS>), g, b, 0, stream, P, G, A, posB.as<T4>(), phase, N);
+            hipLaunchKernelGGL((k_dfsph_vupdate_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
+        } else if constexpr (KSET == KS_MULLER) {
+            const HitBuffer hb = hit_buffer();
+            launch_listed(k_dfsph_div_lists<R, KSET, HAS_B, DENS, true>, k_dfsph_div_lists<R, KSET, HAS_B, DENS>, g.x, P, G, A, hb,
+                          posB.as<T4>(), phase, N);
+            launch_listed(k_dfsph_vupdate_lists<R, KSET, HAS_B, true>, k_dfsph_vupdate_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
+        }
+    }
+    // one solve (DENS: the density solve) in place on u, K in place on K (the sorted K_prev on entry).  eta > 0: stop after the iteration
+    // l with l >= min_iters and avg e <= eta, or at the cap (nrs_set_max_iterations, 0 = 100), the average not formed (nor read back)
+    // before min_iters; eta = 0: exactly min_iters iterations and no read-back.  The warm-start pair counts as no iteration.
+    template <bool HAS_B, bool DENS> int dfsph_solve(T4 *u, R *K, R *err, uint32_t minIters, double eta, uint32_t *iters)
+    {
+        const uint32_t N = (uint32_t)n;
+        const DfsphArrays<R> A = dfsph_view(u, K, err);
+        const bool fixed = eta == 0.0;
+        const uint32_t cap = fixed ? minIters : (maxIters ? maxIters : 100u);
+        if (dfWarm) dfsph_pair<HAS_B, DENS>(A, DFSPH_PHASE_WARM);
+        uint32_t l = 0;
+        for (;;) {
+            dfsph_pair<HAS_B, DENS>(A, (l || dfWarm) ? DFSPH_PHASE_MORE : DFSPH_PHASE_FIRST);
+            ++l;
+            const bool last = l >= cap;
+            if (fixed) {
+                if (last) break;
+            } else if (l >= minIters || last) {
+                double acc = 0.0;
+                NRSCHK(reduce_sum(err, N, &acc));
+                if (last || acc / (double)N <= eta) break;
+            }
+        }
+        *iters = l;
+        return NRS_OK;
+    }
+    template <bool HAS_B> int dfsph_tail(int stop)
+    {
+        const uint32_t N = (uint32_t)n;
+        bool more;
+        NRSCHK(pci_prefix<HAS_B>(stop, &more));
+        if (!more) return NRS_OK;
+        NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
+        uint32_t l = 0;
+        NRSCHK((dfsph_solve<HAS_B, true>(velAdv.as<T4>(), presB.as<R>(), pciErr.as<R>(), dfMin, dfEta, &l)));
+        lastIters = l;
+        dfDenN = N;
+        NRSCHK(ev_end());
+        if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
+        return integrate_adv(NRS_STAGE_P_INTEGRATE);
+    }
+
     // ---- host-driven IISPH step (multi-GPU: the loop exit needs the average over ALL ranks) ---------------------------------
     int iisph_phase(int phase, double *sum, uint64_t *count) override
     {
@@ -1543,6 +1693,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
         if (pcisph()) return fail(NRS_E_INVALID, "PCISPH contexts have no slab decomposition");
         if (pbf()) return fail(NRS_E_INVALID, "PBF contexts have no slab decomposition");
+        if (dfsph()) return fail(NRS_E_INVALID, "DFSPH contexts have no slab decomposition");
         if (iisph() && halo < 8) return fail(NRS_E_INVALID, "IISPH slabs need a halo of at least 8 cells (2 * iterations + 4)");
         if (halo < 2) return fail(NRS_E_INVALID, "halo must be >= 2 cells (one cell for the density of the ring + one)");
         if ((long long)hi - lo < 2ll * halo) return fail(NRS_E_INVALID, "slab narrower than two halos");
@@ -1891,6 +2042,21 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             *out = which == NRS_STAT_DENSITY_ERROR ? pciLastErr : (double)pbfEps;
             return NRS_OK;
         }
+        if (which == NRS_STAT_DFSPH_DENSITY_AVG || which == NRS_STAT_DFSPH_DIVERGENCE_AVG || which == NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS ||
+            (dfsph() && which == NRS_STAT_DENSITY_ERROR)) {
+            if (!dfsph()) return fail(NRS_E_STATE, "DFSPH statistic requested from another context");
+            if (which == NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS) { *out = (double)dfDivIters; return NRS_OK; }
+            // formed on request from the e_i the last iteration of the solve left (deterministic: the exit test's own reductions)
+            const bool div = which == NRS_STAT_DFSPH_DIVERGENCE_AVG;
+            const uint32_t cnt = div ? dfDivN : dfDenN;
+            if (!cnt) return fail(NRS_E_STATE, div ? "no DFSPH divergence solve yet (or it is off)" : "no DFSPH density solve yet");
+            void *e = div ? dfErrV.p : pciErr.p;
+            if (which == NRS_STAT_DENSITY_ERROR) return max_of<false>(e, cnt, out);
+            double acc = 0.0;
+            NRSCHK(reduce_sum((const R *)e, cnt, &acc));
+            *out = acc / (double)cnt;
+            return NRS_OK;
+        }
         if (which == NRS_STAT_DENSITY_ERROR || which == NRS_STAT_PCISPH_DELTA) {
             if (!pcisph()) return fail(NRS_E_STATE, "PCISPH statistic requested from another context");
             if (pciLastErr < 0.0) return fail(NRS_E_STATE, "no PCISPH solve yet");
@@ -1926,7 +2092,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             std::swap(posA.p, posB.p);
             std::swap(velA.p, velB.p);
         }
-        if (iisph() || pcisph() || pbf()) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB, PBF its lambda)
+        if (iisph() || pcisph() || pbf() || dfsph()) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB, PBF its lambda, DFSPH K)
+        if (dfsph()) std::swap(dfKvA.p, dfKvB.p);
         return NRS_OK;
     }
     int step(int nsteps, int stop) override
@@ -1938,9 +2105,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             return fail(NRS_E_INVALID, "stage not part of a PCISPH step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
         if (pbf() && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
             return fail(NRS_E_INVALID, "stage not part of a PBF step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
+        if (dfsph() && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
+            return fail(NRS_E_INVALID, "stage not part of a DFSPH step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
         if (n == 0) return NRS_OK;
         if (pcisph()) NRSCHK(pcisph_prepare());
         if (pbf()) NRSCHK(pbf_prepare());
+        if (dfsph()) NRSCHK(dfsph_prepare());
         for (int s = 0; s < nsteps; ++s) {
             fusedThisStep = false;
             splitClearedCells = false;
@@ -1950,6 +2120,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (iisph()) { if (nb) NRSCHK(iisph_tail<true>(stop)); else NRSCHK(iisph_tail<false>(stop)); }
             else if (pcisph()) { if (nb) NRSCHK(pcisph_tail<true>(stop)); else NRSCHK(pcisph_tail<false>(stop)); }
             else if (pbf()) { if (nb) NRSCHK(pbf_tail<true>(stop)); else NRSCHK(pbf_tail<false>(stop)); }
+            else if (dfsph()) { if (nb) NRSCHK(dfsph_tail<true>(stop)); else NRSCHK(dfsph_tail<false>(stop)); }
             else { if (nb) NRSCHK(sesph_tail<true>(stop)); else NRSCHK(sesph_tail<false>(stop)); }
             HIPCHK(hipGetLastError());
             if (stop) { midStep = true; break; }
@@ -2090,7 +2261,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         case NRS_ARR_SORTED_POS: p = sortedIsCurrent ? posA.p : posB.p; sz = v; break;
         case NRS_ARR_SORTED_VEL: p = sortedIsCurrent ? velA.p : velB.p; sz = v; break;
         case NRS_ARR_DENS: p = dens.p; sz = s; break;
-        case NRS_ARR_PRES: p = ((iisph() || pcisph() || pbf()) && sortedIsCurrent) ? presA.p : presB.p; sz = s; break;
+        case NRS_ARR_PRES: p = ((iisph() || pcisph() || pbf() || dfsph()) && sortedIsCurrent) ? presA.p : presB.p; sz = s; break;
         case NRS_ARR_FORCES: p = forces.p; sz = v; break;
         case NRS_ARR_B_HASH: p = bHashCur; sz = 4 * nb; break;
         case NRS_ARR_B_INDEX: p = bIndexCur; sz = 4 * nb; break;
@@ -2112,6 +2283,17 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (!pbf()) return fail(NRS_E_STATE, "PBF array requested from another context");
             if (!pbfVortValid) return fail(NRS_E_STATE, "no PBF step with vorticity confinement yet");
             p = pbfVort.p; sz = v; break;
+        case NRS_ARR_DFSPH_ALPHA:
+        case NRS_ARR_DFSPH_KAPPA_V:
+            if (!dfsph()) return fail(NRS_E_STATE, "DFSPH array requested from another context");
+            if (which == NRS_ARR_DFSPH_ALPHA) {
+                if (!dfAlphaValid) return fail(NRS_E_STATE, "no DFSPH factor launch yet");
+                p = dfAlpha.p;
+            } else {
+                if (!dfKvValid) return fail(NRS_E_STATE, "no DFSPH step yet");
+                p = sortedIsCurrent ? dfKvA.p : dfKvB.p;
+            }
+            sz = s; break;
         default: return fail(NRS_E_INVALID, "unknown array id");
         }
         if (which == NRS_ARR_POS_PRED && !pcisph() && !pbf()) return fail(NRS_E_STATE, "PCISPH / PBF array requested from another context");
@@ -2119,6 +2301,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                               which == NRS_ARR_DENS_CORR || which == NRS_ARR_P_L || which == NRS_ARR_POS_PRED || which == NRS_ARR_VORTICITY;
         if (pcisph() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PCISPH context");
         if (pbf() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PBF context");
+        const bool dfArray = which == NRS_ARR_VEL_ADV || which == NRS_ARR_FORCES_ADV || which == NRS_ARR_FORCES_P || which == NRS_ARR_DENS_CORR ||
+                             which == NRS_ARR_P_L || which == NRS_ARR_DFSPH_ALPHA || which == NRS_ARR_DFSPH_KAPPA_V;
+        if (dfsph() && which >= NRS_ARR_DENS_ADV && !dfArray) return fail(NRS_E_STATE, "IISPH / PCISPH / PBF array requested from a DFSPH context");
         if (which >= NRS_ARR_DENS_ADV && sesph()) return fail(NRS_E_STATE, "IISPH array requested from a SESPH context");
         *dptr = p;
         *bytes = p ? sz : 0;

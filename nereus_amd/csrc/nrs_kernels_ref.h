@@ -1483,6 +1483,262 @@ __global__ __launch_bounds__(BLOCK) void k_pbf_confine_ref(Params<R> P, GridView
     vel[i] = mk4<R>(pbf_confine<R>(P, v, pbf_eta_walk<R, KSET>(P, G, sPos, xs, omega, i, pos1, xs1, om.w), om, epsV), (R)0.0);
 }
 
+// =========================================== DFSPH ===================================================
+// Divergence-free SPH (Bender & Koschier 2015 / 2017): a divergence solve on the step's velocities and a density solve on vel_adv,
+// both Jacobi iterations on velocities with PBF's spiky gradient.  DESIGN.md "DFSPH" defines what is computed here.  Every position is
+// the step's START position (DFSPH moves no particle before the integration), so one neighbour rule holds for the whole step:
+// length(x_i - x_j) < h, j != i by sorted slot, static boundary particles with the same rule.  Sums are formed in the order of
+// density_of (one fluid partial and then one boundary partial per cell), so the list-driven kernels (nrs_kernels_dfsph.h) can be
+// bit-identical to the walks below.  g_ij = (m / rho0) pbf_grad(x_i - x_j), g_ib = (psi_b / rho0) pbf_grad(x_i - x_b).
+template <typename R> struct DfsphArrays {
+    typedef typename Vec4T<R>::type T4;
+    T4 *u;         // the velocities the solve corrects, in place (the divergence solve: the sorted v; the density solve: vel_adv)
+    const R *dens; // rho of the step's density scan
+    R *alpha;      // 1 / D_i, or 0 where D_i <= thr (the factor launch)
+    R *kappa;      // kappa_i of the last A launch (B reads its own and its neighbours')
+    R *K;          // the running total K_i (m^2), in place: the sorted K_prev of the step when the solve starts
+    R *err;        // e_i of the last A launch (input of the exit test's average)
+    R *rhoAdv;     // density mode: rho_adv of the last A launch
+    R thr;         // 1e-6 D_proto
+};
+// K's warm start: kappa_i = DFSPH_WARM K_prev_i / dt^2 where e_i > 0 (a constant, not a setting)
+constexpr double DFSPH_WARM = 0.5;
+// the A launch's phases: the warm-start A (kappa and K from K_prev), the first iteration (K = e alpha) and the later ones (K += e alpha)
+enum { DFSPH_PHASE_WARM = 0, DFSPH_PHASE_FIRST = 1, DFSPH_PHASE_MORE = 2 };
+template <typename R, int KSET> NRS_DEV V3<R> dfsph_g(const Params<R> &P, V3<R> d, R w)
+{
+    return pci_scale<R>(w / P.restDensity, pbf_grad<R, KSET>(P, d));
+}
+// the factor sums: sum g (fluid and boundary), sum |g|^2 (fluid)
+template <typename R> struct DfsphFac {
+    V3<R> g;
+    R gg;
+    NRS_DEV void add(const DfsphFac &o) { g = g + o.g; gg += o.gg; }
+};
+template <typename R> NRS_DEV DfsphFac<R> dfsph_fac_zero()
+{
+    DfsphFac<R> s;
+    s.g = mk3<R>(0, 0, 0);
+    s.gg = (R)0.0;
+    return s;
+}
+// one fluid / boundary neighbour of the factor launch at separation d (its cut-off test already passed)
+template <typename R, int KSET> NRS_DEV void dfsph_fac_fluid(const Params<R> &P, V3<R> d, DfsphFac<R> &s)
+{
+    const V3<R> g = dfsph_g<R, KSET>(P, d, P.particleMass);
+    s.g = s.g + g;
+    s.gg += pbf_dot<R>(g, g);
+}
+template <typename R, int KSET> NRS_DEV void dfsph_fac_boundary(const Params<R> &P, V3<R> d, R psi, DfsphFac<R> &s)
+{
+    s.g = s.g + dfsph_g<R, KSET>(P, d, psi);
+}
+template <typename R> NRS_DEV void dfsph_fac_store(const DfsphArrays<R> &A, uint32_t i, const DfsphFac<R> &s)
+{
+    const R D = pbf_dot<R>(s.g, s.g) + s.gg;
+    A.alpha[i] = D > A.thr ? (R)1.0 / D : (R)0.0;
+}
+// the terms of launch A: (u_i - u_j) . g_ij and u_i . g_ib
+template <typename R, int KSET> NRS_DEV R dfsph_div_fluid(const Params<R> &P, V3<R> d, V3<R> ui, V3<R> uj)
+{
+    return pbf_dot<R>(ui - uj, dfsph_g<R, KSET>(P, d, P.particleMass));
+}
+template <typename R, int KSET> NRS_DEV R dfsph_div_boundary(const Params<R> &P, V3<R> d, R psi, V3<R> ui)
+{
+    return pbf_dot<R>(ui, dfsph_g<R, KSET>(P, d, psi));
+}
+// div_i -> e_i, kappa_i, K_i (and rho_adv_i in density mode); NaN errors give e = inf (the loop then runs to its cap)
+template <typename R, bool DENS> NRS_DEV void dfsph_div_store(const Params<R> &P, const DfsphArrays<R> &A, uint32_t i, R div, int phase)
+{
+    const R dt = P.timestep, rd = P.restDensity;
+    R e;
+    if constexpr (DENS) {
+        const R ra = A.dens[i] + (dt * rd) * div;
+        const R dr = ra - rd;
+        A.rhoAdv[i] = ra;
+        e = dr <= (R)0 ? (R)0 : (dr == dr ? dr / rd : (R)INFINITY);
+    } else {
+        const R x = dt * div;
+        e = x <= (R)0 ? (R)0 : (x == x ? x : (R)INFINITY);
+    }
+    A.err[i] = e;
+    const R dt2 = dt * dt;
+    if (phase == DFSPH_PHASE_WARM) {
+        const R kappa = e > (R)0 ? ((R)DFSPH_WARM * A.K[i]) / dt2 : (R)0.0;
+        A.kappa[i] = kappa;
+        A.K[i] = kappa * dt2;
+    } else {
+        const R ea = e * A.alpha[i];
+        A.kappa[i] = ea / dt2;
+        A.K[i] = (phase == DFSPH_PHASE_FIRST ? (R)0.0 : A.K[i]) + ea;
+    }
+}
+// the terms of launch B: (kappa_i + kappa_j) g_ij and kappa_i g_ib
+template <typename R, int KSET> NRS_DEV V3<R> dfsph_vup_fluid(const Params<R> &P, V3<R> d, R ki, R kj)
+{
+    return pci_scale<R>(ki + kj, dfsph_g<R, KSET>(P, d, P.particleMass));
+}
+template <typename R, int KSET> NRS_DEV V3<R> dfsph_vup_boundary(const Params<R> &P, V3<R> d, R psi, R ki)
+{
+    return pci_scale<R>(ki, dfsph_g<R, KSET>(P, d, psi));
+}
+// u_i -= dt sum (w kept)
+template <typename R> NRS_DEV void dfsph_vup_store(const Params<R> &P, const DfsphArrays<R> &A, uint32_t i, typename Vec4T<R>::type u, V3<R> s)
+{
+    A.u[i] = mk4<R>(xyz<R>(u) - pci_scale<R>(P.timestep, s), u.w);
+}
+
+// the factor sums of particle i, reference order
+template <typename R, int KSET, bool HAS_B>
+NRS_DEV DfsphFac<R> dfsph_factor_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos, uint32_t i,
+                                      V3<R> pos1)
+{
+    const R ir = P.interactionRadius, rd = P.restDensity;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    DfsphFac<R> t = dfsph_fac_zero<R>();
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                DfsphFac<R> c = dfsph_fac_zero<R>();
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
+                        if (j == i || !(length(d) < ir)) continue;
+                        dfsph_fac_fluid<R, KSET>(P, d, c);
+                    }
+                }
+                t.add(c);
+                if (HAS_B) {
+                    DfsphFac<R> cb = dfsph_fac_zero<R>();
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            const V3<R> d = pos1 - xyz<R>(b);
+                            if (!(length(d) < ir)) continue;
+                            dfsph_fac_boundary<R, KSET>(P, d, rd * b.w, cb);
+                        }
+                    }
+                    t.add(cb);
+                }
+            }
+    return t;
+}
+// div_i of particle i (launch A), reference order
+template <typename R, int KSET, bool HAS_B>
+NRS_DEV R dfsph_div_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                         const typename Vec4T<R>::type *__restrict__ u, uint32_t i, V3<R> pos1, V3<R> u1)
+{
+    const R ir = P.interactionRadius, rd = P.restDensity;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    R div = (R)0.0;
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                R c = (R)0.0;
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
+                        if (j == i || !(length(d) < ir)) continue;
+                        c += dfsph_div_fluid<R, KSET>(P, d, u1, xyz<R>(u[j]));
+                    }
+                }
+                div += c;
+                if (HAS_B) {
+                    R cb = (R)0.0;
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            const V3<R> d = pos1 - xyz<R>(b);
+                            if (!(length(d) < ir)) continue;
+                            cb += dfsph_div_boundary<R, KSET>(P, d, rd * b.w, u1);
+                        }
+                    }
+                    div += cb;
+                }
+            }
+    return div;
+}
+// the velocity correction sum of particle i (launch B), reference order
+template <typename R, int KSET, bool HAS_B>
+NRS_DEV V3<R> dfsph_vup_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
+                             const R *__restrict__ kappa, uint32_t i, V3<R> pos1, R ki)
+{
+    const R ir = P.interactionRadius, rd = P.restDensity;
+    const I3 gp = calcGridPos<R>(P, pos1);
+    V3<R> sum = mk3<R>(0, 0, 0);
+    for (int z = -1; z <= 1; z++)
+        for (int y = -1; y <= 1; y++)
+            for (int x = -1; x <= 1; x++) {
+                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
+                V3<R> c = mk3<R>(0, 0, 0);
+                const uint32_t s = G.cellStart[h];
+                if (s != CELL_EMPTY) {
+                    const uint32_t e = G.cellEnd[h];
+                    for (uint32_t j = s; j < e; ++j) {
+                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
+                        if (j == i || !(length(d) < ir)) continue;
+                        c = c + dfsph_vup_fluid<R, KSET>(P, d, ki, kappa[j]);
+                    }
+                }
+                sum = sum + c;
+                if (HAS_B) {
+                    V3<R> cb = mk3<R>(0, 0, 0);
+                    const uint32_t sb = G.bCellStart[h];
+                    if (sb != CELL_EMPTY) {
+                        const uint32_t e = G.bCellEnd[h];
+                        for (uint32_t j = sb; j < e; ++j) {
+                            const typename Vec4T<R>::type b = G.sB[j];
+                            const V3<R> d = pos1 - xyz<R>(b);
+                            if (!(length(d) < ir)) continue;
+                            cb = cb + dfsph_vup_boundary<R, KSET>(P, d, rd * b.w, ki);
+                        }
+                    }
+                    sum = sum + cb;
+                }
+            }
+    return sum;
+}
+
+// the factor launch: alpha_i
+template <typename R, int KSET, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_dfsph_factor_ref(Params<R> P, GridView<R> G, DfsphArrays<R> A,
+                                                            const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    dfsph_fac_store<R>(A, i, dfsph_factor_walk<R, KSET, HAS_B>(P, G, sPos, i, xyz<R>(sPos[i])));
+}
+// launch A: div_i -> e_i, kappa_i, K_i (DENS: the density mode, with rho_adv)
+template <typename R, int KSET, bool HAS_B, bool DENS>
+__global__ __launch_bounds__(BLOCK) void k_dfsph_div_ref(Params<R> P, GridView<R> G, DfsphArrays<R> A,
+                                                         const typename Vec4T<R>::type *__restrict__ sPos, int phase, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const R div = dfsph_div_walk<R, KSET, HAS_B>(P, G, sPos, A.u, i, xyz<R>(sPos[i]), xyz<R>(A.u[i]));
+    dfsph_div_store<R, DENS>(P, A, i, div, phase);
+}
+// launch B: u_i -= dt (sum_j (kappa_i + kappa_j) g_ij + sum_b kappa_i g_ib), in place (B reads only its own u_i)
+template <typename R, int KSET, bool HAS_B>
+__global__ __launch_bounds__(BLOCK) void k_dfsph_vupdate_ref(Params<R> P, GridView<R> G, DfsphArrays<R> A,
+                                                             const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const typename Vec4T<R>::type u = A.u[i];
+    dfsph_vup_store<R>(P, A, i, u, dfsph_vup_walk<R, KSET, HAS_B>(P, G, sPos, A.kappa, i, xyz<R>(sPos[i]), A.kappa[i]));
+}
+
 // deterministic two-pass sum of an SReal array in double (replaces thrust::reduce, sph_cuda.cu:816-819)
 template <typename R>
 __global__ __launch_bounds__(BLOCK) void k_sum_partial(const R *__restrict__ a, double *__restrict__ partial, uint32_t n,

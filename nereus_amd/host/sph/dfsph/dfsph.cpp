@@ -1,0 +1,43 @@
+// dfsph.cpp — Nereus::DFSPH: SPH's update() (upload if dirty, one nrs_step, lazy download) on a context of kind NRS_SOLVER_DFSPH.
+#include "dfsph.h"
+
+#include "nereus_hip.h"
+
+#include <cstdio>
+#include <cstdlib>
+
+NEREUS_NAMESPACE_BEGIN
+
+DFSPH::DFSPH() : SPH(), m_eta(1e-3f), m_etaV(1e-3f), m_minIters(2), m_minItersV(1), m_warmStart(true) {}
+DFSPH::DFSPH(SphSimParams params) : SPH(params), m_eta(1e-3f), m_etaV(1e-3f), m_minIters(2), m_minItersV(1), m_warmStart(true) {}
+DFSPH::~DFSPH() {}
+
+int DFSPH::solverKind() const { return NRS_SOLVER_DFSPH; }
+
+void DFSPH::setSolverSettings(SReal eta, SUint minIters, SReal etaV, SUint minItersV, bool warmStart)
+{
+    if (m_ctx) { // (a context keeps the settings it was created with)
+        std::fprintf(stderr, "Nereus: DFSPH::setSolverSettings must be called before the first update() / updateGpuBoundaries()\n");
+        std::exit(EXIT_FAILURE);
+    }
+    m_eta = eta;
+    m_minIters = minIters;
+    m_etaV = etaV;
+    m_minItersV = minItersV;
+    m_warmStart = warmStart;
+}
+
+void DFSPH::configureContext()
+{
+    if (nrs_dfsph_configure(m_ctx, (double)m_eta, (uint32_t)m_minIters, (double)m_etaV, (uint32_t)m_minItersV, m_warmStart ? 1 : 0) != NRS_OK)
+        fatal("nrs_dfsph_configure");
+}
+
+SUint DFSPH::getLastIterations()
+{
+    uint32_t it = 0;
+    if (m_ctx && nrs_last_iterations(m_ctx, &it) != NRS_OK) fatal("nrs_last_iterations");
+    return (SUint)it;
+}
+
+NEREUS_NAMESPACE_END

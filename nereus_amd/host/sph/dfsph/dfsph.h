@@ -1,0 +1,37 @@
+// dfsph.h — Nereus::DFSPH, divergence-free SPH (Bender & Koschier 2015 / 2017).  Not in the reference: a device step of the library's
+// NRS_SOLVER_DFSPH (DESIGN.md "DFSPH") behind the SPH host surface.  update() is a full step; the pressures read back are the step's
+// K (m^2), the density solve's warm-start total.
+//
+// Checkpoints: saveState() / loadState() carry K as the pressure, so a restored run warm-starts its density solve as the original
+// did; the divergence solve's total Kv is not in the checkpoint and restarts at zero.  A restored run is therefore bit-identical to
+// the original only with the divergence warm start off (warmStart = false, or the divergence solve off).  The checkpoint format is
+// unchanged.
+#pragma once
+#ifndef DFSPH_H
+#define DFSPH_H
+#include "sph.h"
+
+NEREUS_NAMESPACE_BEGIN
+
+class DFSPH : public SPH {
+public:
+    DFSPH();
+    DFSPH(SphSimParams params);
+    virtual ~DFSPH();
+    // Solver settings (nrs_dfsph_configure).  Must be called before the device context exists, i.e. before the first update() or
+    // updateGpuBoundaries().  eta / etaV = the average error each loop accepts (0: exactly minIters / minItersV iterations, nothing
+    // read back), minItersV = 0 turns the divergence solve off, warmStart = start both solves from half the previous step's totals.
+    // Defaults 1e-3, 2, 1e-3, 1, true.
+    void setSolverSettings(SReal eta, SUint minIters, SReal etaV, SUint minItersV, bool warmStart);
+    SUint getLastIterations(); // density-solve iterations of the last step
+    int solverKind() const override;
+
+protected:
+    void configureContext() override; // hands the settings to every context ensureContext creates (a capacity change replaces it)
+    SReal m_eta, m_etaV;
+    SUint m_minIters, m_minItersV;
+    bool m_warmStart;
+};
+
+NEREUS_NAMESPACE_END
+#endif // DFSPH_H

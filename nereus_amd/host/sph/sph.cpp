@@ -234,7 +234,8 @@ void SPH::pushHostToDevice()
 void SPH::pullDeviceToHost() const
 {
     if (!m_deviceNewer || !m_ctx) return;
-    const bool wantPressure = solverKind() == NRS_SOLVER_IISPH || solverKind() == NRS_SOLVER_PCISPH || solverKind() == NRS_SOLVER_PBF;
+    const bool wantPressure = solverKind() == NRS_SOLVER_IISPH || solverKind() == NRS_SOLVER_PCISPH || solverKind() == NRS_SOLVER_PBF ||
+                              solverKind() == NRS_SOLVER_DFSPH;
     if (nrs_download(m_ctx, m_pos, m_vel, wantPressure ? m_pressure : nullptr) != NRS_OK) fatal("nrs_download");
     m_deviceNewer = false;
 }

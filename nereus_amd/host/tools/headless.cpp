@@ -6,7 +6,8 @@
 //                                                               stub, pcisph-solve: PCISPH::setPressureSolve(true), pbf:
 //                                                               Nereus::PBF with its default settings, and pbf-full: PBF with
 //                                                               XSPH 0.01, the tensile correction k = 1e-4, dq = 0.2 and
-//                                                               vorticity confinement eps_v = 0.01)
+//                                                               vorticity confinement eps_v = 0.01; dfsph: Nereus::DFSPH with
+//                                                               its default settings)
 //   headless resume  <sesph|iisph> <in.bin> <steps_a> <steps_b> <ckpt> <out.bin>   run steps_a, saveState, then a NEW
 //                                                               solver loadState()s and runs steps_b (boundaries re-set)
 //   headless cfl     sesph <in.bin> <steps> <out.bin>           run with setAdaptiveTimestep(true)
@@ -22,6 +23,7 @@
 
 #include "common.h"
 #include "iisph/iisph.h"
+#include "dfsph/dfsph.h"
 #include "pbf/pbf.h"
 #include "pcisph/pcisph.h"
 #include "sph.h"
@@ -71,9 +73,10 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool iisph = kind == "iisph", pcisphSolve = kind == "pcisph-solve", pcisph = kind == "pcisph" || pcisphSolve;
-    const bool pbfFull = kind == "pbf-full", pbf = kind == "pbf" || pbfFull;
+    const bool pbfFull = kind == "pbf-full", pbf = kind == "pbf" || pbfFull, dfsph = kind == "dfsph";
     Nereus::SPH *sim = iisph ? (Nereus::SPH *)new Nereus::IISPH()
-                             : (pcisph ? (Nereus::SPH *)new Nereus::PCISPH() : (pbf ? (Nereus::SPH *)new Nereus::PBF() : new Nereus::SPH()));
+                             : (pcisph ? (Nereus::SPH *)new Nereus::PCISPH()
+                                       : (pbf ? (Nereus::SPH *)new Nereus::PBF() : (dfsph ? (Nereus::SPH *)new Nereus::DFSPH() : new Nereus::SPH())));
     if (pcisphSolve) static_cast<Nereus::PCISPH *>(sim)->setPressureSolve(true);
     if (pbfFull) {
         Nereus::PBF *p = static_cast<Nereus::PBF *>(sim);
@@ -124,6 +127,7 @@ int main(int argc, char **argv)
         if (iisph) iters = static_cast<Nereus::IISPH *>(sim)->getLastIterations();
         if (pcisphSolve) iters = static_cast<Nereus::PCISPH *>(sim)->getLastIterations();
         if (pbf) iters = static_cast<Nereus::PBF *>(sim)->getLastIterations();
+        if (dfsph) iters = static_cast<Nereus::DFSPH *>(sim)->getLastIterations();
         dump(argv[5], sim, iters, bi, vbi);
     } else if (mode == "resume" || mode == "cfl") {
         FILE *f = std::fopen(argv[3], "rb");

@@ -3,10 +3,11 @@ with random grid geometry (cell size != h, anisotropic, origins far from the par
 seed in fp64, every 3rd with the Monaghan kernels, every 5th IISPH; every 13th on a grid one or two cells wide in x (no quantised
 scan), every 17th with the grid origin more than 4096 cells away (beyond the quanta's error budget), every 19th with NaN / inf
 coordinates.
-With a solver named (pcisph / pbf), the same scenes run that solver instead (PBF with random loop, XSPH, tensile and vorticity settings),
-production against reference order at the advection stage, at the solve stage and after 3 (6) steps; pcisph-model / pbf-model compare
-the device with the float64 models of tests/ on pieces of those scenes, of the geometry where both find the same pairs (one_vs_model).
-usage: python tools/fuzz_parity.py [seeds=100] [first=0] [oracle | pcisph | pbf | pcisph-model | pbf-model]
+With a solver named (pcisph / pbf / dfsph), the same scenes run that solver instead (PBF with random loop, XSPH, tensile and vorticity
+settings, DFSPH with random settings of both loops and the warm start), production against reference order at the advection stage, at
+the solve stage and after 3 (6) steps; pcisph-model / pbf-model / dfsph-model compare the device with the float64 models of tests/ on
+pieces of those scenes, of the geometry where both find the same pairs (one_vs_model).
+usage: python tools/fuzz_parity.py [seeds=100] [first=0] [oracle | pcisph | pbf | dfsph | pcisph-model | pbf-model | dfsph-model]
   (oracle: compare with the CPU oracle instead: keys bit-exact, floats within the parity tolerances)"""
 import os, sys
 import numpy as np
@@ -14,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nereus_amd import capi
 from nereus_amd.params import default_params
 
-SOLVERS = {"pcisph": capi.PCISPH, "pbf": capi.PBF}
+SOLVERS = {"pcisph": capi.PCISPH, "pbf": capi.PBF, "dfsph": capi.DFSPH}
 
 
 def make_scene(seed, solver=None):
@@ -75,6 +76,9 @@ def make_scene(seed, solver=None):
                    relaxation=float(10 ** rng.uniform(-3, -1)), xsph=float(rng.choice([0.0, rng.uniform(0.0, 0.3)])),
                    k=float(rng.choice([0.0, 10 ** rng.uniform(-4, -3)])), dq=float(rng.uniform(0.1, 0.4)),
                    eps_v=float(rng.choice([0.0, rng.uniform(0.0, 1.0)])))
+    elif solver == capi.DFSPH:   # (likewise)
+        cfg = dict(eta=float(rng.choice([0.0, 10 ** rng.uniform(-4, -2)])), min_iters=int(rng.integers(1, 5)),
+                   eta_v=float(rng.choice([0.0, 10 ** rng.uniform(-4, -2)])), min_v=int(rng.integers(0, 4)), warm=int(rng.integers(0, 2)))
     return dict(p=p, n=n, pos=pos, vel=vel, bi=bi, vbi=vbi, solver=solver, double=double, kset=kset, gs=gs, cs=cs, h=h, cfg=cfg)
 
 
@@ -84,6 +88,8 @@ def _configure(s, sc):
         s.pbf_configure(c["eta"], c["min_iters"], c["relaxation"], c["xsph"])
         s.pbf_set_tensile(c["k"], c["dq"])
         s.pbf_set_vorticity(c["eps_v"])
+    elif sc["solver"] == capi.DFSPH:
+        s.dfsph_configure(c["eta"], c["min_iters"], c["eta_v"], c["min_v"], c["warm"])
 
 
 def _first_difference(seed, sc, names, outs):
@@ -102,7 +108,11 @@ def one_pci(seed, solver):
     sc = make_scene(seed, solver)
     n, pos, vel = sc["n"], sc["pos"], sc["vel"]
     solve = ["sortedPos", "velAdv", "densCorr", "P_l", "forcesP", "posPred"]
-    names = ["advect " + x for x in ("sortedPos", "velAdv", "posPred")] + ["solve " + x for x in solve] + ["iters", "pos", "vel", "pressure"]
+    advect = ["sortedPos", "velAdv", "posPred"]
+    if solver == capi.DFSPH:   # (no predicted positions; the divergence solve's velocities and Kv, the factor, K)
+        solve = ["sortedPos", "velAdv", "densCorr", "P_l", "pres", "dfsphAlpha"]
+        advect = ["sortedPos", "sortedVel", "velAdv", "dfsphKappaV"]
+    names = ["advect " + x for x in advect] + ["solve " + x for x in solve] + ["iters", "pos", "vel", "pressure"]
     outs = []
     for ref in (False, True):
         s = capi.Solver(sc["p"], n, solver=solver, double=sc["double"], kernel_set=sc["kset"], reference_order=ref)
@@ -110,7 +120,7 @@ def one_pci(seed, solver):
         s.set_particles(pos, vel)
         s.set_boundaries(sc["bi"], sc["vbi"], update_grid=False)
         s.step_partial(capi.STAGE_P_ADVECT)
-        o = [s.get(x) for x in ("sortedPos", "velAdv", "posPred")]
+        o = [s.get(x) for x in advect]
         s.set_particles(pos, vel)
         s.step_partial(capi.STAGE_P_SOLVE)
         o += [s.get(x) for x in solve] + [np.array([s.last_iterations])]
@@ -123,7 +133,7 @@ def one_pci(seed, solver):
 
 
 def one(seed, solver=None):
-    if solver in (capi.PCISPH, capi.PBF):
+    if solver in (capi.PCISPH, capi.PBF, capi.DFSPH):
         return one_pci(seed, solver)
     sc = make_scene(seed)
     p, n, pos, vel, bi, vbi, solver, double, kset, gs, cs, h = (sc[k] for k in ("p", "n", "pos", "vel", "bi", "vbi", "solver", "double", "kset", "gs", "cs", "h"))
@@ -239,11 +249,55 @@ def make_model_scene(seed, solver):
                 iters=1, ref=bool(rng.integers(0, 2)))
 
 
+def one_dfsph_vs_model(seed):
+    """DFSPH: the device against tests/dfsph_model.py on make_model_scene, moving (the scene's velocities): one fixed iteration per loop
+    (the divergence solve on or off and the warm start as drawn; from an upload K_prev = Kv_prev = 0), both paths, with the bars of the
+    model tests.  Inputs are the device's sorted state after DENSITY and its vel_adv after P_ADVECT."""
+    from tests import dfsph_model
+    from tests.common import rel_err
+    sc = make_model_scene(seed, capi.DFSPH)
+    p, c = sc["p"], sc["cfg"]
+    tol = 1e-10 if sc["double"] else 1e-4
+    mn_v = min(c["min_v"], 1)
+    s = capi.Solver(p, max(sc["n"], 1), solver=capi.DFSPH, double=sc["double"], kernel_set=sc["kset"], reference_order=sc["ref"])
+    s.dfsph_configure(0.0, 1, 0.0, mn_v, c["warm"])
+    dev = {}
+    for stage, names in ((capi.STAGE_DENSITY, ("sortedPos", "sortedVel", "dens", "dfsphAlpha")), (capi.STAGE_P_ADVECT, ("sortedVel", "velAdv")),
+                         (capi.STAGE_P_SOLVE, ("velAdv", "pres", "P_l", "densCorr"))):
+        s.set_particles(sc["pos"], sc["vel"])
+        s.set_boundaries(sc["bi"], sc["vbi"], update_grid=False)
+        s.step_partial(stage)
+        dev.update({"%d %s" % (stage, nm): s.get(nm) for nm in names})
+    bs = s.get("bSorted") if sc["bi"] is not None else None
+    s.close()
+    x, v0 = dev["4 sortedPos"], dev["4 sortedVel"]
+    pairs = dfsph_model.Pairs(p, x, None if bs is None else bs[:, :3], None if bs is None else bs[:, 3], sc["kset"])
+    alpha, _ = dfsph_model.factor(p, pairs, sc["kset"])
+    fields = [("alpha", dev["4 dfsphAlpha"], alpha)]
+    if mn_v:
+        div = dfsph_model.solve(p, pairs, alpha, v0, min_iters=1, warm=bool(c["warm"]))
+        fields.append(("v_df", dev["7 sortedVel"], div["u"]))
+    den = dfsph_model.solve(p, pairs, alpha, dev["7 velAdv"], rho=dev["4 dens"], min_iters=1, warm=bool(c["warm"]))
+    fields += [("vstar", dev["8 velAdv"], den["u"]), ("K", dev["8 pres"], den["K"]), ("kappa", dev["8 P_l"], den["kappa"]),
+               ("rho_adv", dev["8 densCorr"], den["rho_adv"])]
+    if not all(np.all(np.isfinite(w)) for _, _, w in fields):
+        return "not comparable"
+    tag = "seed %d dfsph vs model (n=%d grid=%s cs/h=%s walls=%s double=%s kset=%d ref=%s cfg=%s)" % (
+        seed, sc["n"], sc["gs"], sc["cs"] / sc["h"], sc["bi"] is not None, sc["double"], sc["kset"], sc["ref"], c)
+    for nm, got, want in fields:
+        got = got[:, :3] if want.ndim == 2 else got
+        if not rel_err(got, want) <= tol:
+            return "%s: %s rel %.3g" % (tag, nm, rel_err(got, want))
+    return None
+
+
 def one_vs_model(seed, solver):
     """the device against the float64 model (tests/pcisph_model.py, tests/pbf_extras_model.py) on make_model_scene: one fixed
     iteration, both paths, both precisions and kernel sets by seed, with the bars of the model tests (rel. 1e-4 fp32, 1e-10 fp64;
     PBF velocities 10x).  Returns None, a failure message, "not comparable" where the model's own result is not finite, or "near cut"
     for a Monaghan scene with a pair within MONAGHAN_CUT_MARGIN of h where the model's positions are no longer the device's."""
+    if solver == capi.DFSPH:
+        return one_dfsph_vs_model(seed)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from tests import pbf_extras_model, pcisph_model
     from tests.common import rel_err
