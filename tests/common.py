@@ -33,6 +33,16 @@ def compressed_block(lattice=(10, 10, 10), solver=IISPH, double=False, kernel_se
     return p, pos, np.zeros_like(pos)
 
 
+def compressed_dam_break(lattice=(12, 10, 9), solver=IISPH, double=False, kernel_set=1, ratio=0.72):
+    """small_dam_break's tank (5-face boundary box, grid from the updateGrid rule) holding a jittered lattice at spacing ratio*h
+    instead of the resting one: the resting dam-break clamps every IISPH pressure to 0.  Returns (params, pos, vel, bi, vbi)."""
+    p, sc = small_dam_break(lattice, solver=solver, double=double, kernel_set=kernel_set)
+    real = np.float64 if double else np.float32
+    pos = scene.fluid_block(*lattice, float(p["interactionRadius"][0]), real=real, jitter=0.02,
+                            spacing=ratio * float(p["interactionRadius"][0]))
+    return p, pos, np.zeros_like(pos), sc["bi"], sc["vbi"]
+
+
 def rel_err(a, b):
     """max |a-b| / max|b| (array-level relative error, robust near zero entries)."""
     a = np.asarray(a, np.float64)
@@ -48,3 +58,16 @@ def check_cell_tables(cs_a, ce_a, cs_b, ce_b):
     np.testing.assert_array_equal(cs_a, cs_b)
     m = cs_b != 0xFFFFFFFF
     np.testing.assert_array_equal(ce_a[m], ce_b[m])
+
+
+def close_masked(got, want, tol, what=""):
+    """NaN-aware comparison: the non-finite entries are the same element for element (NaN where NaN, inf of the same sign), the
+    finite ones are within `tol` array-relative.  Returns the error of the finite entries."""
+    got, want = np.asarray(got), np.asarray(want)
+    fin = np.isfinite(want)
+    np.testing.assert_array_equal(np.isfinite(got), fin, err_msg=what)
+    np.testing.assert_array_equal(got[~fin], want[~fin], err_msg=what)   # (NaN == NaN here)
+    e = rel_err(got[fin], want[fin]) if fin.any() else 0.0
+    print("%s: %.3g (bar %.0e, %d non-finite)" % (what, e, tol, int((~fin).sum())))
+    assert e <= tol, (what, e, tol)
+    return e

@@ -89,3 +89,38 @@ def test_random_scenes_pcisph_pbf_device_equals_model(hip_lib, solver):
     assert not failures, failures[:3]
     skipped = results.count("not comparable") + results.count("near cut")
     assert skipped <= len(seeds) // 10, (results.count("not comparable"), results.count("near cut"))
+
+
+ORACLE_CELLS = [dict(solver=sv, double=d, kset=k) for sv in (0, 1) for d in (False, True) for k in (1, 0)]   # (capi.SESPH / IISPH)
+
+
+@pytest.mark.gpu
+def test_random_scenes_against_oracle(hip_lib):
+    """The soak's scenes against the CPU ORACLE (tools/fuzz_parity.py one_vs_oracle): one partial step, keys bit-exact, SESPH density /
+    pressure / forces and every IISPH intermediate plus the iteration count, non-finite entries element for element, finite ones
+    within the precision's bar.  Seeds 9200-9247 cycle through solver {SESPH, IISPH} x {fp32, fp64} x {Muller, Monaghan} (make_scene's
+    config override; the rest of each scene is the seed's own): 6 scenes per cell, with walls, narrow-x grids, far origins, NaN / inf
+    coordinates and coherent-re-sort sizes among them.  Only a seed whose oracle solve itself overflowed is not comparable: at most
+    10 % of the slice."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from fuzz_parity import make_scene, one_vs_oracle
+
+    seeds = list(range(9200, 9248))
+    cfg = {sd: ORACLE_CELLS[i % len(ORACLE_CELLS)] for i, sd in enumerate(seeds)}
+    scenes = {sd: make_scene(sd, config=cfg[sd]) for sd in seeds}
+    for cell in ORACLE_CELLS:
+        assert sum(all(sc[k] == v for k, v in cell.items()) for sc in scenes.values()) >= 3, cell
+    assert sum(sc["bi"] is not None for sc in scenes.values()) >= 20
+    assert sum(sc["gs"][0] < 4 for sc in scenes.values()) >= 3
+    assert sum(sd % 17 == 16 for sd in seeds) >= 2
+    assert sum(sc["n"] >= 40000 for sc in scenes.values()) >= 3
+    del scenes
+    errors, results = {}, {}
+    for sd in seeds:
+        results[sd] = one_vs_oracle(sd, config=cfg[sd], errors=errors)
+    for k in sorted(errors):
+        print("oracle slice max error solver=%d double=%d kset=%d %s: %.3g" % (k[0], k[1], k[2], k[3], errors[k]))
+    failures = [r for r in results.values() if r and r != "not comparable"]
+    assert not failures, failures[:3]
+    skipped = [sd for sd, r in results.items() if r == "not comparable"]
+    assert len(skipped) <= len(seeds) // 10, skipped
