@@ -199,6 +199,8 @@ enum {
                                    is the sorted K_prev of the step).  NRS_ARR_POS_PRED is refused. */
     NRS_ARR_DFSPH_KAPPA_V = 33, /* DFSPH: SReal[N] sorted Kv, the divergence solve's total (after a partial step up to DENSITY the
                                    sorted Kv_prev of the step); NRS_E_STATE on other contexts and before a step */
+    NRS_ARR_NORMALS = 34,   /* PCISPH, PBF, DFSPH: SVec4[N] sorted, xyz = the Akinci normal n_i and w = rho_i, of the last step that had
+                               gamma > 0 (nrs_set_surface_akinci); NRS_E_STATE before there is one, and on SESPH and IISPH contexts */
 };
 
 const char *nrs_last_error(void);
@@ -311,6 +313,15 @@ int nrs_pbf_set_vorticity(nrs_ctx *ctx, double eps_v);
 int nrs_dfsph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double max_divergence_error,
                         uint32_t min_divergence_iters, int warm_start);
 
+/* Surface tension and wall adhesion of Akinci, Akinci and Teschner (2013) on a PCISPH, PBF or DFSPH context (NRS_E_STATE on SESPH and
+ * IISPH contexts, whose steps are the reference's), DESIGN.md "Akinci surface tension and adhesion": the advection stage's force_adv
+ * gains -gamma m sum_j K_ij (m C(r_ij) r_ij / |r_ij| + n_i - n_j) - beta_adhesion m sum_b psi_b A(r_ib) r_ib / |r_ib|, with the normals
+ * n_i = h sum_j (m / rho_j) grad W(r_ij), K_ij = 2 rho0 / (rho_i + rho_j) and the kernels Cakinci / Aboundary of the parameter block's
+ * ksurf1, ksurf2, bpol.  While gamma > 0 the reference-style cohesion term of nrs_config.surface_tension is left out (two cohesion
+ * models do not stack).  Defaults 0, 0 (off: the step, its launches and its bits are those of a context that never called this).
+ * NRS_E_INVALID for a NaN, infinite or negative value.  Came after nrs_version() 0.3 without a version change, as PBF did. */
+int nrs_set_surface_akinci(nrs_ctx *ctx, double gamma, double beta_adhesion);
+
 /* Per-stage device time, measured with HIP events recorded on the context's stream around the stage's
  * launches.  stage_mask: bit s set = time NRS_STAGE_s (0 = off, 0xffffffff = every stage).  nrs_set_profiling also
  * resets the accumulated times.  nrs_stage_ms returns the time of that stage summed over all steps since the last
@@ -404,8 +415,9 @@ int nrs_boundary_volumes(int device, int precision, const void *bi4, uint64_t nb
 
 /* Test hook: the DEVICE smoothing kernels / vector helpers (common/kernels_impl.cuh:85-203, helper_math.h semantics) on n
  * caller-supplied separations r3 (and second vectors s3, may be NULL), HOST buffers of 3n SReal; which = 0 Wdefault, 1
- * Wdefault_grad, 2 Wpressure_grad, 3 Wviscosity_grad, 4 Wmonaghan, 5 Wmonaghan_grad, 8 dot, 9 length, 10 vec*float, 11 float*vec,
- * 12 vec/float, 13 identity, 14 +, 15 - (the numbering of oracle/ref_kernels_driver.cpp; scalars land in out[3i]).  Lets the
+ * Wdefault_grad, 2 Wpressure_grad, 3 Wviscosity_grad, 4 Wmonaghan, 5 Wmonaghan_grad, 6 Cakinci (c0 = ksurf1, c1 = ksurf2), 7 Aboundary
+ * (c0 = bpol; the reference's unclamped form: NaN where roundoff leaves its radicand negative), 8 dot, 9 length, 10 vec*float,
+ * 11 float*vec, 12 vec/float, 13 identity, 14 +, 15 - (the numbering of oracle/ref_kernels_driver.cpp; scalars land in out[3i]).  Lets the
  * tests compare the product's arithmetic bit for bit with the reference's own header compiled unmodified. */
 int nrs_eval_smoothing(int precision, int which, uint64_t n, const void *r3, const void *s3, double h, double c0, double c1, void *out);
 

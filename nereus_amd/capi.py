@@ -47,6 +47,7 @@ ARRAYS = {
     "densAdv": (20, "s"), "densCorr": (21, "s"), "P_l": (22, "s"), "aii": (23, "s"), "velAdv": (24, "v4"),
     "forcesAdv": (25, "v4"), "forcesP": (26, "v4"), "diiFluid": (27, "v4"), "diiBoundary": (28, "v4"),
     "sumDij": (29, "v4"), "posPred": (30, "v4"), "vorticity": (31, "v4"), "dfsphAlpha": (32, "s"), "dfsphKappaV": (33, "s"),
+    "normals": (34, "v4"),
 }
 
 # every symbol include/nereus_hip.h declares (checked by tests/test_abi.py)
@@ -59,7 +60,7 @@ EXPORTS = [
     "nrs_slab_message_bytes", "nrs_slab_histogram", "nrs_resort_stats", "nrs_snapshot_begin", "nrs_snapshot_wait",
     "nrs_get_stat", "nrs_boundary_volumes", "nrs_eval_smoothing", "nrs_iisph_predict", "nrs_iisph_iterate", "nrs_iisph_finish",
     "nrs_slab_last_counts", "nrs_pcisph_configure", "nrs_pbf_configure", "nrs_pbf_set_tensile",
-    "nrs_pbf_set_vorticity", "nrs_dfsph_configure",
+    "nrs_pbf_set_vorticity", "nrs_dfsph_configure", "nrs_set_surface_akinci",
 ]
 
 
@@ -115,6 +116,7 @@ def load_library(path=None):
     lib.nrs_pbf_set_tensile.argtypes = [vp, C.c_double, C.c_double]
     lib.nrs_pbf_set_vorticity.argtypes = [vp, C.c_double]
     lib.nrs_dfsph_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_uint32, i32]
+    lib.nrs_set_surface_akinci.argtypes = [vp, C.c_double, C.c_double]
     lib.nrs_set_profiling.argtypes = [vp, C.c_uint32]
     lib.nrs_stage_ms.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     lib.nrs_max_density.argtypes = [vp, C.POINTER(C.c_double)]
@@ -307,6 +309,10 @@ class Solver:
         minimum iterations (min_divergence_iters = 0: no divergence solve), and the warm start from the previous step's K / Kv"""
         self._chk(self.lib.nrs_dfsph_configure(self.h, float(max_density_error), int(min_iters), float(max_divergence_error),
                                                int(min_divergence_iters), int(warm_start)))
+
+    def surface_akinci(self, gamma=0.0, beta=0.0):
+        """Akinci surface tension gamma and wall adhesion beta_a on a PCISPH / PBF / DFSPH context (nrs_set_surface_akinci; 0, 0 = off)"""
+        self._chk(self.lib.nrs_set_surface_akinci(self.h, float(gamma), float(beta)))
 
     def set_profiling(self, stages=True):
         """stages: True = all, False = off, or an iterable of stage ids."""

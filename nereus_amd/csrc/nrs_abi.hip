@@ -318,6 +318,11 @@ int nrs_dfsph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_ite
     CTX_GUARD(ctx);
     return ctx->impl->dfsph_configure(max_density_error, min_iters, max_divergence_error, min_divergence_iters, warm_start);
 }
+int nrs_set_surface_akinci(nrs_ctx *ctx, double gamma, double beta_adhesion)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->set_surface_akinci(gamma, beta_adhesion);
+}
 int nrs_set_profiling(nrs_ctx *ctx, uint32_t stage_mask)
 {
     CTX_GUARD(ctx);

@@ -18,6 +18,7 @@
 #include "nrs_kernels_pcisph.h"
 #include "nrs_kernels_pbf.h"
 #include "nrs_kernels_dfsph.h"
+#include "nrs_kernels_akinci.h"
 #include "nrs_kernels_slab.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
@@ -156,6 +157,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool dfAlphaValid = false, dfKvValid = false; // NRS_ARR_DFSPH_ALPHA / _KAPPA_V hold a step's values
     uint32_t dfDenN = 0, dfDivN = 0; // particles whose e of the last density / divergence iteration pciErr / dfErrV hold (0: none)
     uint32_t dfDivIters = 0;          // divergence iterations of the last step
+    // Akinci surface tension and adhesion (nrs_kernels_akinci.h; PCISPH, PBF, DFSPH): gamma = beta_a = 0 is off; akNormals holds the
+    // records (n_i, rho_i), allocated when gamma is first set above 0
+    double akGamma = 0.0, akBeta = 0.0;
+    DevBuf akNormals;
+    bool akNormalsValid = false; // akNormals holds the records of a step
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
     HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
@@ -373,7 +379,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         for (auto &e : evPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        DevBuf *all[] = {&dfAlpha, &dfKvA, &dfKvB, &dfErrV, &pbfVort, &posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
+        DevBuf *all[] = {&dfAlpha, &dfKvA, &dfKvB, &dfErrV, &pbfVort, &akNormals, &posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
                          &inv, &sortTmp, &cellStart, &cellEnd, &bCellStart, &bCellEnd, &bSorted, &bHash, &bIndex,
                          &bHashAlt, &bIndexAlt, &densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP,
                          &posPred, &posPred2, &pciErr, &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
@@ -1276,6 +1282,28 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         pciDeltaValid = true;
         return NRS_OK;
     }
+    int set_surface_akinci(double gamma, double beta) override
+    {
+        if (!pcisph() && !pbf() && !dfsph()) return fail(NRS_E_STATE, "nrs_set_surface_akinci on a context that is not PCISPH, PBF or DFSPH");
+        if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(NRS_E_INVALID, "Akinci gamma must be finite and >= 0 (0 = off)");
+        if (!(beta >= 0.0) || !std::isfinite(beta)) return fail(NRS_E_INVALID, "Akinci beta_adhesion must be finite and >= 0 (0 = off)");
+        if (gamma > 0.0) NRSCHK(akNormals.alloc(sizeof(T4) * cap));
+        akGamma = gamma; akBeta = beta;
+        return NRS_OK;
+    }
+    // the advection launch with the Akinci model on (nrs_kernels_akinci.h); SURF_EFF: the context's fsurf term, off while gamma > 0
+    template <bool HAS_B, bool SURF_EFF> void akinci_advect(const PciArrays<R> &A0, const AkinciView<R> &K)
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        const GridView<R> G = grid_view();
+        if (!plan.lists)
+            hipLaunchKernelGGL((k_akinci_advect_ref<R, KSET, SURF_EFF, HAS_B>), g, b, 0, stream, P, G, A0, K, posB.as<T4>(), velB.as<T4>(),
+                               dens.as<R>(), presB.as<R>(), N);
+        else if constexpr (KSET == KS_MULLER)
+            launch_listed(k_akinci_advect_lists<R, KSET, SURF_EFF, HAS_B, true>, k_akinci_advect_lists<R, KSET, SURF_EFF, HAS_B>, g.x, P, G, A0, K,
+                          hit_buffer(), posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
+    }
     // the density scan and the advection launch of a PCISPH or PBF step (x*0 into posPred); *more = false when the step stops here
     template <bool HAS_B> int pci_prefix(int stop, bool *more)
     {
@@ -1305,7 +1333,19 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         pciXs = 0;
         const PciArrays<R> A0 = pci_view(0, 0);
-        if (!plan.lists)
+        const bool cohesion = akGamma > 0.0;
+        if (cohesion || (HAS_B && akBeta > 0.0)) { // the Akinci model: the normals launch, then the advection launch with its walk
+            const AkinciView<R> K{cohesion ? akNormals.as<T4>() : (T4 *)nullptr, (R)akGamma, (R)akBeta};
+            if (cohesion) {
+                if (!plan.lists)
+                    hipLaunchKernelGGL((k_akinci_normals_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), K.normals, N);
+                else if constexpr (KSET == KS_MULLER)
+                    hipLaunchKernelGGL((k_akinci_normals_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), dens.as<R>(), K.normals, N);
+                akNormalsValid = true;
+            }
+            if (SURF && !cohesion) akinci_advect<HAS_B, SURF>(A0, K);
+            else akinci_advect<HAS_B, false>(A0, K);
+        } else if (!plan.lists)
             hipLaunchKernelGGL((k_pci_advect_ref<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, A0, posB.as<T4>(), velB.as<T4>(), dens.as<R>(),
                                presB.as<R>(), N);
         else if constexpr (KSET == KS_MULLER)
@@ -2283,6 +2323,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (!pbf()) return fail(NRS_E_STATE, "PBF array requested from another context");
             if (!pbfVortValid) return fail(NRS_E_STATE, "no PBF step with vorticity confinement yet");
             p = pbfVort.p; sz = v; break;
+        case NRS_ARR_NORMALS:
+            if (!pcisph() && !pbf() && !dfsph()) return fail(NRS_E_STATE, "Akinci array requested from a SESPH or IISPH context");
+            if (!akNormalsValid) return fail(NRS_E_STATE, "no step with Akinci surface tension (gamma > 0) yet");
+            p = akNormals.p; sz = v; break;
         case NRS_ARR_DFSPH_ALPHA:
         case NRS_ARR_DFSPH_KAPPA_V:
             if (!dfsph()) return fail(NRS_E_STATE, "DFSPH array requested from another context");
@@ -2298,11 +2342,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         if (which == NRS_ARR_POS_PRED && !pcisph() && !pbf()) return fail(NRS_E_STATE, "PCISPH / PBF array requested from another context");
         const bool pciArray = which == NRS_ARR_VEL_ADV || which == NRS_ARR_FORCES_ADV || which == NRS_ARR_FORCES_P ||
-                              which == NRS_ARR_DENS_CORR || which == NRS_ARR_P_L || which == NRS_ARR_POS_PRED || which == NRS_ARR_VORTICITY;
+                              which == NRS_ARR_DENS_CORR || which == NRS_ARR_P_L || which == NRS_ARR_POS_PRED || which == NRS_ARR_VORTICITY || which == NRS_ARR_NORMALS;
         if (pcisph() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PCISPH context");
         if (pbf() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PBF context");
         const bool dfArray = which == NRS_ARR_VEL_ADV || which == NRS_ARR_FORCES_ADV || which == NRS_ARR_FORCES_P || which == NRS_ARR_DENS_CORR ||
-                             which == NRS_ARR_P_L || which == NRS_ARR_DFSPH_ALPHA || which == NRS_ARR_DFSPH_KAPPA_V;
+                             which == NRS_ARR_P_L || which == NRS_ARR_DFSPH_ALPHA || which == NRS_ARR_DFSPH_KAPPA_V || which == NRS_ARR_NORMALS;
         if (dfsph() && which >= NRS_ARR_DENS_ADV && !dfArray) return fail(NRS_E_STATE, "IISPH / PCISPH / PBF array requested from a DFSPH context");
         if (which >= NRS_ARR_DENS_ADV && sesph()) return fail(NRS_E_STATE, "IISPH array requested from a SESPH context");
         *dptr = p;

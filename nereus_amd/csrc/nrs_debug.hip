@@ -1,8 +1,9 @@
 // nrs_debug.hip — test hook: the DEVICE smoothing kernels and vector helpers (nrs_math.h) evaluated on caller-supplied
 // separations, so that tests can compare the product's arithmetic — not only the oracle's — with the reference's own
 // common/kernels_impl.cuh + helper_math.h compiled unmodified (oracle/_ref; fixture tests/golden/ref_kernels_pin.npz).
-// Same function numbering as oracle/ref_kernels_driver.cpp; Cakinci / Aboundary (6, 7) do not exist on the device (the
-// reference never calls them).
+// Same function numbering as oracle/ref_kernels_driver.cpp.  6 / 7 are Cakinci / Aboundary as the reference states them (it never
+// calls them; here they are the kernels of the Akinci surface model, nrs_kernels_akinci.h): 7 is the unclamped form, NaN where the
+// reference gives NaN — the force walk clamps the radicand (Aboundary_clamped).
 #include "nrs_ctx_base.h"
 #include "nrs_math.h"
 
@@ -23,6 +24,8 @@ __global__ void k_eval_smoothing(int which, uint32_t n, const R *__restrict__ r3
     case 3: v = Wviscosity_grad<R>(r, h, c0, c1); break;
     case 4: v.x = Wmonaghan<R>(r, h); break;
     case 5: v = Wmonaghan_grad<R>(r, h); break;
+    case 6: v.x = Cakinci<R>(r, h, c0, c1); break;
+    case 7: v.x = Aboundary<R>(r, h, c0); break;
     case 8: v.x = dot(r, s); break;
     case 9: v.x = length(r); break;
     case 10: v = r * (float)c0; break;
@@ -61,7 +64,7 @@ using namespace nrs;
 extern "C" int nrs_eval_smoothing(int precision, int which, uint64_t n, const void *r3, const void *s3, double h, double c0, double c1, void *out)
 {
     if (precision != 32 && precision != 64) return fail(NRS_E_INVALID, "precision must be 32 or 64");
-    if (which < 0 || which > 15 || which == 6 || which == 7) return fail(NRS_E_INVALID, "no such device function");
+    if (which < 0 || which > 15) return fail(NRS_E_INVALID, "no such device function");
     if (!n) return NRS_OK;
     if (!r3 || !out || n > (1ull << 30)) return fail(NRS_E_INVALID, "bad argument");
     int ndev = 0;

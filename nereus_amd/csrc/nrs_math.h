@@ -195,6 +195,53 @@ template <typename R> NRS_DEV V3<R> Wmonaghan_grad(V3<R> r, R h)
     return gradient;
 }
 
+// Akinci cohesion kernel (:208-228): the reference's expression in its operand types (2.0 * len is a double product)
+template <typename R> NRS_DEV R Cakinci(V3<R> r, R h, R ksurf1, R ksurf2)
+{
+    R len = length(r);
+    R poly = ksurf1;
+    R hr = h - len;
+    if (2.0 * len > h && len <= h) {
+        R a = (hr * hr * hr) * (len * len * len);
+        return poly * a;
+    } else if (len > 0.0 && 2 * len <= h) {
+        R a = 2 * (hr * hr * hr) * (len * len * len);
+        R b = ksurf2;
+        return poly * (a - b);
+    }
+    return (R)0.0;
+}
+// the radicand -4 r^2 / h + 6 r - 2 h of the adhesion kernel (:238-239): b is formed in double and rounded to SReal
+template <typename R> NRS_DEV R Aboundary_radicand(R rl, R h)
+{
+    R a = -((4 * (rl * rl)) / (h));
+    R b = (R)(6.0 * rl - 2.0 * h);
+    return a + b;
+}
+// Akinci adhesion kernel (:233-247): powf on a float, also in the fp64 build; NaN where roundoff leaves the radicand below zero
+// (next to r = h / 2 and r = h), as the reference
+template <typename R> NRS_DEV R Aboundary(V3<R> r, R h, R bpol)
+{
+    R rl = length(r);
+    if (2.0 * rl > h && rl <= h) {
+        R res = powf((float)Aboundary_radicand<R>(rl, h), (float)(1.0 / 4.0));
+        return bpol * res;
+    }
+    return (R)0.0;
+}
+// ... as the force walk evaluates it (DESIGN.md "Akinci surface tension and adhesion"): the radicand clamped at 0, and the fourth
+// root as two correctly rounded float square roots — within one float ulp of powf, and the same bits on every IEEE machine
+template <typename R> NRS_DEV R Aboundary_clamped(V3<R> r, R h, R bpol)
+{
+    R rl = length(r);
+    if (2.0 * rl > h && rl <= h) {
+        const float rad = (float)Aboundary_radicand<R>(rl, h);
+        R res = sqrt_rn(sqrt_rn(rad > 0.0f ? rad : 0.0f));
+        return bpol * res;
+    }
+    return (R)0.0;
+}
+
 template <typename R, int KSET> NRS_DEV R W_dens(V3<R> r, R ir, R kp)
 {
     if (KSET == KS_MULLER) return Wdefault<R>(r, ir, kp);

@@ -8,8 +8,11 @@
 
 NEREUS_NAMESPACE_BEGIN
 
-DFSPH::DFSPH() : SPH(), m_eta(1e-3f), m_etaV(1e-3f), m_minIters(2), m_minItersV(1), m_warmStart(true) {}
-DFSPH::DFSPH(SphSimParams params) : SPH(params), m_eta(1e-3f), m_etaV(1e-3f), m_minIters(2), m_minItersV(1), m_warmStart(true) {}
+DFSPH::DFSPH() : SPH(), m_eta(1e-3f), m_etaV(1e-3f), m_akinciGamma(0.0f), m_akinciBeta(0.0f), m_minIters(2), m_minItersV(1), m_warmStart(true) {}
+DFSPH::DFSPH(SphSimParams params)
+    : SPH(params), m_eta(1e-3f), m_etaV(1e-3f), m_akinciGamma(0.0f), m_akinciBeta(0.0f), m_minIters(2), m_minItersV(1), m_warmStart(true)
+{
+}
 DFSPH::~DFSPH() {}
 
 int DFSPH::solverKind() const { return NRS_SOLVER_DFSPH; }
@@ -27,10 +30,21 @@ void DFSPH::setSolverSettings(SReal eta, SUint minIters, SReal etaV, SUint minIt
     m_warmStart = warmStart;
 }
 
+void DFSPH::setAkinciSurface(SReal gamma, SReal beta)
+{
+    if (m_ctx) {
+        std::fprintf(stderr, "Nereus: DFSPH::setAkinciSurface must be called before the first update() / updateGpuBoundaries()\n");
+        std::exit(EXIT_FAILURE);
+    }
+    m_akinciGamma = gamma;
+    m_akinciBeta = beta;
+}
+
 void DFSPH::configureContext()
 {
     if (nrs_dfsph_configure(m_ctx, (double)m_eta, (uint32_t)m_minIters, (double)m_etaV, (uint32_t)m_minItersV, m_warmStart ? 1 : 0) != NRS_OK)
         fatal("nrs_dfsph_configure");
+    if (nrs_set_surface_akinci(m_ctx, (double)m_akinciGamma, (double)m_akinciBeta) != NRS_OK) fatal("nrs_set_surface_akinci");
 }
 
 SUint DFSPH::getLastIterations()

@@ -23,12 +23,16 @@ public:
     // read back), minItersV = 0 turns the divergence solve off, warmStart = start both solves from half the previous step's totals.
     // Defaults 1e-3, 2, 1e-3, 1, true.
     void setSolverSettings(SReal eta, SUint minIters, SReal etaV, SUint minItersV, bool warmStart);
+    // Surface tension gamma and wall adhesion beta of Akinci et al. 2013 (nrs_set_surface_akinci; 0, 0: off).  Same rule as
+    // setSolverSettings: before the context exists.
+    void setAkinciSurface(SReal gamma, SReal beta);
     SUint getLastIterations(); // density-solve iterations of the last step
     int solverKind() const override;
 
 protected:
     void configureContext() override; // hands the settings to every context ensureContext creates (a capacity change replaces it)
     SReal m_eta, m_etaV;
+    SReal m_akinciGamma, m_akinciBeta;
     SUint m_minIters, m_minItersV;
     bool m_warmStart;
 };

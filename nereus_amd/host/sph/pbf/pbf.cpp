@@ -9,11 +9,13 @@
 NEREUS_NAMESPACE_BEGIN
 
 PBF::PBF()
-    : SPH(), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_tensileK(0.0f), m_tensileDq(0.2f), m_vorticity(0.0f), m_minIters(2)
+    : SPH(), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_tensileK(0.0f), m_tensileDq(0.2f), m_vorticity(0.0f), m_akinciGamma(0.0f),
+      m_akinciBeta(0.0f), m_minIters(2)
 {
 }
 PBF::PBF(SphSimParams params)
-    : SPH(params), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_tensileK(0.0f), m_tensileDq(0.2f), m_vorticity(0.0f), m_minIters(2)
+    : SPH(params), m_eta(0.01f), m_relaxation(0.01f), m_xsph(0.0f), m_tensileK(0.0f), m_tensileDq(0.2f), m_vorticity(0.0f), m_akinciGamma(0.0f),
+      m_akinciBeta(0.0f), m_minIters(2)
 {
 }
 PBF::~PBF() {}
@@ -51,12 +53,23 @@ void PBF::setVorticityConfinement(SReal eps)
     m_vorticity = eps;
 }
 
+void PBF::setAkinciSurface(SReal gamma, SReal beta)
+{
+    if (m_ctx) {
+        std::fprintf(stderr, "Nereus: PBF::setAkinciSurface must be called before the first update() / updateGpuBoundaries()\n");
+        std::exit(EXIT_FAILURE);
+    }
+    m_akinciGamma = gamma;
+    m_akinciBeta = beta;
+}
+
 void PBF::configureContext()
 {
     if (nrs_pbf_configure(m_ctx, (double)m_eta, (uint32_t)m_minIters, (double)m_relaxation, (double)m_xsph) != NRS_OK)
         fatal("nrs_pbf_configure");
     if (nrs_pbf_set_tensile(m_ctx, (double)m_tensileK, (double)m_tensileDq) != NRS_OK) fatal("nrs_pbf_set_tensile");
     if (nrs_pbf_set_vorticity(m_ctx, (double)m_vorticity) != NRS_OK) fatal("nrs_pbf_set_vorticity");
+    if (nrs_set_surface_akinci(m_ctx, (double)m_akinciGamma, (double)m_akinciBeta) != NRS_OK) fatal("nrs_set_surface_akinci");
 }
 
 SUint PBF::getLastIterations()

@@ -21,6 +21,9 @@ public:
     // confinement with factor eps (nrs_pbf_set_vorticity; 0: off).  Same rule as setSolverSettings: before the context exists.
     void setTensileCorrection(SReal k, SReal dq);
     void setVorticityConfinement(SReal eps);
+    // Surface tension gamma and wall adhesion beta of Akinci et al. 2013 (nrs_set_surface_akinci; 0, 0: off).  Same rule as
+    // setSolverSettings: before the context exists.
+    void setAkinciSurface(SReal gamma, SReal beta);
     SUint getLastIterations(); // solver iterations of the last step
     int solverKind() const override;
 
@@ -28,6 +31,7 @@ protected:
     void configureContext() override; // hands the settings to every context ensureContext creates (a capacity change replaces it)
     SReal m_eta, m_relaxation, m_xsph;
     SReal m_tensileK, m_tensileDq, m_vorticity;
+    SReal m_akinciGamma, m_akinciBeta;
     SUint m_minIters;
 };
 

@@ -14,8 +14,8 @@
 
 NEREUS_NAMESPACE_BEGIN
 
-PCISPH::PCISPH() : SPH(), m_pressureSolve(false), m_eta(0.01f) {}
-PCISPH::PCISPH(SphSimParams params) : SPH(params), m_pressureSolve(false), m_eta(0.01f) {}
+PCISPH::PCISPH() : SPH(), m_pressureSolve(false), m_eta(0.01f), m_akinciGamma(0.0f), m_akinciBeta(0.0f) {}
+PCISPH::PCISPH(SphSimParams params) : SPH(params), m_pressureSolve(false), m_eta(0.01f), m_akinciGamma(0.0f), m_akinciBeta(0.0f) {}
 PCISPH::~PCISPH() {}
 void PCISPH::_initialize() { SPH::_initialize(); }
 void PCISPH::_finalize() { SPH::_finalize(); }
@@ -32,9 +32,21 @@ void PCISPH::setPressureSolve(bool on, SReal eta)
     m_eta = eta;
 }
 
+void PCISPH::setAkinciSurface(SReal gamma, SReal beta)
+{
+    if (m_ctx) {
+        std::fprintf(stderr, "Nereus: PCISPH::setAkinciSurface must be called before the first update() / updateGpuBoundaries()\n");
+        std::exit(EXIT_FAILURE);
+    }
+    m_akinciGamma = gamma;
+    m_akinciBeta = beta;
+}
+
 void PCISPH::configureContext()
 {
-    if (m_pressureSolve && nrs_pcisph_configure(m_ctx, (double)m_eta, 3, 0.0, 0.0) != NRS_OK) fatal("nrs_pcisph_configure");
+    if (!m_pressureSolve) return;
+    if (nrs_pcisph_configure(m_ctx, (double)m_eta, 3, 0.0, 0.0) != NRS_OK) fatal("nrs_pcisph_configure");
+    if (nrs_set_surface_akinci(m_ctx, (double)m_akinciGamma, (double)m_akinciBeta) != NRS_OK) fatal("nrs_set_surface_akinci");
 }
 
 SUint PCISPH::getLastIterations()

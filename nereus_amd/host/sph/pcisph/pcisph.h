@@ -21,6 +21,9 @@ public:
     // Opt in to the PCISPH pressure solve (off: the reference's stub).  Must be called before the device context exists, i.e.
     // before the first update() or updateGpuBoundaries(); eta = largest density error max(rho - rho0, 0) / rho0 the loop accepts.
     void setPressureSolve(bool on, SReal eta = 0.01f);
+    // Surface tension gamma and wall adhesion beta of Akinci et al. 2013 (nrs_set_surface_akinci; 0, 0: off) for the opted-in pressure
+    // solve (the stub ignores them).  Same rule as setPressureSolve: before the context exists.
+    void setAkinciSurface(SReal gamma, SReal beta);
     SUint getLastIterations(); // solver iterations of the last step (0 for the stub)
     virtual int solverKind() const;
 
@@ -28,6 +31,7 @@ protected:
     virtual void configureContext(); // hands eta to every context ensureContext creates (a capacity change replaces it)
     bool m_pressureSolve;
     SReal m_eta;
+    SReal m_akinciGamma, m_akinciBeta;
 };
 
 NEREUS_NAMESPACE_END

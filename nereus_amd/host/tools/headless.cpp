@@ -7,7 +7,8 @@
 //                                                               Nereus::PBF with its default settings, and pbf-full: PBF with
 //                                                               XSPH 0.01, the tensile correction k = 1e-4, dq = 0.2 and
 //                                                               vorticity confinement eps_v = 0.01; dfsph: Nereus::DFSPH with
-//                                                               its default settings)
+//                                                               its default settings, and dfsph-akinci: DFSPH with
+//                                                               setAkinciSurface(1, 1))
 //   headless resume  <sesph|iisph> <in.bin> <steps_a> <steps_b> <ckpt> <out.bin>   run steps_a, saveState, then a NEW
 //                                                               solver loadState()s and runs steps_b (boundaries re-set)
 //   headless cfl     sesph <in.bin> <steps> <out.bin>           run with setAdaptiveTimestep(true)
@@ -73,7 +74,8 @@ int main(int argc, char **argv)
         return 0;
     }
     const bool iisph = kind == "iisph", pcisphSolve = kind == "pcisph-solve", pcisph = kind == "pcisph" || pcisphSolve;
-    const bool pbfFull = kind == "pbf-full", pbf = kind == "pbf" || pbfFull, dfsph = kind == "dfsph";
+    const bool pbfFull = kind == "pbf-full", pbf = kind == "pbf" || pbfFull;
+    const bool dfsphAkinci = kind == "dfsph-akinci", dfsph = kind == "dfsph" || dfsphAkinci;
     Nereus::SPH *sim = iisph ? (Nereus::SPH *)new Nereus::IISPH()
                              : (pcisph ? (Nereus::SPH *)new Nereus::PCISPH()
                                        : (pbf ? (Nereus::SPH *)new Nereus::PBF() : (dfsph ? (Nereus::SPH *)new Nereus::DFSPH() : new Nereus::SPH())));
@@ -84,6 +86,7 @@ int main(int argc, char **argv)
         p->setTensileCorrection((SReal)1e-4, (SReal)0.2);
         p->setVorticityConfinement((SReal)0.01);
     }
+    if (dfsphAkinci) static_cast<Nereus::DFSPH *>(sim)->setAkinciSurface((SReal)1.0, (SReal)1.0);
     sim->_initialize();
     std::vector<SVec4> bi;
     std::vector<SReal> vbi;
