@@ -134,6 +134,8 @@ typedef struct nrs_config {
  * PBF and DFSPH steps have the same stages (and the same refusals).  DFSPH: DENSITY also holds the factor launch (alpha), P_ADVECT
  * the divergence solve on the sorted velocities ahead of the advection launch, P_SOLVE the density solve on vel_adv, P_INTEGRATE
  * v = vel_adv, x += dt v. */
+/* On a context whose boundary bodies move (nrs_set_boundary_bodies) NRS_STAGE_HASH also holds the step's rebuild of the boundary
+ * tables on the device: pose + hash, radix sort, reorder, near-boundary bits. */
 enum {
     NRS_STAGE_HASH = 1,      /* calcHash                     sph_cuda.cu:230 */
     NRS_STAGE_SORT = 2,      /* sortParticles                sph_cuda.cu:58 */
@@ -201,6 +203,9 @@ enum {
                                    sorted Kv_prev of the step); NRS_E_STATE on other contexts and before a step */
     NRS_ARR_NORMALS = 34,   /* PCISPH, PBF, DFSPH: SVec4[N] sorted, xyz = the Akinci normal n_i and w = rho_i, of the last step that had
                                gamma > 0 (nrs_set_surface_akinci); NRS_E_STATE before there is one, and on SESPH and IISPH contexts */
+    NRS_ARR_B_BODY = 35,    /* uint32[Nb]: the body id of every SORTED boundary particle (nrs_set_boundary_bodies); NRS_E_STATE without
+                               an assignment.  On a context with bodies NRS_ARR_B_SORTED, _B_HASH, _B_INDEX and the boundary cell
+                               tables show the pose of the last step */
 };
 
 const char *nrs_last_error(void);
@@ -233,6 +238,31 @@ uint64_t nrs_num_particles(nrs_ctx *ctx);
  * build the boundary cell ranges.  nb = 0 clears the boundaries.  The (possibly new) grid is visible
  * through nrs_get_params. */
 int nrs_set_boundaries(nrs_ctx *ctx, const void *bi4, const void *vbi, uint64_t nb, int update_grid);
+
+/* ---- kinematic boundary bodies (DESIGN.md "Kinematic boundary bodies"; came after nrs_version() 0.3 without a version change) ----
+ * The boundary particles of the last nrs_set_boundaries are grouped into rigid bodies whose poses the context advances at the start
+ * of every step, x += dt v, q = exp(dt omega / 2) q with dt the step's time step, and whose boundary tables it rebuilds on the
+ * device, on its stream, with no host wait.  The fluid sees the walls at the step's pose; DFSPH also sees their velocity.  One-way:
+ * the fluid does not push back.
+ * nrs_set_boundary_bodies: body_of[i] is the body of boundary particle i, in upload order.  Body 0 is the static world and is never
+ * transformed; bodies 1 .. nbodies-1 are rigid.  The uploaded positions are each body's rest pose, its origin c_k the mean of its
+ * rest positions.  body_of == NULL or nbodies <= 1 clears the assignment (the walls return to the uploaded positions), and so does
+ * every later nrs_set_boundaries.  NRS_E_STATE before any nrs_set_boundaries and while a host-driven IISPH step is in progress;
+ * NRS_E_INVALID for nb different from the context's boundary count, an id >= nbodies, nbodies > NRS_MAX_BODIES or a slab context
+ * (nrs_slab_configure on a context with bodies fails the same way).
+ * The grid is not re-derived: nrs_set_boundaries(update_grid) sees the rest poses only, the caller sizes it for the whole motion (a
+ * body that leaves it wraps through the hash, as fluid particles do).  The volumes V_b are kept: they are invariant within a rigid
+ * body; bodies that come to overlap each other are the caller's business.  The host classes' checkpoints do not hold poses. */
+enum { NRS_MAX_BODIES = 16 };
+int nrs_set_boundary_bodies(nrs_ctx *ctx, const uint32_t *body_of, uint64_t nb, uint32_t nbodies);
+/* World-frame linear velocity of the body's origin and angular velocity about it, held until changed (default 0).  NRS_E_INVALID for
+ * body 0, an unknown body, a NaN or an infinite value.  Does not wait for the device. */
+int nrs_set_body_velocity(nrs_ctx *ctx, uint32_t body, const double v[3], const double omega[3]);
+/* A teleport: origin x and orientation q = (w, x, y, z), normalised by the library (NRS_E_INVALID for a zero or non-finite one).  The
+ * next step rebuilds the tables at this pose (after advancing it, if the body has a velocity). */
+int nrs_set_body_pose(nrs_ctx *ctx, uint32_t body, const double x[3], const double q[4]);
+/* The pose the last completed or enqueued step used (or the one set since). */
+int nrs_get_body_pose(nrs_ctx *ctx, uint32_t body, double x[3], double q[4]);
 
 /* update() x nsteps with state resident on the device (no per-step PCIe traffic).  Asynchronous for the caller: a call with
  * nsteps >= 2 hands the steps to a thread owned by the context and returns at once (before the device has finished, usually before

@@ -24,6 +24,7 @@ FLAG_FAST_ARITH = 32
 FLAG_IISPH_SELF_BY_SLOT = 64
 FLAG_NO_WALL_WORKGROUPS = 128
 FLAG_STAGED_SCAN = 256
+MAX_BODIES = 16
 E_NOTREADY = -6
 STAT_MOVERS, STAT_HIT_OVERFLOW, STAT_HIT_MEAN, STAT_HIT_MAX, STAT_UNSTAGED = 0, 1, 2, 3, 4
 STAT_DENSITY_ERROR, STAT_PCISPH_DELTA, STAT_PBF_EPSILON = 5, 6, 7
@@ -47,7 +48,7 @@ ARRAYS = {
     "densAdv": (20, "s"), "densCorr": (21, "s"), "P_l": (22, "s"), "aii": (23, "s"), "velAdv": (24, "v4"),
     "forcesAdv": (25, "v4"), "forcesP": (26, "v4"), "diiFluid": (27, "v4"), "diiBoundary": (28, "v4"),
     "sumDij": (29, "v4"), "posPred": (30, "v4"), "vorticity": (31, "v4"), "dfsphAlpha": (32, "s"), "dfsphKappaV": (33, "s"),
-    "normals": (34, "v4"),
+    "normals": (34, "v4"), "b_body": (35, "u"),
 }
 
 # every symbol include/nereus_hip.h declares (checked by tests/test_abi.py)
@@ -61,6 +62,7 @@ EXPORTS = [
     "nrs_get_stat", "nrs_boundary_volumes", "nrs_eval_smoothing", "nrs_iisph_predict", "nrs_iisph_iterate", "nrs_iisph_finish",
     "nrs_slab_last_counts", "nrs_pcisph_configure", "nrs_pbf_configure", "nrs_pbf_set_tensile",
     "nrs_pbf_set_vorticity", "nrs_dfsph_configure", "nrs_set_surface_akinci",
+    "nrs_set_boundary_bodies", "nrs_set_body_velocity", "nrs_set_body_pose", "nrs_get_body_pose",
 ]
 
 
@@ -103,6 +105,11 @@ def load_library(path=None):
     lib.nrs_num_particles.argtypes = [vp]
     lib.nrs_num_particles.restype = u64
     lib.nrs_set_boundaries.argtypes = [vp, vp, vp, u64, i32]
+    dp = C.POINTER(C.c_double)
+    lib.nrs_set_boundary_bodies.argtypes = [vp, vp, u64, C.c_uint32]
+    lib.nrs_set_body_velocity.argtypes = [vp, C.c_uint32, dp, dp]
+    lib.nrs_set_body_pose.argtypes = [vp, C.c_uint32, dp, dp]
+    lib.nrs_get_body_pose.argtypes = [vp, C.c_uint32, dp, dp]
     lib.nrs_step.argtypes = [vp, i32]
     lib.nrs_step_partial.argtypes = [vp, i32]
     lib.nrs_synchronize.argtypes = [vp]
@@ -239,6 +246,32 @@ class Solver:
         vbi = np.ascontiguousarray(vbi, dtype=self.real).reshape(-1)
         assert vbi.shape[0] == bi4.shape[0]
         self._chk(self.lib.nrs_set_boundaries(self.h, _ptr(bi4), _ptr(vbi), bi4.shape[0], int(update_grid)))
+
+    # ---- kinematic boundary bodies -----------------------------------------------------------------
+    def set_boundary_bodies(self, body_of, nbodies):
+        """group the boundary particles of the last set_boundaries into rigid bodies (nrs_set_boundary_bodies): body_of[i] in
+        0 .. nbodies-1, body 0 the static world; None or nbodies <= 1 clears the assignment"""
+        if body_of is None:
+            self._chk(self.lib.nrs_set_boundary_bodies(self.h, None, 0, int(nbodies)))
+            return
+        body_of = np.ascontiguousarray(body_of, dtype=np.uint32).reshape(-1)
+        self._chk(self.lib.nrs_set_boundary_bodies(self.h, _ptr(body_of), body_of.shape[0], int(nbodies)))
+
+    def set_body_velocity(self, body, v, omega=(0.0, 0.0, 0.0)):
+        """world-frame linear velocity of the body's origin and angular velocity about it, held until changed"""
+        v, w = (C.c_double * 3)(*[float(a) for a in v]), (C.c_double * 3)(*[float(a) for a in omega])
+        self._chk(self.lib.nrs_set_body_velocity(self.h, int(body), v, w))
+
+    def set_body_pose(self, body, x, q=(1.0, 0.0, 0.0, 0.0)):
+        """teleport: origin x and orientation q = (w, x, y, z), normalised by the library"""
+        x, q = (C.c_double * 3)(*[float(a) for a in x]), (C.c_double * 4)(*[float(a) for a in q])
+        self._chk(self.lib.nrs_set_body_pose(self.h, int(body), x, q))
+
+    def body_pose(self, body):
+        """(x, q) of the body as the last step used it, float64 arrays"""
+        x, q = (C.c_double * 3)(), (C.c_double * 4)()
+        self._chk(self.lib.nrs_get_body_pose(self.h, int(body), x, q))
+        return np.array(x[:]), np.array(q[:])
 
     @property
     def n(self):

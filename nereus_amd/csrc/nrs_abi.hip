@@ -213,6 +213,29 @@ int nrs_set_boundaries(nrs_ctx *ctx, const void *bi4, const void *vbi, uint64_t 
     CTX_GUARD(ctx);
     return ctx->impl->set_boundaries(bi4, vbi, nb, update_grid);
 }
+int nrs_set_boundary_bodies(nrs_ctx *ctx, const uint32_t *body_of, uint64_t nb, uint32_t nbodies)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->set_boundary_bodies(body_of, nb, nbodies);
+}
+int nrs_set_body_velocity(nrs_ctx *ctx, uint32_t body, const double v[3], const double omega[3])
+{
+    CTX_GUARD(ctx);
+    if (!v || !omega) return fail(NRS_E_INVALID, "NULL argument");
+    return ctx->impl->set_body_velocity(body, v, omega);
+}
+int nrs_set_body_pose(nrs_ctx *ctx, uint32_t body, const double x[3], const double q[4])
+{
+    CTX_GUARD(ctx);
+    if (!x || !q) return fail(NRS_E_INVALID, "NULL argument");
+    return ctx->impl->set_body_pose(body, x, q);
+}
+int nrs_get_body_pose(nrs_ctx *ctx, uint32_t body, double x[3], double q[4])
+{
+    CTX_GUARD(ctx);
+    if (!x || !q) return fail(NRS_E_INVALID, "NULL argument");
+    return ctx->impl->get_body_pose(body, x, q);
+}
 int nrs_step(nrs_ctx *ctx, int nsteps)
 {
     if (!ctx || !ctx->impl) return fail(NRS_E_INVALID, "NULL context");

@@ -77,6 +77,10 @@ struct CtxBase {
     virtual int set_n(uint64_t n) = 0;
     virtual uint64_t get_n() = 0;
     virtual int set_boundaries(const void *bi4, const void *vbi, uint64_t nb, int update_grid) = 0;
+    virtual int set_boundary_bodies(const uint32_t *bodyOf, uint64_t nb, uint32_t nbodies) = 0;
+    virtual int set_body_velocity(uint32_t body, const double *v, const double *omega) = 0;
+    virtual int set_body_pose(uint32_t body, const double *x, const double *q) = 0;
+    virtual int get_body_pose(uint32_t body, double *x, double *q) = 0;
     virtual int step(int nsteps, int stop) = 0;
     virtual int sync() = 0;
     virtual int download(void *pos4, void *vel4, void *pres) = 0;

@@ -19,6 +19,7 @@
 #include "nrs_kernels_pbf.h"
 #include "nrs_kernels_dfsph.h"
 #include "nrs_kernels_akinci.h"
+#include "nrs_kernels_bodies.h"
 #include "nrs_kernels_slab.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
@@ -379,7 +380,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         for (auto &e : evPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        DevBuf *all[] = {&dfAlpha, &dfKvA, &dfKvB, &dfErrV, &pbfVort, &akNormals, &posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
+        DevBuf *all[] = {&bdRest, &bdVbi, &bdBodyOf, &bdWorld, &bdBodySorted, &bdVel, &bdSortTmp, &dfAlpha, &dfKvA, &dfKvB, &dfErrV, &pbfVort, &akNormals, &posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
                          &inv, &sortTmp, &cellStart, &cellEnd, &bCellStart, &bCellEnd, &bSorted, &bHash, &bIndex,
                          &bHashAlt, &bIndexAlt, &densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP,
                          &posPred, &posPred2, &pciErr, &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
@@ -651,9 +652,192 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             hipLaunchKernelGGL((k_mark_near_boundary<R>), dim3(nblocks(nb)), dim3(BLOCK), 0, stream, P, bHashCur, (uint32_t)nb, nearBits.as<uint32_t>());
             nearBitsValid = true;
         }
+        if (nBodies) { // the tables above hold the REST poses: sorted ids for them, and a rebuild at the poses before the next step
+            hipLaunchKernelGGL(k_gather_body, dim3(nblocks(nb)), dim3(BLOCK), 0, stream, bIndexCur, bdBodyOf.as<uint32_t>(), bdBodySorted.as<uint32_t>(),
+                               (uint32_t)nb);
+            HIPCHK(hipMemsetAsync(bdVel.p, 0, sizeof(T4) * nb, stream));
+            bodiesDirty = bodies_displaced();
+        }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
         t.release(); dBi.release(); dVbi.release();
+        return NRS_OK;
+    }
+
+    // ---- kinematic boundary bodies (nrs_kernels_bodies.h; DESIGN.md "Kinematic boundary bodies") ------------------------------------
+    // Host pose state in double; body 0 is the static world.  nBodies = 0: no assignment.  The context is "moving" while a body has a
+    // velocity or a pose was set since the last rebuild (bodiesDirty); only then does a step touch the boundary tables.
+    struct Body { double c[3], x[3], q[4], v[3], w[3]; };
+    uint32_t nBodies = 0;
+    Body bodies[NRS_MAX_BODIES];
+    bool bodiesDirty = false;
+    bool movingStep = false; // this step rebuilt the tables: DFSPH's A launches take the wall velocities
+    DevBuf bdRest, bdVbi, bdBodyOf, bdWorld, bdBodySorted, bdVel, bdSortTmp;
+    static bool body_has_velocity(const Body &b) { return b.v[0] != 0.0 || b.v[1] != 0.0 || b.v[2] != 0.0 || b.w[0] != 0.0 || b.w[1] != 0.0 || b.w[2] != 0.0; }
+    bool bodies_displaced() const
+    {
+        for (uint32_t k = 1; k < nBodies; ++k) {
+            const Body &b = bodies[k];
+            if (b.x[0] != b.c[0] || b.x[1] != b.c[1] || b.x[2] != b.c[2] || b.q[0] != 1.0 || b.q[1] != 0.0 || b.q[2] != 0.0 || b.q[3] != 0.0) return true;
+        }
+        return false;
+    }
+    bool bodies_moving() const
+    {
+        if (!nBodies) return false;
+        if (bodiesDirty) return true;
+        for (uint32_t k = 1; k < nBodies; ++k) if (body_has_velocity(bodies[k])) return true;
+        return false;
+    }
+    void clear_bodies() { nBodies = 0; bodiesDirty = false; movingStep = false; }
+    size_t body_sort_bytes(unsigned bits)
+    {
+        size_t tmp = 0;
+        rocprim::double_buffer<uint32_t> k(bHash.as<uint32_t>(), bHashAlt.as<uint32_t>());
+        rocprim::double_buffer<uint32_t> v(bIndex.as<uint32_t>(), bIndexAlt.as<uint32_t>());
+        if (rocprim::radix_sort_pairs(nullptr, tmp, k, v, (size_t)nb, 0u, bits, stream) != hipSuccess) return 0;
+        return tmp;
+    }
+    int set_boundary_bodies(const uint32_t *bodyOf, uint64_t nbGiven, uint32_t nbodies) override
+    {
+        NRSCHK(refuse_mid_iisph("nrs_set_boundary_bodies"));
+        if (!nb) return fail(NRS_E_STATE, "nrs_set_boundary_bodies before nrs_set_boundaries");
+        if (!bodyOf || nbodies <= 1) { // clear: the walls return to the uploaded positions
+            const bool had = nBodies != 0;
+            const bool displaced = had && (bodies_displaced() || bodiesDirty);
+            clear_bodies();
+            if (displaced) NRSCHK(rebuild_boundary_tables());
+            return NRS_OK;
+        }
+        if (slabOn) return fail(NRS_E_INVALID, "slab contexts have no boundary bodies");
+        if (nbGiven != nb) return fail(NRS_E_INVALID, "nb differs from the context's boundary particle count");
+        if (nbodies > (uint32_t)NRS_MAX_BODIES) return fail(NRS_E_INVALID, "more than NRS_MAX_BODIES bodies");
+        double sum[NRS_MAX_BODIES][3] = {{0.0}};
+        uint64_t cnt[NRS_MAX_BODIES] = {0};
+        for (uint64_t i = 0; i < nb; ++i) {
+            const uint32_t k = bodyOf[i];
+            if (k >= nbodies) return fail(NRS_E_INVALID, "body id >= nbodies");
+            sum[k][0] += (double)hostBi[i].x; sum[k][1] += (double)hostBi[i].y; sum[k][2] += (double)hostBi[i].z;
+            ++cnt[k];
+        }
+        const bool displaced = nBodies && (bodies_displaced() || bodiesDirty);
+        clear_bodies();
+        if (displaced) NRSCHK(rebuild_boundary_tables()); // (a new assignment starts from the rest poses)
+        NRSCHK(bdRest.alloc(sizeof(T4) * nb)); NRSCHK(bdVbi.alloc(sizeof(R) * nb)); NRSCHK(bdBodyOf.alloc(4 * nb));
+        NRSCHK(bdWorld.alloc(sizeof(T4) * nb)); NRSCHK(bdBodySorted.alloc(4 * nb)); NRSCHK(bdVel.alloc(sizeof(T4) * nb));
+        const size_t tmp = std::max(body_sort_bytes(sort_end_bit()), body_sort_bytes(32u));
+        if (!tmp) return fail(NRS_E_HIP, "rocprim::radix_sort_pairs: no temporary storage size for the boundary sort");
+        NRSCHK(bdSortTmp.alloc(tmp));
+        HIPCHK(hipMemcpyAsync(bdRest.p, hostBi.data(), sizeof(T4) * nb, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(bdVbi.p, hostVbi.data(), sizeof(R) * nb, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(bdBodyOf.p, bodyOf, 4 * nb, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_gather_body, dim3(nblocks(nb)), dim3(BLOCK), 0, stream, bIndexCur, bdBodyOf.as<uint32_t>(), bdBodySorted.as<uint32_t>(),
+                           (uint32_t)nb);
+        HIPCHK(hipMemsetAsync(bdVel.p, 0, sizeof(T4) * nb, stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream)); // the caller may reuse body_of on return
+        for (uint32_t k = 0; k < nbodies; ++k) {
+            Body &b = bodies[k];
+            for (int a = 0; a < 3; ++a) {
+                b.c[a] = cnt[k] ? sum[k][a] / (double)cnt[k] : 0.0;
+                b.x[a] = b.c[a]; b.v[a] = 0.0; b.w[a] = 0.0;
+            }
+            b.q[0] = 1.0; b.q[1] = b.q[2] = b.q[3] = 0.0;
+        }
+        nBodies = nbodies;
+        return NRS_OK;
+    }
+    int check_body(uint32_t body) const
+    {
+        if (!nBodies) return fail(NRS_E_INVALID, "the context has no boundary bodies (nrs_set_boundary_bodies first)");
+        if (body == 0) return fail(NRS_E_INVALID, "body 0 is the static world");
+        if (body >= nBodies) return fail(NRS_E_INVALID, "unknown body");
+        return NRS_OK;
+    }
+    int set_body_velocity(uint32_t body, const double *v, const double *omega) override
+    {
+        NRSCHK(check_body(body));
+        for (int a = 0; a < 3; ++a)
+            if (!std::isfinite(v[a]) || !std::isfinite(omega[a])) return fail(NRS_E_INVALID, "body velocity must be finite");
+        for (int a = 0; a < 3; ++a) { bodies[body].v[a] = v[a]; bodies[body].w[a] = omega[a]; }
+        return NRS_OK;
+    }
+    int set_body_pose(uint32_t body, const double *x, const double *q) override
+    {
+        NRSCHK(check_body(body));
+        const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        if (!std::isfinite(x[0]) || !std::isfinite(x[1]) || !std::isfinite(x[2]) || !std::isfinite(nq)) return fail(NRS_E_INVALID, "body pose must be finite");
+        if (!(nq > 0.0)) return fail(NRS_E_INVALID, "zero quaternion");
+        for (int a = 0; a < 3; ++a) bodies[body].x[a] = x[a];
+        for (int a = 0; a < 4; ++a) bodies[body].q[a] = q[a] / nq;
+        bodiesDirty = true;
+        return NRS_OK;
+    }
+    int get_body_pose(uint32_t body, double *x, double *q) override
+    {
+        NRSCHK(check_body(body));
+        for (int a = 0; a < 3; ++a) x[a] = bodies[body].x[a];
+        for (int a = 0; a < 4; ++a) q[a] = bodies[body].q[a];
+        return NRS_OK;
+    }
+    // x += dt v; q = exp(dt omega / 2) q (the exact exponential map, identity when |omega| = 0), renormalised
+    static void advance_body(Body &b, double dt)
+    {
+        for (int a = 0; a < 3; ++a) b.x[a] += dt * b.v[a];
+        const double wn = std::sqrt(b.w[0] * b.w[0] + b.w[1] * b.w[1] + b.w[2] * b.w[2]);
+        if (wn == 0.0) return;
+        const double half = 0.5 * dt * wn, s = std::sin(half) / wn;
+        const double e[4] = {std::cos(half), s * b.w[0], s * b.w[1], s * b.w[2]};
+        const double *q = b.q;
+        double r[4] = {e[0] * q[0] - e[1] * q[1] - e[2] * q[2] - e[3] * q[3], e[0] * q[1] + e[1] * q[0] + e[2] * q[3] - e[3] * q[2],
+                       e[0] * q[2] - e[1] * q[3] + e[2] * q[0] + e[3] * q[1], e[0] * q[3] + e[1] * q[2] - e[2] * q[1] + e[3] * q[0]};
+        const double nr = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+        for (int a = 0; a < 4; ++a) b.q[a] = r[a] / nr;
+    }
+    // Start of a step of a moving context: advance the poses (host, double), round the table to SReal, rebuild the boundary tables on
+    // the stream.  No synchronisation, no allocation, no read-back.  Timed as NRS_STAGE_HASH.
+    int advance_bodies_and_rebuild()
+    {
+        movingStep = bodies_moving();
+        if (!movingStep) return NRS_OK;
+        const double dt = (double)PU.timestep;
+        BodyTable<R> T;
+        std::memset(&T, 0, sizeof(T));
+        for (uint32_t k = 1; k < nBodies; ++k) {
+            Body &b = bodies[k];
+            if (body_has_velocity(b)) advance_body(b, dt);
+            const double w = b.q[0], x = b.q[1], y = b.q[2], z = b.q[3];
+            const double rot[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                                   2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                                   2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
+            BodyPose<R> &o = T.b[k];
+            for (int a = 0; a < 9; ++a) o.rot[a] = (R)rot[a];
+            for (int a = 0; a < 3; ++a) { o.x[a] = (R)b.x[a]; o.c[a] = (R)b.c[a]; o.v[a] = (R)b.v[a]; o.w[a] = (R)b.w[a]; }
+        }
+        const uint32_t NB = (uint32_t)nb;
+        const unsigned bits = sort_end_bit();
+        if (body_sort_bytes(bits) > bdSortTmp.bytes || (size_t)P.numCells * 4 > bCellStart.bytes)
+            return fail(NRS_E_STATE, "boundary bodies: the grid outgrew the storage sized at nrs_set_boundary_bodies (assign the bodies again)");
+        NRSCHK(ev_begin(NRS_STAGE_HASH));
+        hipLaunchKernelGGL((k_boundary_pose_hash<R>), dim3(nblocks(NB)), dim3(BLOCK), 0, stream, P, T, bdRest.as<T4>(), bdVbi.as<R>(),
+                           bdBodyOf.as<uint32_t>(), bdWorld.as<T4>(), bHash.as<uint32_t>(), bIndex.as<uint32_t>(), NB);
+        rocprim::double_buffer<uint32_t> k(bHash.as<uint32_t>(), bHashAlt.as<uint32_t>());
+        rocprim::double_buffer<uint32_t> v(bIndex.as<uint32_t>(), bIndexAlt.as<uint32_t>());
+        size_t tmp = bdSortTmp.bytes;
+        HIPCHK(rocprim::radix_sort_pairs(bdSortTmp.p, tmp, k, v, (size_t)NB, 0u, bits, stream));
+        bHashCur = k.current();
+        bIndexCur = v.current();
+        HIPCHK(hipMemsetAsync(bCellStart.p, 0xff, (size_t)P.numCells * 4, stream));
+        hipLaunchKernelGGL((k_reorder_boundary_bodies<R>), dim3(nblocks(NB)), dim3(BLOCK), 0, stream, bHashCur, bIndexCur, T, bdWorld.as<T4>(),
+                           bdBodyOf.as<uint32_t>(), bSorted.as<T4>(), bdBodySorted.as<uint32_t>(), bdVel.as<T4>(), bCellStart.as<uint32_t>(),
+                           bCellEnd.as<uint32_t>(), NB);
+        if (nearBitsValid) {
+            HIPCHK(hipMemsetAsync(nearBits.p, 0, (((size_t)P.numCells + 31) / 32) * 4, stream));
+            hipLaunchKernelGGL((k_mark_near_boundary<R>), dim3(nblocks(NB)), dim3(BLOCK), 0, stream, P, bHashCur, NB, nearBits.as<uint32_t>());
+        }
+        HIPCHK(hipGetLastError());
+        NRSCHK(ev_end());
+        bodiesDirty = false;
         return NRS_OK;
     }
 
@@ -663,6 +847,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (nbNew > (uint64_t)HIT_INDEX) return fail(NRS_E_INVALID, "too many boundary particles (max 2^27-1)");
         if (nbNew && (!bi4 || !vbi)) return fail(NRS_E_INVALID, "bi4/vbi is NULL");
         nb = nbNew;
+        clear_bodies(); // (a new set of boundary particles has no body assignment)
         hostBi.assign((const T4 *)bi4, (const T4 *)bi4 + nb);
         hostVbi.assign((const R *)vbi, (const R *)vbi + nb);
         if (!nb) { nearBitsValid = false; return NRS_OK; }
@@ -1627,6 +1812,22 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const uint32_t N = (uint32_t)n;
         const dim3 g(nblocks(N)), b(BLOCK);
         const GridView<R> G = grid_view();
+        if constexpr (HAS_B) {
+            if (movingStep) { // A with the wall velocities (nrs_kernels_bodies.h); B is unchanged
+                const T4 *bU = bdVel.as<T4>();
+                if (!plan.lists) {
+                    hipLaunchKernelGGL((k_dfsph_div_mv_ref<R, KSET, DENS>), g, b, 0, stream, P, G, A, posB.as<T4>(), bU, phase, N);
+                    hipLaunchKernelGGL((k_dfsph_vupdate_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
+                } else if constexpr (KSET == KS_MULLER) {
+                    const HitBuffer hb = hit_buffer();
+                    launch_listed(k_dfsph_div_mv_lists<R, KSET, DENS, true>, k_dfsph_div_mv_lists<R, KSET, DENS>, g.x, P, G, A, hb, posB.as<T4>(),
+                                  bU, phase, N);
+                    launch_listed(k_dfsph_vupdate_lists<R, KSET, HAS_B, true>, k_dfsph_vupdate_lists<R, KSET, HAS_B>, g.x, P, G, A, hb,
+                                  posB.as<T4>(), N);
+                }
+                return;
+            }
+        }
         if (!plan.lists) {
             hipLaunchKernelGGL((k_dfsph_div_ref<R, KSET, HAS_B, DENS>), g, b, 0, stream, P, G, A, posB.as<T4>(), phase, N);
             hipLaunchKernelGGL((k_dfsph_vupdate_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
@@ -1689,6 +1890,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (n == 0) return NRS_OK;
             fusedThisStep = false; splitClearedCells = false;
             plan = plan_step(0);
+            NRSCHK(advance_bodies_and_rebuild());
             NRSCHK(stage_prefix(0));
             if (nb) NRSCHK(iisph_predict<true>(0)); else NRSCHK(iisph_predict<false>(0));
             iisphPhase = 1;
@@ -1731,6 +1933,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // IISPH: every solver iteration consumes two cells of halo validity, the predict stages three and the pressure force one
         // (DESIGN.md §5): 2 iterations — the reference's minimum — need 8 cells
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
+        if (nBodies) return fail(NRS_E_INVALID, "contexts with boundary bodies have no slab decomposition");
         if (pcisph()) return fail(NRS_E_INVALID, "PCISPH contexts have no slab decomposition");
         if (pbf()) return fail(NRS_E_INVALID, "PBF contexts have no slab decomposition");
         if (dfsph()) return fail(NRS_E_INVALID, "DFSPH contexts have no slab decomposition");
@@ -2155,6 +2358,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             fusedThisStep = false;
             splitClearedCells = false;
             plan = plan_step(stop);
+            NRSCHK(advance_bodies_and_rebuild());
             NRSCHK(stage_prefix(stop));
             if (stop && stop <= NRS_STAGE_REORDER) { midStep = true; break; }
             if (iisph()) { if (nb) NRSCHK(iisph_tail<true>(stop)); else NRSCHK(iisph_tail<false>(stop)); }
@@ -2327,6 +2531,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (!pcisph() && !pbf() && !dfsph()) return fail(NRS_E_STATE, "Akinci array requested from a SESPH or IISPH context");
             if (!akNormalsValid) return fail(NRS_E_STATE, "no step with Akinci surface tension (gamma > 0) yet");
             p = akNormals.p; sz = v; break;
+        case NRS_ARR_B_BODY:
+            if (!nBodies) return fail(NRS_E_STATE, "no boundary body assignment (nrs_set_boundary_bodies)");
+            *dptr = bdBodySorted.p; *bytes = 4 * nb; // (not a solver array: none of the per-solver refusals below apply)
+            return NRS_OK;
         case NRS_ARR_DFSPH_ALPHA:
         case NRS_ARR_DFSPH_KAPPA_V:
             if (!dfsph()) return fail(NRS_E_STATE, "DFSPH array requested from another context");

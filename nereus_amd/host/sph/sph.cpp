@@ -78,7 +78,7 @@ SReal nereusDefaultSoundSpeed() { return defaultSoundSpeed(); }
 SPH::SPH()
     : m_gridSortBits(32), m_pos(nullptr), m_vel(nullptr), m_density(nullptr), m_pressure(nullptr), m_forces(nullptr),
       m_colors(nullptr), m_numParticles(0), m_hostCapacity(0), m_bi(nullptr), m_vbi(nullptr), m_num_boundaries(0),
-      m_ctx(nullptr), m_ctxCapacity(0), m_hostDirty(true), m_deviceNewer(false), m_boundariesPending(false),
+      m_ctx(nullptr), m_ctxCapacity(0), m_hostDirty(true), m_deviceNewer(false), m_boundariesPending(false), m_numBodies(0),
       m_eagerSync(false), m_initialized(false), m_cfl(false), m_cflLambda(0.4f), m_asyncReadback(false),
       m_framesInFlight(0), m_frame(nullptr), m_frameCount(0), m_frameStep(0), m_frameIsCurrent(false)
 {
@@ -109,7 +109,7 @@ SPH::SPH(SphSimParams params)
     : m_params(params), m_gridSortBits(32), m_pos(nullptr), m_vel(nullptr), m_density(nullptr), m_pressure(nullptr),
       m_forces(nullptr), m_colors(nullptr), m_numParticles(0), m_hostCapacity(0), m_bi(nullptr), m_vbi(nullptr),
       m_num_boundaries(0), m_ctx(nullptr), m_ctxCapacity(0), m_hostDirty(true), m_deviceNewer(false),
-      m_boundariesPending(false), m_eagerSync(false), m_initialized(false), m_cfl(false), m_cflLambda(0.4f), m_asyncReadback(false),
+      m_boundariesPending(false), m_numBodies(0), m_eagerSync(false), m_initialized(false), m_cfl(false), m_cflLambda(0.4f), m_asyncReadback(false),
       m_framesInFlight(0), m_frame(nullptr), m_frameCount(0), m_frameStep(0), m_frameIsCurrent(false)
 {
     kernelFactors(m_params, 2);
@@ -211,7 +211,33 @@ void SPH::ensureContext()
     if (m_boundariesPending && m_bi && m_vbi && m_num_boundaries) {
         if (nrs_set_boundaries(m_ctx, m_bi, m_vbi, m_num_boundaries, 0) != NRS_OK) fatal("nrs_set_boundaries");
         m_boundariesPending = false;
+        if (!m_bodyOf.empty() && nrs_set_boundary_bodies(m_ctx, m_bodyOf.data(), m_bodyOf.size(), m_numBodies) != NRS_OK)
+            fatal("nrs_set_boundary_bodies");
     }
+}
+
+void SPH::setBoundaryBodies(const SUint *bodyOf, SUint nbodies)
+{
+    ensureContext();
+    if (nrs_set_boundary_bodies(m_ctx, bodyOf, bodyOf ? m_num_boundaries : 0, nbodies) != NRS_OK) fatal("nrs_set_boundary_bodies");
+    if (bodyOf && nbodies > 1) m_bodyOf.assign(bodyOf, bodyOf + m_num_boundaries);
+    else m_bodyOf.clear();
+    m_numBodies = m_bodyOf.empty() ? 0 : nbodies;
+}
+void SPH::setBodyVelocity(SUint body, const double v[3], const double omega[3])
+{
+    ensureContext();
+    if (nrs_set_body_velocity(m_ctx, body, v, omega) != NRS_OK) fatal("nrs_set_body_velocity");
+}
+void SPH::setBodyPose(SUint body, const double x[3], const double q[4])
+{
+    ensureContext();
+    if (nrs_set_body_pose(m_ctx, body, x, q) != NRS_OK) fatal("nrs_set_body_pose");
+}
+void SPH::getBodyPose(SUint body, double x[3], double q[4])
+{
+    ensureContext();
+    if (nrs_get_body_pose(m_ctx, body, x, q) != NRS_OK) fatal("nrs_get_body_pose");
 }
 
 nrs_ctx *SPH::deviceContext()
@@ -439,6 +465,8 @@ void SPH::updateGpuBoundaries(SUint nb_boundary_spheres)
     // grid from the boundary AABB (updateGrid), then hash / sort / cell ranges of the boundary particles
     if (nrs_set_params(m_ctx, &m_params) != NRS_OK) fatal("nrs_set_params");
     if (nrs_set_boundaries(m_ctx, m_bi, m_vbi, m_num_boundaries, 1) != NRS_OK) fatal("nrs_set_boundaries");
+    m_bodyOf.clear(); // (nrs_set_boundaries clears the body assignment)
+    m_numBodies = 0;
     if (nrs_get_params(m_ctx, &m_params) != NRS_OK) fatal("nrs_get_params");
     m_boundariesPending = false;
     std::cout << "boundaries updated !" << std::endl;

@@ -87,6 +87,15 @@ public:
     void updateGpuBoundaries(SUint nb_boundary_spheres);
 
     // ---- additions of this build (not in the reference) ----
+    // Kinematic boundary bodies (nrs_set_boundary_bodies and friends, DESIGN.md "Kinematic boundary bodies"), after
+    // updateGpuBoundaries: bodyOf[i] in 0 .. nbodies-1 per boundary particle, body 0 the static world; the context moves bodies
+    // 1 .. nbodies-1 every update() and rebuilds the boundary tables on the device.  A later updateGpuBoundaries clears the assignment.
+    // The assignment is kept and applied again when the device context is rebuilt (capacity growth), the poses then restart at rest;
+    // saveState / loadState do not hold poses.  Errors end the program, as every device error of this class does.
+    void setBoundaryBodies(const SUint *bodyOf, SUint nbodies);
+    void setBodyVelocity(SUint body, const double v[3], const double omega[3]);
+    void setBodyPose(SUint body, const double x[3], const double q[4]);
+    void getBodyPose(SUint body, double x[3], double q[4]);
     void reserveParticles(SUint capacity);        // grow host+device storage up front
     void setEagerSync(bool on) { m_eagerSync = on; } // true: D2H at the end of every update() like the reference
     const SphSimParams &getParams() const { return m_params; }
@@ -137,6 +146,8 @@ protected:
     bool m_hostDirty;           // host arrays changed since the last upload
     mutable bool m_deviceNewer; // device holds a newer state than the host arrays
     bool m_boundariesPending;   // boundaries known but not yet uploaded into (a new) context
+    std::vector<SUint> m_bodyOf; // boundary body assignment (empty: none), re-applied to a new context
+    SUint m_numBodies;
     bool m_eagerSync;
     bool m_initialized;
     bool m_cfl;

@@ -14,6 +14,10 @@
 //   headless cfl     sesph <in.bin> <steps> <out.bin>           run with setAdaptiveTimestep(true)
 //   headless mainscene <sesph|iisph> <steps> <out.bin>          main.cpp:533-553: generateParticleCube + sampleBox +
 //                                                               getVbi + updateGpuBoundaries, gravity as given
+//   headless piston  <solver> <steps> <out.bin>                 a box of fluid (generateParticleCube) in the sampled box, and one
+//                                                               wall, a plate of boundary particles behind the fluid that is body 1
+//                                                               and moves at 1 m/s along +x (setBoundaryBodies / setBodyVelocity);
+//                                                               the dumped bi are the rest positions, the plate last
 // in.bin : u32 n, u32 nb, then pos4[n], vel4[n], bi4[nb], vbi[nb] (SReal)
 // out.bin: u32 n, u32 nb, u32 iters, u32 sizeof(params), params, pos4[n], vel4[n], pressure[n], bi4[nb], vbi[nb]
 #include <cstdio>
@@ -180,6 +184,33 @@ int main(int argc, char **argv)
         for (int s = 0; s < steps; ++s) sim->update();
         if (iisph) iters = static_cast<Nereus::IISPH *>(sim)->getLastIterations();
         dump(argv[4], sim, iters, bi, vbi);
+    } else if (mode == "piston") {
+        if (argc < 5) die("piston needs <steps> <out.bin>");
+        sim->generateParticleCube(make_SVec4(-0.4f, 0.04f, 0.5f, 1.f), make_SVec4(0.5f, 0.5f, 0.5f, 1.f), make_SVec4(0, 0, 0, 0));
+        sample_spheres::ss::sampleBox(bi, make_SVec3(-1, -1, -1), make_SVec3(3.f, 3.f, 3.f), 0.02);
+        sample_spheres::boundary_forces::getVbi(vbi, bi, sim->getInteractionRadius());
+        std::vector<SVec4> plate;
+        for (int iy = 0; iy < 16; ++iy)
+            for (int iz = 0; iz < 16; ++iz) plate.push_back(make_SVec4(-0.70f, -0.26f + 0.04f * iy, 0.20f + 0.04f * iz, 1.f));
+        std::vector<SReal> plateVbi;
+        sample_spheres::boundary_forces::getVbi(plateVbi, plate, sim->getInteractionRadius());
+        std::vector<SUint> bodyOf(bi.size(), 0u);
+        bodyOf.insert(bodyOf.end(), plate.size(), 1u);
+        bi.insert(bi.end(), plate.begin(), plate.end());
+        vbi.insert(vbi.end(), plateVbi.begin(), plateVbi.end());
+        sim->setNumBoundaries(bi.size());
+        sim->setBi((SReal *)bi.data());
+        sim->setVbi(vbi.data());
+        sim->updateGpuBoundaries(bi.size());
+        sim->setBoundaryBodies(bodyOf.data(), 2);
+        const double v[3] = {1.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+        sim->setBodyVelocity(1, v, w);
+        const int steps = std::atoi(argv[3]);
+        for (int s = 0; s < steps; ++s) sim->update();
+        double x[3], q[4];
+        sim->getBodyPose(1, x, q);
+        std::printf("piston: plate origin x = %.9g after %d steps\n", x[0], steps);
+        dump(argv[4], sim, 0, bi, vbi);
     } else {
         die("unknown mode");
     }
