@@ -1245,6 +1245,42 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             hipLaunchKernelGGL(plain, dim3(blocks), dim3(BLOCK), 0, stream, args..., WallList{}, 0u);
         }
     }
+    // One neighbour pass of PCISPH, PBF, DFSPH or the Akinci normals (nrs_kernels_walk.h) over the sorted slots: the reference-order
+    // kernel or, with plan.lists (Muller kernels only), the list kernel — with wall workgroups where the pass has a boundary term,
+    // one plain launch where it walks fluid neighbours only.
+    template <bool HAS_B, typename Pass> void launch_pass(const Pass &pass)
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        const GridView<R> G = grid_view();
+        const T4 *sPos = posB.as<T4>();
+        if (!plan.lists) {
+            hipLaunchKernelGGL((k_walk_ref<Pass, HAS_B && Pass::WALLED>), g, b, 0, stream, pass, G, sPos, N);
+        } else if constexpr (KSET == KS_MULLER) {
+            if constexpr (Pass::WALLED) launch_listed(k_walk_lists<Pass, HAS_B, true>, k_walk_lists<Pass, HAS_B>, g.x, pass, G, hit_buffer(), sPos, N);
+            else hipLaunchKernelGGL((k_walk_lists<Pass, false>), g, b, 0, stream, pass, G, hit_buffer(), sPos, N, WallList{}, 0u);
+        }
+    }
+    // The exit rule of the three solver loops: iterate(l) queues iteration l (from 0); after min_iters iterations measure(&e) reads the
+    // error measure back, and the loop stops on e <= eta or at the cap.  fixed: exactly `cap` iterations and nothing read back.
+    template <typename Iterate, typename Measure>
+    int solve_loop(bool fixed, uint32_t minIters, uint32_t cap, double eta, Iterate &&iterate, Measure &&measure, uint32_t *iters, double *err)
+    {
+        uint32_t l = 0;
+        for (;;) {
+            iterate(l);
+            ++l;
+            const bool last = l >= cap;
+            if (fixed) {
+                if (last) break;
+            } else if (l >= minIters || last) {
+                NRSCHK(measure(err));
+                if (last || *err <= eta) break;
+            }
+        }
+        *iters = l;
+        return NRS_OK;
+    }
 
     // predictAdvection (sph_cuda.cu:513-697)
     template <bool HAS_B> int iisph_predict(int stop)
@@ -1444,22 +1480,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             pciDeltaValid = true;
             return NRS_OK;
         }
-        const double m = (double)PU.particleMass, rd = (double)PU.restDensity, h = (double)PU.interactionRadius, dt = (double)PU.timestep;
-        const R sp = (R)(pciSpacing > 0.0 ? pciSpacing : std::cbrt(m / rd));
-        if (!(sp > (R)0) || !std::isfinite((double)sp) || !(h > 0.0) || h / (double)sp > 64.0)
-            return fail(NRS_E_INVALID, "PCISPH: prototype spacing must be positive and at least h / 64");
-        const int kmax = (int)std::ceil(h / (double)sp) + 1;
-        hipLaunchKernelGGL((k_pci_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
-        HIPCHK(hipGetLastError());
+        const double m = (double)PU.particleMass, rd = (double)PU.restDensity, dt = (double)PU.timestep;
         double o[5];
-        HIPCHK(hipMemcpyAsync(o, redPartial.p, sizeof(o), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (o[4] == 0.0) {
-            char buf[200];
-            snprintf(buf, sizeof(buf), "PCISPH: the prototype particle (lattice spacing %g, h %g) has no neighbour within h: no pressure scale delta",
-                     (double)sp, h);
-            return fail(NRS_E_INVALID, buf);
-        }
+        NRSCHK(prototype_sums(true, pciSpacing > 0.0 ? pciSpacing : std::cbrt(m / rd), "PCISPH", "pressure scale delta", o));
         const double q = dt * m / rd, beta = 2.0 * q * q;
         const double d = -1.0 / (beta * (-(o[0] * o[0] + o[1] * o[1] + o[2] * o[2]) - o[3]));
         if (!std::isfinite(d)) return fail(NRS_E_INVALID, "PCISPH: the prototype gives no finite pressure scale delta");
@@ -1522,10 +1545,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (cohesion || (HAS_B && akBeta > 0.0)) { // the Akinci model: the normals launch, then the advection launch with its walk
             const AkinciView<R> K{cohesion ? akNormals.as<T4>() : (T4 *)nullptr, (R)akGamma, (R)akBeta};
             if (cohesion) {
-                if (!plan.lists)
-                    hipLaunchKernelGGL((k_akinci_normals_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), K.normals, N);
-                else if constexpr (KSET == KS_MULLER)
-                    hipLaunchKernelGGL((k_akinci_normals_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), dens.as<R>(), K.normals, N);
+                launch_pass<HAS_B>(AkinciNormalsPass<R, KSET>{P, dens.as<R>(), K.normals});
                 akNormalsValid = true;
             }
             if (SURF && !cohesion) akinci_advect<HAS_B, SURF>(A0, K);
@@ -1544,34 +1564,27 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         const uint32_t N = (uint32_t)n;
         const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        const HitBuffer hb = hit_buffer();
         bool more;
         NRSCHK(pci_prefix<HAS_B>(stop, &more));
         if (!more) return NRS_OK;
         // the predictive-corrective loop: stop after the iteration l with l >= min_iters and max e <= eta, or at the cap; the max is
         // not formed (nor read back) before min_iters
         NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
-        const uint32_t cap = maxIters ? maxIters : 50u;
         uint32_t l = 0;
         double err = -1.0;
-        for (;;) {
-            const PciArrays<R> A = pci_view(pciXs, pciXs ^ 1);
-            if (!plan.lists) {
-                hipLaunchKernelGGL((k_pci_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
-                hipLaunchKernelGGL((k_pci_pforce_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
-            } else if constexpr (KSET == KS_MULLER) {
-                launch_listed(k_pci_density_lists<R, KSET, HAS_B, true>, k_pci_density_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
-                launch_listed(k_pci_pforce_lists<R, KSET, HAS_B, true>, k_pci_pforce_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
-            }
-            pciXs ^= 1;
-            ++l;
-            const bool last = l >= cap;
-            if (l >= pciMinIters || last) {
-                NRSCHK(max_of<false>(pciErr.p, N, &err));
-                if (last || err <= pciEta) break;
-            }
-        }
+        NRSCHK(solve_loop(
+            false, pciMinIters, maxIters ? maxIters : 50u, pciEta,
+            [&](uint32_t) {
+                const PciArrays<R> A = pci_view(pciXs, pciXs ^ 1);
+                launch_pass<HAS_B>(PciDensityPass<R, KSET>{P, A});
+                if (!plan.lists) // (hand-written, nrs_kernels_pcisph.h)
+                    hipLaunchKernelGGL((k_pci_pforce_ref<R, KSET, HAS_B>), g, b, 0, stream, P, grid_view(), A, posB.as<T4>(), N);
+                else if constexpr (KSET == KS_MULLER)
+                    launch_listed(k_pci_pforce_lists<R, KSET, HAS_B, true>, k_pci_pforce_lists<R, KSET, HAS_B>, g.x, P, grid_view(), A, hit_buffer(),
+                                  posB.as<T4>(), N);
+                pciXs ^= 1;
+            },
+            [&](double *e) { return max_of<false>(pciErr.p, N, e); }, &l, &err));
         lastIters = l;
         pciLastErr = err;
         HIPCHK(hipMemcpyAsync(presB.p, P_l.p, sizeof(R) * N, hipMemcpyDeviceToDevice, stream)); // (the step's pressures, NRS_ARR_PRES)
@@ -1637,26 +1650,34 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // cbrt(m / rho0) (k_pbf_prototype, the solver's own gradient on the device); once per parameter or settings change.  W_q likewise.
     // D_proto = |sum g|^2 + sum |g|^2 of the prototype particle (k_pbf_prototype); `who` and `what` name the caller and its result in
     // the errors
-    int pbf_prototype_d(const char *who, const char *what, double *d)
+    // The five prototype sums (k_pci_prototype: g = W_grad, or k_pbf_prototype: g = (m / rho0) grad W_spiky) of a particle on the cubic
+    // lattice of the given spacing: o[0..2] = sum g, o[3] = sum g . g, o[4] = neighbours (at least one, or an error)
+    int prototype_sums(bool pci, double spacing, const char *who, const char *what, double *o)
     {
-        const double m = (double)PU.particleMass, rd = (double)PU.restDensity, h = (double)PU.interactionRadius;
-        const R sp = (R)std::cbrt(m / rd);
+        const double h = (double)PU.interactionRadius;
+        const R sp = (R)spacing;
         char buf[200];
         if (!(sp > (R)0) || !std::isfinite((double)sp) || !(h > 0.0) || h / (double)sp > 64.0) {
-            snprintf(buf, sizeof(buf), "%s: the prototype spacing cbrt(m / rho0) must be positive and at least h / 64", who);
+            snprintf(buf, sizeof(buf), "%s: the prototype spacing (default cbrt(m / rho0)) must be positive and at least h / 64", who);
             return fail(NRS_E_INVALID, buf);
         }
         const int kmax = (int)std::ceil(h / (double)sp) + 1;
-        hipLaunchKernelGGL((k_pbf_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
+        if (pci) hipLaunchKernelGGL((k_pci_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
+        else hipLaunchKernelGGL((k_pbf_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
         HIPCHK(hipGetLastError());
-        double o[5];
-        HIPCHK(hipMemcpyAsync(o, redPartial.p, sizeof(o), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(o, redPartial.p, 5 * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         if (o[4] == 0.0) {
             snprintf(buf, sizeof(buf), "%s: the prototype particle (lattice spacing %g, h %g) has no neighbour within h: no %s", who, (double)sp, h,
                      what);
             return fail(NRS_E_INVALID, buf);
         }
+        return NRS_OK;
+    }
+    int pbf_prototype_d(const char *who, const char *what, double *d)
+    {
+        double o[5];
+        NRSCHK(prototype_sums(false, std::cbrt((double)PU.particleMass / (double)PU.restDensity), who, what, o));
         *d = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3];
         return NRS_OK;
     }
@@ -1679,8 +1700,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         const uint32_t N = (uint32_t)n;
         const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        const HitBuffer hb = hit_buffer();
         bool more;
         NRSCHK(pci_prefix<HAS_B>(stop, &more));
         if (!more) return NRS_OK;
@@ -1693,32 +1712,16 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const PbfTensile<R> T{(R)pbfTensK, pbfWq};
         uint32_t l = 0;
         double err = -1.0;
-        for (;;) {
-            const PbfArrays<R> A = pbf_view(pciXs, pciXs ^ 1);
-            if (!plan.lists) {
-                hipLaunchKernelGGL((k_pbf_lambda_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
-                if (tens)
-                    hipLaunchKernelGGL((k_pbf_correct_s_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, T, posB.as<T4>(), N);
-                else
-                    hipLaunchKernelGGL((k_pbf_correct_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
-            } else if constexpr (KSET == KS_MULLER) {
-                launch_listed(k_pbf_lambda_lists<R, KSET, HAS_B, true>, k_pbf_lambda_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
-                if (tens)
-                    launch_listed(k_pbf_correct_s_lists<R, KSET, HAS_B, true>, k_pbf_correct_s_lists<R, KSET, HAS_B>, g.x, P, G, A, T, hb,
-                                  posB.as<T4>(), N);
-                else
-                    launch_listed(k_pbf_correct_lists<R, KSET, HAS_B, true>, k_pbf_correct_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
-            }
-            pciXs ^= 1;
-            ++l;
-            const bool last = l >= cap;
-            if (fixed) {
-                if (last) break;
-            } else if (l >= pbfMinIters || last) {
-                NRSCHK(max_of<false>(pciErr.p, N, &err));
-                if (last || err <= pbfEta) break;
-            }
-        }
+        NRSCHK(solve_loop(
+            fixed, pbfMinIters, cap, pbfEta,
+            [&](uint32_t) {
+                const PbfArrays<R> A = pbf_view(pciXs, pciXs ^ 1);
+                launch_pass<HAS_B>(PbfLambdaPass<R, KSET>{P, A});
+                if (tens) launch_pass<HAS_B>(PbfCorrectPass<R, KSET, true>{P, A, T});
+                else launch_pass<HAS_B>(PbfCorrectPass<R, KSET, false>{P, A, {}});
+                pciXs ^= 1;
+            },
+            [&](double *e) { return max_of<false>(pciErr.p, N, e); }, &l, &err));
         lastIters = l;
         pciLastErr = err;
         pbfErrPending = fixed ? N : 0u;
@@ -1730,25 +1733,13 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ev_begin(NRS_STAGE_P_INTEGRATE));
         const T4 *xs = (const T4 *)pci_xs_current();
         const bool xsph = pbfXsph > 0.0, vort = pbfVortEps > 0.0;
-        if (xsph) {
-            if (!plan.lists)
-                hipLaunchKernelGGL((k_pbf_xsph_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), xs, velB.as<T4>(), (R)pbfXsph, N);
-            else if constexpr (KSET == KS_MULLER)
-                hipLaunchKernelGGL((k_pbf_xsph_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), xs, velB.as<T4>(), (R)pbfXsph, N);
-        }
+        if (xsph) launch_pass<HAS_B>(PbfXsphPass<R, KSET>{{}, P, xs, velB.as<T4>(), (R)pbfXsph});
         // vorticity confinement: omega from u = (x* - x) / dt, then the confinement on the velocity XSPH left (or u); both read x_j
         if (vort) {
             T4 *om = pbfVort.as<T4>();
             const int given = xsph ? 1 : 0;
-            if (!plan.lists) {
-                hipLaunchKernelGGL((k_pbf_vorticity_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), xs, om, N);
-                hipLaunchKernelGGL((k_pbf_confine_ref<R, KSET>), g, b, 0, stream, P, G, posB.as<T4>(), xs, (const T4 *)om, velB.as<T4>(),
-                                   given, (R)pbfVortEps, N);
-            } else if constexpr (KSET == KS_MULLER) {
-                hipLaunchKernelGGL((k_pbf_vorticity_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), xs, om, N);
-                hipLaunchKernelGGL((k_pbf_confine_lists<R, KSET>), g, b, 0, stream, P, G, hb, posB.as<T4>(), xs, (const T4 *)om,
-                                   velB.as<T4>(), given, (R)pbfVortEps, N);
-            }
+            launch_pass<HAS_B>(PbfVorticityPass<R, KSET>{{}, P, xs, om});
+            launch_pass<HAS_B>(PbfConfinePass<R, KSET>{{}, P, xs, (const T4 *)om, velB.as<T4>(), given, (R)pbfVortEps});
             pbfVortValid = true;
         }
         uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
@@ -1795,48 +1786,25 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
     template <bool HAS_B> void dfsph_factor()
     {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        const DfsphArrays<R> A = dfsph_view(nullptr, nullptr, nullptr);
-        if (!plan.lists)
-            hipLaunchKernelGGL((k_dfsph_factor_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
-        else if constexpr (KSET == KS_MULLER)
-            launch_listed(k_dfsph_factor_lists<R, KSET, HAS_B, true>, k_dfsph_factor_lists<R, KSET, HAS_B>, g.x, P, G, A, hit_buffer(),
-                          posB.as<T4>(), N);
+        launch_pass<HAS_B>(DfsphFactorPass<R, KSET>{{P, dfsph_view(nullptr, nullptr, nullptr)}});
         dfAlphaValid = true;
     }
     // one A/B pair on u
     template <bool HAS_B, bool DENS> void dfsph_pair(const DfsphArrays<R> &A, int phase)
     {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
+        const DfsphPassBase<R, KSET> base{P, A};
+        const bool moving = HAS_B && movingStep; // A with the wall velocities (DfsphDivPass's MOVING); B is unchanged
         if constexpr (HAS_B) {
-            if (movingStep) { // A with the wall velocities (nrs_kernels_bodies.h); B is unchanged
-                const T4 *bU = bdVel.as<T4>();
-                if (!plan.lists) {
-                    hipLaunchKernelGGL((k_dfsph_div_mv_ref<R, KSET, DENS>), g, b, 0, stream, P, G, A, posB.as<T4>(), bU, phase, N);
-                    hipLaunchKernelGGL((k_dfsph_vupdate_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
-                } else if constexpr (KSET == KS_MULLER) {
-                    const HitBuffer hb = hit_buffer();
-                    launch_listed(k_dfsph_div_mv_lists<R, KSET, DENS, true>, k_dfsph_div_mv_lists<R, KSET, DENS>, g.x, P, G, A, hb, posB.as<T4>(),
-                                  bU, phase, N);
-                    launch_listed(k_dfsph_vupdate_lists<R, KSET, HAS_B, true>, k_dfsph_vupdate_lists<R, KSET, HAS_B>, g.x, P, G, A, hb,
-                                  posB.as<T4>(), N);
-                }
-                return;
-            }
+            if (moving) launch_pass<HAS_B>(DfsphDivPass<R, KSET, DENS, true>{base, bdVel.as<T4>(), phase});
         }
-        if (!plan.lists) {
-            hipLaunchKernelGGL((k_dfsph_div_ref<R, KSET, HAS_B, DENS>), g, b, 0, stream, P, G, A, posB.as<T4>(), phase, N);
-            hipLaunchKernelGGL((k_dfsph_vupdate_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, A, posB.as<T4>(), N);
-        } else if constexpr (KSET == KS_MULLER) {
-            const HitBuffer hb = hit_buffer();
-            launch_listed(k_dfsph_div_lists<R, KSET, HAS_B, DENS, true>, k_dfsph_div_lists<R, KSET, HAS_B, DENS>, g.x, P, G, A, hb,
-                          posB.as<T4>(), phase, N);
-            launch_listed(k_dfsph_vupdate_lists<R, KSET, HAS_B, true>, k_dfsph_vupdate_lists<R, KSET, HAS_B>, g.x, P, G, A, hb, posB.as<T4>(), N);
-        }
+        if (!moving) launch_pass<HAS_B>(DfsphDivPass<R, KSET, DENS>{base, {}, phase});
+        const uint32_t N = (uint32_t)n; // B: hand-written (nrs_kernels_dfsph.h)
+        const dim3 g(nblocks(N)), b(BLOCK);
+        if (!plan.lists)
+            hipLaunchKernelGGL((k_dfsph_vupdate_ref<R, KSET, HAS_B>), g, b, 0, stream, P, grid_view(), A, posB.as<T4>(), N);
+        else if constexpr (KSET == KS_MULLER)
+            launch_listed(k_dfsph_vupdate_lists<R, KSET, HAS_B, true>, k_dfsph_vupdate_lists<R, KSET, HAS_B>, g.x, P, grid_view(), A, hit_buffer(),
+                          posB.as<T4>(), N);
     }
     // one solve (DENS: the density solve) in place on u, K in place on K (the sorted K_prev on entry).  eta > 0: stop after the iteration
     // l with l >= min_iters and avg e <= eta, or at the cap (nrs_set_max_iterations, 0 = 100), the average not formed (nor read back)
@@ -1848,21 +1816,16 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const bool fixed = eta == 0.0;
         const uint32_t cap = fixed ? minIters : (maxIters ? maxIters : 100u);
         if (dfWarm) dfsph_pair<HAS_B, DENS>(A, DFSPH_PHASE_WARM);
-        uint32_t l = 0;
-        for (;;) {
-            dfsph_pair<HAS_B, DENS>(A, (l || dfWarm) ? DFSPH_PHASE_MORE : DFSPH_PHASE_FIRST);
-            ++l;
-            const bool last = l >= cap;
-            if (fixed) {
-                if (last) break;
-            } else if (l >= minIters || last) {
+        double avg = 0.0;
+        return solve_loop(
+            fixed, minIters, cap, eta, [&](uint32_t l) { dfsph_pair<HAS_B, DENS>(A, (l || dfWarm) ? DFSPH_PHASE_MORE : DFSPH_PHASE_FIRST); },
+            [&](double *e) {
                 double acc = 0.0;
                 NRSCHK(reduce_sum(err, N, &acc));
-                if (last || acc / (double)N <= eta) break;
-            }
-        }
-        *iters = l;
-        return NRS_OK;
+                *e = acc / (double)N;
+                return (int)NRS_OK;
+            },
+            iters, &avg);
     }
     template <bool HAS_B> int dfsph_tail(int stop)
     {

@@ -10,7 +10,7 @@
 // Fluid neighbours are the j != i with length(r_ij) < h at the sorted start positions; boundary particles are not tested — Aboundary's
 // branch is the cut-off.  A pair whose C (A) is exactly 0 adds no cohesion (adhesion) term, so r = 0 never forms 0 * NaN.
 // Order of every sum: the 27 cells in z, y, x order, in each cell a fluid partial (j ascending) and then a boundary partial, each added
-// to its running total — the order of pci_density_walk.  The list-driven kernels (Muller set, plan.lists) form the same partials from
+// to its running total — the order of walk_cells (nrs_kernels_walk.h), which the normals pass uses.  The list-driven kernels (Muller set, plan.lists) form the same partials from
 // the hit lists, so both paths give the same bits; a particle whose list overflowed takes the reference-order walk.
 #pragma once
 #include "nrs_kernels_pcisph.h"
@@ -56,32 +56,35 @@ template <typename R> NRS_DEV V3<R> akinci_force(const Params<R> &P, const Akinc
     return pci_scale<R>(-K.gamma * P.particleMass, S) + pci_scale<R>(-K.beta * P.particleMass, B);
 }
 
-// ---- reference-order walks ------------------------------------------------------------------------------------------------------------
-template <typename R, int KSET>
-NRS_DEV V3<R> akinci_normal_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                                 const R *__restrict__ sDens, uint32_t i, V3<R> pos1)
-{
-    const R ir = P.interactionRadius;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    V3<R> sum = mk3<R>(0, 0, 0);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                V3<R> c = mk3<R>(0, 0, 0);
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        if (j == i) continue;
-                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                        if (length(d) < ir) c = c + akinci_normal_term<R, KSET>(P, d, sDens[j]);
-                    }
-                }
-                sum = sum + c;
-            }
-    return sum;
-}
+// ---- the normals pass (fluid neighbours only): n_i = h sum_j (m / rho_j) grad W(r_ij), stored with rho_i -----------------------------------
+template <typename R, int KSET> struct AkinciNormalsPass {
+    typedef R Real;
+    typedef typename Vec4T<R>::type T4;
+    static constexpr int KS = KSET;
+    static constexpr bool WALLED = false;
+    Params<R> P;
+    const R *__restrict__ sDens;
+    T4 *__restrict__ normals;
+    typedef V3<R> Acc;
+    struct Own {};
+    struct Nb { R rho; };
+    NRS_DEV Own own(uint32_t, V3<R>) const { return Own{}; }
+    NRS_DEV Acc zero() const { return mk3<R>(0, 0, 0); }
+    NRS_DEV Acc start(const Own &) const { return zero(); }
+    NRS_DEV Nb gather(uint32_t j) const { return Nb{sDens[j]}; }
+    // (Muller: Wdefault_grad with the length the walk's test formed, which is what W_grad computes again)
+    NRS_DEV void fluid(const Own &, V3<R> pos1, const T4 &q, const Nb &nb, float rlen, Acc &part) const
+    {
+        const V3<R> d = pos1 - xyz<R>(q);
+        if constexpr (KSET == KS_MULLER)
+            part = part + pci_scale<R>(P.particleMass / nb.rho, Wdefault_grad_len<R>(d, rlen, P.interactionRadius, P.kpoly_grad));
+        else part = part + akinci_normal_term<R, KSET>(P, d, nb.rho);
+    }
+    NRS_DEV void boundary(const Own &, V3<R>, uint32_t, const T4 &, Acc &) const {}
+    NRS_DEV void store(uint32_t i, V3<R>, const Own &, Acc sum) const { normals[i] = akinci_normal_pack<R>(P, sum, sDens[i]); }
+};
+
+// ---- the force walk, reference order (hand-written: two accumulators) ---------------------------------------------------
 // S (when gamma > 0) and B (when beta_a > 0 and HAS_B) of particle i
 template <typename R, int KSET, bool HAS_B>
 NRS_DEV void akinci_force_walk(const Params<R> &P, const GridView<R> &G, const AkinciView<R> &K,
@@ -125,16 +128,6 @@ NRS_DEV void akinci_force_walk(const Params<R> &P, const GridView<R> &G, const A
             }
 }
 
-template <typename R, int KSET>
-__global__ __launch_bounds__(BLOCK) void k_akinci_normals_ref(Params<R> P, GridView<R> G, const typename Vec4T<R>::type *__restrict__ sPos,
-                                                              const R *__restrict__ sDens, typename Vec4T<R>::type *__restrict__ normals,
-                                                              uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> sum = akinci_normal_walk<R, KSET>(P, G, sPos, sDens, i, xyz<R>(sPos[i]));
-    normals[i] = akinci_normal_pack<R>(P, sum, sDens[i]);
-}
 // the advection launch with the model on: k_pci_advect_ref's gather (SURF: the context's fsurf term, off while gamma > 0) + the walk
 template <typename R, int KSET, bool SURF, bool HAS_B>
 __global__ __launch_bounds__(BLOCK) void k_akinci_advect_ref(Params<R> P, GridView<R> G, PciArrays<R> A, AkinciView<R> K,
@@ -152,40 +145,6 @@ __global__ __launch_bounds__(BLOCK) void k_akinci_advect_ref(Params<R> P, GridVi
 }
 
 // ---- list-driven kernels (Muller set) -------------------------------------------------------------------------------------------------
-// Fluid entries only, so one plain launch over every slot, as k_pbf_xsph_lists (the wall workgroups exist to keep the boundary code out
-// of the interior waves; this walk has none, and the counts of a deferred particle are complete).
-template <typename R, int KSET>
-__global__ __launch_bounds__(BLOCK) void k_akinci_normals_lists(Params<R> P, GridView<R> G, HitBuffer hb,
-                                                                const typename Vec4T<R>::type *__restrict__ sPos,
-                                                                const R *__restrict__ sDens, typename Vec4T<R>::type *__restrict__ normals,
-                                                                uint32_t n)
-{
-    static_assert(KSET == KS_MULLER, "list-driven Akinci kernels: Muller kernels only (the Monaghan support is 2h, Ctx::Features::listKernels)");
-    const uint32_t i = xcd_tile(blockIdx.x, gridDim.x) * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> pos1 = xyz<R>(sPos[i]);
-    const R ir = P.interactionRadius, kpg = P.kpoly_grad, pm = P.particleMass;
-    const HitCounts hc = unpack_counts(hb.counts[i]);
-    V3<R> sum = mk3<R>(0, 0, 0);
-    if (hc.over) {
-        sum = akinci_normal_walk<R, KSET>(P, G, sPos, sDens, i, pos1);
-    } else {
-        V3<R> part = mk3<R>(0, 0, 0);
-        uint32_t prevTag = 0xffffffffu;
-        struct Nb { typename Vec4T<R>::type q; R rho; };
-        walk_fluid_batched(hb.hits + i, hb.stride, hc.nf, [&](uint32_t j) { return Nb{sPos[j], sDens[j]}; },
-                           [&](uint32_t j, uint32_t tag, const Nb &nb) {
-                               if (tag != prevTag) { sum = sum + part; part = mk3<R>(0, 0, 0); prevTag = tag; }
-                               if (j == i) return;
-                               const V3<R> d = pos1 - xyz<R>(nb.q);
-                               const float rlen = length_listed(dot(d, d));
-                               if (rlen < ir) part = part + pci_scale<R>(pm / nb.rho, Wdefault_grad_len<R>(d, rlen, ir, kpg));
-                           });
-        sum = sum + part;
-    }
-    normals[i] = akinci_normal_pack<R>(P, sum, sDens[i]);
-}
-
 template <typename R, int KSET, bool SURF, bool HAS_B>
 NRS_DEV void akinci_advect_lists_particle(const Params<R> &P, const GridView<R> &G, const PciArrays<R> &A, const AkinciView<R> &K,
                                           const HitBuffer &hb, const typename Vec4T<R>::type *__restrict__ sPos,

@@ -17,8 +17,8 @@
 //   u_b = v_k + (w_y a_z - w_z a_y, w_z a_x - w_x a_z, w_x a_y - w_y a_x),      u_b = 0 for body 0.
 //
 // DFSPH is the one solver that works at the velocity level: its A launch uses sum_b (u_i - u_b) . g_ib while the context is moving
-// (k_dfsph_div_mv_ref / k_dfsph_div_mv_lists below, the same sums in the same order as k_dfsph_div_ref / k_dfsph_div_lists, so the
-// two give the same bits).  B is unchanged: the boundary carries no kappa.
+// (DfsphDivPass's MOVING flag and dfsph_div_boundary_mv, nrs_kernels_dfsph.h: the same walks as every other pass, so the two kernel
+// paths give the same bits).  B is unchanged: the boundary carries no kappa.
 #pragma once
 #include "nrs_kernels_dfsph.h"
 
@@ -101,111 +101,6 @@ static __global__ __launch_bounds__(BLOCK) void k_gather_body(const uint32_t *__
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i < n) sBody[i] = bodyOf[index[i]];
-}
-
-// ---- DFSPH launch A with moving walls: (u_i - u_b) . g_ib --------------------------------------------------------------------------
-template <typename R, int KSET> NRS_DEV R dfsph_div_boundary_mv(const Params<R> &P, V3<R> d, R psi, V3<R> ui, V3<R> ub)
-{
-    return pbf_dot<R>(ui - ub, dfsph_g<R, KSET>(P, d, psi));
-}
-// div_i of particle i, reference order (dfsph_div_walk with the wall velocities bU, sorted as G.sB)
-template <typename R, int KSET>
-NRS_DEV R dfsph_div_walk_mv(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                            const typename Vec4T<R>::type *__restrict__ u, const typename Vec4T<R>::type *__restrict__ bU, uint32_t i,
-                            V3<R> pos1, V3<R> u1)
-{
-    const R ir = P.interactionRadius, rd = P.restDensity;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    R div = (R)0.0;
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                R c = (R)0.0;
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                        if (j == i || !(length(d) < ir)) continue;
-                        c += dfsph_div_fluid<R, KSET>(P, d, u1, xyz<R>(u[j]));
-                    }
-                }
-                div += c;
-                R cb = (R)0.0;
-                const uint32_t sb = G.bCellStart[h];
-                if (sb != CELL_EMPTY) {
-                    const uint32_t e = G.bCellEnd[h];
-                    for (uint32_t j = sb; j < e; ++j) {
-                        const typename Vec4T<R>::type b = G.sB[j];
-                        const V3<R> d = pos1 - xyz<R>(b);
-                        if (!(length(d) < ir)) continue;
-                        cb += dfsph_div_boundary_mv<R, KSET>(P, d, rd * b.w, u1, xyz<R>(bU[j]));
-                    }
-                }
-                div += cb;
-            }
-    return div;
-}
-template <typename R, int KSET, bool DENS>
-__global__ __launch_bounds__(BLOCK) void k_dfsph_div_mv_ref(Params<R> P, GridView<R> G, DfsphArrays<R> A,
-                                                            const typename Vec4T<R>::type *__restrict__ sPos,
-                                                            const typename Vec4T<R>::type *__restrict__ bU, int phase, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const R div = dfsph_div_walk_mv<R, KSET>(P, G, sPos, A.u, bU, i, xyz<R>(sPos[i]), xyz<R>(A.u[i]));
-    dfsph_div_store<R, DENS>(P, A, i, div, phase);
-}
-
-// list-driven: a particle without boundary hits is dfsph_div_lists_particle's; one with them walks the (cell, kind) groups in the
-// reference's order with the moving-wall term; an overflowed list takes dfsph_div_walk_mv
-template <typename R, int KSET, bool HAS_B, bool DENS>
-NRS_DEV void dfsph_div_mv_lists_particle(const Params<R> &P, const GridView<R> &G, const DfsphArrays<R> &A, const HitBuffer &hb,
-                                         const typename Vec4T<R>::type *__restrict__ sPos,
-                                         const typename Vec4T<R>::type *__restrict__ bU, int phase, uint32_t i)
-{
-    static_assert(KSET == KS_MULLER, "list-driven DFSPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::Features::listKernels)");
-    const HitCounts hc = unpack_counts(hb.counts[i]);
-    if (!HAS_B || (!hc.over && hc.nb == 0)) {
-        dfsph_div_lists_particle<R, KSET, HAS_B, DENS>(P, G, A, hb, sPos, phase, i);
-        return;
-    }
-    const V3<R> pos1 = xyz<R>(sPos[i]);
-    const V3<R> u1 = xyz<R>(A.u[i]);
-    const R ir = P.interactionRadius, rd = P.restDensity;
-    R div;
-    if (hc.over) {
-        div = dfsph_div_walk_mv<R, KSET>(P, G, sPos, A.u, bU, i, pos1, u1);
-    } else {
-        div = (R)0.0;
-        R part = (R)0.0;
-        for_each_hit(hb.hits + i, hb.stride, hc, [&](uint32_t j, bool isB, bool fresh) {
-            if (fresh) { div += part; part = (R)0.0; }
-            if (isB) {
-                const typename Vec4T<R>::type b = G.sB[j];
-                const V3<R> d = pos1 - xyz<R>(b);
-                if (!(length(d) < ir)) return;
-                part += dfsph_div_boundary_mv<R, KSET>(P, d, rd * b.w, u1, xyz<R>(bU[j]));
-            } else if (j != i) {
-                const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                if (!(length(d) < ir)) return;
-                part += dfsph_div_fluid<R, KSET>(P, d, u1, xyz<R>(A.u[j]));
-            }
-        });
-        div += part;
-    }
-    dfsph_div_store<R, DENS>(P, A, i, div, phase);
-}
-template <typename R, int KSET, bool DENS, bool WALLS = false>
-__global__ __launch_bounds__(BLOCK) void k_dfsph_div_mv_lists(Params<R> P, GridView<R> G, DfsphArrays<R> A, HitBuffer hb,
-                                                              const typename Vec4T<R>::type *__restrict__ sPos,
-                                                              const typename Vec4T<R>::type *__restrict__ bU, int phase, uint32_t n,
-                                                              WallList wl, uint32_t wallBlocks)
-{
-    wall_split<true, WALLS>(hb, wl, wallBlocks, n, [&](auto hasB, uint32_t i) {
-        dfsph_div_mv_lists_particle<R, KSET, decltype(hasB)::value, DENS>(P, G, A, hb, sPos, bU, phase, i);
-    });
 }
 
 } // namespace nrs

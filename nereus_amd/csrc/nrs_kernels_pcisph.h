@@ -1,4 +1,4 @@
-// nrs_kernels_pcisph.h — list-driven kernels of the PCISPH chain (Muller kernels).
+// nrs_kernels_pcisph.h — the list-driven advection launch (Muller kernels) and the two neighbour passes of the PCISPH chain.
 //
 // The chain is: the step's one density scan (k_density_tiled<..., WIDE>, the launch of the IISPH chain) publishes hit lists that keep
 // every candidate with length(r)^2 <= h^2 at the step's start positions; the advection launch takes the non-pressure forces from them
@@ -6,10 +6,10 @@
 // density and the pressure update, and B, the pressure force and the next predicted positions.  Each applies the tests of the
 // definition (nrs_kernels_ref.h, "PCISPH": j != i, length(x_i - x_j) < h at the start positions, length(x*_i - x*_j) < h at the
 // predicted ones) and forms the sums in the order of the reference-order walks (one partial per (cell, kind) group, fluid before
-// boundary inside a cell), so both paths give the same bits.  A particle whose list overflowed takes pci_density_walk / pci_pforce_walk,
-// the functions the k_pci_*_ref kernels call.
+// boundary inside a cell), so both paths give the same bits.  A and B are passes of the shared walks (nrs_kernels_walk.h: walk_hits over
+// the lists, walk_cells for the reference-order kernels and for a particle whose list overflowed); only their terms are written here.
 #pragma once
-#include "nrs_kernels_iisph.h"
+#include "nrs_kernels_walk.h"
 
 namespace nrs {
 
@@ -43,64 +43,43 @@ __global__ __launch_bounds__(BLOCK) void k_pci_advect_lists(Params<R> P, GridVie
 }
 
 // ---- iteration launch A: predicted density, p += delta (rho* - rho0) clamped at 0, e_i ----------------------------------------------
-template <typename R, int KSET, bool HAS_B>
-NRS_DEV void pci_density_lists_particle(const Params<R> &P, const GridView<R> &G, const PciArrays<R> &A, const HitBuffer &hb,
-                                        const typename Vec4T<R>::type *__restrict__ sPos, uint32_t i)
-{
-    static_assert(KSET == KS_MULLER, "list-driven PCISPH kernels: Muller kernels only (the Monaghan support is 2h, Ctx::Features::listKernels)");
-    const V3<R> pos1 = xyz<R>(sPos[i]);
-    const V3<R> xs1 = xyz<R>(A.xsIn[i]);
-    const R ir = P.interactionRadius, kp = P.kpoly, pm = P.particleMass, rd = P.restDensity;
-    const HitCounts hc = unpack_counts(hb.counts[i]);
-    R rs;
-    if (hc.over) {
-        rs = pci_density_walk<R, KSET, HAS_B>(P, G, sPos, A.xsIn, i, pos1, xs1);
-    } else {
-        rs = (R)0.0;
-        rs += pm * W_dens<R, KSET>(mk3<R>(0, 0, 0), ir, kp);
-        R part = (R)0.0;
-        if (!HAS_B || hc.nb == 0) { // no boundary hits: the fluid entries alone, batched, one partial per cell tag
-            uint32_t prevTag = 0xffffffffu;
-            struct Nb { typename Vec4T<R>::type q, x; };
-            walk_fluid_batched(hb.hits + i, hb.stride, hc.nf, [&](uint32_t j) { return Nb{sPos[j], A.xsIn[j]}; },
-                               [&](uint32_t j, uint32_t tag, const Nb &nb) {
-                                   if (tag != prevTag) { rs += part; part = (R)0.0; prevTag = tag; }
-                                   if (j == i) return;
-                                   const V3<R> d0 = pos1 - xyz<R>(nb.q);
-                                   if (!(length_listed(dot(d0, d0)) < ir)) return;
-                                   const V3<R> d = xs1 - xyz<R>(nb.x);
-                                   if (length(d) < ir) part += pm * W_dens<R, KSET>(d, ir, kp);
-                               });
-        } else { // (cell, kind) groups in the reference's order, every partial into the one total
-            for_each_hit(hb.hits + i, hb.stride, hc, [&](uint32_t j, bool isB, bool fresh) {
-                if (fresh) { rs += part; part = (R)0.0; }
-                if (HAS_B && isB) {
-                    const typename Vec4T<R>::type b = G.sB[j];
-                    if (!(length(pos1 - xyz<R>(b)) < ir)) return;
-                    const V3<R> d = xs1 - xyz<R>(b);
-                    if (length(d) < ir) part += (rd * b.w) * W_dens<R, KSET>(d, ir, kp);
-                } else if (j != i) {
-                    if (!(length(pos1 - xyz<R>(sPos[j])) < ir)) return;
-                    const V3<R> d = xs1 - xyz<R>(A.xsIn[j]);
-                    if (length(d) < ir) part += pm * W_dens<R, KSET>(d, ir, kp);
-                }
-            });
-        }
-        rs += part;
+template <typename R, int KSET> struct PciDensityPass {
+    typedef R Real;
+    typedef typename Vec4T<R>::type T4;
+    static constexpr int KS = KSET;
+    static constexpr bool WALLED = true;
+    Params<R> P;
+    PciArrays<R> A;
+    typedef R Acc;
+    struct Own { V3<R> xs1; };
+    struct Nb { T4 x; };
+    NRS_DEV Own own(uint32_t i, V3<R>) const { return Own{xyz<R>(A.xsIn[i])}; }
+    NRS_DEV Acc zero() const { return (R)0.0; }
+    NRS_DEV Acc start(const Own &) const
+    {
+        R rs = (R)0.0;
+        rs += P.particleMass * W_dens<R, KSET>(mk3<R>(0, 0, 0), P.interactionRadius, P.kpoly);
+        return rs;
     }
-    pci_pressure_update<R>(P, A, i, rs);
-}
-template <typename R, int KSET, bool HAS_B, bool WALLS = false>
-__global__ __launch_bounds__(BLOCK) void k_pci_density_lists(Params<R> P, GridView<R> G, PciArrays<R> A, HitBuffer hb,
-                                                             const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n, WallList wl,
-                                                             uint32_t wallBlocks)
-{
-    wall_split<HAS_B, WALLS>(hb, wl, wallBlocks, n, [&](auto hasB, uint32_t i) {
-        pci_density_lists_particle<R, KSET, decltype(hasB)::value>(P, G, A, hb, sPos, i);
-    });
-}
+    NRS_DEV Nb gather(uint32_t j) const { return Nb{A.xsIn[j]}; }
+    NRS_DEV void fluid(const Own &o, V3<R>, const T4 &, const Nb &nb, float, Acc &part) const
+    {
+        const R ir = P.interactionRadius;
+        const V3<R> d = o.xs1 - xyz<R>(nb.x);
+        if (length(d) < ir) part += P.particleMass * W_dens<R, KSET>(d, ir, P.kpoly);
+    }
+    NRS_DEV void boundary(const Own &o, V3<R>, uint32_t, const T4 &b, Acc &part) const
+    {
+        const R ir = P.interactionRadius;
+        const V3<R> d = o.xs1 - xyz<R>(b);
+        if (length(d) < ir) part += (P.restDensity * b.w) * W_dens<R, KSET>(d, ir, P.kpoly);
+    }
+    NRS_DEV void store(uint32_t i, V3<R>, const Own &, Acc rs) const { pci_pressure_update<R>(P, A, i, rs); }
+};
 
 // ---- iteration launch B: pressure force, x* = x + dt (vel_adv + dt Fp / m) into the other buffer ------------------------------------
+// (kept hand-written: in the shared form of nrs_kernels_walk.h the fp32 list kernel with boundary code and without wall workgroups needs
+// more than 96 VGPRs and loses a wave, DESIGN.md "One neighbour walk")
 template <typename R, int KSET, bool HAS_B>
 NRS_DEV void pci_pforce_lists_particle(const Params<R> &P, const GridView<R> &G, const PciArrays<R> &A, const HitBuffer &hb,
                                        const typename Vec4T<R>::type *__restrict__ sPos, uint32_t i)

@@ -848,7 +848,7 @@ __global__ __launch_bounds__(BLOCK) void k_iisph_integrate(Params<R> P, typename
 // with length(x_i - x_j) < h at the step's START positions (the neighbourhood of the step's density scan) AND length(x*_i - x*_j) < h
 // at the predicted ones; boundary particles are static (x*_b = x_b); the fluid sums skip j == i by sorted slot.  Sums are formed in
 // the order of density_of: cells z, y, x of the start cell, in each a fluid partial (j ascending) and then a boundary partial, each
-// added to the running total — so the list-driven kernels (nrs_kernels_pcisph.h) can be bit-identical to the walks below.
+// added to the running total — which both walks of nrs_kernels_walk.h keep.
 template <typename R> struct PciArrays {
     typedef typename Vec4T<R>::type T4;
     T4 *velAdv, *forcesAdv, *forcesP; // vel_adv, the non-pressure force, the pressure force Fp
@@ -912,47 +912,8 @@ template <typename R> NRS_DEV void pci_advect_store(const Params<R> &P, const Pc
     A.xsOut[i] = mk4<R>(pci_predict<R>(P, pos1, vel_adv, zero), (R)1.0);
 }
 
-// predicted density of particle i (iteration launch A), reference order
-template <typename R, int KSET, bool HAS_B>
-NRS_DEV R pci_density_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                           const typename Vec4T<R>::type *__restrict__ xs, uint32_t i, V3<R> pos1, V3<R> xs1)
-{
-    const R ir = P.interactionRadius, kp = P.kpoly, pm = P.particleMass, rd = P.restDensity;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    R dens = (R)0.0;
-    dens += pm * W_dens<R, KSET>(mk3<R>(0, 0, 0), ir, kp);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                R c = (R)0.0;
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
-                        const V3<R> d = xs1 - xyz<R>(xs[j]);
-                        if (length(d) < ir) c += pm * W_dens<R, KSET>(d, ir, kp);
-                    }
-                }
-                dens += c;
-                if (HAS_B) {
-                    R cb = (R)0.0;
-                    const uint32_t sb = G.bCellStart[h];
-                    if (sb != CELL_EMPTY) {
-                        const uint32_t e = G.bCellEnd[h];
-                        for (uint32_t j = sb; j < e; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            if (!(length(pos1 - xyz<R>(b)) < ir)) continue;
-                            const V3<R> d = xs1 - xyz<R>(b);
-                            if (length(d) < ir) cb += (rd * b.w) * W_dens<R, KSET>(d, ir, kp);
-                        }
-                    }
-                    dens += cb;
-                }
-            }
-    return dens;
-}
+// (kept hand-written: in the shared form of nrs_kernels_walk.h the fp32 list kernel with boundary code and without wall workgroups needs
+// more than 96 VGPRs and loses a wave, DESIGN.md "One neighbour walk")
 // pressure force on particle i (iteration launch B), reference order
 template <typename R, int KSET, bool HAS_B>
 NRS_DEV V3<R> pci_pforce_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
@@ -1008,16 +969,6 @@ __global__ __launch_bounds__(BLOCK) void k_pci_advect_ref(Params<R> P, GridView<
     const ForceAcc<R> F = gather_forces<R, KSET, SURF, HAS_B>(P, G, i, pos1, vel1, sDens[i], (R)0.0, sPos, sVel, sDens, sPres);
     pci_advect_store<R>(P, A, i, pos1, vel1, pci_advect_force<R>(P, F));
 }
-// iteration launch A: predicted density, pressure update, density error
-template <typename R, int KSET, bool HAS_B>
-__global__ __launch_bounds__(BLOCK) void k_pci_density_ref(Params<R> P, GridView<R> G, PciArrays<R> A,
-                                                           const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const R rs = pci_density_walk<R, KSET, HAS_B>(P, G, sPos, A.xsIn, i, xyz<R>(sPos[i]), xyz<R>(A.xsIn[i]));
-    pci_pressure_update<R>(P, A, i, rs);
-}
 // iteration launch B: pressure force and the next predicted positions
 template <typename R, int KSET, bool HAS_B>
 __global__ __launch_bounds__(BLOCK) void k_pci_pforce_ref(Params<R> P, GridView<R> G, PciArrays<R> A,
@@ -1056,8 +1007,8 @@ __global__ __launch_bounds__(64) void k_pci_prototype(Params<R> P, R spacing, in
 // Position-based fluids (Macklin & Mueller 2013): a density constraint solved by Jacobi projection.  The reference names it among
 // its future works only; DESIGN.md "PBF" defines what is computed here.  The neighbour rule and the order of every sum are those of
 // the PCISPH loop above (start-position AND predicted-position cut-off, j != i by sorted slot, static boundary particles, one
-// fluid partial and then one boundary partial per cell in the order of density_of), so the list-driven kernels (nrs_kernels_pbf.h)
-// can be bit-identical to the walks below.  The advection launch is PCISPH's (k_pci_advect_*).
+// fluid partial and then one boundary partial per cell in the order of density_of), as both walks of nrs_kernels_walk.h form them (the
+// passes: nrs_kernels_pbf.h).  The advection launch is PCISPH's (k_pci_advect_*).
 template <typename R> struct PbfArrays {
     typedef typename Vec4T<R>::type T4;
     R *densPred, *lambda, *err; // rho*, lambda, e = max(rho* - rho0, 0) / rho0 (input of the exit test's max)
@@ -1131,7 +1082,7 @@ template <typename R, int KSET> NRS_DEV V3<R> pbf_correct_fluid(const Params<R> 
     return pci_scale<R>(li + lj, pci_scale<R>(P.particleMass / P.restDensity, pbf_grad<R, KSET>(P, d)));
 }
 // the tensile correction s_corr of launch B: s_ij = -k (W(x*_ij) / W_q)^4, W_q = W((dq h, 0, 0)).  Its instances are kernels of their
-// own (k_pbf_correct_s_*): a template flag on k_pbf_correct_* would rename the instances without it.
+// own (PbfCorrectPass<R, KSET, true>, nrs_kernels_pbf.h).
 template <typename R> struct PbfTensile {
     R k, wq;
 };
@@ -1143,13 +1094,6 @@ template <typename R, int KSET> NRS_DEV V3<R> pbf_correct_fluid_s(const Params<R
     const R r2 = r * r;
     const R s = -T.k * (r2 * r2);
     return pci_scale<R>(li + lj + s, pci_scale<R>(P.particleMass / P.restDensity, pbf_grad<R, KSET>(P, d)));
-}
-// the fluid term of launch B, with or without s_corr
-template <typename R, int KSET, bool TENS>
-NRS_DEV V3<R> pbf_correct_term(const Params<R> &P, V3<R> d, R li, R lj, const PbfTensile<R> &T)
-{
-    if constexpr (TENS) return pbf_correct_fluid_s<R, KSET>(P, d, li, lj, T);
-    else return pbf_correct_fluid<R, KSET>(P, d, li, lj);
 }
 template <typename R, int KSET> NRS_DEV V3<R> pbf_correct_boundary(const Params<R> &P, V3<R> d, R psi, R li)
 {
@@ -1169,143 +1113,6 @@ template <typename R, int KSET> NRS_DEV V3<R> pbf_xsph_fluid(const Params<R> &P,
     return pci_scale<R>((P.particleMass / P.restDensity) * W_dens<R, KSET>(d, ir, P.kpoly), vj - vi);
 }
 
-// launch A of particle i, reference order
-template <typename R, int KSET, bool HAS_B>
-NRS_DEV PbfSums<R> pbf_lambda_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                                   const typename Vec4T<R>::type *__restrict__ xs, uint32_t i, V3<R> pos1, V3<R> xs1)
-{
-    const R ir = P.interactionRadius, rd = P.restDensity;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    PbfSums<R> t = pbf_zero<R>();
-    t.rho += P.particleMass * W_dens<R, KSET>(mk3<R>(0, 0, 0), ir, P.kpoly);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                PbfSums<R> c = pbf_zero<R>();
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
-                        pbf_lambda_fluid<R, KSET>(P, xs1 - xyz<R>(xs[j]), c);
-                    }
-                }
-                t.add(c);
-                if (HAS_B) {
-                    PbfSums<R> cb = pbf_zero<R>();
-                    const uint32_t sb = G.bCellStart[h];
-                    if (sb != CELL_EMPTY) {
-                        const uint32_t e = G.bCellEnd[h];
-                        for (uint32_t j = sb; j < e; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            if (!(length(pos1 - xyz<R>(b)) < ir)) continue;
-                            pbf_lambda_boundary<R, KSET>(P, xs1 - xyz<R>(b), rd * b.w, cb);
-                        }
-                    }
-                    t.add(cb);
-                }
-            }
-    return t;
-}
-// launch B of particle i (the correction dx_i), reference order
-template <typename R, int KSET, bool HAS_B, bool TENS = false>
-NRS_DEV V3<R> pbf_correct_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                               const typename Vec4T<R>::type *__restrict__ xs, const R *__restrict__ lambda, uint32_t i, V3<R> pos1,
-                               V3<R> xs1, R li, PbfTensile<R> T = PbfTensile<R>{})
-{
-    const R ir = P.interactionRadius, rd = P.restDensity;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    V3<R> dx = mk3<R>(0, 0, 0);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                V3<R> c = mk3<R>(0, 0, 0);
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
-                        c = c + pbf_correct_term<R, KSET, TENS>(P, xs1 - xyz<R>(xs[j]), li, lambda[j], T);
-                    }
-                }
-                dx = dx + c;
-                if (HAS_B) {
-                    V3<R> cb = mk3<R>(0, 0, 0);
-                    const uint32_t sb = G.bCellStart[h];
-                    if (sb != CELL_EMPTY) {
-                        const uint32_t e = G.bCellEnd[h];
-                        for (uint32_t j = sb; j < e; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            if (!(length(pos1 - xyz<R>(b)) < ir)) continue;
-                            cb = cb + pbf_correct_boundary<R, KSET>(P, xs1 - xyz<R>(b), rd * b.w, li);
-                        }
-                    }
-                    dx = dx + cb;
-                }
-            }
-    return dx;
-}
-// the XSPH sum of particle i over its fluid neighbours, reference order (v_j formed from x*_j and x_j)
-template <typename R, int KSET>
-NRS_DEV V3<R> pbf_xsph_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                            const typename Vec4T<R>::type *__restrict__ xs, uint32_t i, V3<R> pos1, V3<R> xs1, V3<R> v1)
-{
-    const R ir = P.interactionRadius;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    V3<R> sum = mk3<R>(0, 0, 0);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                V3<R> c = mk3<R>(0, 0, 0);
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        const V3<R> xj = xyz<R>(sPos[j]);
-                        if (j == i || !(length(pos1 - xj) < ir)) continue;
-                        const V3<R> xsj = xyz<R>(xs[j]);
-                        c = c + pbf_xsph_fluid<R, KSET>(P, xs1 - xsj, pbf_vel<R>(P, xsj, xj), v1);
-                    }
-                }
-                sum = sum + c;
-            }
-    return sum;
-}
-
-// launch A: rho*, lambda, e
-template <typename R, int KSET, bool HAS_B>
-__global__ __launch_bounds__(BLOCK) void k_pbf_lambda_ref(Params<R> P, GridView<R> G, PbfArrays<R> A,
-                                                          const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    pbf_lambda_store<R>(P, A, i, pbf_lambda_walk<R, KSET, HAS_B>(P, G, sPos, A.xsIn, i, xyz<R>(sPos[i]), xyz<R>(A.xsIn[i])));
-}
-// launch B: the correction and the next predicted positions
-template <typename R, int KSET, bool HAS_B>
-__global__ __launch_bounds__(BLOCK) void k_pbf_correct_ref(Params<R> P, GridView<R> G, PbfArrays<R> A,
-                                                           const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> xs1 = xyz<R>(A.xsIn[i]);
-    pbf_correct_store<R>(A, i, xs1, pbf_correct_walk<R, KSET, HAS_B>(P, G, sPos, A.xsIn, A.lambda, i, xyz<R>(sPos[i]), xs1, A.lambda[i]));
-}
-// XSPH: vel_i = v_i + c sum_j (m / rho0) W (v_j - v_i), v = (x* - x) / dt (before k_pbf_integrate, which then takes vel as given)
-template <typename R, int KSET>
-__global__ __launch_bounds__(BLOCK) void k_pbf_xsph_ref(Params<R> P, GridView<R> G, const typename Vec4T<R>::type *__restrict__ sPos,
-                                                        const typename Vec4T<R>::type *__restrict__ xs,
-                                                        typename Vec4T<R>::type *__restrict__ vel, R c, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> pos1 = xyz<R>(sPos[i]), xs1 = xyz<R>(xs[i]);
-    const V3<R> v1 = pbf_vel<R>(P, xs1, pos1);
-    vel[i] = mk4<R>(v1 + pci_scale<R>(c, pbf_xsph_walk<R, KSET>(P, G, sPos, xs, i, pos1, xs1, v1)), (R)0.0);
-}
 // PBF integration: v = (x* - x) / dt (or, after the XSPH launch, the velocity it left), x = x* with pos.w kept, vel.w = 0.  The sort
 // keys of the next step and the movers of the coherent re-sort as k_iisph_integrate emits them.
 template <typename R>
@@ -1351,17 +1158,6 @@ __global__ __launch_bounds__(64) void k_pbf_prototype(Params<R> P, R spacing, in
     out[0] = sx; out[1] = sy; out[2] = sz; out[3] = gg; out[4] = cnt;
 }
 
-// launch B with the tensile correction: k_pbf_correct_ref with (lambda_i + lambda_j + s_ij) on fluid pairs
-template <typename R, int KSET, bool HAS_B>
-__global__ __launch_bounds__(BLOCK) void k_pbf_correct_s_ref(Params<R> P, GridView<R> G, PbfArrays<R> A, PbfTensile<R> T,
-                                                             const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> xs1 = xyz<R>(A.xsIn[i]);
-    pbf_correct_store<R>(A, i, xs1,
-                         pbf_correct_walk<R, KSET, HAS_B, true>(P, G, sPos, A.xsIn, A.lambda, i, xyz<R>(sPos[i]), xs1, A.lambda[i], T));
-}
 // W_q = W((dq h, 0, 0)), the reference value of s_corr, with the solver's own W.  One thread.
 template <typename R, int KSET>
 __global__ __launch_bounds__(64) void k_pbf_wq(Params<R> P, R dq, double *__restrict__ out)
@@ -1404,92 +1200,13 @@ NRS_DEV V3<R> pbf_confine(const Params<R> &P, V3<R> v, V3<R> eta, typename Vec4T
     const V3<R> N = pci_scale<R>((R)1.0 / en, eta);
     return v + pci_scale<R>(P.timestep * epsV, pbf_cross<R>(N, xyz<R>(om)));
 }
-// the vorticity sum of particle i, reference order
-template <typename R, int KSET>
-NRS_DEV V3<R> pbf_vort_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                            const typename Vec4T<R>::type *__restrict__ xs, uint32_t i, V3<R> pos1, V3<R> xs1, V3<R> u1)
-{
-    const R ir = P.interactionRadius;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    V3<R> sum = mk3<R>(0, 0, 0);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                V3<R> c = mk3<R>(0, 0, 0);
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        const V3<R> xj = xyz<R>(sPos[j]);
-                        if (j == i || !(length(pos1 - xj) < ir)) continue;
-                        const V3<R> xsj = xyz<R>(xs[j]);
-                        c = c + pbf_vort_fluid<R, KSET>(P, xs1 - xsj, pbf_vel<R>(P, xsj, xj), u1);
-                    }
-                }
-                sum = sum + c;
-            }
-    return sum;
-}
-// the confinement sum eta of particle i, reference order
-template <typename R, int KSET>
-NRS_DEV V3<R> pbf_eta_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                           const typename Vec4T<R>::type *__restrict__ xs, const typename Vec4T<R>::type *__restrict__ omega,
-                           uint32_t i, V3<R> pos1, V3<R> xs1, R wi)
-{
-    const R ir = P.interactionRadius;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    V3<R> sum = mk3<R>(0, 0, 0);
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                V3<R> c = mk3<R>(0, 0, 0);
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        if (j == i || !(length(pos1 - xyz<R>(sPos[j])) < ir)) continue;
-                        c = c + pbf_eta_fluid<R, KSET>(P, xs1 - xyz<R>(xs[j]), omega[j].w, wi);
-                    }
-                }
-                sum = sum + c;
-            }
-    return sum;
-}
-// vorticity launch: omega[i] = (omega_i, |omega_i|)
-template <typename R, int KSET>
-__global__ __launch_bounds__(BLOCK) void k_pbf_vorticity_ref(Params<R> P, GridView<R> G, const typename Vec4T<R>::type *__restrict__ sPos,
-                                                             const typename Vec4T<R>::type *__restrict__ xs,
-                                                             typename Vec4T<R>::type *__restrict__ omega, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> pos1 = xyz<R>(sPos[i]), xs1 = xyz<R>(xs[i]);
-    omega[i] = pbf_vort_pack<R>(pbf_vort_walk<R, KSET>(P, G, sPos, xs, i, pos1, xs1, pbf_vel<R>(P, xs1, pos1)));
-}
-// confinement launch: vel[i] = v_i + dt eps_v (N_i x omega_i), v_i = vel[i] (velGiven: the XSPH launch ran) or u_i
-template <typename R, int KSET>
-__global__ __launch_bounds__(BLOCK) void k_pbf_confine_ref(Params<R> P, GridView<R> G, const typename Vec4T<R>::type *__restrict__ sPos,
-                                                           const typename Vec4T<R>::type *__restrict__ xs,
-                                                           const typename Vec4T<R>::type *__restrict__ omega,
-                                                           typename Vec4T<R>::type *__restrict__ vel, int velGiven, R epsV, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const V3<R> pos1 = xyz<R>(sPos[i]), xs1 = xyz<R>(xs[i]);
-    const typename Vec4T<R>::type om = omega[i];
-    const V3<R> v = velGiven ? xyz<R>(vel[i]) : pbf_vel<R>(P, xs1, pos1);
-    vel[i] = mk4<R>(pbf_confine<R>(P, v, pbf_eta_walk<R, KSET>(P, G, sPos, xs, omega, i, pos1, xs1, om.w), om, epsV), (R)0.0);
-}
-
 // =========================================== DFSPH ===================================================
 // Divergence-free SPH (Bender & Koschier 2015 / 2017): a divergence solve on the step's velocities and a density solve on vel_adv,
 // both Jacobi iterations on velocities with PBF's spiky gradient.  DESIGN.md "DFSPH" defines what is computed here.  Every position is
 // the step's START position (DFSPH moves no particle before the integration), so one neighbour rule holds for the whole step:
 // length(x_i - x_j) < h, j != i by sorted slot, static boundary particles with the same rule.  Sums are formed in the order of
-// density_of (one fluid partial and then one boundary partial per cell), so the list-driven kernels (nrs_kernels_dfsph.h) can be
-// bit-identical to the walks below.  g_ij = (m / rho0) pbf_grad(x_i - x_j), g_ib = (psi_b / rho0) pbf_grad(x_i - x_b).
+// density_of (one fluid partial and then one boundary partial per cell), as both walks of nrs_kernels_walk.h form them (the passes:
+// nrs_kernels_dfsph.h).  g_ij = (m / rho0) pbf_grad(x_i - x_j), g_ib = (psi_b / rho0) pbf_grad(x_i - x_b).
 template <typename R> struct DfsphArrays {
     typedef typename Vec4T<R>::type T4;
     T4 *u;         // the velocities the solve corrects, in place (the divergence solve: the sorted v; the density solve: vel_adv)
@@ -1588,86 +1305,8 @@ template <typename R> NRS_DEV void dfsph_vup_store(const Params<R> &P, const Dfs
     A.u[i] = mk4<R>(xyz<R>(u) - pci_scale<R>(P.timestep, s), u.w);
 }
 
-// the factor sums of particle i, reference order
-template <typename R, int KSET, bool HAS_B>
-NRS_DEV DfsphFac<R> dfsph_factor_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos, uint32_t i,
-                                      V3<R> pos1)
-{
-    const R ir = P.interactionRadius, rd = P.restDensity;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    DfsphFac<R> t = dfsph_fac_zero<R>();
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                DfsphFac<R> c = dfsph_fac_zero<R>();
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                        if (j == i || !(length(d) < ir)) continue;
-                        dfsph_fac_fluid<R, KSET>(P, d, c);
-                    }
-                }
-                t.add(c);
-                if (HAS_B) {
-                    DfsphFac<R> cb = dfsph_fac_zero<R>();
-                    const uint32_t sb = G.bCellStart[h];
-                    if (sb != CELL_EMPTY) {
-                        const uint32_t e = G.bCellEnd[h];
-                        for (uint32_t j = sb; j < e; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            const V3<R> d = pos1 - xyz<R>(b);
-                            if (!(length(d) < ir)) continue;
-                            dfsph_fac_boundary<R, KSET>(P, d, rd * b.w, cb);
-                        }
-                    }
-                    t.add(cb);
-                }
-            }
-    return t;
-}
-// div_i of particle i (launch A), reference order
-template <typename R, int KSET, bool HAS_B>
-NRS_DEV R dfsph_div_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
-                         const typename Vec4T<R>::type *__restrict__ u, uint32_t i, V3<R> pos1, V3<R> u1)
-{
-    const R ir = P.interactionRadius, rd = P.restDensity;
-    const I3 gp = calcGridPos<R>(P, pos1);
-    R div = (R)0.0;
-    for (int z = -1; z <= 1; z++)
-        for (int y = -1; y <= 1; y++)
-            for (int x = -1; x <= 1; x++) {
-                const uint32_t h = calcGridHash<R>(P, gp.x + x, gp.y + y, gp.z + z);
-                R c = (R)0.0;
-                const uint32_t s = G.cellStart[h];
-                if (s != CELL_EMPTY) {
-                    const uint32_t e = G.cellEnd[h];
-                    for (uint32_t j = s; j < e; ++j) {
-                        const V3<R> d = pos1 - xyz<R>(sPos[j]);
-                        if (j == i || !(length(d) < ir)) continue;
-                        c += dfsph_div_fluid<R, KSET>(P, d, u1, xyz<R>(u[j]));
-                    }
-                }
-                div += c;
-                if (HAS_B) {
-                    R cb = (R)0.0;
-                    const uint32_t sb = G.bCellStart[h];
-                    if (sb != CELL_EMPTY) {
-                        const uint32_t e = G.bCellEnd[h];
-                        for (uint32_t j = sb; j < e; ++j) {
-                            const typename Vec4T<R>::type b = G.sB[j];
-                            const V3<R> d = pos1 - xyz<R>(b);
-                            if (!(length(d) < ir)) continue;
-                            cb += dfsph_div_boundary<R, KSET>(P, d, rd * b.w, u1);
-                        }
-                    }
-                    div += cb;
-                }
-            }
-    return div;
-}
+// (kept hand-written: in the shared form of nrs_kernels_walk.h the fp32 list kernel with boundary code and without wall workgroups needs
+// more than 96 VGPRs and loses a wave, DESIGN.md "One neighbour walk")
 // the velocity correction sum of particle i (launch B), reference order
 template <typename R, int KSET, bool HAS_B>
 NRS_DEV V3<R> dfsph_vup_walk(const Params<R> &P, const GridView<R> &G, const typename Vec4T<R>::type *__restrict__ sPos,
@@ -1707,26 +1346,6 @@ NRS_DEV V3<R> dfsph_vup_walk(const Params<R> &P, const GridView<R> &G, const typ
                 }
             }
     return sum;
-}
-
-// the factor launch: alpha_i
-template <typename R, int KSET, bool HAS_B>
-__global__ __launch_bounds__(BLOCK) void k_dfsph_factor_ref(Params<R> P, GridView<R> G, DfsphArrays<R> A,
-                                                            const typename Vec4T<R>::type *__restrict__ sPos, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    dfsph_fac_store<R>(A, i, dfsph_factor_walk<R, KSET, HAS_B>(P, G, sPos, i, xyz<R>(sPos[i])));
-}
-// launch A: div_i -> e_i, kappa_i, K_i (DENS: the density mode, with rho_adv)
-template <typename R, int KSET, bool HAS_B, bool DENS>
-__global__ __launch_bounds__(BLOCK) void k_dfsph_div_ref(Params<R> P, GridView<R> G, DfsphArrays<R> A,
-                                                         const typename Vec4T<R>::type *__restrict__ sPos, int phase, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const R div = dfsph_div_walk<R, KSET, HAS_B>(P, G, sPos, A.u, i, xyz<R>(sPos[i]), xyz<R>(A.u[i]));
-    dfsph_div_store<R, DENS>(P, A, i, div, phase);
 }
 // launch B: u_i -= dt (sum_j (kappa_i + kappa_j) g_ij + sum_b kappa_i g_ib), in place (B reads only its own u_i)
 template <typename R, int KSET, bool HAS_B>
