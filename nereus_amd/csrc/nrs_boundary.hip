@@ -99,11 +99,9 @@ template <typename R, typename T4> static int boundary_volumes(const void *bi4, 
     DevBuf dBi, dKey, dKey2, dVal, dVal2, dStart, dEnd, dOut, dTmp;
     hipStream_t st = nullptr;
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    auto done = [&](int rc) {
+    auto done = [&](int rc) { // (the buffers free themselves on return, behind this)
         (void)hipStreamSynchronize(st);
         (void)hipStreamDestroy(st);
-        DevBuf *all[] = {&dBi, &dKey, &dKey2, &dVal, &dVal2, &dStart, &dEnd, &dOut, &dTmp};
-        for (DevBuf *b : all) b->release();
         return rc;
     };
 #define BCHK(expr) do { int r_ = (expr); if (r_ != NRS_OK) return done(r_); } while (0)

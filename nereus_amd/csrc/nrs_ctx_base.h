@@ -1,5 +1,6 @@
 // nrs_ctx_base.h — what the C ABI translation unit (nrs_abi.hip) and the per-variant context translation units
-// (nrs_inst_*.hip) share: error plumbing, device buffers, the abstract context.
+// (nrs_inst_*.hip) share: HIPCHK on top of the error plumbing (nrs_error.h), the owners of device memory, pinned host memory and
+// events, the abstract context.
 #pragma once
 #include <cstring>
 #include <hip/hip_runtime.h>
@@ -7,18 +8,14 @@
 #include <cmath>
 #include <cstdio>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
-#include "../../include/nereus_hip.h"
+#include "nrs_error.h"
 
 namespace nrs {
 
-extern thread_local std::string g_err; // defined in nrs_abi.hip
-static inline int fail(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
 #define HIPCHK(expr)                                                                                     \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
@@ -26,15 +23,22 @@ static inline int fail(int code, const std::string &msg)
             return fail(NRS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + \
                                        std::to_string(__LINE__) + ")");                                  \
     } while (0)
-#define NRSCHK(expr)              \
-    do {                          \
-        int r_ = (expr);          \
-        if (r_ != NRS_OK) return r_; \
-    } while (0)
 
+// The three owners below free what they hold when they go out of scope, on every path: nothing else in the library calls hipFree,
+// hipHostFree or hipEventDestroy on them.  Move-only; a moved-from owner is empty.
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int alloc(size_t n)
     {
         if (n <= bytes && p) return NRS_OK;
@@ -51,6 +55,29 @@ struct DevBuf {
         bytes = 0;
     }
     template <typename T> T *as() const { return (T *)p; }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value, "a DevBuf owns its allocation");
+
+// page-locked host memory; reads like the T * it holds.  The user calls hipHostMalloc on .p, so a failure names the call that made it.
+template <typename T> struct PinnedBuf {
+    T *p = nullptr;
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept { if (this != &o) { release(); p = o.p; o.p = nullptr; } return *this; }
+    ~PinnedBuf() { release(); }
+    void release() { if (p) (void)hipHostFree((void *)p); p = nullptr; }
+    operator T *() const { return p; }
+};
+
+// a hipEvent_t the user creates in .e; reads like one
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept { if (this != &o) { release(); e = o.e; o.e = nullptr; } return *this; }
+    ~Event() { release(); }
+    void release() { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    operator hipEvent_t() const { return e; }
 };
 
 // hipSetDevice for the duration of a call that is not bound to a context's own device bookkeeping (nrs_boundary_volumes,

@@ -5,9 +5,19 @@
 // predictAdvection/pressureSolve sph/sph_cuda.cu:513-899) — minus the per-step PCIe copies: the
 // "unsorted" arrays of step t+1 are the integrated sorted arrays of step t (buffer swap), which is what
 // the reference obtains by copying sorted→host→device.
+//
+// Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the array-state machine, the step plan, the
+// sort stage, the solver tails, the slab code.  Host bookkeeping that depends on none of them lives in plain structs the context
+// holds as members: the body poses (nrs_host_bodies.h), the stage timer (nrs_host_profile.h), the snapshot ring
+// (nrs_host_snapshot.h), the solver settings and their validation (nrs_host_settings.h).  Every buffer, pinned landing and event
+// frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
 #pragma once
 #include <sched.h>
 #include "nrs_ctx_base.h"
+#include "nrs_host_bodies.h"
+#include "nrs_host_profile.h"
+#include "nrs_host_settings.h"
+#include "nrs_host_snapshot.h"
 #include <rocprim/rocprim.hpp>
 
 #include "nrs_kernels_ref.h"
@@ -126,21 +136,17 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // PCISPH (nrs_kernels_pcisph.h): the two predicted-position buffers (xsCur = the newest) and the density errors the exit test
     // takes the max of; velAdv, forcesAdv, forcesP, densCorr (rho*) and P_l (p) are shared with the IISPH names
     DevBuf posPred, posPred2, pciErr;
-    double pciEta = 0.01, pciSpacing = 0.0, pciDeltaGiven = 0.0;
-    uint32_t pciMinIters = 3;
+    PciSettings pciS;
     bool pciDeltaValid = false; // pciDelta belongs to the current parameters and settings
     R pciDelta = (R)0;
     double pciLastErr = -1.0; // max e_i after the last iteration of the last solve (< 0: no solve yet)
     // PBF (nrs_kernels_pbf.h) shares all of these: posPred / posPred2, pciErr, velAdv, forcesAdv, densCorr (rho*), P_l (lambda), forcesP
     // (the last correction dx) and pciLastErr
-    double pbfEta = 0.01, pbfRelax = 0.01, pbfXsph = 0.0;
-    uint32_t pbfMinIters = 2;
+    PbfSettings pbfS;
     bool pbfEpsValid = false; // pbfEps belongs to the current parameters and settings
     R pbfEps = (R)0;
     uint32_t pbfErrPending = 0; // fixed-count solve: max e over this many particles is formed on request (get_stat), not in the step
-    // PBF tensile correction (k = 0: off) and vorticity confinement (eps_v = 0: off); pbfVort holds (omega, |omega|), allocated when
-    // confinement is first enabled
-    double pbfTensK = 0.0, pbfTensDq = 0.2, pbfVortEps = 0.0;
+    // PBF tensile correction and vorticity confinement (pbfS); pbfVort holds (omega, |omega|), allocated when confinement is first enabled
     bool pbfWqValid = false; // pbfWq belongs to the current parameters and dq
     R pbfWq = (R)0;
     DevBuf pbfVort;
@@ -150,9 +156,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // IISPH's warm-start pressure does; Kv in its own pair (dfKvA: slot order of posA, dfKvB: sorted), alpha and the divergence
     // solve's e in their own buffers.
     DevBuf dfAlpha, dfKvA, dfKvB, dfErrV;
-    double dfEta = 1e-3, dfEtaV = 1e-3;
-    uint32_t dfMin = 2, dfMinV = 1;
-    bool dfWarm = true;
+    DfsphSettings dfS;
     bool dfThrValid = false; // dfThr belongs to the current parameters
     R dfThr = (R)0;
     bool dfAlphaValid = false, dfKvValid = false; // NRS_ARR_DFSPH_ALPHA / _KAPPA_V hold a step's values
@@ -160,7 +164,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint32_t dfDivIters = 0;          // divergence iterations of the last step
     // Akinci surface tension and adhesion (nrs_kernels_akinci.h; PCISPH, PBF, DFSPH): gamma = beta_a = 0 is off; akNormals holds the
     // records (n_i, rho_i), allocated when gamma is first set above 0
-    double akGamma = 0.0, akBeta = 0.0;
+    AkinciSettings akS;
     DevBuf akNormals;
     bool akNormalsValid = false; // akNormals holds the records of a step
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
@@ -188,10 +192,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     DevBuf rsMovers, rsMoversAlt, rsStayers, rsMerged, rsTileMovers, rsTileOffset, rsGroupTotal, rsGroupPrefix, rsScalars, rsPrevPacked;
     bool slotOrderValid = false; // posA/velA are in the slot order of hashCur (a full fused step was the last thing that happened)
     uint32_t *packKeys = nullptr, *packVals = nullptr; // where slab_pack / slab_unpack write the next step's keys / values
-    uint64_t *rsHostTotal = nullptr, *rsHostTotalDev = nullptr; // (launch number << 32 | mover count), written by
-                                                                // k_resort_scan_tiles into pinned, mapped host memory
+    PinnedBuf<uint64_t> rsHostTotal; // (launch number << 32 | mover count), written by k_resort_scan_tiles into pinned, mapped host
+    uint64_t *rsHostTotalDev = nullptr; // memory through this device pointer
     uint32_t rsSeq = 0;
-    hipEvent_t rsEvent = nullptr;
+    Event rsEvent;
     bool rsPending = false; // movers/stayers of the keys in hashNext have been split; the count is on its way
     bool splitClearedCells = false; // this step's k_resort_split also reset the cell table
     uint64_t rsSteps = 0, rsFallbacks = 0;
@@ -214,8 +218,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint32_t classifiedN = 0;
     // slab runs, in-place partition: the owned particles are not compacted; dead slots carry the key 0xffffffff
     DevBuf rsTileDead, rsTileDeadOffset, rsGroupDeadTotal, rsGroupDeadPrefix;
-    hipEvent_t packEvent = nullptr;
-    uint32_t *slabHostTotals = nullptr; // page-locked landing place of the stream totals
+    Event packEvent;
+    PinnedBuf<uint32_t> slabHostTotals; // page-locked landing place of the stream totals
     bool holesPending = false; // posA/velA[0, physN) contain dead slots (keys in hashNext tell which); n counts live ones
     uint32_t physN = 0;        // physical extent of the arrays while holesPending
     bool rsTilesDirty = false; // rsTileMovers holds counts no scan has consumed
@@ -231,13 +235,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool rsCountKnown = false; // the mover count of the pending split is already on the host (slab runs)
     uint32_t rsKnownCount = 0;
     bool fusedThisStep = false;
-    // profiling
-    struct Ev { int stage; hipEvent_t a, b; bool cont; };
-    std::vector<Ev> evPool;
-    size_t evUsed = 0;
-    float stageMs[NRS_STAGE_COUNT] = {0};
-    uint32_t stageLaunches[NRS_STAGE_COUNT] = {0};
-    bool evOpen = false;
+    StageTimer timer; // profiling (nrs_host_profile.h)
 
     // ---- the state of the particle arrays and of the keys prepared for the next step --------------------------------
     // The fields above are not independent: they encode ONE of the states below (DESIGN.md §5 has the transition table).
@@ -375,23 +373,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return s;
     }
 
+    // (the members free themselves after this body: the stream has drained by then)
     ~Ctx() override
     {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (auto &e : evPool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        DevBuf *all[] = {&bdRest, &bdVbi, &bdBodyOf, &bdWorld, &bdBodySorted, &bdVel, &bdSortTmp, &dfAlpha, &dfKvA, &dfKvB, &dfErrV, &pbfVort, &akNormals, &posA, &posB, &velA, &velB, &presA, &presB, &dens, &forces, &hashA, &hashB, &indexA, &indexB,
-                         &inv, &sortTmp, &cellStart, &cellEnd, &bCellStart, &bCellEnd, &bSorted, &bHash, &bIndex,
-                         &bHashAlt, &bIndexAlt, &densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP,
-                         &posPred, &posPred2, &pciErr, &diiF, &diiB, &sumDij, &diiSum, &redPartial, &redOut, &errWord, &hitBuf, &hitCounts, &qpos, &gatherPos, &fastQ, &nearBits, &wallList, &wallMask, &wallTile, &wallTileOffset, &wallGroupTotal, &wallGroupPrefix, &wallScalars, &ghostPos, &ghostVel, &slabCounts, &slabTotals,
-                         &rsMovers, &rsMoversAlt, &rsStayers, &rsMerged, &rsTileMovers, &rsTileOffset, &rsGroupTotal, &rsGroupPrefix, &rsScalars, &rsPrevPacked,
-                         &rsTileDead, &rsTileDeadOffset, &rsGroupDeadTotal, &rsGroupDeadPrefix, &slabFlags};
-        for (DevBuf *b : all) b->release();
-        if (rsEvent) (void)hipEventDestroy(rsEvent);
-        if (packEvent) (void)hipEventDestroy(packEvent);
-        if (slabHostTotals) (void)hipHostFree(slabHostTotals);
-        if (rsHostTotal) (void)hipHostFree(rsHostTotal);
-        snapshot_release();
         if (ownStream && stream) (void)hipStreamDestroy(stream);
     }
 
@@ -485,13 +471,13 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(rsTileDead.alloc(4 * nTiles)); NRSCHK(rsTileDeadOffset.alloc(4 * nTiles));
             NRSCHK(rsGroupDeadTotal.alloc(4 * nGroups)); NRSCHK(rsGroupDeadPrefix.alloc(4 * nGroups));
             HIPCHK(hipMemsetAsync(rsTileDead.p, 0, 4 * nTiles, stream));
-            HIPCHK(hipEventCreateWithFlags(&packEvent, hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&packEvent.e, hipEventDisableTiming));
             HIPCHK(hipMemsetAsync(rsTileMovers.p, 0, 4 * nTiles, stream));
             HIPCHK(hipMemsetAsync(rsScalars.p, 0, 16, stream));
-            HIPCHK(hipHostMalloc((void **)&rsHostTotal, 64, hipHostMallocMapped));
+            HIPCHK(hipHostMalloc((void **)&rsHostTotal.p, 64, hipHostMallocMapped));
             std::memset(rsHostTotal, 0, 64);
             HIPCHK(hipHostGetDevicePointer((void **)&rsHostTotalDev, rsHostTotal, 0));
-            HIPCHK(hipEventCreateWithFlags(&rsEvent, hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&rsEvent.e, hipEventDisableTiming));
             rocprim::double_buffer<uint64_t> mk(rsMovers.as<uint64_t>(), rsMoversAlt.as<uint64_t>());
             for (unsigned bits : {24u, 27u, 30u}) {
                 size_t t = 0;
@@ -652,44 +638,23 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             hipLaunchKernelGGL((k_mark_near_boundary<R>), dim3(nblocks(nb)), dim3(BLOCK), 0, stream, P, bHashCur, (uint32_t)nb, nearBits.as<uint32_t>());
             nearBitsValid = true;
         }
-        if (nBodies) { // the tables above hold the REST poses: sorted ids for them, and a rebuild at the poses before the next step
+        if (bodies.n) { // the tables above hold the REST poses: sorted ids for them, and a rebuild at the poses before the next step
             hipLaunchKernelGGL(k_gather_body, dim3(nblocks(nb)), dim3(BLOCK), 0, stream, bIndexCur, bdBodyOf.as<uint32_t>(), bdBodySorted.as<uint32_t>(),
                                (uint32_t)nb);
             HIPCHK(hipMemsetAsync(bdVel.p, 0, sizeof(T4) * nb, stream));
-            bodiesDirty = bodies_displaced();
+            bodies.dirty = bodies.displaced();
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
-        t.release(); dBi.release(); dVbi.release();
         return NRS_OK;
     }
 
     // ---- kinematic boundary bodies (nrs_kernels_bodies.h; DESIGN.md "Kinematic boundary bodies") ------------------------------------
-    // Host pose state in double; body 0 is the static world.  nBodies = 0: no assignment.  The context is "moving" while a body has a
-    // velocity or a pose was set since the last rebuild (bodiesDirty); only then does a step touch the boundary tables.
-    struct Body { double c[3], x[3], q[4], v[3], w[3]; };
-    uint32_t nBodies = 0;
-    Body bodies[NRS_MAX_BODIES];
-    bool bodiesDirty = false;
+    // The poses live in `bodies` (host, double: nrs_host_bodies.h); only while it is moving does a step touch the boundary tables.
+    BodyPoses bodies;
     bool movingStep = false; // this step rebuilt the tables: DFSPH's A launches take the wall velocities
     DevBuf bdRest, bdVbi, bdBodyOf, bdWorld, bdBodySorted, bdVel, bdSortTmp;
-    static bool body_has_velocity(const Body &b) { return b.v[0] != 0.0 || b.v[1] != 0.0 || b.v[2] != 0.0 || b.w[0] != 0.0 || b.w[1] != 0.0 || b.w[2] != 0.0; }
-    bool bodies_displaced() const
-    {
-        for (uint32_t k = 1; k < nBodies; ++k) {
-            const Body &b = bodies[k];
-            if (b.x[0] != b.c[0] || b.x[1] != b.c[1] || b.x[2] != b.c[2] || b.q[0] != 1.0 || b.q[1] != 0.0 || b.q[2] != 0.0 || b.q[3] != 0.0) return true;
-        }
-        return false;
-    }
-    bool bodies_moving() const
-    {
-        if (!nBodies) return false;
-        if (bodiesDirty) return true;
-        for (uint32_t k = 1; k < nBodies; ++k) if (body_has_velocity(bodies[k])) return true;
-        return false;
-    }
-    void clear_bodies() { nBodies = 0; bodiesDirty = false; movingStep = false; }
+    void clear_bodies() { bodies.clear(); movingStep = false; }
     size_t body_sort_bytes(unsigned bits)
     {
         size_t tmp = 0;
@@ -703,8 +668,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(refuse_mid_iisph("nrs_set_boundary_bodies"));
         if (!nb) return fail(NRS_E_STATE, "nrs_set_boundary_bodies before nrs_set_boundaries");
         if (!bodyOf || nbodies <= 1) { // clear: the walls return to the uploaded positions
-            const bool had = nBodies != 0;
-            const bool displaced = had && (bodies_displaced() || bodiesDirty);
+            const bool had = bodies.n != 0;
+            const bool displaced = had && (bodies.displaced() || bodies.dirty);
             clear_bodies();
             if (displaced) NRSCHK(rebuild_boundary_tables());
             return NRS_OK;
@@ -720,7 +685,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             sum[k][0] += (double)hostBi[i].x; sum[k][1] += (double)hostBi[i].y; sum[k][2] += (double)hostBi[i].z;
             ++cnt[k];
         }
-        const bool displaced = nBodies && (bodies_displaced() || bodiesDirty);
+        const bool displaced = bodies.n && (bodies.displaced() || bodies.dirty);
         clear_bodies();
         if (displaced) NRSCHK(rebuild_boundary_tables()); // (a new assignment starts from the rest poses)
         NRSCHK(bdRest.alloc(sizeof(T4) * nb)); NRSCHK(bdVbi.alloc(sizeof(R) * nb)); NRSCHK(bdBodyOf.alloc(4 * nb));
@@ -736,80 +701,25 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         HIPCHK(hipMemsetAsync(bdVel.p, 0, sizeof(T4) * nb, stream));
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream)); // the caller may reuse body_of on return
-        for (uint32_t k = 0; k < nbodies; ++k) {
-            Body &b = bodies[k];
-            for (int a = 0; a < 3; ++a) {
-                b.c[a] = cnt[k] ? sum[k][a] / (double)cnt[k] : 0.0;
-                b.x[a] = b.c[a]; b.v[a] = 0.0; b.w[a] = 0.0;
-            }
-            b.q[0] = 1.0; b.q[1] = b.q[2] = b.q[3] = 0.0;
-        }
-        nBodies = nbodies;
+        bodies.init(nbodies, sum, cnt);
         return NRS_OK;
     }
-    int check_body(uint32_t body) const
-    {
-        if (!nBodies) return fail(NRS_E_INVALID, "the context has no boundary bodies (nrs_set_boundary_bodies first)");
-        if (body == 0) return fail(NRS_E_INVALID, "body 0 is the static world");
-        if (body >= nBodies) return fail(NRS_E_INVALID, "unknown body");
-        return NRS_OK;
-    }
-    int set_body_velocity(uint32_t body, const double *v, const double *omega) override
-    {
-        NRSCHK(check_body(body));
-        for (int a = 0; a < 3; ++a)
-            if (!std::isfinite(v[a]) || !std::isfinite(omega[a])) return fail(NRS_E_INVALID, "body velocity must be finite");
-        for (int a = 0; a < 3; ++a) { bodies[body].v[a] = v[a]; bodies[body].w[a] = omega[a]; }
-        return NRS_OK;
-    }
-    int set_body_pose(uint32_t body, const double *x, const double *q) override
-    {
-        NRSCHK(check_body(body));
-        const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-        if (!std::isfinite(x[0]) || !std::isfinite(x[1]) || !std::isfinite(x[2]) || !std::isfinite(nq)) return fail(NRS_E_INVALID, "body pose must be finite");
-        if (!(nq > 0.0)) return fail(NRS_E_INVALID, "zero quaternion");
-        for (int a = 0; a < 3; ++a) bodies[body].x[a] = x[a];
-        for (int a = 0; a < 4; ++a) bodies[body].q[a] = q[a] / nq;
-        bodiesDirty = true;
-        return NRS_OK;
-    }
-    int get_body_pose(uint32_t body, double *x, double *q) override
-    {
-        NRSCHK(check_body(body));
-        for (int a = 0; a < 3; ++a) x[a] = bodies[body].x[a];
-        for (int a = 0; a < 4; ++a) q[a] = bodies[body].q[a];
-        return NRS_OK;
-    }
-    // x += dt v; q = exp(dt omega / 2) q (the exact exponential map, identity when |omega| = 0), renormalised
-    static void advance_body(Body &b, double dt)
-    {
-        for (int a = 0; a < 3; ++a) b.x[a] += dt * b.v[a];
-        const double wn = std::sqrt(b.w[0] * b.w[0] + b.w[1] * b.w[1] + b.w[2] * b.w[2]);
-        if (wn == 0.0) return;
-        const double half = 0.5 * dt * wn, s = std::sin(half) / wn;
-        const double e[4] = {std::cos(half), s * b.w[0], s * b.w[1], s * b.w[2]};
-        const double *q = b.q;
-        double r[4] = {e[0] * q[0] - e[1] * q[1] - e[2] * q[2] - e[3] * q[3], e[0] * q[1] + e[1] * q[0] + e[2] * q[3] - e[3] * q[2],
-                       e[0] * q[2] - e[1] * q[3] + e[2] * q[0] + e[3] * q[1], e[0] * q[3] + e[1] * q[2] - e[2] * q[1] + e[3] * q[0]};
-        const double nr = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
-        for (int a = 0; a < 4; ++a) b.q[a] = r[a] / nr;
-    }
+    int set_body_velocity(uint32_t body, const double *v, const double *omega) override { return bodies.set_velocity(body, v, omega); }
+    int set_body_pose(uint32_t body, const double *x, const double *q) override { return bodies.set_pose(body, x, q); }
+    int get_body_pose(uint32_t body, double *x, double *q) override { return bodies.get_pose(body, x, q); }
     // Start of a step of a moving context: advance the poses (host, double), round the table to SReal, rebuild the boundary tables on
     // the stream.  No synchronisation, no allocation, no read-back.  Timed as NRS_STAGE_HASH.
     int advance_bodies_and_rebuild()
     {
-        movingStep = bodies_moving();
+        movingStep = bodies.moving();
         if (!movingStep) return NRS_OK;
-        const double dt = (double)PU.timestep;
+        bodies.advance((double)PU.timestep);
         BodyTable<R> T;
         std::memset(&T, 0, sizeof(T));
-        for (uint32_t k = 1; k < nBodies; ++k) {
-            Body &b = bodies[k];
-            if (body_has_velocity(b)) advance_body(b, dt);
-            const double w = b.q[0], x = b.q[1], y = b.q[2], z = b.q[3];
-            const double rot[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
-                                   2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
-                                   2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
+        for (uint32_t k = 1; k < bodies.n; ++k) {
+            const BodyPoses::Body &b = bodies.b[k];
+            double rot[9];
+            bodies.rotation(k, rot);
             BodyPose<R> &o = T.b[k];
             for (int a = 0; a < 9; ++a) o.rot[a] = (R)rot[a];
             for (int a = 0; a < 3; ++a) { o.x[a] = (R)b.x[a]; o.c[a] = (R)b.c[a]; o.v[a] = (R)b.v[a]; o.w[a] = (R)b.w[a]; }
@@ -837,7 +747,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         HIPCHK(hipGetLastError());
         NRSCHK(ev_end());
-        bodiesDirty = false;
+        bodies.dirty = false;
         return NRS_OK;
     }
 
@@ -879,59 +789,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
 
     // ---- profiling helpers ------------------------------------------------------------------------
-    // cont: second part of a stage whose first part ran earlier (time is added, the launch count is not)
-    int ev_begin(int stage, bool cont = false)
-    {
-        evOpen = (profMask >> stage) & 1u;
-        if (!evOpen) return NRS_OK;
-        if (evUsed == evPool.size()) {
-            Ev e; e.stage = stage;
-            HIPCHK(hipEventCreate(&e.a));
-            HIPCHK(hipEventCreate(&e.b));
-            evPool.push_back(e);
-        }
-        evPool[evUsed].stage = stage;
-        evPool[evUsed].cont = cont;
-        HIPCHK(hipEventRecord(evPool[evUsed].a, stream));
-        return NRS_OK;
-    }
-    int ev_end()
-    {
-        if (!evOpen) return NRS_OK;
-        evOpen = false;
-        HIPCHK(hipEventRecord(evPool[evUsed].b, stream));
-        ++evUsed;
-        return NRS_OK;
-    }
+    int ev_begin(int stage, bool cont = false) { return timer.begin(stage, cont, profMask, stream); }
+    int ev_end() { return timer.end(stream); }
     int set_profiling(uint32_t mask) override
     {
-        NRSCHK(ev_collect());
+        NRSCHK(timer.reset(stream));
         profMask = mask;
-        std::memset(stageMs, 0, sizeof(stageMs));
-        std::memset(stageLaunches, 0, sizeof(stageLaunches));
         return NRS_OK;
     }
-    int ev_collect()
-    {
-        if (!evUsed) return NRS_OK;
-        HIPCHK(hipStreamSynchronize(stream));
-        for (size_t i = 0; i < evUsed; ++i) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, evPool[i].a, evPool[i].b));
-            stageMs[evPool[i].stage] += ms;
-            stageLaunches[evPool[i].stage] += evPool[i].cont ? 0 : 1;
-        }
-        evUsed = 0;
-        return NRS_OK;
-    }
-    int stage_ms(int stage, float *ms, uint32_t *launches) override
-    {
-        if (stage < 0 || stage >= NRS_STAGE_COUNT) return fail(NRS_E_INVALID, "bad stage");
-        NRSCHK(ev_collect()); // resolves the pending event pairs (synchronizes the stream)
-        *ms = stageMs[stage];
-        if (launches) *launches = stageLaunches[stage];
-        return NRS_OK;
-    }
+    int stage_ms(int stage, float *ms, uint32_t *launches) override { return timer.read(stage, ms, launches, stream); }
 
     GridView<R> grid_view() const
     {
@@ -1282,6 +1148,39 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return NRS_OK;
     }
 
+    // The head of an IISPH, PCISPH, PBF or DFSPH step: this step's wall list (timed with the reorder stage, whose tile counts it
+    // finishes), then the one neighbourhood scan of the step, whose hit lists drive the rest of the chain (nrs_kernels_iisph.h).  The
+    // scan opens `stage`; the caller ends it.
+    template <bool HAS_B> int begin_density_scan(int stage)
+    {
+        const uint32_t N = (uint32_t)n;
+        const dim3 g(nblocks(N)), b(BLOCK);
+        const GridView<R> G = grid_view();
+        if (plan.walls) {
+            NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
+            NRSCHK(build_wall_list(N));
+            NRSCHK(ev_end());
+        }
+        NRSCHK(ev_begin(stage));
+        const WallList wv = wall_view();
+        if (!plan.lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
+        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hit_buffer(), posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
+        return NRS_OK;
+    }
+    // The last launch of an IISPH, PCISPH, PBF or DFSPH step, inside the stage the caller opened: like the fused SESPH force kernel it
+    // also writes the next step's sort keys (plan.keys) and counts the movers per tile (plan.resort).  launch(hash, index, prevHash,
+    // tileMovers) gets where those go, or nulls; the stage ends behind it, the keys are ready and the split is queued.
+    template <typename Launch> int launch_last(Launch &&launch)
+    {
+        uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
+        if (plan.resort) NRSCHK(clean_tile_counts());
+        launch(nh, ni, plan.resort ? (const uint32_t *)hashCur : (const uint32_t *)nullptr, plan.resort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr);
+        NRSCHK(ev_end());
+        if (plan.keys) keys_ready(nh, ni);
+        if (plan.resort) NRSCHK(queue_resort_split((uint32_t)n));
+        return NRS_OK;
+    }
+
     // predictAdvection (sph_cuda.cu:513-697)
     template <bool HAS_B> int iisph_predict(int stop)
     {
@@ -1289,17 +1188,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const dim3 g(nblocks(N)), b(BLOCK);
         const GridView<R> G = grid_view();
         IisphArrays<R> I = iisph_view();
-        // one neighbourhood scan per step: its hit lists drive the rest of the chain (nrs_kernels_iisph.h)
         const HitBuffer hb = hit_buffer();
-        if (plan.walls) {
-            NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
-            NRSCHK(build_wall_list(N));
-            NRSCHK(ev_end());
-        }
-        NRSCHK(ev_begin(NRS_STAGE_I_DENSITY));
-        const WallList wv = wall_view();
-        if (!plan.lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
-        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hb, posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
+        NRSCHK(begin_density_scan<HAS_B>(NRS_STAGE_I_DENSITY));
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_I_DENSITY) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_I_DISPLACEMENT));
@@ -1365,16 +1255,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const uint32_t N = (uint32_t)n;
         const dim3 g(nblocks(N)), b(BLOCK);
         NRSCHK(ev_begin(stage));
-        // (as the fused SESPH force kernel does)
-        uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
-        if (plan.resort) NRSCHK(clean_tile_counts());
-        hipLaunchKernelGGL((k_iisph_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), velAdv.as<T4>(), forcesP.as<T4>(), N,
-                           nh, ni, plan.resort ? (const uint32_t *)hashCur : (const uint32_t *)nullptr,
-                           plan.resort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr, slabOn ? 1 : 0);
-        NRSCHK(ev_end());
-        if (plan.keys) keys_ready(nh, ni);
-        if (plan.resort) NRSCHK(queue_resort_split(N));
-        return NRS_OK;
+        return launch_last([&](uint32_t *nh, uint32_t *ni, const uint32_t *prevHash, uint32_t *tileMovers) {
+            hipLaunchKernelGGL((k_iisph_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), velAdv.as<T4>(), forcesP.as<T4>(), N,
+                               nh, ni, prevHash, tileMovers, slabOn ? 1 : 0);
+        });
     }
 
     // The list-driven chain is the reference-order chain only while every value a neighbour gathers is finite (IisphArrays::nonFinite).
@@ -1462,11 +1346,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int pcisph_configure(double eta, uint32_t minIters, double spacing, double delta) override
     {
         if (!pcisph()) return fail(NRS_E_STATE, "nrs_pcisph_configure on a context that is not PCISPH");
-        if (!(eta > 0.0) || !std::isfinite(eta)) return fail(NRS_E_INVALID, "max_density_error must be > 0");
-        if (minIters == 0) return fail(NRS_E_INVALID, "min_iters must be >= 1");
-        if (!(spacing >= 0.0) || !std::isfinite(spacing)) return fail(NRS_E_INVALID, "prototype_spacing must be >= 0 (0 = cbrt(m / rho0))");
-        if (!(delta >= 0.0) || !std::isfinite(delta)) return fail(NRS_E_INVALID, "delta must be >= 0 (0 = from the prototype)");
-        pciEta = eta; pciMinIters = minIters; pciSpacing = spacing; pciDeltaGiven = delta;
+        NRSCHK(pciS.set(eta, minIters, spacing, delta));
         pciDeltaValid = false;
         return NRS_OK;
     }
@@ -1475,14 +1355,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int pcisph_prepare()
     {
         if (pciDeltaValid) return NRS_OK;
-        if (pciDeltaGiven > 0.0) {
-            pciDelta = (R)pciDeltaGiven;
+        if (pciS.deltaGiven > 0.0) {
+            pciDelta = (R)pciS.deltaGiven;
             pciDeltaValid = true;
             return NRS_OK;
         }
         const double m = (double)PU.particleMass, rd = (double)PU.restDensity, dt = (double)PU.timestep;
         double o[5];
-        NRSCHK(prototype_sums(true, pciSpacing > 0.0 ? pciSpacing : std::cbrt(m / rd), "PCISPH", "pressure scale delta", o));
+        NRSCHK(prototype_sums(true, pciS.spacing > 0.0 ? pciS.spacing : std::cbrt(m / rd), "PCISPH", "pressure scale delta", o));
         const double q = dt * m / rd, beta = 2.0 * q * q;
         const double d = -1.0 / (beta * (-(o[0] * o[0] + o[1] * o[1] + o[2] * o[2]) - o[3]));
         if (!std::isfinite(d)) return fail(NRS_E_INVALID, "PCISPH: the prototype gives no finite pressure scale delta");
@@ -1493,10 +1373,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int set_surface_akinci(double gamma, double beta) override
     {
         if (!pcisph() && !pbf() && !dfsph()) return fail(NRS_E_STATE, "nrs_set_surface_akinci on a context that is not PCISPH, PBF or DFSPH");
-        if (!(gamma >= 0.0) || !std::isfinite(gamma)) return fail(NRS_E_INVALID, "Akinci gamma must be finite and >= 0 (0 = off)");
-        if (!(beta >= 0.0) || !std::isfinite(beta)) return fail(NRS_E_INVALID, "Akinci beta_adhesion must be finite and >= 0 (0 = off)");
+        AkinciSettings a;
+        NRSCHK(a.set(gamma, beta));
         if (gamma > 0.0) NRSCHK(akNormals.alloc(sizeof(T4) * cap));
-        akGamma = gamma; akBeta = beta;
+        akS = a;
         return NRS_OK;
     }
     // the advection launch with the Akinci model on (nrs_kernels_akinci.h); SURF_EFF: the context's fsurf term, off while gamma > 0
@@ -1520,30 +1400,21 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const GridView<R> G = grid_view();
         const HitBuffer hb = hit_buffer();
         *more = false;
-        // one neighbourhood scan per step (the wide lists of the IISPH chain): its hit lists drive the rest of the step
-        if (plan.walls) {
-            NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
-            NRSCHK(build_wall_list(N));
-            NRSCHK(ev_end());
-        }
-        NRSCHK(ev_begin(NRS_STAGE_DENSITY));
-        const WallList wv = wall_view();
-        if (!plan.lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
-        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hb, posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
+        NRSCHK(begin_density_scan<HAS_B>(NRS_STAGE_DENSITY));
         if (dfsph()) dfsph_factor<HAS_B>();
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_DENSITY) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_P_ADVECT));
         if (dfsph()) { // the divergence solve on the sorted velocities: the advection reads divergence-free ones
             dfDivIters = 0;
-            if (dfMinV) NRSCHK((dfsph_solve<HAS_B, false>(velB.as<T4>(), dfKvB.as<R>(), dfErrV.as<R>(), dfMinV, dfEtaV, &dfDivIters)));
-            dfDivN = dfMinV ? N : 0u;
+            if (dfS.minItersV) NRSCHK((dfsph_solve<HAS_B, false>(velB.as<T4>(), dfKvB.as<R>(), dfErrV.as<R>(), dfS.minItersV, dfS.etaV, &dfDivIters)));
+            dfDivN = dfS.minItersV ? N : 0u;
         }
         pciXs = 0;
         const PciArrays<R> A0 = pci_view(0, 0);
-        const bool cohesion = akGamma > 0.0;
-        if (cohesion || (HAS_B && akBeta > 0.0)) { // the Akinci model: the normals launch, then the advection launch with its walk
-            const AkinciView<R> K{cohesion ? akNormals.as<T4>() : (T4 *)nullptr, (R)akGamma, (R)akBeta};
+        const bool cohesion = akS.gamma > 0.0;
+        if (cohesion || (HAS_B && akS.beta > 0.0)) { // the Akinci model: the normals launch, then the advection launch with its walk
+            const AkinciView<R> K{cohesion ? akNormals.as<T4>() : (T4 *)nullptr, (R)akS.gamma, (R)akS.beta};
             if (cohesion) {
                 launch_pass<HAS_B>(AkinciNormalsPass<R, KSET>{P, dens.as<R>(), K.normals});
                 akNormalsValid = true;
@@ -1573,7 +1444,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         uint32_t l = 0;
         double err = -1.0;
         NRSCHK(solve_loop(
-            false, pciMinIters, maxIters ? maxIters : 50u, pciEta,
+            false, pciS.minIters, maxIters ? maxIters : 50u, pciS.eta,
             [&](uint32_t) {
                 const PciArrays<R> A = pci_view(pciXs, pciXs ^ 1);
                 launch_pass<HAS_B>(PciDensityPass<R, KSET>{P, A});
@@ -1607,11 +1478,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int pbf_configure(double eta, uint32_t minIters, double relaxation, double xsph) override
     {
         if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_configure on a context that is not PBF");
-        if (!(eta >= 0.0) || !std::isfinite(eta)) return fail(NRS_E_INVALID, "max_density_error must be >= 0 (0 = a fixed min_iters iterations)");
-        if (minIters == 0) return fail(NRS_E_INVALID, "min_iters must be >= 1");
-        if (!(relaxation > 0.0) || !std::isfinite(relaxation)) return fail(NRS_E_INVALID, "relaxation must be > 0");
-        if (!(xsph >= 0.0 && xsph <= 1.0)) return fail(NRS_E_INVALID, "xsph must be in [0, 1]");
-        pbfEta = eta; pbfMinIters = minIters; pbfRelax = relaxation; pbfXsph = xsph;
+        NRSCHK(pbfS.set(eta, minIters, relaxation, xsph));
         pbfEpsValid = false;
         return NRS_OK;
     }
@@ -1630,20 +1497,21 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int pbf_set_tensile(double k, double dq) override
     {
         if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_set_tensile on a context that is not PBF");
-        if (!(k >= 0.0) || !std::isfinite(k)) return fail(NRS_E_INVALID, "tensile k must be finite and >= 0 (0 = off)");
-        if (!(dq > 0.0 && dq < 1.0)) return fail(NRS_E_INVALID, "tensile dq must be in (0, 1)");
+        PbfSettings t = pbfS;
+        NRSCHK(t.set_tensile(k, dq));
         R wq;
         NRSCHK(pbf_eval_wq(dq, &wq));
-        pbfTensK = k; pbfTensDq = dq; pbfWq = wq;
+        pbfS = t; pbfWq = wq;
         pbfWqValid = true;
         return NRS_OK;
     }
     int pbf_set_vorticity(double epsV) override
     {
         if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_set_vorticity on a context that is not PBF");
-        if (!(epsV >= 0.0) || !std::isfinite(epsV)) return fail(NRS_E_INVALID, "vorticity eps_v must be finite and >= 0 (0 = off)");
+        PbfSettings t = pbfS;
+        NRSCHK(t.set_vorticity(epsV));
         if (epsV > 0.0) NRSCHK(pbfVort.alloc(sizeof(T4) * cap));
-        pbfVortEps = epsV;
+        pbfS = t;
         return NRS_OK;
     }
     // eps = relaxation * D_proto, D = |sum g|^2 + sum |g|^2 over the neighbours of a prototype particle on the cubic lattice of spacing
@@ -1683,14 +1551,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
     int pbf_prepare()
     {
-        if (pbfTensK > 0.0 && !pbfWqValid) {
-            NRSCHK(pbf_eval_wq(pbfTensDq, &pbfWq));
+        if (pbfS.tensK > 0.0 && !pbfWqValid) {
+            NRSCHK(pbf_eval_wq(pbfS.tensDq, &pbfWq));
             pbfWqValid = true;
         }
         if (pbfEpsValid) return NRS_OK;
         double d;
         NRSCHK(pbf_prototype_d("PBF", "eps", &d));
-        const double e = pbfRelax * d;
+        const double e = pbfS.relax * d;
         if (!(e > 0.0) || !std::isfinite(e)) return fail(NRS_E_INVALID, "PBF: the prototype gives no finite positive eps");
         pbfEps = (R)e;
         pbfEpsValid = true;
@@ -1706,14 +1574,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // Jacobi projection: with eta > 0 stop after the iteration l with l >= min_iters and max e <= eta, or at the cap, the max not
         // formed (nor read back) before min_iters; with eta = 0 exactly min_iters iterations and no read-back at all
         NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
-        const bool fixed = pbfEta == 0.0;
-        const uint32_t cap = fixed ? pbfMinIters : (maxIters ? maxIters : 50u);
-        const bool tens = pbfTensK > 0.0;
-        const PbfTensile<R> T{(R)pbfTensK, pbfWq};
+        const bool fixed = pbfS.eta == 0.0;
+        const uint32_t cap = fixed ? pbfS.minIters : (maxIters ? maxIters : 50u);
+        const bool tens = pbfS.tensK > 0.0;
+        const PbfTensile<R> T{(R)pbfS.tensK, pbfWq};
         uint32_t l = 0;
         double err = -1.0;
         NRSCHK(solve_loop(
-            fixed, pbfMinIters, cap, pbfEta,
+            fixed, pbfS.minIters, cap, pbfS.eta,
             [&](uint32_t) {
                 const PbfArrays<R> A = pbf_view(pciXs, pciXs ^ 1);
                 launch_pass<HAS_B>(PbfLambdaPass<R, KSET>{P, A});
@@ -1732,25 +1600,20 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // and k_pbf_integrate, which overwrites x, follows it.
         NRSCHK(ev_begin(NRS_STAGE_P_INTEGRATE));
         const T4 *xs = (const T4 *)pci_xs_current();
-        const bool xsph = pbfXsph > 0.0, vort = pbfVortEps > 0.0;
-        if (xsph) launch_pass<HAS_B>(PbfXsphPass<R, KSET>{{}, P, xs, velB.as<T4>(), (R)pbfXsph});
+        const bool xsph = pbfS.xsph > 0.0, vort = pbfS.vortEps > 0.0;
+        if (xsph) launch_pass<HAS_B>(PbfXsphPass<R, KSET>{{}, P, xs, velB.as<T4>(), (R)pbfS.xsph});
         // vorticity confinement: omega from u = (x* - x) / dt, then the confinement on the velocity XSPH left (or u); both read x_j
         if (vort) {
             T4 *om = pbfVort.as<T4>();
             const int given = xsph ? 1 : 0;
             launch_pass<HAS_B>(PbfVorticityPass<R, KSET>{{}, P, xs, om});
-            launch_pass<HAS_B>(PbfConfinePass<R, KSET>{{}, P, xs, (const T4 *)om, velB.as<T4>(), given, (R)pbfVortEps});
+            launch_pass<HAS_B>(PbfConfinePass<R, KSET>{{}, P, xs, (const T4 *)om, velB.as<T4>(), given, (R)pbfS.vortEps});
             pbfVortValid = true;
         }
-        uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
-        if (plan.resort) NRSCHK(clean_tile_counts());
-        hipLaunchKernelGGL((k_pbf_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), xs, (xsph || vort) ? 1 : 0, N, nh, ni,
-                           plan.resort ? (const uint32_t *)hashCur : (const uint32_t *)nullptr,
-                           plan.resort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr);
-        NRSCHK(ev_end());
-        if (plan.keys) keys_ready(nh, ni);
-        if (plan.resort) NRSCHK(queue_resort_split(N));
-        return NRS_OK;
+        return launch_last([&](uint32_t *nh, uint32_t *ni, const uint32_t *prevHash, uint32_t *tileMovers) {
+            hipLaunchKernelGGL((k_pbf_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), xs, (xsph || vort) ? 1 : 0, N, nh, ni,
+                               prevHash, tileMovers);
+        });
     }
 
     // ---- DFSPH step (nrs_kernels_dfsph.h; DESIGN.md "DFSPH") -------------------------------------------------------------------------
@@ -1766,11 +1629,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int dfsph_configure(double eta, uint32_t minIters, double etaV, uint32_t minItersV, int warm) override
     {
         if (!dfsph()) return fail(NRS_E_STATE, "nrs_dfsph_configure on a context that is not DFSPH");
-        if (!std::isfinite(eta) || eta < 0.0 || !std::isfinite(etaV) || etaV < 0.0)
-            return fail(NRS_E_INVALID, "DFSPH: max_density_error and max_divergence_error must be finite and >= 0");
-        if (minIters == 0) return fail(NRS_E_INVALID, "DFSPH: min_iters must be >= 1");
-        if (warm != 0 && warm != 1) return fail(NRS_E_INVALID, "DFSPH: warm_start must be 0 or 1");
-        dfEta = eta; dfMin = minIters; dfEtaV = etaV; dfMinV = minItersV; dfWarm = warm != 0;
+        NRSCHK(dfS.set(eta, minIters, etaV, minItersV, warm));
         return NRS_OK;
     }
     // thr = 1e-6 D_proto, D_proto = |sum g|^2 + sum |g|^2 of PBF's prototype (k_pbf_prototype); once per parameter change
@@ -1815,10 +1674,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const DfsphArrays<R> A = dfsph_view(u, K, err);
         const bool fixed = eta == 0.0;
         const uint32_t cap = fixed ? minIters : (maxIters ? maxIters : 100u);
-        if (dfWarm) dfsph_pair<HAS_B, DENS>(A, DFSPH_PHASE_WARM);
+        if (dfS.warm) dfsph_pair<HAS_B, DENS>(A, DFSPH_PHASE_WARM);
         double avg = 0.0;
         return solve_loop(
-            fixed, minIters, cap, eta, [&](uint32_t l) { dfsph_pair<HAS_B, DENS>(A, (l || dfWarm) ? DFSPH_PHASE_MORE : DFSPH_PHASE_FIRST); },
+            fixed, minIters, cap, eta, [&](uint32_t l) { dfsph_pair<HAS_B, DENS>(A, (l || dfS.warm) ? DFSPH_PHASE_MORE : DFSPH_PHASE_FIRST); },
             [&](double *e) {
                 double acc = 0.0;
                 NRSCHK(reduce_sum(err, N, &acc));
@@ -1835,7 +1694,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!more) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
         uint32_t l = 0;
-        NRSCHK((dfsph_solve<HAS_B, true>(velAdv.as<T4>(), presB.as<R>(), pciErr.as<R>(), dfMin, dfEta, &l)));
+        NRSCHK((dfsph_solve<HAS_B, true>(velAdv.as<T4>(), presB.as<R>(), pciErr.as<R>(), dfS.minIters, dfS.eta, &l)));
         lastIters = l;
         dfDenN = N;
         NRSCHK(ev_end());
@@ -1896,7 +1755,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // IISPH: every solver iteration consumes two cells of halo validity, the predict stages three and the pressure force one
         // (DESIGN.md §5): 2 iterations — the reference's minimum — need 8 cells
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
-        if (nBodies) return fail(NRS_E_INVALID, "contexts with boundary bodies have no slab decomposition");
+        if (bodies.n) return fail(NRS_E_INVALID, "contexts with boundary bodies have no slab decomposition");
         if (pcisph()) return fail(NRS_E_INVALID, "PCISPH contexts have no slab decomposition");
         if (pbf()) return fail(NRS_E_INVALID, "PBF contexts have no slab decomposition");
         if (dfsph()) return fail(NRS_E_INVALID, "DFSPH contexts have no slab decomposition");
@@ -1958,7 +1817,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                                posA.as<T4>(), (uint32_t)n, lo0, nbins, bins.as<uint32_t>());
         HIPCHK(hipMemcpyAsync(out, bins.p, (size_t)nbins * 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        bins.release();
         return NRS_OK;
     }
 
@@ -1980,8 +1838,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ghostPos.alloc(sizeof(T4) * mcap));
         NRSCHK(ghostVel.alloc(sizeof(T4) * mcap));
         bool inplace = false;
-        if (!slabHostTotals) HIPCHK(hipHostMalloc((void **)&slabHostTotals, 128, hipHostMallocDefault));
-        if (!packEvent) HIPCHK(hipEventCreateWithFlags(&packEvent, hipEventDisableTiming)); // (contexts without re-sort buffers have none yet)
+        if (!slabHostTotals) HIPCHK(hipHostMalloc((void **)&slabHostTotals.p, 128, hipHostMallocDefault));
+        if (!packEvent) HIPCHK(hipEventCreateWithFlags(&packEvent.e, hipEventDisableTiming)); // (contexts without re-sort buffers have none yet)
         if (N) {
             const bool fusedClass = classifiedValid && slotOrderValid && classifiedN == N && rsMovers.p && hashCur && hashNext &&
                                     hashNext != hashCur;
@@ -2151,7 +2009,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // ONE host synchronisation for the exchange: the headers of the received messages (how many migrants, how many halo copies)
         // are copied to page-locked memory behind the receives, and the same wait covers the stream totals of the pack (finish_pack)
         uint32_t hL[4] = {0, 0, 0, 0}, hR[4] = {0, 0, 0, 0};
-        if (!slabHostTotals) HIPCHK(hipHostMalloc((void **)&slabHostTotals, 128, hipHostMallocDefault));
+        if (!slabHostTotals) HIPCHK(hipHostMalloc((void **)&slabHostTotals.p, 128, hipHostMallocDefault));
         if (recvL) HIPCHK(hipMemcpyAsync(slabHostTotals + 16, recvL, 16, hipMemcpyDeviceToHost, stream));
         if (recvR) HIPCHK(hipMemcpyAsync(slabHostTotals + 20, recvR, 16, hipMemcpyDeviceToHost, stream));
         if (recvL || recvR) HIPCHK(hipStreamSynchronize(stream));
@@ -2334,7 +2192,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(end_of_step());
         }
         HIPCHK(hipGetLastError());
-        if (evUsed > 8192) NRSCHK(ev_collect()); // bound the pool of pending event pairs
+        if (timer.used > 8192) NRSCHK(timer.collect(stream)); // bound the pool of pending event pairs
         return NRS_OK;
     }
     // the device-side guard (GridView::err) fired since the last check: report it, once
@@ -2354,89 +2212,18 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return check_device_error();
     }
     // ---- asynchronous snapshots for a viewer (include/nereus_hip.h: nrs_snapshot_*) ---------------------------
-    struct Snap {
-        DevBuf dPos, dVel;
-        void *hPos = nullptr, *hVel = nullptr;
-        size_t hBytes = 0;
-        hipEvent_t staged = nullptr, done = nullptr;
-        uint64_t n = 0, step = 0;
-        bool withVel = false, pending = false;
-    };
-    Snap snaps[2];
-    int snapHead = 0, snapTail = 0; // next slot to fill / oldest pending slot
-    hipStream_t copyStream = nullptr;
+    SnapshotRing snapshots;
     uint64_t stepsDone = 0;
-    void snapshot_release()
-    {
-        for (Snap &sn : snaps) {
-            if (sn.pending && sn.done) (void)hipEventSynchronize(sn.done);
-            sn.dPos.release(); sn.dVel.release();
-            if (sn.hPos) (void)hipHostFree(sn.hPos);
-            if (sn.hVel) (void)hipHostFree(sn.hVel);
-            if (sn.staged) (void)hipEventDestroy(sn.staged);
-            if (sn.done) (void)hipEventDestroy(sn.done);
-            sn = Snap();
-        }
-        if (copyStream) (void)hipStreamDestroy(copyStream);
-        copyStream = nullptr;
-    }
     int snapshot_begin(int withVel) override
     {
         NRSCHK(validate("nrs_snapshot_begin"));
         if (midStep) return fail(NRS_E_STATE, "state is mid-update");
         NRSCHK(compact_holes());
-        if (!copyStream) HIPCHK(hipStreamCreateWithFlags(&copyStream, hipStreamNonBlocking));
-        Snap &sn = snaps[snapHead];
-        if (sn.pending) { // both slots in flight: the oldest is this one
-            HIPCHK(hipEventSynchronize(sn.done));
-            sn.pending = false;
-            snapTail = (snapHead + 1) % 2;
-        }
-        const size_t bytes = sizeof(T4) * (size_t)cap;
-        if (!sn.staged) {
-            HIPCHK(hipEventCreateWithFlags(&sn.staged, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&sn.done, hipEventDisableTiming));
-        }
-        NRSCHK(sn.dPos.alloc(bytes));
-        if (!sn.hPos) HIPCHK(hipHostMalloc(&sn.hPos, bytes, hipHostMallocDefault));
-        if (withVel) {
-            NRSCHK(sn.dVel.alloc(bytes));
-            if (!sn.hVel) HIPCHK(hipHostMalloc(&sn.hVel, bytes, hipHostMallocDefault));
-        }
-        const size_t live = sizeof(T4) * (size_t)n;
-        if (live) {
-            HIPCHK(hipMemcpyAsync(sn.dPos.p, posA.p, live, hipMemcpyDeviceToDevice, stream));
-            if (withVel) HIPCHK(hipMemcpyAsync(sn.dVel.p, velA.p, live, hipMemcpyDeviceToDevice, stream));
-        }
-        HIPCHK(hipEventRecord(sn.staged, stream));
-        HIPCHK(hipStreamWaitEvent(copyStream, sn.staged, 0));
-        if (live) {
-            HIPCHK(hipMemcpyAsync(sn.hPos, sn.dPos.p, live, hipMemcpyDeviceToHost, copyStream));
-            if (withVel) HIPCHK(hipMemcpyAsync(sn.hVel, sn.dVel.p, live, hipMemcpyDeviceToHost, copyStream));
-        }
-        HIPCHK(hipEventRecord(sn.done, copyStream));
-        sn.n = n; sn.step = stepsDone; sn.withVel = withVel != 0; sn.pending = true;
-        snapHead = (snapHead + 1) % 2;
-        return NRS_OK;
+        return snapshots.begin(posA.p, withVel ? velA.p : nullptr, sizeof(T4), cap, n, stepsDone, stream);
     }
     int snapshot_wait(int block, const void **pos4, const void **vel4, uint64_t *np, uint64_t *step) override
     {
-        Snap &sn = snaps[snapTail];
-        if (!sn.pending) return fail(NRS_E_STATE, "no snapshot in flight (nrs_snapshot_begin first)");
-        if (block) {
-            HIPCHK(hipEventSynchronize(sn.done));
-        } else {
-            const hipError_t e = hipEventQuery(sn.done);
-            if (e == hipErrorNotReady) return NRS_E_NOTREADY;
-            HIPCHK(e);
-        }
-        sn.pending = false;
-        snapTail = (snapTail + 1) % 2;
-        if (pos4) *pos4 = sn.hPos;
-        if (vel4) *vel4 = sn.withVel ? sn.hVel : nullptr;
-        if (np) *np = sn.n;
-        if (step) *step = sn.step;
-        return NRS_OK;
+        return snapshots.wait(block, pos4, vel4, np, step);
     }
 
     int download(void *pos4, void *vel4, void *pres) override
@@ -2495,7 +2282,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (!akNormalsValid) return fail(NRS_E_STATE, "no step with Akinci surface tension (gamma > 0) yet");
             p = akNormals.p; sz = v; break;
         case NRS_ARR_B_BODY:
-            if (!nBodies) return fail(NRS_E_STATE, "no boundary body assignment (nrs_set_boundary_bodies)");
+            if (!bodies.n) return fail(NRS_E_STATE, "no boundary body assignment (nrs_set_boundary_bodies)");
             *dptr = bdBodySorted.p; *bytes = 4 * nb; // (not a solver array: none of the per-solver refusals below apply)
             return NRS_OK;
         case NRS_ARR_DFSPH_ALPHA:

@@ -43,18 +43,16 @@ template <typename R> static int eval_smoothing(int which, uint64_t n, const voi
 {
     DevBuf dr, ds, dout;
     const size_t bytes = sizeof(R) * 3 * n;
-    auto done = [&](int rc) { dr.release(); ds.release(); dout.release(); return rc; };
-    int rc = dr.alloc(bytes); // (every way out goes through done(): a failed second allocation must not leak the first)
-    if (rc == NRS_OK) rc = dout.alloc(bytes);
-    if (rc == NRS_OK && s3) rc = ds.alloc(bytes);
-    if (rc != NRS_OK) return done(rc);
-    if (hipMemcpy(dr.p, r3, bytes, hipMemcpyHostToDevice) != hipSuccess) return done(fail(NRS_E_HIP, "hipMemcpy"));
-    if (s3 && hipMemcpy(ds.p, s3, bytes, hipMemcpyHostToDevice) != hipSuccess) return done(fail(NRS_E_HIP, "hipMemcpy"));
+    NRSCHK(dr.alloc(bytes));
+    NRSCHK(dout.alloc(bytes));
+    if (s3) NRSCHK(ds.alloc(bytes));
+    if (hipMemcpy(dr.p, r3, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(NRS_E_HIP, "hipMemcpy");
+    if (s3 && hipMemcpy(ds.p, s3, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(NRS_E_HIP, "hipMemcpy");
     hipLaunchKernelGGL((k_eval_smoothing<R>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, nullptr, which, (uint32_t)n, dr.as<R>(),
                        s3 ? ds.as<R>() : (const R *)nullptr, (R)h, (R)c0, (R)c1, dout.as<R>());
-    if (hipDeviceSynchronize() != hipSuccess) return done(fail(NRS_E_HIP, "k_eval_smoothing failed"));
-    if (hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(fail(NRS_E_HIP, "hipMemcpy"));
-    return done(NRS_OK);
+    if (hipDeviceSynchronize() != hipSuccess) return fail(NRS_E_HIP, "k_eval_smoothing failed");
+    if (hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(NRS_E_HIP, "hipMemcpy");
+    return NRS_OK;
 }
 
 } // namespace nrs

@@ -39,7 +39,9 @@ constexpr bool SURF = USE_SURFACE_TENSION != 0;
 Params<SR> g_params;          // the reference's `__constant__ SphSimParams sph_params` (sph_kernel_impl.cuh:66)
 bool g_paramsSet = false;
 uint32_t g_lastIters = 0;
-DevBuf g_tmpKeys, g_tmpVals, g_sortTmp, g_sB, g_inv, g_partial, g_out;
+// scratch that lives as long as the process: never destroyed, so that no hipFree runs while the process exits (die() calls exit())
+DevBuf &g_tmpKeys = *new DevBuf, &g_tmpVals = *new DevBuf, &g_sortTmp = *new DevBuf, &g_sB = *new DevBuf, &g_inv = *new DevBuf,
+       &g_partial = *new DevBuf, &g_out = *new DevBuf;
 
 [[noreturn]] void die(const char *what, hipError_t e)
 {

@@ -1,7 +1,7 @@
 """Shared scene builders and comparison helpers for the parity tests."""
 import numpy as np
 
-from nereus_amd import scene
+from nereus_amd import capi, scene
 from tests.oracle_lib import IISPH, SESPH, Oracle
 
 
@@ -71,3 +71,69 @@ def close_masked(got, want, tol, what=""):
     print("%s: %.3g (bar %.0e, %d non-finite)" % (what, e, tol, int((~fin).sum())))
     assert e <= tol, (what, e, tol)
     return e
+
+
+# ---- the plate scene of the kinematic-body tests -------------------------------------------------------------------------------
+SOLVERS = [capi.SESPH, capi.IISPH, capi.PCISPH, capi.PBF, capi.DFSPH]
+SOLVER_NAMES = {capi.SESPH: "sesph", capi.IISPH: "iisph", capi.PCISPH: "pcisph", capi.PBF: "pbf", capi.DFSPH: "dfsph"}
+PLATE_V = (9.0, 0.0, 0.0)            # two cell faces (2 h = 0.0914) in 11 steps of 1 ms
+DOT_V, BAR_W = (0.5, 0.3, 0.0), (0.0, 0.0, 30.0)
+_plate_cache = {}
+
+
+def plate_scene(double=False, kernel_set=capi.MULLER, plate_gap=None, squeeze=1.0):
+    """The scene of tests/test_bodies_gpu.py: small_dam_break moved three cells from the wall x = 0 inside its boundary box (body 0), a
+    plate (body 1), a single particle (body 2) and a bar (body 3).  (params, pos, vel, bi, vbi, body_of, parts); plate_gap: distance
+    of the plate from the fluid's first layer (default: the plate starts one spacing in front of the wall x = 0); squeeze < 1 contracts the fluid column towards its lower corner on the plate's
+    side (the resting lattice is below rest density, and DFSPH's density solve would have nothing to do)"""
+    key = (double, kernel_set, plate_gap, squeeze)
+    if key in _plate_cache:
+        return _plate_cache[key]
+    real = np.float64 if double else np.float32
+    p, sc = small_dam_break(double=double, kernel_set=kernel_set)
+    h = float(p["interactionRadius"][0])
+    d = h - 0.005
+    pos = sc["pos"].copy()
+    pos[:, 0] = (pos[:, 0].astype(np.float64) + 3.0 * h).astype(real)
+    if squeeze != 1.0:
+        lo = pos[:, :3].astype(np.float64).min(axis=0)
+        pos[:, :3] = (lo + (pos[:, :3].astype(np.float64) - lo) * squeeze).astype(real)
+    x0 = d if plate_gap is None else float(pos[:, 0].min()) - plate_gap
+
+    def pts(a):
+        o = np.ones((len(a), 4), real)
+        o[:, :3] = np.asarray(a, np.float64).astype(real)
+        return o
+
+    jy, jz = np.meshgrid(np.arange(15), np.arange(11), indexing="ij")
+    plate = pts(np.stack([np.full(jy.size, x0), (jy.ravel() + 1) * d, (jz.ravel() + 1) * d], axis=1))
+    dot = pts([[0.9, 0.33, 0.21]])
+    bar = pts(np.stack([0.7 + np.arange(7) * d, np.full(7, 0.4), np.full(7, 0.23)], axis=1))
+    parts = [sc["bi"].astype(real), plate, dot, bar]
+    bi = np.concatenate(parts)
+    vbi = np.concatenate([sc["vbi"].astype(real)] + [capi.boundary_volumes(a, h, double=double) for a in parts[1:]])
+    body_of = np.concatenate([np.full(len(a), k, np.uint32) for k, a in enumerate(parts)])
+    assert len(bi) % 256 != 0 and len(bi) > 256
+    _plate_cache[key] = (p, pos, sc["vel"].copy(), bi, vbi, body_of, parts)
+    return _plate_cache[key]
+
+
+def plate_solver(sc, solver, bodies=True, moving=True, plate_v=PLATE_V, **kw):
+    """a Solver on plate_scene() with fixed iteration counts; bodies assigned, and moving, unless told otherwise"""
+    p, pos, vel, bi, vbi, body_of, _ = sc
+    s = capi.Solver(p, len(pos), solver=solver, **kw)
+    s.set_particles(pos, vel)
+    s.set_boundaries(bi, vbi, update_grid=True)
+    if solver == capi.DFSPH:
+        s.dfsph_configure(0.0, 3, 0.0, 3, 1)
+    if solver == capi.PBF:
+        s.pbf_configure(0.0, 3, 0.01, 0.0)
+    if solver in (capi.PCISPH, capi.IISPH):
+        s.set_max_iterations(4)
+    if bodies:
+        s.set_boundary_bodies(body_of, 4)
+        if moving:
+            s.set_body_velocity(1, plate_v)
+            s.set_body_velocity(2, DOT_V)
+            s.set_body_velocity(3, (0, 0, 0), BAR_W)
+    return s
