@@ -428,12 +428,16 @@ int nrs_resort_stats(nrs_ctx *ctx, uint64_t *steps, uint64_t *fallbacks);
  *   NRS_STAT_DFSPH_DENSITY_AVG           DFSPH: avg_i e_i of the last density iteration
  *   NRS_STAT_DFSPH_DIVERGENCE_AVG        DFSPH: avg_i e_i of the last divergence iteration (NRS_E_STATE when the solve is off)
  *   NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS DFSPH: divergence iterations of the last step (nrs_last_iterations gives the density solve's)
+ *   NRS_STAT_SLAB_PARTITION kind of the last nrs_slab_pack: 0 = compacting (the owned particles were moved to the front), 1 = in
+ *                           place (they kept their slots), 2 = in place from the classification the last step's force kernel left;
+ *                           NRS_E_STATE before the first pack.  Read-only, does not touch the device.  Came after nrs_version() 0.3
+ *                           without a version change.
  * The DFSPH values are formed on request from the e_i the solve left.
  * The HIT_* / UNSTAGED values need the shared hit lists of the production kernels (NRS_E_STATE otherwise); the PCISPH / PBF / DFSPH
  * values a context of that kind that has completed a solve. */
 enum { NRS_STAT_MOVERS = 0, NRS_STAT_HIT_OVERFLOW = 1, NRS_STAT_HIT_MEAN = 2, NRS_STAT_HIT_MAX = 3, NRS_STAT_UNSTAGED = 4,
        NRS_STAT_DENSITY_ERROR = 5, NRS_STAT_PCISPH_DELTA = 6, NRS_STAT_PBF_EPSILON = 7, NRS_STAT_DFSPH_DENSITY_AVG = 8,
-       NRS_STAT_DFSPH_DIVERGENCE_AVG = 9, NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS = 10 };
+       NRS_STAT_DFSPH_DIVERGENCE_AVG = 9, NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS = 10, NRS_STAT_SLAB_PARTITION = 11 };
 int nrs_get_stat(nrs_ctx *ctx, int which, double *out);
 
 /* Akinci boundary volumes on the device (no context needed): vbi[i] = 1 / sum_k W_poly6(|x_i - x_k|, h) over the boundary

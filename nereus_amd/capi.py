@@ -29,6 +29,7 @@ E_NOTREADY = -6
 STAT_MOVERS, STAT_HIT_OVERFLOW, STAT_HIT_MEAN, STAT_HIT_MAX, STAT_UNSTAGED = 0, 1, 2, 3, 4
 STAT_DENSITY_ERROR, STAT_PCISPH_DELTA, STAT_PBF_EPSILON = 5, 6, 7
 STAT_DFSPH_DENSITY_AVG, STAT_DFSPH_DIVERGENCE_AVG, STAT_DFSPH_DIVERGENCE_ITERATIONS = 8, 9, 10
+STAT_SLAB_PARTITION = 11   # kind of the last slab_pack: 0 compacting, 1 in place, 2 in place from the force kernel's classification
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6

@@ -1943,6 +1943,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         pendInplace = inplace;
         pendN = N;
         pendCap = mcap;
+        lastPartition = pendFused ? 2 : (inplace ? 1 : 0);
         if (counts) { // the caller wants the counts now: that is the synchronisation it asked for
             NRSCHK(finish_pack());
             std::memcpy(counts, lastCounts, ST_COUNT * sizeof(uint32_t));
@@ -1954,6 +1955,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint32_t pendN = 0;
     uint64_t pendCap = 0;
     uint32_t lastCounts[ST_COUNT] = {0, 0, 0, 0, 0, 0};
+    int lastPartition = -1; // NRS_STAT_SLAB_PARTITION: 0 compacting, 1 in place, 2 in place from the force kernel's classification
     int finish_pack()
     {
         if (!packPending) return NRS_OK;
@@ -2097,6 +2099,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int get_stat(int which, double *out) override
     {
         if (which == NRS_STAT_MOVERS) { *out = lastMovers; return NRS_OK; }
+        if (which == NRS_STAT_SLAB_PARTITION) {
+            if (lastPartition < 0) return fail(NRS_E_STATE, "no nrs_slab_pack yet");
+            *out = lastPartition;
+            return NRS_OK;
+        }
         if (pbf() && (which == NRS_STAT_DENSITY_ERROR || which == NRS_STAT_PBF_EPSILON)) {
             if (pbfErrPending) { // (fixed-count mode: pciErr still holds the e_i of the last iteration)
                 NRSCHK(max_of<false>(pciErr.p, pbfErrPending, &pciLastErr));

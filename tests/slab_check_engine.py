@@ -1,9 +1,11 @@
 """A checker engine for nereus_amd.slab.SlabDriver: same interface as HipSlabEngine, numpy partitioning and
-the CPU oracle for the physics.  Test infrastructure only (lets the exchange protocol run under gloo on CPU)."""
+the CPU oracle for the physics.  Test infrastructure only (lets the exchange protocol run under gloo on CPU).  The partition is
+tests/slab_model.py, the statement the device's streams are compared with bit for bit (tests/test_slab_partition_gpu.py)."""
 import numpy as np
 import torch
 
 from nereus_amd.slab import HALO_CELLS, cell_of
+from tests import slab_model
 from tests.oracle_lib import IISPH, SESPH, STOP_I_SOLVE, Oracle
 
 
@@ -40,51 +42,33 @@ class OracleSlabEngine:
         return hdr, pos, vel
 
     def pack(self, send_left, send_right):
-        ox, cs = float(self.p["worldOrigin"][0][0]), float(self.p["cellSize"][0][0])
+        """the partition itself is tests/slab_model.py (shared with the device tests); this engine only moves its result into the
+        message tensors"""
         if self.iisph:  # the warm-start pressure travels in vel.w, as in the library (k_pressure_to_velw)
             self.vel = self.vel.copy()
             self.vel[:, 3] = self.pres
-        live = self.pos[:, 3] == 1.0
-        pos, vel = self.pos[live], self.vel[live]
-        cx = cell_of(pos[:, 0], ox, cs)
-        stay = (cx >= self.lo) & (cx < self.hi)
-        mig_l, mig_r = cx < self.lo, cx >= self.hi
-        halo_l = stay & (cx < self.lo + self.halo)
-        halo_r = stay & (cx >= self.hi - self.halo)
-        ghost = (mig_l & (cx >= self.lo - self.halo)) | (mig_r & (cx < self.hi + self.halo))
-        def tag(a):
-            a = a.copy()
-            a[:, 3] = 2.0
-            return a
-        for buf, mig, hal in ((send_left, mig_l, halo_l), (send_right, mig_r, halo_r)):
+        part = slab_model.partition(self.p, self.lo, self.hi, self.halo, self.pos, self.vel, np.float32, cap=self.cap,
+                                    left=send_left is not None, right=send_right is not None)
+        c = part.counts
+        for buf, image, nm, nh in ((send_left, part.msg_left, c[1], c[2]), (send_right, part.msg_right, c[3], c[4])):
             if buf is None:
-                assert not mig.any(), "particles left through an end of the slab chain"
+                assert nm == 0, "particles left through an end of the slab chain"
                 continue
-            hdr, bp, bv = self._views(buf)
-            nm, nh = int(mig.sum()), int(hal.sum())
             assert nm + nh <= self.cap
-            hdr[:] = (nm, nh, 0, 0)
-            bp[:nm], bv[:nm] = pos[mig], vel[mig]
-            bp[nm:nm + nh], bv[nm:nm + nh] = tag(pos[hal]), vel[hal]
-        self._ghost = (tag(pos[ghost]), vel[ghost])
-        self.pos, self.vel = pos[stay], vel[stay]
+            hdr, bp, bv = self._views(buf)
+            ih, ip, iv = slab_model.views(image, self.cap, np.float32)
+            hdr[:] = ih
+            bp[:nm + nh], bv[:nm + nh] = ip[:nm + nh], iv[:nm + nh]
+        assert c[5] <= self.cap   # (ghosts are migrants, and the migrants fit: the model never had to cut the ghost arrays short)
+        self._ghost = (part.ghost_pos, part.ghost_vel)
+        self.pos, self.vel = part.stay_pos, part.stay_vel
         self._n_owned = len(self.pos)
-        return [int(stay.sum()), int(mig_l.sum()), int(halo_l.sum()), int(mig_r.sum()), int(halo_r.sum()), int(ghost.sum())]
+        return list(c)
 
     def unpack(self, recv_left, recv_right):
-        mig_p, mig_v, hal_p, hal_v = [], [], [], []
-        for buf in (recv_left, recv_right):
-            if buf is None:
-                continue
-            hdr, bp, bv = self._views(buf)
-            nm, nh = int(hdr[0]), int(hdr[1])
-            mig_p.append(bp[:nm].copy()); mig_v.append(bv[:nm].copy())
-            hal_p.append(bp[nm:nm + nh].copy()); hal_v.append(bv[nm:nm + nh].copy())
-        owned_p = np.concatenate([self.pos] + mig_p)
-        owned_v = np.concatenate([self.vel] + mig_v)
-        self._n_owned = len(owned_p)
-        self.pos = np.concatenate([owned_p, self._ghost[0]] + hal_p)
-        self.vel = np.concatenate([owned_v, self._ghost[1]] + hal_v)
+        img = [None if b is None else b.numpy() for b in (recv_left, recv_right)]
+        self.pos, self.vel, self._n_owned = slab_model.unpack_arrays(self.pos, self.vel, self._ghost[0], self._ghost[1], img[0], img[1],
+                                                                     self.cap, np.float32)
         if self.iisph:
             self.pres = self.vel[:, 3].copy()
             self.vel[:, 3] = 0.0

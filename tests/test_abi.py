@@ -22,6 +22,16 @@ def test_header_and_binding_agree():
     assert _declared_symbols() == sorted(capi.EXPORTS)
 
 
+def test_slab_partition_stat_is_declared_and_bound():
+    """NRS_STAT_SLAB_PARTITION (the kind of the last nrs_slab_pack) has the same number in the header and in the binding, and is the
+    newest entry of the enum: it came after nrs_version() 0.3 without a version change, so existing numbers must not move."""
+    text = open(os.path.join(ROOT, "include", "nereus_hip.h")).read()
+    stats = dict((k, int(v)) for k, v in re.findall(r"\b(NRS_STAT_[A-Z_]+) = (\d+)", text))
+    assert stats["NRS_STAT_SLAB_PARTITION"] == capi.STAT_SLAB_PARTITION == 11 == max(stats.values())
+    assert stats["NRS_STAT_MOVERS"] == capi.STAT_MOVERS == 0 and stats["NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS"] == 10
+    assert sorted(stats.values()) == list(range(12))
+
+
 def test_library_exports_every_declared_symbol():
     lib = capi.load_library()
     for name in _declared_symbols():

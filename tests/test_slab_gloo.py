@@ -6,6 +6,8 @@ partition/pack/unpack + HIP step), two ranks sharing the one GPU of the test box
 memory because gloo cannot carry device tensors (on a multi-GPU node the backend is nccl = RCCL over xGMI).
 Both are compared with the single-domain oracle on the union scene, particle by particle through an id carried
 in vel.w (tolerance: the slab path orders in-cell sums differently).
+The checker engine's partition is tests/slab_model.py, the numpy statement that tests/test_slab_partition_gpu.py compares the device's
+streams with bit for bit: the protocol tests and the device tests share one statement of nrs_slab_pack / nrs_slab_unpack.
 """
 import os
 import socket
