@@ -9,14 +9,16 @@
 // Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the array-state machine, the step plan, the
 // sort stage, the solver tails, the slab code.  Host bookkeeping that depends on none of them lives in plain structs the context
 // holds as members: the body poses (nrs_host_bodies.h), the stage timer (nrs_host_profile.h), the snapshot ring
-// (nrs_host_snapshot.h), the solver settings and their validation (nrs_host_settings.h).  Every buffer, pinned landing and event
-// frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
+// (nrs_host_snapshot.h), the solver settings and their validation (nrs_host_settings.h), the decisions of the slab exchange — window,
+// partition form, stream totals, unpack offsets — (nrs_host_slab.h).  Every buffer, pinned landing and event frees itself (DevBuf,
+// PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
 #pragma once
 #include <sched.h>
 #include "nrs_ctx_base.h"
 #include "nrs_host_bodies.h"
 #include "nrs_host_profile.h"
 #include "nrs_host_settings.h"
+#include "nrs_host_slab.h"
 #include "nrs_host_snapshot.h"
 #include <rocprim/rocprim.hpp>
 
@@ -68,13 +70,9 @@ static inline hipError_t sort_movers(void *tmp, size_t &bytes, rocprim::double_b
     return rocprim::radix_sort_keys<MoverSortCfg<8>>(tmp, bytes, k, m, 32u, 32u + bits, stream);
 }
 
-static uint32_t next_pow2(uint32_t v) // sph/sph.cpp:300-311
-{
-    v--;
-    v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16;
-    v++;
-    return v;
-}
+static_assert(SLT_STAY == ST_STAY && SLT_MIG_L == ST_MIG_L && SLT_HALO_L == ST_HALO_L && SLT_MIG_R == ST_MIG_R && SLT_HALO_R == ST_HALO_R &&
+              SLT_GHOST == ST_GHOST && SLT_COUNT == ST_COUNT && SLT_CHANGED == ST_CHANGED && SLT_TOTALS == ST_TOTALS,
+              "nrs_host_slab.h numbers the stream totals as nrs_kernels_slab.h does");
 
 template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     typedef typename Vec4T<R>::type T4;
@@ -84,16 +82,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // width) stop growing with the number of ranks.  Cell coordinates stay global (calcGridPos is unchanged), only the hash
     // rebases x: the sort order, and with it every per-particle result, is the one of the global grid.
     Params<R> PU, P;
-    int winBase = 0;
-    uint32_t winW = 0; // 0: no window
+    SlabHost sx; // the window, the last pack and its totals (nrs_host_slab.h)
     void derive_kernel_params()
     {
         P = PU;
         P.numBodies = 0;
-        if (winW && winW < PU.gridSize[0]) {
-            P.numBodies = (uint32_t)winBase;
-            P.gridSize[0] = winW;
-            P.numCells = winW * PU.gridSize[1] * PU.gridSize[2];
+        if (sx.winW && sx.winW < PU.gridSize[0]) {
+            P.numBodies = (uint32_t)sx.winBase;
+            P.gridSize[0] = sx.winW;
+            P.numCells = sx.winW * PU.gridSize[1] * PU.gridSize[2];
         }
         // compact scan candidates (nrs_math.h): quanta per metre, threshold of the superset test, and whether the geometry allows
         // it at all (a pair inside the interaction radius must be less than two cells apart on every axis)
@@ -206,20 +203,32 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     SlabCfg slab = {INT_MIN / 2, INT_MAX / 2, 2};
     DevBuf ghostPos, ghostVel, slabCounts, slabTotals;
     uint64_t nOwned = 0;
-    uint32_t ghostCount = 0;
     bool cellsClean = false; // cellStart is all-EMPTY
-    bool packedHashValid = false;
-    bool packResort = false; // this pack compacted the previous sorted keys next to the new ones
-    uint32_t packChanged = 0; // ... and counted the owned particles that stay but changed cell
-    bool packInplace = false; // the last pack left the owned particles where they were (holesPending until the next reorder)
+    bool packedHashValid = false; // packKeys hold the keys of the particles that stayed, for the current grid
     // fused classification: the force kernel of the last step already wrote stream flags / counts / dead marks for these cuts
     DevBuf slabFlags;
     bool classifiedValid = false;
     uint32_t classifiedN = 0;
     // slab runs, in-place partition: the owned particles are not compacted; dead slots carry the key 0xffffffff
     DevBuf rsTileDead, rsTileDeadOffset, rsGroupDeadTotal, rsGroupDeadPrefix;
+    // page-locked landing place (HT_WORDS words) of what the host reads in an exchange, and the event behind the pack's part of it
+    enum { HT_TOTALS = 0,              // the ST_TOTALS stream totals of the pack
+           HT_SCAN = 8,                // pre-classified form: rsScalars, of which ...
+           HT_SCAN_CHANGED = HT_SCAN + 1, HT_SCAN_DEAD = HT_SCAN + 2, // ... the cell changers and the dead slots (scan_movers(), scan_dead())
+           HT_HEADER_L = 16, HT_HEADER_R = 20, // the 16-byte headers of the received messages
+           HT_WORDS = 32 };
+    PinnedBuf<uint32_t> slabHostTotals;
     Event packEvent;
-    PinnedBuf<uint32_t> slabHostTotals; // page-locked landing place of the stream totals
+    int ensure_host_totals()
+    {
+        if (!slabHostTotals) HIPCHK(hipHostMalloc((void **)&slabHostTotals.p, HT_WORDS * 4, hipHostMallocDefault));
+        return NRS_OK;
+    }
+    int ensure_pack_event()
+    {
+        if (!packEvent) HIPCHK(hipEventCreateWithFlags(&packEvent.e, hipEventDisableTiming));
+        return NRS_OK;
+    }
     bool holesPending = false; // posA/velA[0, physN) contain dead slots (keys in hashNext tell which); n counts live ones
     uint32_t physN = 0;        // physical extent of the arrays while holesPending
     bool rsTilesDirty = false; // rsTileMovers holds counts no scan has consumed
@@ -260,7 +269,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (classifiedValid && (!slotOrderValid || !hashCur || !hashNext)) return AS_INVALID;
         if (slotOrderValid && (!hashCur || !hashNext)) return AS_INVALID;
         if (holesPending) {
-            if (!(packInplace && hashReady && rsPending && rsCountKnown) || physN < n || physN > cap || rsKnownCount > physN) return AS_INVALID;
+            if (!(sx.inplace() && hashReady && rsPending && rsCountKnown) || physN < n || physN > cap || rsKnownCount > physN) return AS_INVALID;
             return AS_HOLES;
         }
         if (rsCountKnown && rsKnownCount > n) return AS_INVALID;
@@ -287,7 +296,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         char buf[320];
         snprintf(buf, sizeof(buf), "internal state inconsistent at %s (n %llu cap %llu physN %u owned %llu | hashReady %d rsPending %d countKnown %d "
                  "known %u holes %d inplace %d classified %d slotOrder %d slab %d)", where, (unsigned long long)n, (unsigned long long)cap, physN,
-                 (unsigned long long)nOwned, hashReady, rsPending, rsCountKnown, rsKnownCount, holesPending, packInplace, classifiedValid,
+                 (unsigned long long)nOwned, hashReady, rsPending, rsCountKnown, rsKnownCount, holesPending, sx.inplace(), classifiedValid,
                  slotOrderValid, slabOn);
         return fail(NRS_E_STATE, buf);
     }
@@ -471,7 +480,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(rsTileDead.alloc(4 * nTiles)); NRSCHK(rsTileDeadOffset.alloc(4 * nTiles));
             NRSCHK(rsGroupDeadTotal.alloc(4 * nGroups)); NRSCHK(rsGroupDeadPrefix.alloc(4 * nGroups));
             HIPCHK(hipMemsetAsync(rsTileDead.p, 0, 4 * nTiles, stream));
-            HIPCHK(hipEventCreateWithFlags(&packEvent.e, hipEventDisableTiming));
             HIPCHK(hipMemsetAsync(rsTileMovers.p, 0, 4 * nTiles, stream));
             HIPCHK(hipMemsetAsync(rsScalars.p, 0, 16, stream));
             HIPCHK(hipHostMalloc((void **)&rsHostTotal.p, 64, hipHostMallocMapped));
@@ -529,7 +537,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // ... and W_q of the tensile correction on these
         if (q.interactionRadius != PU.interactionRadius || q.kpoly != PU.kpoly) pbfWqValid = false;
         PU = q;
-        if (!sameGrid && slabOn) choose_window(slab.lo, slab.hi, slab.halo, true);
+        if (!sameGrid && slabOn) sx.choose_window(PU.gridSize, slab.lo, slab.hi, slab.halo, true);
         derive_kernel_params();
         const bool regrid = P.numCells != cellsBefore;
         if (regrid) NRSCHK(alloc_cells());
@@ -782,7 +790,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (C > (1ull << 31)) return fail(NRS_E_INVALID, "grid from boundary AABB exceeds 2^31 cells");
             PU.gridSize[0] = g[0]; PU.gridSize[1] = g[1]; PU.gridSize[2] = g[2];
             PU.numCells = (uint32_t)C;
-            if (slabOn) choose_window(slab.lo, slab.hi, slab.halo, true);
+            if (slabOn) sx.choose_window(PU.gridSize, slab.lo, slab.hi, slab.halo, true);
             derive_kernel_params();
         }
         return rebuild_boundary_tables();
@@ -1749,19 +1757,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
     int slabMaxIters() const { return (slab.halo - 4) / 2; }
 
-    // ---- slab decomposition (nrs_kernels_slab.h) -------------------------------------------------------
+    // ---- slab decomposition (nrs_kernels_slab.h; the host decisions: nrs_host_slab.h) ------------------------------------
     int slab_configure(int lo, int hi, int halo) override
     {
-        // IISPH: every solver iteration consumes two cells of halo validity, the predict stages three and the pressure force one
-        // (DESIGN.md §5): 2 iterations — the reference's minimum — need 8 cells
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
-        if (bodies.n) return fail(NRS_E_INVALID, "contexts with boundary bodies have no slab decomposition");
-        if (pcisph()) return fail(NRS_E_INVALID, "PCISPH contexts have no slab decomposition");
-        if (pbf()) return fail(NRS_E_INVALID, "PBF contexts have no slab decomposition");
-        if (dfsph()) return fail(NRS_E_INVALID, "DFSPH contexts have no slab decomposition");
-        if (iisph() && halo < 8) return fail(NRS_E_INVALID, "IISPH slabs need a halo of at least 8 cells (2 * iterations + 4)");
-        if (halo < 2) return fail(NRS_E_INVALID, "halo must be >= 2 cells (one cell for the density of the ring + one)");
-        if ((long long)hi - lo < 2ll * halo) return fail(NRS_E_INVALID, "slab narrower than two halos");
+        NRSCHK(slab_refuse_configure(cfg.solver, bodies.n != 0, lo, hi, halo));
         if (classifiedValid && (slab.lo != lo || slab.hi != hi || slab.halo != halo)) {
             // the last force kernel classified (and marked dead keys) for the old cuts: partition the slow way once
             classifiedValid = false;
@@ -1772,7 +1772,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         nOwned = n;
         // cell-table window of this rank (see PU / P): re-chosen only when the slab no longer fits the current one
         const uint32_t cellsBefore = P.numCells, baseBefore = P.numBodies;
-        if (choose_window(lo, hi, halo, false)) {
+        if (sx.choose_window(PU.gridSize, lo, hi, halo, false)) {
             NRSCHK(invalidate_grid_state());
             derive_kernel_params();
             if (P.numCells != cellsBefore || P.numBodies != baseBefore) {
@@ -1782,27 +1782,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             }
         }
         return NRS_OK;
-    }
-    // Window [winBase, winBase + winW) of cell-x columns covering the slab, its halo, two columns of drift and WINDOW_SLACK columns
-    // of room for moving cuts; returns true when it changed.  force: choose afresh (the global grid changed).
-    static constexpr int WINDOW_SLACK = 8;
-    bool choose_window(int lo, int hi, int halo, bool force)
-    {
-        const long long GX = (long long)PU.gridSize[0];
-        const bool pow2 = is_pow2(PU.gridSize[0]) && is_pow2(PU.gridSize[1]) && is_pow2(PU.gridSize[2]);
-        long long a = std::max<long long>(0, (long long)lo - halo - 2), b = std::min<long long>(GX, (long long)hi + halo + 2);
-        if (!pow2 || b <= a) {
-            const bool changed = winW != 0;
-            winW = 0; winBase = 0;
-            return changed;
-        }
-        if (!force && winW && a >= winBase && b <= (long long)winBase + (long long)winW) return false; // still fits
-        a = std::max<long long>(0, a - WINDOW_SLACK); b = std::min<long long>(GX, b + WINDOW_SLACK);
-        const uint32_t w = next_pow2((uint32_t)(b - a));
-        const int baseOld = winBase; const uint32_t wOld = winW;
-        if (w >= (uint32_t)GX) { winW = 0; winBase = 0; }
-        else { winW = w; winBase = (int)a; }
-        return winW != wOld || winBase != baseOld;
     }
     uint64_t num_owned() override { return slabOn ? nOwned : n; }
     int slab_histogram(int lo0, uint32_t nbins, uint32_t *out) override
@@ -1820,6 +1799,16 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return NRS_OK;
     }
 
+    // The stream totals (and, in the pre-classified form, the scalars of the re-sort's scan) on their way to the host, and the event
+    // finish_pack() waits for.  Page-locked destination: the copy is complete when the event behind it is (a pageable destination is
+    // only guaranteed after a stream synchronization, which would also wait for the split queued behind it).
+    int totals_to_host(bool withScan)
+    {
+        HIPCHK(hipMemcpyAsync(slabHostTotals + HT_TOTALS, slabTotals.p, ST_TOTALS * 4, hipMemcpyDeviceToHost, stream));
+        if (withScan) HIPCHK(hipMemcpyAsync(slabHostTotals + HT_SCAN, rsScalars.p, 16, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipEventRecord(packEvent, stream));
+        return NRS_OK;
+    }
     int slab_pack(void *sendL, void *sendR, uint64_t mcap, uint32_t *counts) override
     {
         NRSCHK(validate("nrs_slab_pack"));
@@ -1837,168 +1826,101 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(slabTotals.alloc(ST_TOTALS * 4));
         NRSCHK(ghostPos.alloc(sizeof(T4) * mcap));
         NRSCHK(ghostVel.alloc(sizeof(T4) * mcap));
-        bool inplace = false;
-        if (!slabHostTotals) HIPCHK(hipHostMalloc((void **)&slabHostTotals.p, 128, hipHostMallocDefault));
-        if (!packEvent) HIPCHK(hipEventCreateWithFlags(&packEvent.e, hipEventDisableTiming)); // (contexts without re-sort buffers have none yet)
+        NRSCHK(ensure_host_totals());
+        NRSCHK(ensure_pack_event());
+        const SlabChoice ch = choose_form(SlabFacts{classifiedValid, slotOrderValid, rsMovers.p != nullptr, hashCur != nullptr, hashNext != nullptr,
+                                                    hashNext != hashCur, classifiedN, N, RESORT_MIN_PARTICLES});
+        const bool inplace = ch.form != SlabForm::COMPACT, pre = ch.form == SlabForm::PRECLASSIFIED;
         if (N) {
-            const bool fusedClass = classifiedValid && slotOrderValid && classifiedN == N && rsMovers.p && hashCur && hashNext &&
-                                    hashNext != hashCur;
-            classifiedValidAtPack = fusedClass;
-            if (fusedClass) {
-                // the force kernel of the last step classified every slot for these cuts (flags, stream populations per
-                // 2048 slots, dead marks in the keys, movers / dead per 256 slots): scan, copy out the few particles of
-                // the message and ghost streams, split
-                inplace = true;
-                packResort = true;
-                packKeys = hashNext; packVals = indexNext;
-                hipLaunchKernelGGL(k_slab_scan, dim3(ST_TOTALS), dim3(SLAB_BLOCK), 0, stream, slabCounts.as<uint32_t>(), nbk,
-                                   slabTotals.as<uint32_t>());
-                SlabOut<R> out;
-                out.stayPos = posB.as<T4>(); out.stayVel = velB.as<T4>();
-                out.hash = packKeys; out.index = packVals;
-                out.prevHash = hashCur; out.prevPacked = nullptr;
-                out.tileMovers = rsTileMovers.as<uint32_t>(); out.tileDead = rsTileDead.as<uint32_t>();
-                out.flags = slabFlags.as<uint8_t>();
-                out.ghostPos = ghostPos.as<T4>(); out.ghostVel = ghostVel.as<T4>();
-                out.sendL = (unsigned char *)sendL; out.sendR = (unsigned char *)sendR;
-                out.cap = (uint32_t)mcap;
-                hipLaunchKernelGGL((k_slab_scatter<R, true, true>), dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(),
-                                   velA.as<T4>(), N, slabCounts.as<uint32_t>(), nbk, slabTotals.as<uint32_t>(), out);
-                hipLaunchKernelGGL(k_slab_headers, dim3(1), dim3(64), 0, stream, slabTotals.as<uint32_t>(), (unsigned char *)sendL,
-                                   (unsigned char *)sendR);
-                const uint32_t nTiles = nblocks(N);
-                NRSCHK(launch_resort_scan(nTiles, true)); // also totals the cell changers and the dead slots
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(slabHostTotals, slabTotals.p, ST_TOTALS * 4, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipMemcpyAsync(slabHostTotals + 8, rsScalars.p, 16, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipEventRecord(packEvent, stream));
-                hipLaunchKernelGGL((k_resort_split<true>), dim3(nTiles), dim3(BLOCK), 0, stream, hashCur, hashNext, offsets_movers(),
-                                   offsets_dead(), rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, (uint32_t *)nullptr);
-                HIPCHK(hipGetLastError());
-                rsTilesDirty = false; // the scan resets the counts it reads
-            } else {
-                // coherent re-sort of the next step: possible when the arrays are still in the slot order of the last sort and
-                // the fused force kernel left the new keys per slot
-                const bool resort = rsMovers.p && slotOrderValid && hashCur && hashNext && hashNext != hashCur;
-                // ... and then the owned particles need not be moved at all (in-place partition, see k_slab_scatter)
-                inplace = resort && (uint64_t)N >= RESORT_MIN_PARTICLES;
+            // pre-classified: the force kernel of the last step classified every slot for these cuts (flags, stream populations per
+            // 2048 slots, dead marks in the keys, movers / dead per 256 slots); what is left is to scan, copy out the few particles
+            // of the message and ghost streams, and split
+            if (!pre)
                 hipLaunchKernelGGL((k_slab_count<R>), dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(), N,
-                                   slabCounts.as<uint32_t>(), nbk, resort ? hashCur : (const uint32_t *)nullptr,
-                                   resort ? hashNext : (const uint32_t *)nullptr);
-                hipLaunchKernelGGL(k_slab_scan, dim3(ST_TOTALS), dim3(SLAB_BLOCK), 0, stream, slabCounts.as<uint32_t>(), nbk,
-                                   slabTotals.as<uint32_t>());
-                SlabOut<R> out;
-                out.stayPos = posB.as<T4>(); out.stayVel = velB.as<T4>();
-                // the hash pass of the next step, done here (into the key buffers the last sort did not end in)
-                packKeys = other(hashA, hashB, hashCur);
-                packVals = other(indexA, indexB, indexCur);
-                if (inplace) { packKeys = hashNext; packVals = indexNext; } // the fused kernel's keys / slot numbers stay where they are
-                out.hash = packKeys; out.index = packVals;
-                out.prevHash = resort ? hashCur : nullptr;
-                out.prevPacked = (resort && !inplace) ? rsPrevPacked.as<uint32_t>() : nullptr;
-                out.tileMovers = resort ? rsTileMovers.as<uint32_t>() : nullptr;
-                out.tileDead = inplace ? rsTileDead.as<uint32_t>() : nullptr;
-                if (resort) NRSCHK(clean_tile_counts());
-                if (resort) rsTilesDirty = true; // (never clear it here: the counts of an unused classification may still be in the arrays)
-                packResort = resort;
-                out.ghostPos = ghostPos.as<T4>(); out.ghostVel = ghostVel.as<T4>();
-                out.sendL = (unsigned char *)sendL; out.sendR = (unsigned char *)sendR;
-                out.cap = (uint32_t)mcap;
-                if (inplace)
-                    hipLaunchKernelGGL((k_slab_scatter<R, true>), dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(), velA.as<T4>(), N,
-                                       slabCounts.as<uint32_t>(), nbk, slabTotals.as<uint32_t>(), out);
-                else
-                    hipLaunchKernelGGL((k_slab_scatter<R, false>), dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(), velA.as<T4>(), N,
-                                       slabCounts.as<uint32_t>(), nbk, slabTotals.as<uint32_t>(), out);
-                hipLaunchKernelGGL(k_slab_headers, dim3(1), dim3(64), 0, stream, slabTotals.as<uint32_t>(), (unsigned char *)sendL,
-                                   (unsigned char *)sendR);
-                HIPCHK(hipGetLastError());
-                // page-locked destination: the copy is complete when the event behind it is (a pageable destination is only
-                // guaranteed after a stream synchronization, which would also wait for the split queued below)
-                HIPCHK(hipMemcpyAsync(slabHostTotals, slabTotals.p, ST_TOTALS * 4, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipEventRecord(packEvent, stream));
-                if (inplace) {
-                    // the split of the slots we keep does not depend on what arrives: queue it now, so that it runs while the
-                    // messages travel
-                    const uint32_t nTiles = nblocks(N);
-                    NRSCHK(launch_resort_scan(nTiles, true));
-                    hipLaunchKernelGGL((k_resort_split<true>), dim3(nTiles), dim3(BLOCK), 0, stream, hashCur, hashNext, offsets_movers(),
-                                       offsets_dead(), rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, (uint32_t *)nullptr);
-                    HIPCHK(hipGetLastError());
-                    rsTilesDirty = false; // the scan resets the counts it reads
-                }
+                                   slabCounts.as<uint32_t>(), nbk, ch.resort ? hashCur : (const uint32_t *)nullptr,
+                                   ch.resort ? hashNext : (const uint32_t *)nullptr);
+            hipLaunchKernelGGL(k_slab_scan, dim3(ST_TOTALS), dim3(SLAB_BLOCK), 0, stream, slabCounts.as<uint32_t>(), nbk, slabTotals.as<uint32_t>());
+            // in place, the fused kernel's keys / slot numbers stay where they are; the compacting form does the hash pass of the next
+            // step here, into the key buffers the last sort did not end in
+            packKeys = inplace ? hashNext : other(hashA, hashB, hashCur);
+            packVals = inplace ? indexNext : other(indexA, indexB, indexCur);
+            SlabOut<R> out;
+            out.stayPos = posB.as<T4>(); out.stayVel = velB.as<T4>();
+            out.hash = packKeys; out.index = packVals;
+            out.prevHash = ch.resort ? hashCur : nullptr;
+            out.prevPacked = (ch.resort && !inplace) ? rsPrevPacked.as<uint32_t>() : nullptr;
+            out.tileMovers = ch.resort ? rsTileMovers.as<uint32_t>() : nullptr;
+            out.tileDead = inplace ? rsTileDead.as<uint32_t>() : nullptr;
+            out.flags = pre ? slabFlags.as<uint8_t>() : nullptr;
+            out.ghostPos = ghostPos.as<T4>(); out.ghostVel = ghostVel.as<T4>();
+            out.sendL = (unsigned char *)sendL; out.sendR = (unsigned char *)sendR;
+            out.cap = (uint32_t)mcap;
+            if (ch.resort && !pre) { // the scatter counts per tile (pre-classified: the force kernel did, and its counts are still there)
+                NRSCHK(clean_tile_counts());
+                rsTilesDirty = true; // (never clear it here: the counts of an unused classification may still be in the arrays)
             }
+            const auto scatter = pre ? k_slab_scatter<R, true, true> : inplace ? k_slab_scatter<R, true> : k_slab_scatter<R, false>;
+            hipLaunchKernelGGL(scatter, dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(), velA.as<T4>(), N, slabCounts.as<uint32_t>(),
+                               nbk, slabTotals.as<uint32_t>(), out);
         } else {
             HIPCHK(hipMemsetAsync(slabTotals.p, 0, ST_TOTALS * 4, stream));
-            hipLaunchKernelGGL(k_slab_headers, dim3(1), dim3(64), 0, stream, slabTotals.as<uint32_t>(), (unsigned char *)sendL,
-                               (unsigned char *)sendR);
-            HIPCHK(hipEventRecord(packEvent, stream));
         }
-        // Round 3: nothing above waits.  The messages are complete in stream order, so the caller can enqueue its sends right behind
-        // this call; the stream totals (how many stay, leave, ghost) are read back by finish_pack() — in nrs_slab_unpack, together
-        // with the headers of the received messages: ONE host synchronisation per exchange instead of two — or by whichever entry
-        // point needs the particle count first (settle()).
-        packPending = true;
-        pendFused = N && classifiedValidAtPack;
-        pendInplace = inplace;
-        pendN = N;
-        pendCap = mcap;
-        lastPartition = pendFused ? 2 : (inplace ? 1 : 0);
+        hipLaunchKernelGGL(k_slab_headers, dim3(1), dim3(64), 0, stream, slabTotals.as<uint32_t>(), (unsigned char *)sendL, (unsigned char *)sendR);
+        HIPCHK(hipGetLastError());
+        // In place, the split of the slots we keep does not depend on what arrives: it is queued now, so that it runs while the
+        // messages travel.  Its scan also totals the cell changers and the dead slots, which in the pre-classified form nothing else
+        // has counted: there the scan comes before the copy and the event.  Otherwise the event comes first, and finish_pack() never
+        // waits for the scan.  (N == 0: the totals are zero and nobody reads the landing; only the event is needed.)
+        const uint32_t nTiles = nblocks(N);
+        if (!N) HIPCHK(hipEventRecord(packEvent, stream));
+        else if (!pre) NRSCHK(totals_to_host(false));
+        if (inplace) NRSCHK(launch_resort_scan(nTiles, true));
+        if (pre) NRSCHK(totals_to_host(true));
+        if (inplace) {
+            hipLaunchKernelGGL((k_resort_split<true>), dim3(nTiles), dim3(BLOCK), 0, stream, hashCur, hashNext, offsets_movers(), offsets_dead(),
+                               rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, (uint32_t *)nullptr);
+            HIPCHK(hipGetLastError());
+            rsTilesDirty = false; // the scan resets the counts it reads
+        }
+        // Nothing above waits.  The messages are complete in stream order, so the caller can enqueue its sends right behind this call;
+        // the stream totals (how many stay, leave, ghost) are read back by finish_pack() — in nrs_slab_unpack, together with the
+        // headers of the received messages: ONE host synchronisation per exchange instead of two — or by whichever entry point needs
+        // the particle count first (settle()).
+        sx.queue(ch, N, mcap);
         if (counts) { // the caller wants the counts now: that is the synchronisation it asked for
             NRSCHK(finish_pack());
-            std::memcpy(counts, lastCounts, ST_COUNT * sizeof(uint32_t));
+            std::memcpy(counts, sx.totals, ST_COUNT * sizeof(uint32_t));
         }
         return NRS_OK;
     }
     // ---- the host half of nrs_slab_pack, run when the stream totals are needed ---------------------------------------------
-    bool packPending = false, pendFused = false, pendInplace = false, classifiedValidAtPack = false;
-    uint32_t pendN = 0;
-    uint64_t pendCap = 0;
-    uint32_t lastCounts[ST_COUNT] = {0, 0, 0, 0, 0, 0};
-    int lastPartition = -1; // NRS_STAT_SLAB_PARTITION: 0 compacting, 1 in place, 2 in place from the force kernel's classification
     int finish_pack()
     {
-        if (!packPending) return NRS_OK;
-        packPending = false;
-        const uint32_t N = pendN;
-        const bool inplace = pendInplace;
-        uint32_t tot[ST_TOTALS] = {0, 0, 0, 0, 0, 0, 0};
+        if (!sx.pending) return NRS_OK;
+        sx.pending = false; // (whatever the wait returns)
         HIPCHK(hipEventSynchronize(packEvent));
-        if (N) {
-            std::memcpy(tot, slabHostTotals, sizeof(tot));
-            if (pendFused) { // (pre-classified partition: cell changers and dead slots come from the re-sort's scan)
-                tot[ST_CHANGED] = slabHostTotals[8 + 1];
-                tot[ST_STAY] = N - slabHostTotals[8 + 2];
-            }
-        }
-        if ((uint64_t)tot[ST_STAY] + tot[ST_MIG_L] + tot[ST_MIG_R] > N || tot[ST_CHANGED] > tot[ST_STAY])
-            return fail(NRS_E_HIP, "inconsistent slab stream totals");
-        const bool overflow = (uint64_t)tot[ST_MIG_L] + tot[ST_HALO_L] > pendCap || (uint64_t)tot[ST_MIG_R] + tot[ST_HALO_R] > pendCap ||
-                              tot[ST_GHOST] > pendCap;
+        SlabFinish f;
+        const int rc = sx.finish(slabHostTotals + HT_TOTALS, slabHostTotals[HT_SCAN_CHANGED], slabHostTotals[HT_SCAN_DEAD], f);
+        if (!f.stored) return rc;
         to_fresh();
-        if (inplace) {
+        if (f.form != SlabForm::COMPACT) {
             // hashNext / indexNext hold key and slot of every live slot, 0xffffffff marks the dead ones; arrivals are added to the mover
             // count by nrs_slab_unpack
-            to_holes(N, tot[ST_CHANGED]);
+            to_holes(sx.N, f.movers);
         } else {
-            if (N) { std::swap(posA.p, posB.p); std::swap(velA.p, velB.p); }
-            else { packKeys = hashA.as<uint32_t>(); packVals = indexA.as<uint32_t>(); packResort = false; }
-            packedHashValid = N != 0; // k_slab_scatter hashed the particles that stay (with the current parameters)
+            if (sx.N) { std::swap(posA.p, posB.p); std::swap(velA.p, velB.p); }
+            else { packKeys = hashA.as<uint32_t>(); packVals = indexA.as<uint32_t>(); }
+            packedHashValid = sx.N != 0; // k_slab_scatter hashed the particles that stay (with the current parameters)
         }
-        packInplace = inplace;
-        n = tot[ST_STAY];
+        n = f.n;
         nOwned = n;
-        ghostCount = tot[ST_GHOST];
-        packChanged = tot[ST_CHANGED];
-        std::memcpy(lastCounts, tot, ST_COUNT * sizeof(uint32_t));
-        if (overflow) return fail(NRS_E_CAPACITY, "slab message capacity exceeded");
-        return NRS_OK;
+        return rc; // (NRS_E_CAPACITY: reported with the counts stored)
     }
     int settle() override { return finish_pack(); }
     int slab_last_counts(uint32_t *counts) override
     {
         NRSCHK(finish_pack());
-        std::memcpy(counts, lastCounts, ST_COUNT * sizeof(uint32_t));
+        std::memcpy(counts, sx.totals, ST_COUNT * sizeof(uint32_t));
         return NRS_OK;
     }
     uint32_t cap_blocks() const { return (uint32_t)((cap + SLAB_TILE - 1) / SLAB_TILE); }
@@ -2010,61 +1932,55 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!slabOn) return fail(NRS_E_STATE, "nrs_slab_configure first");
         // ONE host synchronisation for the exchange: the headers of the received messages (how many migrants, how many halo copies)
         // are copied to page-locked memory behind the receives, and the same wait covers the stream totals of the pack (finish_pack)
-        uint32_t hL[4] = {0, 0, 0, 0}, hR[4] = {0, 0, 0, 0};
-        if (!slabHostTotals) HIPCHK(hipHostMalloc((void **)&slabHostTotals.p, 128, hipHostMallocDefault));
-        if (recvL) HIPCHK(hipMemcpyAsync(slabHostTotals + 16, recvL, 16, hipMemcpyDeviceToHost, stream));
-        if (recvR) HIPCHK(hipMemcpyAsync(slabHostTotals + 20, recvR, 16, hipMemcpyDeviceToHost, stream));
-        if (recvL || recvR) HIPCHK(hipStreamSynchronize(stream));
-        if (recvL) std::memcpy(hL, slabHostTotals + 16, 16);
-        if (recvR) std::memcpy(hR, slabHostTotals + 20, 16);
+        NRSCHK(ensure_host_totals());
+        uint32_t *hL = recvL ? slabHostTotals + HT_HEADER_L : nullptr, *hR = recvR ? slabHostTotals + HT_HEADER_R : nullptr;
+        if (hL) HIPCHK(hipMemcpyAsync(hL, recvL, 16, hipMemcpyDeviceToHost, stream));
+        if (hR) HIPCHK(hipMemcpyAsync(hR, recvR, 16, hipMemcpyDeviceToHost, stream));
+        if (hL || hR) HIPCHK(hipStreamSynchronize(stream));
         NRSCHK(finish_pack());
-        if ((uint64_t)hL[0] + hL[1] > mcap || (uint64_t)hR[0] + hR[1] > mcap) return fail(NRS_E_INVALID, "corrupt slab message header");
-        const bool inplace = packInplace && holesPending;
-        const uint64_t arrivals = (uint64_t)hL[0] + hR[0] + ghostCount + hL[1] + hR[1];
-        const uint64_t total = n + arrivals;                           // live particles of the next step
-        const uint64_t base = inplace ? (uint64_t)physN : (uint64_t)n; // first free physical slot
-        if (base + arrivals > cap) return fail(NRS_E_CAPACITY, "owned + halo particles exceed the context capacity");
+        SlabArrivals ar;
+        NRSCHK(sx.unpack(hL, hR, n, physN, holesPending, mcap, cap, ar));
         const unsigned char *bL = (const unsigned char *)recvL, *bR = (const unsigned char *)recvR;
         auto mp = [&](const unsigned char *b) { return (const T4 *)(b + 16); };
         auto mv = [&](const unsigned char *b) { return (const T4 *)(b + 16 + (size_t)mcap * sizeof(T4)); };
+        const uint32_t migL = hL ? hL[0] : 0u, migR = hR ? hR[0] : 0u;
         AppendPieces<R> A;
-        const uint32_t len[5] = {hL[0], hR[0], ghostCount, hL[1], hR[1]};
         A.srcPos[0] = bL ? mp(bL) : nullptr;           A.srcVel[0] = bL ? mv(bL) : nullptr;            // migrants from the left
         A.srcPos[1] = bR ? mp(bR) : nullptr;           A.srcVel[1] = bR ? mv(bR) : nullptr;            // migrants from the right
         A.srcPos[2] = ghostPos.as<T4>();               A.srcVel[2] = ghostVel.as<T4>();               // our ghosts
-        A.srcPos[3] = bL ? mp(bL) + hL[0] : nullptr;   A.srcVel[3] = bL ? mv(bL) + hL[0] : nullptr;    // halo from the left
-        A.srcPos[4] = bR ? mp(bR) + hR[0] : nullptr;   A.srcVel[4] = bR ? mv(bR) + hR[0] : nullptr;    // halo from the right
-        A.start[0] = 0;
-        for (int k = 0; k < 5; ++k) A.start[k + 1] = A.start[k] + len[k];
-        const bool compactResort = !inplace && packResort;
+        A.srcPos[3] = bL ? mp(bL) + migL : nullptr;    A.srcVel[3] = bL ? mv(bL) + migL : nullptr;     // halo from the left
+        A.srcPos[4] = bR ? mp(bR) + migR : nullptr;    A.srcVel[4] = bR ? mv(bR) + migR : nullptr;     // halo from the right
+        std::memcpy(A.start, ar.start, sizeof(A.start));
+        // compacting form with a re-sort: the append extends the compacted old keys and the tile counts of the scatter
+        const bool compactResort = sx.form == SlabForm::COMPACT && sx.resort;
         if (A.start[5])
             hipLaunchKernelGGL((k_slab_append<R>), dim3((A.start[5] + SLAB_BLOCK - 1) / SLAB_BLOCK), dim3(SLAB_BLOCK), 0, stream, P, A,
                                posA.as<T4>(), velA.as<T4>(), packKeys, packVals,
                                compactResort ? rsPrevPacked.as<uint32_t>() : (uint32_t *)nullptr,
-                               compactResort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr, (uint32_t)base,
-                               inplace ? rsMovers.as<uint64_t>() : (uint64_t *)nullptr, inplace ? rsKnownCount : 0u);
+                               compactResort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr, (uint32_t)ar.base,
+                               ar.inplace ? rsMovers.as<uint64_t>() : (uint64_t *)nullptr, ar.inplace ? rsKnownCount : 0u);
         HIPCHK(hipGetLastError());
-        nOwned = n + hL[0] + hR[0];
-        n = total;
+        nOwned = ar.nOwned;
+        n = ar.n;
         if (iisph() && n)
             hipLaunchKernelGGL((k_velw_to_pressure<R>), dim3(nblocks(n)), dim3(BLOCK), 0, stream, velA.as<T4>(), presA.as<R>(), (uint32_t)n);
         // pack + unpack have written the radix keys/values of every local particle
         hashNext = packKeys; indexNext = packVals;
         hashReady = packedHashValid;
-        if (inplace) {
-            physN += (uint32_t)arrivals;
-            rsKnownCount += (uint32_t)arrivals; // every arrival is a mover (k_slab_append put it behind the cell changers)
-        } else if (hashReady && packResort && n >= RESORT_MIN_PARTICLES) {
+        if (ar.inplace) {
+            physN += (uint32_t)ar.arrivals;
+            rsKnownCount += (uint32_t)ar.arrivals; // every arrival is a mover (k_slab_append put it behind the cell changers)
+        } else if (hashReady && compactResort && n >= RESORT_MIN_PARTICLES) {
             // coherent re-sort: the owned particles that stayed in their cell are still in sorted order
             // (the partition and the append have counted the movers of every tile of the new arrays)
             const uint32_t N = (uint32_t)n, nTiles = nblocks(N);
             NRSCHK(launch_resort_scan(nTiles, false));
             hipLaunchKernelGGL((k_resort_split<false>), dim3(nTiles), dim3(BLOCK), 0, stream, rsPrevPacked.as<uint32_t>(), hashNext,
                                offsets_movers(), offsets_movers(), rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, (uint32_t *)nullptr);
-            split_queued_known(packChanged + A.start[5]); // everything appended is a mover, and the partition counted the cell changers
+            split_queued_known(sx.totals[ST_CHANGED] + A.start[5]); // everything appended is a mover, and the partition counted the cell changers
             rsTilesDirty = false; // the scan resets the counts it reads
         }
-        packResort = false;
+        sx.resort = false;
         return NRS_OK;
     }
 
@@ -2100,8 +2016,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         if (which == NRS_STAT_MOVERS) { *out = lastMovers; return NRS_OK; }
         if (which == NRS_STAT_SLAB_PARTITION) {
-            if (lastPartition < 0) return fail(NRS_E_STATE, "no nrs_slab_pack yet");
-            *out = lastPartition;
+            if (!sx.packed) return fail(NRS_E_STATE, "no nrs_slab_pack yet");
+            *out = (int)sx.form;
             return NRS_OK;
         }
         if (pbf() && (which == NRS_STAT_DENSITY_ERROR || which == NRS_STAT_PBF_EPSILON)) {
@@ -2172,12 +2088,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (iisphPhase) return fail(NRS_E_STATE, "a host-driven IISPH step is in progress (nrs_iisph_finish first)");
         NRSCHK(validate("nrs_step"));
         if (midStep) return fail(NRS_E_STATE, "state is mid-update after nrs_step_partial; upload particles first");
-        if (pcisph() && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
-            return fail(NRS_E_INVALID, "stage not part of a PCISPH step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
-        if (pbf() && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
-            return fail(NRS_E_INVALID, "stage not part of a PBF step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
-        if (dfsph() && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
-            return fail(NRS_E_INVALID, "stage not part of a DFSPH step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
+        const char *const predictive = predictive_solver_name(cfg.solver);
+        if (predictive && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
+            return fail(NRS_E_INVALID, std::string("stage not part of a ") + predictive + " step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
         if (n == 0) return NRS_OK;
         if (pcisph()) NRSCHK(pcisph_prepare());
         if (pbf()) NRSCHK(pbf_prepare());

@@ -1,5 +1,5 @@
-// host_parts_main.cpp — stand-alone driver of the library's HIP-free host components (nrs_host_bodies.h, nrs_host_settings.h) for
-// tests/test_host_parts_cpu.py: one command per line on stdin, one answer per line on stdout.  Doubles travel as C99 hex floats (or
+// host_parts_main.cpp — stand-alone driver of the library's HIP-free host components (nrs_host_bodies.h, nrs_host_settings.h,
+// nrs_host_slab.h) for tests/test_host_parts_cpu.py: one command per line on stdin, one answer per line on stdout.  Doubles travel as C99 hex floats (or
 // nan / inf), so nothing is rounded on the way.  Built by the test with the host compiler, plain and under the sanitizers.
 #include <cstdio>
 #include <cstdlib>
@@ -10,6 +10,7 @@
 
 #include "nrs_host_bodies.h"
 #include "nrs_host_settings.h"
+#include "nrs_host_slab.h"
 
 namespace nrs {
 thread_local std::string g_err;
@@ -33,6 +34,7 @@ int main()
     PbfSettings pbf;
     DfsphSettings df;
     AkinciSettings ak;
+    SlabHost sx;
     std::string line;
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
@@ -115,6 +117,42 @@ int main()
             need(2);
             answer(ak.set(a[0], a[1]));
             printf("ak %a %a\n", ak.gamma, ak.beta);
+        } else if (cmd == "win") { // win gx gy gz lo hi halo force
+            need(7);
+            const uint32_t grid[3] = {(uint32_t)a[0], (uint32_t)a[1], (uint32_t)a[2]};
+            const bool changed = sx.choose_window(grid, (int)a[3], (int)a[4], (int)a[5], a[6] != 0.0);
+            printf("win %d %d %u\n", changed ? 1 : 0, sx.winBase, sx.winW);
+        } else if (cmd == "form") { // form classifiedValid slotOrderValid resortBuffers hashCur hashNext hashDistinct classifiedN N resortMin
+            need(9);
+            const SlabChoice c = choose_form(SlabFacts{a[0] != 0.0, a[1] != 0.0, a[2] != 0.0, a[3] != 0.0, a[4] != 0.0, a[5] != 0.0, (uint32_t)a[6],
+                                                       (uint32_t)a[7], (uint64_t)a[8]});
+            printf("form %d %d\n", (int)c.form, c.resort ? 1 : 0);
+        } else if (cmd == "cfg") { // cfg solver has_bodies lo hi halo
+            need(5);
+            answer(slab_refuse_configure((int)a[0], a[1] != 0.0, (int)a[2], (int)a[3], (int)a[4]));
+        } else if (cmd == "queue") { // queue form resort N message_capacity: what nrs_slab_pack leaves behind
+            need(4);
+            sx.queue(SlabChoice{(SlabForm)(int)a[0], a[1] != 0.0}, (uint32_t)a[2], (uint64_t)a[3]);
+            answer(NRS_OK);
+        } else if (cmd == "fin") { // fin t0 .. t6 scan_changed scan_dead
+            need(9);
+            uint32_t raw[SLT_TOTALS];
+            for (int k = 0; k < SLT_TOTALS; ++k) raw[k] = (uint32_t)a[k];
+            SlabFinish f;
+            answer(sx.finish(raw, (uint32_t)a[7], (uint32_t)a[8], f));
+            printf("fin %d %u %d %u %d", f.stored ? 1 : 0, f.n, (int)f.form, f.movers, sx.pending ? 1 : 0);
+            for (int k = 0; k < SLT_TOTALS; ++k) printf(" %u", sx.totals[k]);
+            printf("\n");
+        } else if (cmd == "unp") { // unp has_left migrants halo has_right migrants halo n physN holes message_capacity capacity
+            need(11);
+            const uint32_t hL[4] = {(uint32_t)a[1], (uint32_t)a[2], 0, 0}, hR[4] = {(uint32_t)a[4], (uint32_t)a[5], 0, 0};
+            SlabArrivals r;
+            const int rc = sx.unpack(a[0] != 0.0 ? hL : nullptr, a[3] != 0.0 ? hR : nullptr, (uint64_t)a[6], (uint32_t)a[7], a[8] != 0.0, (uint64_t)a[9],
+                                     (uint64_t)a[10], r);
+            answer(rc);
+            if (rc == NRS_OK)
+                printf("unp %d %u %u %u %u %u %u %llu %llu %llu %llu\n", r.inplace ? 1 : 0, r.start[0], r.start[1], r.start[2], r.start[3], r.start[4],
+                       r.start[5], (unsigned long long)r.base, (unsigned long long)r.arrivals, (unsigned long long)r.n, (unsigned long long)r.nOwned);
         } else {
             fprintf(stderr, "host_parts_main: unknown command '%s'\n", cmd.c_str());
             return 2;

@@ -1,4 +1,4 @@
-"""The library's HIP-free host components (nereus_amd/csrc/nrs_host_bodies.h, nrs_host_settings.h) without a GPU: a stand-alone
+"""The library's HIP-free host components (nereus_amd/csrc/nrs_host_bodies.h, nrs_host_settings.h, nrs_host_slab.h) without a GPU: a stand-alone
 program (tests/host_parts_main.cpp) built with the host compiler, -ffp-contract=off as the library is, fed commands on stdin.
 
   * the pose integration against tests/bodies_model.advance, for 1 and for 50 consecutive steps.  x: 1 ulp per component per step
@@ -9,6 +9,11 @@ program (tests/host_parts_main.cpp) built with the host compiler, -ffp-contract=
   * the refusals of BodyPoses and of every invalid-argument branch of the four settings validators: codes and texts as the parent
     commit's nrs_ctx_impl.h states them (written out below, not read from the code under test), and a refused call changes nothing.
   * moving() / displaced() before and after set_pose, set_velocity, a rebuild and clear.
+  * the host decisions of the slab exchange (nrs_host_slab.h): the cell-table window, the full truth table of the partition form,
+    the refusals of nrs_slab_configure in their order of precedence, what finish() makes of a pack's stream totals (consistency,
+    overflow after storing) and the arithmetic of the unpack (header and capacity refusals at the limit and one over, piece offsets,
+    n and n_owned).  The expectations restate the rule of the commit before the header existed (its nrs_ctx_impl.h: choose_window,
+    slab_configure, slab_pack, finish_pack, slab_unpack); nothing is read from the code under test.
   * the same program once more under -fsanitize=address,undefined (a host program of its own: nothing is preloaded).
 """
 import os
@@ -23,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CXX = os.environ.get("CXX", "g++")
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-I", os.path.join(ROOT, "nereus_amd", "csrc")]
 SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]
-E_INVALID = -1
+E_INVALID, E_HIP, E_CAPACITY = -1, -2, -3
 Q_MEASURED = {1: 0.0, 50: 2.7756e-17}  # steps: largest |dq| measured (docstring)
 Q_BOUND = {k: min(4.0 * v if v else 4.0 * 2.0 ** -52, 1e-13) for k, v in Q_MEASURED.items()}
 DT = 1e-3
@@ -278,7 +283,197 @@ def test_moving_and_displaced(plain):
     check_moving_displaced(plain)
 
 
+# ---- the slab exchange's host decisions (nrs_host_slab.h) ------------------------------------------------------------------------
+def ints(ans, word):
+    assert ans[0] == word, ans
+    return [int(t) for t in ans[1].split()]
+
+
+def check_slab_window(exe):
+    g = (256, 64, 64)
+    # the slab [100, 120) with halo 2 and two columns of drift is [96, 124); 8 columns of slack either side: [88, 132), 44 columns,
+    # rounded up to 64.  [100, 128) still fits [88, 152).  [56, 204) does not, and with its slack needs 256 columns: the whole grid.
+    ans = run(exe, [cmd("win", g, 100, 120, 2, 0), cmd("win", g, 104, 124, 2, 0), cmd("win", g, 60, 200, 2, 0), cmd("win", g, 60, 200, 2, 0)])
+    assert [ints(a, "win") for a in ans] == [[1, 88, 64], [0, 88, 64], [1, 0, 0], [0, 0, 0]]
+    # a grid with an axis that is no power of two has no window; "changed" only if there was one
+    for bad in ((256, 48, 64), (256, 64, 96), (192, 64, 64)):
+        ans = run(exe, [cmd("win", bad, 100, 120, 2, 0), cmd("win", g, 100, 120, 2, 0), cmd("win", bad, 100, 120, 2, 0), cmd("win", bad, 100, 120, 2, 1)])
+        assert [ints(a, "win") for a in ans] == [[0, 0, 0], [1, 88, 64], [1, 0, 0], [0, 0, 0]], bad
+    # force chooses afresh although the old window fits: [100, 128) with slack is [92, 136)
+    ans = run(exe, [cmd("win", g, 100, 120, 2, 0), cmd("win", g, 104, 124, 2, 1), cmd("win", g, 104, 124, 2, 1)])
+    assert [ints(a, "win") for a in ans] == [[1, 88, 64], [1, 92, 64], [0, 92, 64]]
+    # clipped at both ends of the grid ([236, 256) with slack starts at 228); an empty range (the slab lies outside the grid) has no window
+    ans = run(exe, [cmd("win", g, 0, 20, 2, 0), cmd("win", g, 240, 256, 2, 0), cmd("win", g, 300, 320, 2, 0), cmd("win", g, -50, -20, 2, 0)])
+    assert [ints(a, "win") for a in ans] == [[1, 0, 32], [1, 228, 32], [1, 0, 0], [0, 0, 0]]
+
+
+RESORT_MIN = 32768  # nrs_kernels_resort.h
+
+
+def form_model(cv, so, rb, hc, hn, hd, cn, n):
+    """slab_pack's conditions before the header existed: (form, counts cell changers)"""
+    if n == 0:
+        return 0, 0
+    if cv and so and cn == n and rb and hc and hn and hd:
+        return 2, 1
+    resort = rb and so and hc and hn and hd
+    return (1 if resort and n >= RESORT_MIN else 0), int(bool(resort))
+
+
+def check_slab_form(exe):
+    cases = []
+    for m in range(64):
+        b = [(m >> k) & 1 for k in range(6)]
+        for n in (0, 1, RESORT_MIN - 1, RESORT_MIN, 100000):
+            for cn in (n, n + 1, 0):
+                cases.append(b + [cn, n])
+    ans = run(exe, [cmd("form", c, RESORT_MIN) for c in cases])
+    seen = set()
+    for c, a in zip(cases, ans):
+        want = form_model(*c)
+        assert tuple(ints(a, "form")) == want, (c, a)
+        seen.add((want, c[7] >= RESORT_MIN))
+    # every outcome occurs, among them: compacting with cell changers counted one particle below the threshold, in place at it, and
+    # pre-classified below it (the form does not look at the threshold: the step that classifies does)
+    assert seen >= {((0, 0), False), ((0, 0), True), ((0, 1), False), ((1, 1), True), ((2, 1), False), ((2, 1), True)}
+    all_true = [1, 1, 1, 1, 1, 1]
+    one = lambda c: tuple(ints(run(exe, [cmd("form", c, RESORT_MIN)])[0], "form"))
+    assert one(all_true + [RESORT_MIN - 1, RESORT_MIN - 1]) == (2, 1)
+    assert one(all_true + [RESORT_MIN, RESORT_MIN - 1]) == (0, 1) and one(all_true + [RESORT_MIN - 1, RESORT_MIN]) == (1, 1)  # classifiedN != N
+    assert one([1, 1, 1, 1, 1, 0, RESORT_MIN, RESORT_MIN]) == (0, 0)   # hashNext == hashCur
+    assert one(all_true + [0, 0]) == (0, 0)                            # N == 0
+
+
+SESPH, IISPH, PCISPH, PBF, DFSPH = range(5)
+T_BODIES = "contexts with boundary bodies have no slab decomposition"
+T_IISPH = "IISPH slabs need a halo of at least 8 cells (2 * iterations + 4)"
+T_HALO = "halo must be >= 2 cells (one cell for the density of the ring + one)"
+T_NARROW = "slab narrower than two halos"
+CONFIGURE = [
+    # (solver, has bodies, lo, hi, halo, refusal text or None), in the order of precedence: every line is also wrong in all later ways
+    (SESPH, 1, 5, 6, 1, T_BODIES), (IISPH, 1, 5, 6, 1, T_BODIES), (PCISPH, 1, 5, 6, 1, T_BODIES), (PBF, 1, 5, 6, 1, T_BODIES),
+    (DFSPH, 1, 5, 6, 1, T_BODIES), (SESPH, 1, 0, 100, 2, T_BODIES),
+    (PCISPH, 0, 5, 6, 1, "PCISPH contexts have no slab decomposition"), (PCISPH, 0, 0, 100, 8, "PCISPH contexts have no slab decomposition"),
+    (PBF, 0, 5, 6, 1, "PBF contexts have no slab decomposition"), (PBF, 0, 0, 100, 8, "PBF contexts have no slab decomposition"),
+    (DFSPH, 0, 5, 6, 1, "DFSPH contexts have no slab decomposition"), (DFSPH, 0, 0, 100, 8, "DFSPH contexts have no slab decomposition"),
+    (IISPH, 0, 5, 6, 1, T_IISPH), (IISPH, 0, 0, 100, 7, T_IISPH), (IISPH, 0, 0, 100, -3, T_IISPH),
+    (SESPH, 0, 5, 6, 1, T_HALO), (SESPH, 0, 0, 100, 1, T_HALO), (SESPH, 0, 0, 100, 0, T_HALO), (SESPH, 0, 0, 100, -1, T_HALO),
+    (SESPH, 0, 5, 8, 2, T_NARROW), (SESPH, 0, 8, 5, 2, T_NARROW), (IISPH, 0, 0, 15, 8, T_NARROW), (SESPH, 0, -2 ** 31, -2 ** 31 + 3, 2, T_NARROW),
+    (SESPH, 0, 5, 9, 2, None), (IISPH, 0, 0, 16, 8, None), (SESPH, 0, -2 ** 31, 2 ** 31 - 1, 2, None), (SESPH, 0, -3, 1, 2, None),
+]
+
+
+def check_slab_configure(exe):
+    ans = run(exe, [cmd("cfg", *c[:5]) for c in CONFIGURE])
+    for c, a in zip(CONFIGURE, ans):
+        assert refusal(a) == ((0, "") if c[5] is None else (E_INVALID, c[5])), (c, a)
+
+
+COMPACT, INPLACE, PRECLASSIFIED = 0, 1, 2
+T_TOTALS, T_OVERFLOW = "inconsistent slab stream totals", "slab message capacity exceeded"
+
+
+def finish(exe, form, n, mcap, raw, scan=(0, 0), before=()):
+    """the answers to one queue + fin: (code, text), [stored, n, form, movers, pending], the seven stored totals"""
+    ans = run(exe, list(before) + [cmd("queue", form, 1, n, mcap), cmd("fin", raw, scan)])[-3:]
+    assert refusal(ans[0])[0] == 0
+    v = ints(ans[2], "fin")
+    return refusal(ans[1]), v[:5], v[5:]
+
+
+def check_slab_finish(exe):
+    # totals: stay, migrants / halo copies to the left, to the right, ghosts, cell changers
+    raw = [90, 4, 6, 5, 7, 8, 30]
+    for form in (COMPACT, INPLACE):
+        assert finish(exe, form, 100, 12, raw) == ((0, ""), [1, 90, form, 30, 0], raw)
+    # pre-classified: the cell changers and the stay count (N - dead) come from the re-sort's scan, whatever k_slab_scan's say
+    assert finish(exe, PRECLASSIFIED, 100, 12, [1, 4, 6, 5, 7, 8, 99], scan=(30, 10)) == ((0, ""), [1, 90, PRECLASSIFIED, 30, 0], raw)
+    # ... and in the other forms the scan's figures are not looked at
+    assert finish(exe, INPLACE, 100, 12, raw, scan=(55, 66)) == ((0, ""), [1, 90, INPLACE, 30, 0], raw)
+    # N == 0: the landing is not read (nothing was copied there)
+    assert finish(exe, COMPACT, 0, 12, raw) == ((0, ""), [1, 0, COMPACT, 0, 0], [0] * 7)
+    # inconsistent totals: nothing is stored (the totals of the pack before stay), the pack is no longer pending
+    first = [cmd("queue", COMPACT, 0, 50, 12), cmd("fin", [40, 1, 1, 1, 1, 1, 3], (0, 0))]
+    for form, n, bad, scan in ((COMPACT, 100, [92, 4, 6, 5, 7, 8, 30], (0, 0)),     # stay + migrants = 101 > N
+                               (INPLACE, 100, [90, 4, 6, 5, 7, 8, 91], (0, 0)),     # more cell changers than stayers
+                               (PRECLASSIFIED, 100, raw, (91, 10)),                 # the same from the scan
+                               (PRECLASSIFIED, 100, raw, (30, 0)),                  # no dead slot, yet 9 migrants
+                               (PRECLASSIFIED, 100, raw, (30, 101))):               # more dead slots than slots (N - dead wraps)
+        assert finish(exe, form, n, 12, bad, scan, before=first) == ((E_HIP, T_TOTALS), [0, 0, 0, 0, 0], [40, 1, 1, 1, 1, 1, 3]), (form, bad, scan)
+    assert finish(exe, COMPACT, 100, 12, [91, 4, 6, 5, 7, 8, 91])[0] == (0, "")     # at both limits
+    # each overflow condition at the limit and one over; the counts are stored either way
+    for form in (COMPACT, INPLACE, PRECLASSIFIED):
+        scan = (30, 10)
+        for t in ([90, 4, 8, 5, 7, 8, 30], [90, 4, 6, 5, 7, 12, 30], [90, 3, 9, 6, 6, 12, 30]):   # left, right + ghosts, all three at 12
+            assert finish(exe, form, 100, 12, t, scan) == ((0, ""), [1, 90, form, 30, 0], t)
+        for t in ([90, 4, 9, 5, 7, 8, 30], [90, 4, 6, 5, 8, 8, 30], [90, 4, 6, 5, 7, 13, 30]):     # left, right, ghosts at 13
+            assert finish(exe, form, 100, 12, t, scan) == ((E_CAPACITY, T_OVERFLOW), [1, 90, form, 30, 0], t)
+
+
+T_HEADER, T_CONTEXT = "corrupt slab message header", "owned + halo particles exceed the context capacity"
+
+
+def unpack(exe, form, ghosts, left, right, n, phys, holes, mcap, cap):
+    """queue + fin (a pack of n + 10 particles, of which n stay and `ghosts` are ghosts) and the unpack"""
+    before = [cmd("queue", form, 0, n + 10, 1000), cmd("fin", [n, 0, 0, 0, 0, ghosts, 0], (0, 10))]
+    hdr = lambda h: (0, 0, 0) if h is None else (1,) + tuple(h)
+    ans = run(exe, before + [cmd("unp", hdr(left), hdr(right), n, phys, holes, mcap, cap)])[3:]
+    return refusal(ans[0]), (ints(ans[1], "unp") if len(ans) > 1 else None)
+
+
+def check_slab_unpack(exe):
+    # hand-written: 92 owned, 5 ghosts, 3 migrants + 4 halo copies from the left, 2 + 6 from the right.  Pieces in the order
+    # migrants left, migrants right, ghosts, halo left, halo right: offsets 0, 3, 5, 10, 14, 20.
+    start = [0, 3, 5, 10, 14, 20]
+    # compacting form: appended behind the n owned particles
+    assert unpack(exe, COMPACT, 5, (3, 4), (2, 6), 92, 0, 0, 10, 112) == ((0, ""), [0] + start + [92, 20, 112, 97])
+    # in place with the holes still there: appended behind the physical extent
+    for form in (INPLACE, PRECLASSIFIED):
+        assert unpack(exe, form, 5, (3, 4), (2, 6), 92, 102, 1, 10, 122) == ((0, ""), [1] + start + [102, 20, 112, 97])
+        # ... and once something has compacted the holes (a download between pack and unpack), behind the n live ones
+        assert unpack(exe, form, 5, (3, 4), (2, 6), 92, 102, 0, 10, 112) == ((0, ""), [0] + start + [92, 20, 112, 97])
+    # a missing left / right / both messages: its pieces are empty, whatever the bytes would have said
+    assert unpack(exe, COMPACT, 5, None, (2, 6), 92, 0, 0, 10, 200) == ((0, ""), [0, 0, 0, 2, 7, 7, 13, 92, 13, 105, 94])
+    assert unpack(exe, COMPACT, 5, (3, 4), None, 92, 0, 0, 10, 200) == ((0, ""), [0, 0, 3, 3, 8, 12, 12, 92, 12, 104, 95])
+    assert unpack(exe, INPLACE, 5, None, None, 92, 102, 1, 10, 200) == ((0, ""), [1, 0, 0, 0, 5, 5, 5, 102, 5, 97, 92])
+    # header sums at the message capacity and one over, on either side; the header is checked before the capacity
+    assert unpack(exe, COMPACT, 5, (3, 7), (4, 6), 92, 0, 0, 10, 200)[0] == (0, "")
+    assert unpack(exe, COMPACT, 5, (4, 7), (4, 6), 92, 0, 0, 10, 200) == ((E_INVALID, T_HEADER), None)
+    assert unpack(exe, COMPACT, 5, (3, 7), (10, 1), 92, 0, 0, 10, 200) == ((E_INVALID, T_HEADER), None)
+    assert unpack(exe, COMPACT, 5, (2 ** 32 - 1, 1), None, 92, 0, 0, 10, 200) == ((E_INVALID, T_HEADER), None)   # (no 32-bit wrap)
+    assert unpack(exe, COMPACT, 5, (4, 7), (4, 6), 92, 0, 0, 10, 5) == ((E_INVALID, T_HEADER), None)
+    # base + arrivals at the context capacity and one over, in both placements
+    assert unpack(exe, COMPACT, 5, (3, 4), (2, 6), 92, 0, 0, 10, 111) == ((E_CAPACITY, T_CONTEXT), None)
+    assert unpack(exe, INPLACE, 5, (3, 4), (2, 6), 92, 102, 1, 10, 122)[0] == (0, "")
+    assert unpack(exe, INPLACE, 5, (3, 4), (2, 6), 92, 102, 1, 10, 121) == ((E_CAPACITY, T_CONTEXT), None)
+
+
+def test_slab_window(plain):
+    check_slab_window(plain)
+
+
+def test_slab_form_truth_table(plain):
+    check_slab_form(plain)
+
+
+def test_slab_configure_refusals_in_order(plain):
+    check_slab_configure(plain)
+
+
+def test_slab_finish(plain):
+    check_slab_finish(plain)
+
+
+def test_slab_unpack_arithmetic(plain):
+    check_slab_unpack(plain)
+
+
 def test_under_sanitizers(sanitized):
+    check_slab_window(sanitized)
+    check_slab_form(sanitized)
+    check_slab_configure(sanitized)
+    check_slab_finish(sanitized)
+    check_slab_unpack(sanitized)
     check_poses(sanitized)
     check_refusals(sanitized)
     check_settings_accepted(sanitized)

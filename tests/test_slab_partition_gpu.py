@@ -104,9 +104,10 @@ def assert_image(buf, image, what):
 
 
 def check_pack_unpack(s, pos, vel, lo, hi, halo, double, deferred, route=0, n_neigh=40, seed=0, pres=None, left=True, right=True,
-                      slack=3):
+                      slack=3, between=None):
     """upload-free core of most cases: `s` holds pos / vel (slot order) and is configured; pack, compare counts, messages and the
-    untouched bytes with the model, unpack two model-made neighbour messages, compare download() and num_owned"""
+    untouched bytes with the model, unpack two model-made neighbour messages, compare download() and num_owned.  between(s, m), if
+    given, is called between the pack and the unpack"""
     real = real_of(double)
     p = s.params
     (pl, vl, llo, lhi), (pr, vr, rlo, rhi) = neighbours(p, lo, hi, halo, real, n_neigh, seed)
@@ -142,6 +143,8 @@ def check_pack_unpack(s, pos, vel, lo, hi, halo, double, deferred, route=0, n_ne
             assert_image(sl, m.msg_left, "left message")
         if right:
             assert_image(sr, m.msg_right, "right message")
+        if between is not None:
+            between(s, m)
         s.slab_unpack(ptr(rl), ptr(rr), cap)
         assert s.n == len(m.pos) and s.n_owned == m.n_owned
         if pres is None:
@@ -477,5 +480,84 @@ def test_step_after_in_place_partition_merges(hip_lib, double, route):
         own = gp[:, 3] == 1
         want = np.sort(np.concatenate([svel[m.streams["stay"], 3]]))
         assert own.sum() == m.counts[0] and np.array_equal(np.sort(gv[own, 3]), want)   # ids of the owned particles
+    finally:
+        s.close()
+
+
+# ---- call sequences around an exchange -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("double", [False, True])
+@pytest.mark.parametrize("first", ["compacting", "in_place"])
+def test_pack_right_after_a_pack_nobody_finished(hip_lib, double, first):
+    """nrs_slab_pack(counts = NULL) and at once the next pack: the second call reads the first one's totals itself (and, after an
+    in-place first pack, compacts its holes) and partitions what the first one kept — the model's stay stream, in slot order.  The
+    second pack takes the compacting form; its counts, messages, ghosts and arrivals are the model's bit for bit."""
+    real = real_of(double)
+    if first == "in_place":
+        s, pos, vel, lo, hi = to_stepped_state(double, 2)
+        halo, cap, n_neigh = 2, 16384, 300
+    else:
+        lo, hi, halo, cap, n_neigh = 1, 7, 2, 2049, 40
+        s = solver(2049 + 1024, double)
+        pos, vel = random_input(91, 2049, lo, hi, halo, real, s.params)
+        s.set_particles(pos, vel)
+        s.slab_configure(lo, hi, halo)
+    try:
+        m1 = slab_model.partition(s.params, lo, hi, halo, pos, vel, real, cap=cap, left=False, right=False)
+        assert not m1.overflow and 0 < m1.counts[0] < len(pos) and m1.counts[1] > 0 and m1.counts[3] > 0
+        assert s.slab_pack(None, None, cap, want_counts=False) is None
+        m2 = check_pack_unpack(s, m1.stay_pos, m1.stay_vel, lo, hi, halo, double, deferred=False, route=0, n_neigh=n_neigh, seed=92)
+        assert m2.counts[0] == m1.counts[0] and m2.counts[1] == m2.counts[3] == m2.counts[5] == 0 and m2.counts[2] > 0 and m2.counts[4] > 0
+    finally:
+        s.close()
+
+
+@pytest.mark.parametrize("double", [False, True])
+@pytest.mark.parametrize("route", [2, 1])
+def test_download_between_in_place_pack_and_unpack(hip_lib, double, route):
+    """an in-place pack, then download() — which compacts the holes: the stay stream in slot order — and only then the unpack: the
+    arrivals go behind the compacted particles, and the arrays are the model's bit for bit as in the plain sequence"""
+    s, spos, svel, lo, hi = to_stepped_state(double, route)
+
+    def download_the_stayers(s, m):
+        gp, gv = s.download()
+        assert np.array_equal(bits(gp), bits(m.stay_pos)) and np.array_equal(bits(gv), bits(m.stay_vel))
+        assert s.n == m.counts[0] == s.n_owned
+
+    try:
+        m = check_pack_unpack(s, spos, svel, lo, hi, 2, double, deferred=False, route=route, n_neigh=300, seed=80 + route,
+                              between=download_the_stayers)
+        assert m.counts[1] > 0 and m.counts[3] > 0 and m.counts[5] > 0 and len(m.pos) > m.n_owned > m.counts[0]
+    finally:
+        s.close()
+
+
+@pytest.mark.parametrize("double", [False, True])
+@pytest.mark.parametrize("route", [2, 1])
+def test_new_grid_origin_after_in_place_exchange(hip_lib, double, route):
+    """an in-place pack and unpack (the arrays keep their holes), then nrs_set_params with another grid origin: the prepared keys and
+    the queued split are void, the holes are compacted at once — download() gives the model's arrays after the unpack — and the next
+    step hashes and sorts from scratch (no step of the coherent re-sort is counted) and keeps every particle"""
+    s, spos, svel, lo, hi = to_stepped_state(double, route)
+    try:
+        real, p = real_of(double), s.params
+        m = slab_model.partition(p, lo, hi, 2, spos, svel, real, cap=16384, left=False, right=False)
+        want_pos, want_vel, n_owned = slab_model.unpack(m, None, None)
+        assert s.slab_pack(None, None, 16384, want_counts=False) is None
+        s.slab_unpack(None, None, 16384)
+        assert s.get_stat(capi.STAT_SLAB_PARTITION) == route and s.n == len(want_pos) and s.n_owned == n_owned == m.counts[0]
+        q = s.params
+        q["worldOrigin"][0][0] -= real(0.25) * q["cellSize"][0][0]   # a quarter cell: every particle stays inside the grid
+        cx = slab.cell_of(want_pos[:, 0], q["worldOrigin"][0][0], q["cellSize"][0][0], real=real)
+        assert cx.min() >= 1 and cx.max() < int(q["gridSize"][0][0]) - 1
+        s.set_params(q)
+        assert s.n == len(want_pos) and s.n_owned == n_owned
+        gp, gv = s.download()
+        assert np.array_equal(bits(gp), bits(want_pos)) and np.array_equal(bits(gv), bits(want_vel))
+        before = s.resort_stats()
+        s.step(1)
+        assert s.resort_stats() == before
+        gp, gv = s.download()
+        assert len(gp) == len(want_pos) and np.isfinite(gp).all() and np.isfinite(gv).all()
+        assert np.array_equal(np.sort(gv[:, 3]), np.sort(want_vel[:, 3]))   # ids: nobody lost, nobody twice
     finally:
         s.close()
