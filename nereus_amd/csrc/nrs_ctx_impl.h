@@ -6,20 +6,23 @@
 // "unsorted" arrays of step t+1 are the integrated sorted arrays of step t (buffer swap), which is what
 // the reference obtains by copying sorted→host→device.
 //
-// Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the array-state machine, the step plan, the
-// sort stage, the solver tails, the slab code.  Host bookkeeping that depends on none of them lives in plain structs the context
-// holds as members: the body poses (nrs_host_bodies.h), the stage timer (nrs_host_profile.h), the snapshot ring
+// Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the sort stage's launches, the solver tails,
+// the slab code.  Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure
+// functions it calls: the body poses (nrs_host_bodies.h), the stage timer (nrs_host_profile.h), the snapshot ring
 // (nrs_host_snapshot.h), the solver settings and their validation (nrs_host_settings.h), the decisions of the slab exchange — window,
-// partition form, stream totals, unpack offsets — (nrs_host_slab.h).  Every buffer, pinned landing and event frees itself (DevBuf,
-// PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
+// partition form, stream totals, unpack offsets — (nrs_host_slab.h), the state of the particle arrays with its transitions and the
+// sort stage's choice (nrs_host_state.h), the step plan and the exit rule of the solver loops (nrs_host_plan.h).  Every buffer, pinned
+// landing and event frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
 #pragma once
 #include <sched.h>
 #include "nrs_ctx_base.h"
 #include "nrs_host_bodies.h"
+#include "nrs_host_plan.h"
 #include "nrs_host_profile.h"
 #include "nrs_host_settings.h"
 #include "nrs_host_slab.h"
 #include "nrs_host_snapshot.h"
+#include "nrs_host_state.h"
 #include <rocprim/rocprim.hpp>
 
 #include "nrs_kernels_ref.h"
@@ -118,8 +121,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     DevBuf posA, posB, velA, velB, presA, presB, dens, forces;
     DevBuf hashA, hashB, indexA, indexB, inv, sortTmp;
     uint32_t *hashCur = nullptr, *indexCur = nullptr; // sorted keys/values after the sort stage
-    bool hashReady = false;                           // the fused force kernel already wrote the next step's keys/values
-    uint32_t *hashNext = nullptr, *indexNext = nullptr;
+    uint32_t *hashNext = nullptr, *indexNext = nullptr; // the next step's keys/values, once the fused force kernel wrote them (st: hashReady)
     // the buffer of the pair (a, b) that cur is not: where a sort or the next step's keys / values go
     static uint32_t *other(const DevBuf &a, const DevBuf &b, const uint32_t *cur) { return cur == a.as<uint32_t>() ? b.as<uint32_t>() : a.as<uint32_t>(); }
     DevBuf cellStart, cellEnd, bCellStart, bCellEnd;
@@ -187,28 +189,20 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     DevBuf fastQ;             // NRS_FLAG_FAST_ARITH: (p/rho^2, 1/rho) per sorted slot, density kernel -> force kernel
     // coherent re-sort (nrs_kernels_resort.h)
     DevBuf rsMovers, rsMoversAlt, rsStayers, rsMerged, rsTileMovers, rsTileOffset, rsGroupTotal, rsGroupPrefix, rsScalars, rsPrevPacked;
-    bool slotOrderValid = false; // posA/velA are in the slot order of hashCur (a full fused step was the last thing that happened)
     uint32_t *packKeys = nullptr, *packVals = nullptr; // where slab_pack / slab_unpack write the next step's keys / values
     PinnedBuf<uint64_t> rsHostTotal; // (launch number << 32 | mover count), written by k_resort_scan_tiles into pinned, mapped host
     uint64_t *rsHostTotalDev = nullptr; // memory through this device pointer
     uint32_t rsSeq = 0;
     Event rsEvent;
-    bool rsPending = false; // movers/stayers of the keys in hashNext have been split; the count is on its way
     bool splitClearedCells = false; // this step's k_resort_split also reset the cell table
-    uint64_t rsSteps = 0, rsFallbacks = 0;
-    double lastMovers = -1.0; // mover count of the last coherent re-sort
-    bool few_movers(uint64_t M, uint64_t N) const { return M * 100ull <= N * (uint64_t)RESORT_MAX_MOVER_PCT; }
+    ResortStats rs; // steps, fallbacks, mover count of the last coherent re-sort (nrs_host_state.h)
     // slab decomposition
     bool slabOn = false;
     SlabCfg slab = {INT_MIN / 2, INT_MAX / 2, 2};
     DevBuf ghostPos, ghostVel, slabCounts, slabTotals;
     uint64_t nOwned = 0;
     bool cellsClean = false; // cellStart is all-EMPTY
-    bool packedHashValid = false; // packKeys hold the keys of the particles that stayed, for the current grid
-    // fused classification: the force kernel of the last step already wrote stream flags / counts / dead marks for these cuts
-    DevBuf slabFlags;
-    bool classifiedValid = false;
-    uint32_t classifiedN = 0;
+    DevBuf slabFlags; // fused classification: the force kernel's stream flags (st: classifiedValid, classifiedN)
     // slab runs, in-place partition: the owned particles are not compacted; dead slots carry the key 0xffffffff
     DevBuf rsTileDead, rsTileDeadOffset, rsGroupDeadTotal, rsGroupDeadPrefix;
     // page-locked landing place (HT_WORDS words) of what the host reads in an exchange, and the event behind the pack's part of it
@@ -229,8 +223,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!packEvent) HIPCHK(hipEventCreateWithFlags(&packEvent.e, hipEventDisableTiming));
         return NRS_OK;
     }
-    bool holesPending = false; // posA/velA[0, physN) contain dead slots (keys in hashNext tell which); n counts live ones
-    uint32_t physN = 0;        // physical extent of the arrays while holesPending
     bool rsTilesDirty = false; // rsTileMovers holds counts no scan has consumed
     int clean_tile_counts()
     {
@@ -241,63 +233,28 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         rsTilesDirty = false;
         return NRS_OK;
     }
-    bool rsCountKnown = false; // the mover count of the pending split is already on the host (slab runs)
-    uint32_t rsKnownCount = 0;
     bool fusedThisStep = false;
     StageTimer timer; // profiling (nrs_host_profile.h)
 
-    // ---- the state of the particle arrays and of the keys prepared for the next step --------------------------------
-    // The fields above are not independent: they encode ONE of the states below (DESIGN.md §5 has the transition table).
-    // Every public entry point calls validate() first, so a sequence of calls that would leave them inconsistent returns
-    // NRS_E_STATE instead of handing a wrong count or a stale table to a kernel (the GPU memory fault of round 1 was exactly
-    // that: a merge sized with a mover count that had been reset before it was read).
-    enum ArrayState {
-        AS_FRESH,        // arrays compact, any order; the next step hashes and sorts from scratch
-        AS_KEYS_READY,   // + hashNext/indexNext hold the next step's keys/values (fused kernel, or slab pack/unpack)
-        AS_SPLIT_QUEUED, // + their movers/stayers split is queued (coherent re-sort); the count is pending or known
-        AS_SLOT_ORDER,   // slab run after a fused step: arrays in the slot order of hashCur, keys per slot, to be re-partitioned
-        AS_HOLES,        // slab in-place partition: arrays [0, physN) with dead slots, split queued, count known
-        AS_INVALID
-    };
+    // ---- the state of the particle arrays and of the keys prepared for the next step (nrs_host_state.h) ---------------------------
+    // The coupled fields live in `st`: everybody reads them (st.fields()), only its named transitions write them, and array_state()
+    // reads the result back as ONE state.  The device pointers they speak about stay here.
+    ArrayTracker st;
     ArrayState array_state() const
     {
-        if (n > cap || (slabOn && nOwned > n)) return AS_INVALID;
-        if (!slabOn && (holesPending || classifiedValid)) return AS_INVALID;
-        if (hashReady && (!hashNext || !indexNext)) return AS_INVALID;
-        if (rsPending && (!hashReady || !rsMovers.p)) return AS_INVALID;
-        if (rsCountKnown && !rsPending) return AS_INVALID;
-        if (classifiedValid && (!slotOrderValid || !hashCur || !hashNext)) return AS_INVALID;
-        if (slotOrderValid && (!hashCur || !hashNext)) return AS_INVALID;
-        if (holesPending) {
-            if (!(sx.inplace() && hashReady && rsPending && rsCountKnown) || physN < n || physN > cap || rsKnownCount > physN) return AS_INVALID;
-            return AS_HOLES;
-        }
-        if (rsCountKnown && rsKnownCount > n) return AS_INVALID;
-        if (rsPending) return AS_SPLIT_QUEUED;
-        if (hashReady) return AS_KEYS_READY;
-        if (slotOrderValid) return AS_SLOT_ORDER;
-        return AS_FRESH;
+        return nrs::array_state(st.fields(), ArrayFacts{n, cap, nOwned, slabOn, sx.inplace(), hashNext != nullptr, indexNext != nullptr,
+                                                        hashCur != nullptr, rsMovers.p != nullptr});
     }
-    // Transitions.  Every write to the coupled fields above goes through one of these (round 3: the fields used to be set one by one
-    // at ~30 places, which is how a count could be reset before it was read); array_state() reads the result back as ONE state.
-    void drop_prepared_keys() { hashReady = false; rsPending = false; rsCountKnown = false; }   // the keys were consumed, or are void
-    void to_fresh() { drop_prepared_keys(); slotOrderValid = false; classifiedValid = false; } // -> AS_FRESH: compact arrays, any order
-    void keys_ready(uint32_t *h, uint32_t *i) { hashNext = h; indexNext = i; hashReady = true; } // -> AS_KEYS_READY
-    void split_queued() { rsPending = true; }                                                    // -> AS_SPLIT_QUEUED, count still on the device
-    void split_queued_known(uint32_t movers) { rsPending = true; rsCountKnown = true; rsKnownCount = movers; } // ..., count on the host
-    void to_holes(uint32_t extent, uint32_t movers)                                             // -> AS_HOLES (in-place slab partition)
-    {
-        holesPending = true; physN = extent; packedHashValid = true; hashReady = true;
-        split_queued_known(movers);
-    }
+    void keys_ready(uint32_t *h, uint32_t *i) { hashNext = h; indexNext = i; st.keys_ready(); } // -> AS_KEYS_READY
     int validate(const char *where) const
     {
         if (array_state() != AS_INVALID) return NRS_OK;
+        const ArrayFields &f = st.fields();
         char buf[320];
         snprintf(buf, sizeof(buf), "internal state inconsistent at %s (n %llu cap %llu physN %u owned %llu | hashReady %d rsPending %d countKnown %d "
-                 "known %u holes %d inplace %d classified %d slotOrder %d slab %d)", where, (unsigned long long)n, (unsigned long long)cap, physN,
-                 (unsigned long long)nOwned, hashReady, rsPending, rsCountKnown, rsKnownCount, holesPending, sx.inplace(), classifiedValid,
-                 slotOrderValid, slabOn);
+                 "known %u holes %d inplace %d classified %d slotOrder %d slab %d)", where, (unsigned long long)n, (unsigned long long)cap, f.physN,
+                 (unsigned long long)nOwned, f.hashReady, f.rsPending, f.rsCountKnown, f.rsKnownCount, f.holesPending, sx.inplace(),
+                 f.classifiedValid, f.slotOrderValid, slabOn);
         return fail(NRS_E_STATE, buf);
     }
 
@@ -308,79 +265,17 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool dfsph() const { return cfg.solver == NRS_SOLVER_DFSPH; }
     bool pow2_grid() const { return is_pow2(P.gridSize[0]) && is_pow2(P.gridSize[1]) && is_pow2(P.gridSize[2]); }
 
-    // ---- which kernels a step launches ------------------------------------------------------------------------------------
-    // The flag- and type-derived half of the choice is fixed at init() and decides which optional buffers exist (init(),
-    // rebuild_boundary_tables()); plan_step() adds the grid facts of the step.  The launch sites read the plan, nothing else.
-    struct Features {
-        bool listKernels; // the solver has list-driven kernels for this kernel set (IISPH, PCISPH: Muller only, the Monaghan support is 2h)
-        bool lists;       // hitBuf, hitCounts, qpos (+ gatherPos for SESPH)
-        bool fast;        // fastQ
-        bool resort;      // the coherent re-sort buffers
-    };
-    Features features() const
+    // ---- which kernels a step launches (nrs_host_plan.h) -----------------------------------------------------------------------
+    PlanFacts plan_facts() const
     {
-        const uint32_t f = cfg.flags;
-        Features ft;
-        ft.listKernels = sesph() || KSET == KS_MULLER;
-        ft.lists = ft.listKernels && !(f & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_SHARED_LISTS));
-        ft.fast = ft.lists && (f & NRS_FLAG_FAST_ARITH) && sesph() && std::is_same<R, float>::value && KSET == KS_MULLER;
-        ft.resort = !(f & (NRS_FLAG_REFERENCE_ORDER | NRS_FLAG_NO_FUSION | NRS_FLAG_FULL_SORT)) && cap >= RESORT_MIN_PARTICLES;
-        return ft;
+        return PlanFacts{cfg.flags, cfg.solver, KSET == KS_MULLER, std::is_same<R, float>::value, cap, n, qOk, pow2_grid(), nearBitsValid, nb != 0,
+                         slabOn, P.numCells};
     }
-    struct StepPlan {
-        bool ref = true;        // reference-order kernels; none of the fields below except quant
-        bool quant = false;     // the reorder writes qpos and the grid view hands it to the scans
-        bool lists = false;     // the density scan builds hit lists and the gathers after it consume them
-        bool wallTiles = false; // the reorder counts the wall slots per tile ...
-        bool walls = false;     // ... and the wall list is built: the gathers run wall workgroups + interior workgroups
-        bool staged = false;    // SESPH: the LDS-staged density launch
-        bool fast = false;      // SESPH: fast arithmetic in the force walk
-        bool keys = false;      // the step's last launch writes the next step's sort keys (SESPH: the fused force launch)
-        bool resort = false;    // ... and counts the movers: the split of the coherent re-sort is queued behind it
-        bool classify = false;  // ... and classifies for the next slab partition
-        bool watch = false;     // IISPH: the list-driven chain flags non-finite gathers (IisphArrays::nonFinite, iisph_tail)
-    };
+    Features features() const { return plan_features(plan_facts()); }
     // Chosen at the start of every step (step(), nrs_iisph_predict) and held until its end: a host-driven IISPH step spans three calls.
     // iisph_tail replaces it with plan_step(stop, true) for the reference-order repeat of a diverged step.
     StepPlan plan;
-    StepPlan plan_step(int stop, bool ref = false) const
-    {
-        const Features ft = features();
-        StepPlan s;
-        // the tiled kernels assume the power-of-two grids the reference's hash assumes (sph_kernel_impl.cuh:120)
-        s.ref = ref || (cfg.flags & NRS_FLAG_REFERENCE_ORDER) || !pow2_grid();
-        // hit lists are built (and the kernels that consume them used) only when the scan that builds them can run
-        s.quant = ft.lists && qOk;
-        if (s.ref) return s;
-        // SESPH: density -> forces, shared only when the step goes on past the density; IISPH, PCISPH: one scan feeds the chain
-        // (nrs_kernels_iisph.h, nrs_kernels_pcisph.h)
-        s.lists = s.quant && (!sesph() || stop != NRS_STAGE_DENSITY);
-        // LDS-staged density scan (nrs_kernels_staged.h): fp32 SESPH on power-of-two grids.  Measured at 10 M particles it is
-        // SLOWER than the global-memory scan in the exact arithmetic (0.84 vs 0.71 ms: the kernel is bound by vector-instruction
-        // issue, not by the latency the staging removes), and since the quantised scan (0.52 ms) also slower than the
-        // exact path in its own fast arithmetic (0.70-0.88 ms): it runs only when NRS_FLAG_STAGED_SCAN asks for it.
-        s.staged = (cfg.flags & NRS_FLAG_STAGED_SCAN) && std::is_same<R, float>::value && KSET == KS_MULLER && sesph() && s.quant &&
-                   P.numCells <= (1u << 30);
-        // fast arithmetic (reciprocals, rsq, fused multiply-adds) in the FORCE walk: fp32 Muller SESPH with shared lists; the density
-        // kernel (exact) leaves the (p/rho^2, 1/rho) pairs it needs; everything else keeps IEEE arithmetic
-        s.fast = ft.fast && s.lists;
-        // wall workgroups (nrs_kernels_tiled.h): the scan and the gathers over its lists (SESPH forces; IISPH displacement, advection,
-        // pressure, pressure force).  The reorder counts the tiles even when the step stops after the density; the staged launch
-        // has no wall workgroups.
-        s.wallTiles = !(cfg.flags & NRS_FLAG_NO_WALL_WORKGROUPS) && nearBitsValid && nb != 0 && s.quant && !s.staged;
-        s.walls = s.wallTiles && s.lists;
-        // a full step also leaves the next step's sort keys (and the split of the coherent re-sort) — IISPH not in slab runs, whose
-        // arrays are re-partitioned first
-        s.keys = stop == 0 && !(cfg.flags & NRS_FLAG_NO_FUSION) && !(iisph() && slabOn);
-        const bool resort = s.keys && ft.resort && n >= RESORT_MIN_PARTICLES;
-        s.resort = resort && !slabOn;
-        // slab runs: the next partition's classification rides in the same launch (k_slab_count and most of k_slab_scatter then have
-        // nothing left to do)
-        s.classify = resort && slabOn;
-        // (not in slab runs, whose loop the host drives; PCISPH has no reference-order repeat)
-        s.watch = iisph() && s.lists && !slabOn;
-        return s;
-    }
+    StepPlan plan_step(int stop, bool ref = false) const { return nrs::plan_step(plan_facts(), stop, ref); }
 
     // (the members free themselves after this body: the stream has drained by then)
     ~Ctx() override
@@ -550,8 +445,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int invalidate_grid_state()
     {
         NRSCHK(compact_holes());
-        to_fresh();
-        packedHashValid = false; cellsClean = false;
+        st.grid_changed();
+        cellsClean = false;
         return NRS_OK;
     }
     int get_params(void *params) override
@@ -579,7 +474,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (slabOn) nOwned = n; // (until the next partition says otherwise)
         midStep = false;
         iisphPhase = 0; iisphIter = 0; // new particles abandon a host-driven IISPH step that was in progress
-        to_fresh();
+        st.to_fresh();
         return NRS_OK;
     }
     int set_n(uint64_t nn) override
@@ -587,7 +482,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(validate("nrs_set_num_particles"));
         if (nn > cap) return fail(NRS_E_CAPACITY, "n exceeds capacity");
         NRSCHK(compact_holes());
-        if (nn != n) to_fresh();
+        if (nn != n) st.to_fresh();
         if (nn != n) { iisphPhase = 0; iisphIter = 0; } // (the hit lists of a predicted step belong to the old particle set)
         n = nn;
         if (slabOn) nOwned = n;
@@ -839,17 +734,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         const uint32_t N = (uint32_t)n;
         const dim3 g(nblocks(N)), b(BLOCK);
-        if (holesPending) { // in-place slab partition: only the merge path can consume arrays with holes
-            const bool canMerge = hashReady && rsPending && rsCountKnown && stop != NRS_STAGE_HASH && stop != NRS_STAGE_SORT &&
-                                  few_movers(rsKnownCount, n);
-            if (!canMerge) {
-                if (hashReady && rsPending && rsCountKnown) { ++rsSteps; ++rsFallbacks; }
-                NRSCHK(compact_holes()); // also drops the prepared keys: hash and sort from scratch below
-            }
-        }
+        // which of merge, full sort or compact-first this step takes (nrs_host_state.h); the launches below read the choice
+        const SortPrefix c = choose_sort_prefix(st.fields(), stop, n, rs);
+        if (c.compactFirst) NRSCHK(compact_holes()); // also drops the prepared keys: hash and sort from scratch below
         uint32_t *kIn = hashA.as<uint32_t>(), *kAlt = hashB.as<uint32_t>();
         uint32_t *vIn = indexA.as<uint32_t>(), *vAlt = indexB.as<uint32_t>();
-        if (hashReady) { // keys/values of this step were produced by the previous step's fused force kernel
+        if (c.useKeys) { // keys/values of this step were produced by the previous step's fused force kernel
             kIn = hashNext; vIn = indexNext;
             kAlt = other(hashA, hashB, kIn); vAlt = other(indexA, indexB, vIn);
         } else {
@@ -857,40 +747,33 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             hipLaunchKernelGGL((k_hash<R>), g, b, 0, stream, P, posA.as<T4>(), kIn, vIn, N);
             NRSCHK(ev_end());
         }
-        const bool resort = hashReady && rsPending && stop != NRS_STAGE_HASH && stop != NRS_STAGE_SORT;
-        const bool countKnown = rsCountKnown; // (slab runs: the host already has the mover count)
-        drop_prepared_keys(); // (consumed by this step)
+        st.drop_prepared_keys(); // (consumed by this step)
         hashCur = kIn; indexCur = vIn;
         if (stop == NRS_STAGE_HASH) return NRS_OK;
 
         const uint64_t *merged = nullptr;
-        NRSCHK(ev_begin(NRS_STAGE_SORT, resort));
-        if (resort) {
+        NRSCHK(ev_begin(NRS_STAGE_SORT, c.resort));
+        if (c.resort) {
             // the split of these keys into movers / stayers was queued behind the force kernel; its mover count sizes
             // the mover sort and the merge (see nrs_kernels_resort.h)
-            uint32_t M = rsKnownCount;
-            if (!countKnown) NRSCHK(wait_mover_count(&M));
-            ++rsSteps;
-            lastMovers = (double)M;
-            if (M > N) return fail(NRS_E_STATE, "coherent re-sort: mover count exceeds the particle count (stale count)");
-            if (few_movers(M, N)) {
-                if (M == 0) {
-                    merged = rsStayers.as<uint64_t>();
-                } else {
-                    rocprim::double_buffer<uint64_t> mk(rsMovers.as<uint64_t>(), rsMoversAlt.as<uint64_t>());
-                    size_t tmp = sortTmp.bytes;
-                    HIPCHK(sort_movers(sortTmp.p, tmp, mk, (size_t)M, sort_end_bit(), stream));
-                    tmp = sortTmp.bytes;
-                    HIPCHK(rocprim::merge(sortTmp.p, tmp, rsStayers.as<uint64_t>(), mk.current(), rsMerged.as<uint64_t>(), (size_t)(N - M),
-                                          (size_t)M, rocprim::less<uint64_t>(), stream));
-                    merged = rsMerged.as<uint64_t>();
-                }
-            } else {
-                ++rsFallbacks;
+            uint32_t M = c.knownCount; // (slab runs: the host already has the mover count)
+            if (!c.countKnown) NRSCHK(wait_mover_count(&M));
+            SortKind kind;
+            NRSCHK(choose_sort(M, N, rs, kind));
+            if (kind == SortKind::MERGE_STAYERS) {
+                merged = rsStayers.as<uint64_t>();
+            } else if (kind == SortKind::MERGE_MOVERS) {
+                rocprim::double_buffer<uint64_t> mk(rsMovers.as<uint64_t>(), rsMoversAlt.as<uint64_t>());
+                size_t tmp = sortTmp.bytes;
+                HIPCHK(sort_movers(sortTmp.p, tmp, mk, (size_t)M, sort_end_bit(), stream));
+                tmp = sortTmp.bytes;
+                HIPCHK(rocprim::merge(sortTmp.p, tmp, rsStayers.as<uint64_t>(), mk.current(), rsMerged.as<uint64_t>(), (size_t)(N - M),
+                                      (size_t)M, rocprim::less<uint64_t>(), stream));
+                merged = rsMerged.as<uint64_t>();
             }
         }
         if (!merged) {
-            if (!resort) lastMovers = -1.0;
+            if (!c.resort) rs.lastMovers = -1.0;
             rocprim::double_buffer<uint32_t> k(kIn, kAlt);
             rocprim::double_buffer<uint32_t> v(vIn, vAlt);
             size_t tmp = sortTmp.bytes;
@@ -905,7 +788,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ev_begin(NRS_STAGE_REORDER));
         if (!cellsClean) HIPCHK(hipMemsetAsync(cellStart.p, 0xff, (size_t)P.numCells * 4, stream));
         cellsClean = false;
-        holesPending = false; // the gather below reads only live slots
+        st.holes_consumed(); // the gather below reads only live slots
         const uint32_t *nearB = plan.wallTiles ? nearBits.as<uint32_t>() : (const uint32_t *)nullptr;
         qword_t *qp = plan.quant ? qpos.as<qword_t>() : (qword_t *)nullptr;
         if (merged)
@@ -953,10 +836,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // partition: compact them now (stable) and forget the prepared re-sort; the next step hashes and sorts from scratch.
     int compact_holes()
     {
-        if (!holesPending) return NRS_OK;
-        holesPending = false;
-        const uint32_t NP = physN, nTiles = nblocks(NP);
-        drop_prepared_keys(); packedHashValid = false;
+        if (!st.fields().holesPending) return NRS_OK;
+        const uint32_t NP = st.fields().physN, nTiles = nblocks(NP);
+        st.holes_compacted();
         if (!NP) return NRS_OK;
         NRSCHK(clean_tile_counts());
         hipLaunchKernelGGL(k_holes_count, dim3(nTiles), dim3(BLOCK), 0, stream, hashNext, rsTileDead.as<uint32_t>(), NP);
@@ -978,11 +860,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ev_begin(NRS_STAGE_SORT));
         const uint32_t nTiles = nblocks(N);
         NRSCHK(launch_resort_scan(nTiles, false));
-        const bool clear = (uint64_t)P.numCells > 8ull * n; // the step's cell-table reset rides along (see step())
+        const bool clear = sparse_cell_table(P.numCells, n); // the step's cell-table reset rides along (see step())
         hipLaunchKernelGGL((k_resort_split<false>), dim3(nTiles), dim3(BLOCK), 0, stream, hashCur, hashNext, offsets_movers(), offsets_movers(),
                            rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, clear ? cellStart.as<uint32_t>() : (uint32_t *)nullptr);
         splitClearedCells = clear;
-        split_queued();
+        st.split_queued();
         NRSCHK(ev_end());
         return NRS_OK;
     }
@@ -1031,7 +913,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                 fo.prevHash = hashCur;
                 fo.tileMovers = rsTileMovers.as<uint32_t>();
             }
-            classifiedValid = false;
+            st.classification_dropped();
             if (plan.classify) {
                 const uint32_t nbk = std::max<uint32_t>(1u, (N + SLAB_TILE - 1) / SLAB_TILE);
                 NRSCHK(slabFlags.alloc(cap));
@@ -1041,8 +923,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                 fo.slabBlockCounts = slabCounts.as<uint32_t>();
                 fo.slabBlocks = nbk;
                 fo.tileDead = rsTileDead.as<uint32_t>();
-                classifiedValid = true;
-                classifiedN = N;
+                st.classified(N);
                 rsTilesDirty = true; // until a pack's scan consumes the tile counts
             }
         }
@@ -1135,27 +1016,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             else hipLaunchKernelGGL((k_walk_lists<Pass, false>), g, b, 0, stream, pass, G, hit_buffer(), sPos, N, WallList{}, 0u);
         }
     }
-    // The exit rule of the three solver loops: iterate(l) queues iteration l (from 0); after min_iters iterations measure(&e) reads the
-    // error measure back, and the loop stops on e <= eta or at the cap.  fixed: exactly `cap` iterations and nothing read back.
-    template <typename Iterate, typename Measure>
-    int solve_loop(bool fixed, uint32_t minIters, uint32_t cap, double eta, Iterate &&iterate, Measure &&measure, uint32_t *iters, double *err)
-    {
-        uint32_t l = 0;
-        for (;;) {
-            iterate(l);
-            ++l;
-            const bool last = l >= cap;
-            if (fixed) {
-                if (last) break;
-            } else if (l >= minIters || last) {
-                NRSCHK(measure(err));
-                if (last || *err <= eta) break;
-            }
-        }
-        *iters = l;
-        return NRS_OK;
-    }
-
     // The head of an IISPH, PCISPH, PBF or DFSPH step: this step's wall list (timed with the reorder stage, whose tile counts it
     // finishes), then the one neighbourhood scan of the step, whose hit lists drive the rest of the chain (nrs_kernels_iisph.h).  The
     // scan opens `stage`; the caller ends it.
@@ -1762,11 +1622,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
         NRSCHK(slab_refuse_configure(cfg.solver, bodies.n != 0, lo, hi, halo));
-        if (classifiedValid && (slab.lo != lo || slab.hi != hi || slab.halo != halo)) {
-            // the last force kernel classified (and marked dead keys) for the old cuts: partition the slow way once
-            classifiedValid = false;
-            slotOrderValid = false;
-        }
+        // the last force kernel classified (and marked dead keys) for the old cuts: partition the slow way once
+        if (st.fields().classifiedValid && (slab.lo != lo || slab.hi != hi || slab.halo != halo)) st.cuts_changed();
         slab.lo = lo; slab.hi = hi; slab.halo = halo;
         slabOn = true;
         nOwned = n;
@@ -1828,8 +1685,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ghostVel.alloc(sizeof(T4) * mcap));
         NRSCHK(ensure_host_totals());
         NRSCHK(ensure_pack_event());
-        const SlabChoice ch = choose_form(SlabFacts{classifiedValid, slotOrderValid, rsMovers.p != nullptr, hashCur != nullptr, hashNext != nullptr,
-                                                    hashNext != hashCur, classifiedN, N, RESORT_MIN_PARTICLES});
+        const SlabChoice ch = choose_form(SlabFacts{st.fields().classifiedValid, st.fields().slotOrderValid, rsMovers.p != nullptr, hashCur != nullptr,
+                                                    hashNext != nullptr, hashNext != hashCur, st.fields().classifiedN, N, RESORT_MIN_PARTICLES});
         const bool inplace = ch.form != SlabForm::COMPACT, pre = ch.form == SlabForm::PRECLASSIFIED;
         if (N) {
             // pre-classified: the force kernel of the last step classified every slot for these cuts (flags, stream populations per
@@ -1902,15 +1759,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         SlabFinish f;
         const int rc = sx.finish(slabHostTotals + HT_TOTALS, slabHostTotals[HT_SCAN_CHANGED], slabHostTotals[HT_SCAN_DEAD], f);
         if (!f.stored) return rc;
-        to_fresh();
+        st.to_fresh();
         if (f.form != SlabForm::COMPACT) {
             // hashNext / indexNext hold key and slot of every live slot, 0xffffffff marks the dead ones; arrivals are added to the mover
             // count by nrs_slab_unpack
-            to_holes(sx.N, f.movers);
+            st.to_holes(sx.N, f.movers);
         } else {
             if (sx.N) { std::swap(posA.p, posB.p); std::swap(velA.p, velB.p); }
             else { packKeys = hashA.as<uint32_t>(); packVals = indexA.as<uint32_t>(); }
-            packedHashValid = sx.N != 0; // k_slab_scatter hashed the particles that stay (with the current parameters)
+            st.pack_hashed(sx.N != 0); // k_slab_scatter hashed the particles that stay (with the current parameters)
         }
         n = f.n;
         nOwned = n;
@@ -1939,7 +1796,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (hL || hR) HIPCHK(hipStreamSynchronize(stream));
         NRSCHK(finish_pack());
         SlabArrivals ar;
-        NRSCHK(sx.unpack(hL, hR, n, physN, holesPending, mcap, cap, ar));
+        NRSCHK(sx.unpack(hL, hR, n, st.fields().physN, st.fields().holesPending, mcap, cap, ar));
         const unsigned char *bL = (const unsigned char *)recvL, *bR = (const unsigned char *)recvR;
         auto mp = [&](const unsigned char *b) { return (const T4 *)(b + 16); };
         auto mv = [&](const unsigned char *b) { return (const T4 *)(b + 16 + (size_t)mcap * sizeof(T4)); };
@@ -1958,7 +1815,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                                posA.as<T4>(), velA.as<T4>(), packKeys, packVals,
                                compactResort ? rsPrevPacked.as<uint32_t>() : (uint32_t *)nullptr,
                                compactResort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr, (uint32_t)ar.base,
-                               ar.inplace ? rsMovers.as<uint64_t>() : (uint64_t *)nullptr, ar.inplace ? rsKnownCount : 0u);
+                               ar.inplace ? rsMovers.as<uint64_t>() : (uint64_t *)nullptr, ar.inplace ? st.fields().rsKnownCount : 0u);
         HIPCHK(hipGetLastError());
         nOwned = ar.nOwned;
         n = ar.n;
@@ -1966,18 +1823,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             hipLaunchKernelGGL((k_velw_to_pressure<R>), dim3(nblocks(n)), dim3(BLOCK), 0, stream, velA.as<T4>(), presA.as<R>(), (uint32_t)n);
         // pack + unpack have written the radix keys/values of every local particle
         hashNext = packKeys; indexNext = packVals;
-        hashReady = packedHashValid;
-        if (ar.inplace) {
-            physN += (uint32_t)ar.arrivals;
-            rsKnownCount += (uint32_t)ar.arrivals; // every arrival is a mover (k_slab_append put it behind the cell changers)
-        } else if (hashReady && compactResort && n >= RESORT_MIN_PARTICLES) {
+        st.arrivals_appended(ar.inplace, (uint32_t)ar.arrivals);
+        if (!ar.inplace && st.fields().hashReady && compactResort && n >= RESORT_MIN_PARTICLES) {
             // coherent re-sort: the owned particles that stayed in their cell are still in sorted order
             // (the partition and the append have counted the movers of every tile of the new arrays)
             const uint32_t N = (uint32_t)n, nTiles = nblocks(N);
             NRSCHK(launch_resort_scan(nTiles, false));
             hipLaunchKernelGGL((k_resort_split<false>), dim3(nTiles), dim3(BLOCK), 0, stream, rsPrevPacked.as<uint32_t>(), hashNext,
                                offsets_movers(), offsets_movers(), rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, (uint32_t *)nullptr);
-            split_queued_known(sx.totals[ST_CHANGED] + A.start[5]); // everything appended is a mover, and the partition counted the cell changers
+            st.split_queued_known(sx.totals[ST_CHANGED] + A.start[5]); // everything appended is a mover, and the partition counted the cell changers
             rsTilesDirty = false; // the scan resets the counts it reads
         }
         sx.resort = false;
@@ -2009,12 +1863,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
     void resort_stats(uint64_t *steps, uint64_t *fallbacks) override
     {
-        if (steps) *steps = rsSteps;
-        if (fallbacks) *fallbacks = rsFallbacks;
+        if (steps) *steps = rs.steps;
+        if (fallbacks) *fallbacks = rs.fallbacks;
     }
     int get_stat(int which, double *out) override
     {
-        if (which == NRS_STAT_MOVERS) { *out = lastMovers; return NRS_OK; }
+        if (which == NRS_STAT_MOVERS) { *out = rs.lastMovers; return NRS_OK; }
         if (which == NRS_STAT_SLAB_PARTITION) {
             if (!sx.packed) return fail(NRS_E_STATE, "no nrs_slab_pack yet");
             *out = (int)sx.form;
@@ -2067,14 +1921,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // bookkeeping at the end of a completed step (cell-table undo, buffer swaps)
     int end_of_step()
     {
-        if ((uint64_t)P.numCells > 8ull * n) { // big, mostly empty table: undo only the touched cells
+        if (sparse_cell_table(P.numCells, n)) { // big, mostly empty table: undo only the touched cells
             if (!splitClearedCells)
                 hipLaunchKernelGGL(k_clear_cells, dim3(nblocks(n)), dim3(BLOCK), 0, stream, hashCur, cellStart.as<uint32_t>(), (uint32_t)n);
             cellsClean = true;
         }
         // the integrated sorted arrays become the next step's input (replaces D2H + H2D)
         ++stepsDone;
-        slotOrderValid = fusedThisStep; // A holds the new state in the slot order of hashCur
+        st.step_ended(fusedThisStep); // fused: A holds the new state in the slot order of hashCur
         if (!fusedThisStep) { // the fused kernel already wrote the new state into A
             std::swap(posA.p, posB.p);
             std::swap(velA.p, velB.p);

@@ -1,6 +1,8 @@
 // host_parts_main.cpp — stand-alone driver of the library's HIP-free host components (nrs_host_bodies.h, nrs_host_settings.h,
-// nrs_host_slab.h) for tests/test_host_parts_cpu.py: one command per line on stdin, one answer per line on stdout.  Doubles travel as C99 hex floats (or
-// nan / inf), so nothing is rounded on the way.  Built by the test with the host compiler, plain and under the sanitizers.
+// nrs_host_slab.h, nrs_host_state.h, nrs_host_plan.h) for tests/test_host_parts_cpu.py and tests/test_host_state_cpu.py: one command
+// per line on stdin, one answer per line on stdout (the commands that enumerate a cross product themselves answer with one word per
+// case, in the order stated at the command).  Doubles travel as C99 hex floats (or nan / inf), so nothing is rounded on the way.
+// Built by the test with the host compiler, plain and under the sanitizers.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -9,8 +11,10 @@
 #include <vector>
 
 #include "nrs_host_bodies.h"
+#include "nrs_host_plan.h"
 #include "nrs_host_settings.h"
 #include "nrs_host_slab.h"
+#include "nrs_host_state.h"
 
 namespace nrs {
 thread_local std::string g_err;
@@ -25,6 +29,34 @@ static void answer(int rc)
 {
     if (rc == NRS_OK) printf("rc 0\n");
     else printf("rc %d %s\n", rc, g_err.c_str());
+}
+
+// one transition of the tracker: op numbers in the order nrs_host_state.h declares them, a / b its arguments (0 where it has none)
+static void apply(ArrayTracker &t, int op, uint32_t a, uint32_t b)
+{
+    switch (op) {
+    case 0: t.drop_prepared_keys(); break;
+    case 1: t.to_fresh(); break;
+    case 2: t.keys_ready(); break;
+    case 3: t.split_queued(); break;
+    case 4: t.split_queued_known(a); break;
+    case 5: t.to_holes(a, b); break;
+    case 6: t.holes_consumed(); break;
+    case 7: t.holes_compacted(); break;
+    case 8: t.grid_changed(); break;
+    case 9: t.classification_dropped(); break;
+    case 10: t.classified(a); break;
+    case 11: t.cuts_changed(); break;
+    case 12: t.pack_hashed(a != 0); break;
+    case 13: t.arrivals_appended(a != 0, b); break;
+    case 14: t.step_ended(a != 0); break;
+    default: fprintf(stderr, "host_parts_main: unknown transition %d\n", op); exit(2);
+    }
+}
+static unsigned field_bits(const ArrayFields &f)
+{
+    return (f.hashReady ? 1u : 0u) | (f.rsPending ? 2u : 0u) | (f.rsCountKnown ? 4u : 0u) | (f.slotOrderValid ? 8u : 0u) | (f.classifiedValid ? 16u : 0u) |
+           (f.holesPending ? 32u : 0u) | (f.packedHashValid ? 64u : 0u);
 }
 
 int main()
@@ -153,6 +185,117 @@ int main()
             if (rc == NRS_OK)
                 printf("unp %d %u %u %u %u %u %u %llu %llu %llu %llu\n", r.inplace ? 1 : 0, r.start[0], r.start[1], r.start[2], r.start[3], r.start[4],
                        r.start[5], (unsigned long long)r.base, (unsigned long long)r.arrivals, (unsigned long long)r.n, (unsigned long long)r.nOwned);
+        } else if (cmd == "astates") {
+            // astates n cap nOwned physN known: the state for every mask of 12 bits, bit k of the mask being, from 0: hashReady rsPending
+            // rsCountKnown slotOrderValid classifiedValid holesPending | slabOn inplace hashNext indexNext hashCur rsMovers
+            need(5);
+            std::string out(4096, '?');
+            for (unsigned m = 0; m < 4096u; ++m) {
+                auto bit = [&](int k) { return ((m >> k) & 1u) != 0; };
+                ArrayFields f;
+                f.hashReady = bit(0); f.rsPending = bit(1); f.rsCountKnown = bit(2); f.slotOrderValid = bit(3); f.classifiedValid = bit(4);
+                f.holesPending = bit(5); f.physN = (uint32_t)a[3]; f.rsKnownCount = (uint32_t)a[4];
+                const ArrayFacts facts = {(uint64_t)a[0], (uint64_t)a[1], (uint64_t)a[2], bit(6), bit(7), bit(8), bit(9), bit(10), bit(11)};
+                out[m] = (char)('0' + (int)array_state(f, facts));
+            }
+            printf("astates %s\n", out.c_str());
+        } else if (cmd == "seqs") { // seqs depth n cap nOwned (op a b)...: every sequence of 0 .. depth of the given transitions from the
+            // initial fields, shorter ones first, each length in the order of counting with the first transition as the most
+            // significant digit; one line per sequence: field bits, known count, classifiedN, physN, state under the given facts
+            // (slab run, in place, every pointer there)
+            if (a.size() < 4 || (a.size() - 4) % 3) { fprintf(stderr, "host_parts_main: seqs depth n cap nOwned (op a b)...\n"); return 2; }
+            const size_t nops = (a.size() - 4) / 3;
+            const ArrayFacts facts = {(uint64_t)a[1], (uint64_t)a[2], (uint64_t)a[3], true, true, true, true, true, true};
+            for (int len = 0; len <= (int)a[0]; ++len) {
+                size_t total = 1;
+                for (int k = 0; k < len; ++k) total *= nops;
+                for (size_t id = 0; id < total; ++id) {
+                    ArrayTracker t;
+                    size_t div = total;
+                    for (int k = 0; k < len; ++k) {
+                        div /= nops;
+                        const size_t o = (id / div) % nops;
+                        apply(t, (int)a[4 + 3 * o], (uint32_t)a[5 + 3 * o], (uint32_t)a[6 + 3 * o]);
+                    }
+                    const ArrayFields &f = t.fields();
+                    printf("%u %u %u %u %d\n", field_bits(f), f.rsKnownCount, f.classifiedN, f.physN, (int)array_state(f, facts));
+                }
+            }
+            printf("seqs done\n");
+        } else if (cmd == "plans") { // plans flag*7 stop*3 cap*3 n*3 cells*2: features and plan as four hex digits per case, the loops
+            // nested in this order (outermost first): flag mask (bit k = the k-th flag given), solver 0..4, muller, fp32, the mask of
+            // qOk pow2Grid nearBitsValid walls slabOn ref (bit 0..5), stop, cap, n, cells.  Bits of the word, from 0: listKernels lists
+            // fast resort | ref quant lists wallTiles walls staged fast keys resort classify watch
+            need(18);
+            std::string out;
+            out.reserve(128u * 5 * 4 * 64 * 3 * 27 * 2 * 4);
+            static const char hexd[] = "0123456789abcdef";
+            for (unsigned fm = 0; fm < 128u; ++fm) {
+                uint32_t flags = 0;
+                for (int k = 0; k < 7; ++k) if ((fm >> k) & 1u) flags |= (uint32_t)a[k];
+                for (int solver = 0; solver < 5; ++solver)
+                    for (int mu = 0; mu < 2; ++mu)
+                        for (int f32 = 0; f32 < 2; ++f32)
+                            for (unsigned bm = 0; bm < 64u; ++bm)
+                                for (int is = 0; is < 3; ++is)
+                                    for (int ic = 0; ic < 3; ++ic)
+                                        for (int in_ = 0; in_ < 3; ++in_)
+                                            for (int ie = 0; ie < 2; ++ie) {
+                                                const PlanFacts pf = {flags, solver, mu != 0, f32 != 0, (uint64_t)a[10 + ic], (uint64_t)a[13 + in_],
+                                                                      (bm & 1u) != 0, (bm & 2u) != 0, (bm & 4u) != 0, (bm & 8u) != 0, (bm & 16u) != 0,
+                                                                      (uint32_t)a[16 + ie]};
+                                                const Features ft = plan_features(pf);
+                                                const StepPlan s = plan_step(pf, (int)a[7 + is], (bm & 32u) != 0);
+                                                const bool b[15] = {ft.listKernels, ft.lists, ft.fast, ft.resort, s.ref, s.quant, s.lists, s.wallTiles,
+                                                                    s.walls, s.staged, s.fast, s.keys, s.resort, s.classify, s.watch};
+                                                unsigned w = 0;
+                                                for (int k = 0; k < 15; ++k) w |= b[k] ? 1u << k : 0u;
+                                                for (int k = 3; k >= 0; --k) out.push_back(hexd[(w >> (4 * k)) & 15u]);
+                                            }
+            }
+            printf("plans %s\n", out.c_str());
+        } else if (cmd == "sortp") { // sortp holesPending hashReady rsPending rsCountKnown known stop n
+            need(7);
+            ArrayFields f;
+            f.holesPending = a[0] != 0.0; f.hashReady = a[1] != 0.0; f.rsPending = a[2] != 0.0; f.rsCountKnown = a[3] != 0.0;
+            f.rsKnownCount = (uint32_t)a[4];
+            ResortStats rs;
+            const SortPrefix c = choose_sort_prefix(f, (int)a[5], (uint64_t)a[6], rs);
+            printf("sortp %d %d %d %d %u %llu %llu %a\n", c.compactFirst ? 1 : 0, c.useKeys ? 1 : 0, c.resort ? 1 : 0, c.countKnown ? 1 : 0, c.knownCount,
+                   (unsigned long long)rs.steps, (unsigned long long)rs.fallbacks, rs.lastMovers);
+        } else if (cmd == "sortc") { // sortc M N
+            need(2);
+            ResortStats rs;
+            SortKind kind;
+            answer(choose_sort((uint64_t)a[0], (uint64_t)a[1], rs, kind));
+            printf("sortc %d %llu %llu %a\n", (int)kind, (unsigned long long)rs.steps, (unsigned long long)rs.fallbacks, rs.lastMovers);
+        } else if (cmd == "sparse") { // sparse numCells n
+            need(2);
+            printf("sparse %d\n", sparse_cell_table((uint64_t)a[0], (uint64_t)a[1]) ? 1 : 0);
+        } else if (cmd == "loop") {
+            // loop fixed minIters cap eta cross failAt: the error measure is 0.25 from iteration `cross` on (0: never) and 1 + l before;
+            // measure fails after iteration failAt (0: never).  Answers rc, then iterate calls, iters (12345: not written), the last
+            // error, whether iterate got 0, 1, 2, ... and the iterations after which measure was called
+            need(6);
+            uint32_t iterates = 0, iters = 12345u;
+            double err = -1.0;
+            std::vector<uint32_t> measured;
+            uint32_t next = 0;
+            bool ordered = true;
+            const int rc = solve_loop(
+                a[0] != 0.0, (uint32_t)a[1], (uint32_t)a[2], a[3],
+                [&](uint32_t l) { ordered = ordered && l == next++; ++iterates; },
+                [&](double *e) {
+                    measured.push_back(iterates);
+                    if (a[5] != 0.0 && iterates == (uint32_t)a[5]) return fail(NRS_E_HIP, "measure failed");
+                    *e = (a[4] != 0.0 && iterates >= (uint32_t)a[4]) ? 0.25 : 1.0 + (double)iterates;
+                    return (int)NRS_OK;
+                },
+                &iters, &err);
+            answer(rc);
+            printf("loop %u %u %a %d", iterates, iters, err, ordered ? 1 : 0);
+            for (uint32_t l : measured) printf(" %u", l);
+            printf("\n");
         } else {
             fprintf(stderr, "host_parts_main: unknown command '%s'\n", cmd.c_str());
             return 2;
