@@ -11,8 +11,10 @@
 // functions it calls: the body poses (nrs_host_bodies.h), the stage timer (nrs_host_profile.h), the snapshot ring
 // (nrs_host_snapshot.h), the solver settings and their validation (nrs_host_settings.h), the decisions of the slab exchange — window,
 // partition form, stream totals, unpack offsets — (nrs_host_slab.h), the state of the particle arrays with its transitions and the
-// sort stage's choice (nrs_host_state.h), the step plan and the exit rule of the solver loops (nrs_host_plan.h).  Every buffer, pinned
-// landing and event frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
+// sort stage's choice (nrs_host_state.h), the step plan and the exit rule of the solver loops (nrs_host_plan.h), what differs by solver
+// — stages, stale and derived constants, buffers, what an array or statistic id means — with one state struct per solver
+// (nrs_host_solver.h).  Every buffer, pinned landing and event frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only
+// synchronises.
 #pragma once
 #include <sched.h>
 #include "nrs_ctx_base.h"
@@ -22,6 +24,7 @@
 #include "nrs_host_settings.h"
 #include "nrs_host_slab.h"
 #include "nrs_host_snapshot.h"
+#include "nrs_host_solver.h"
 #include "nrs_host_state.h"
 #include <rocprim/rocprim.hpp>
 
@@ -129,43 +132,42 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // boundaries
     DevBuf bSorted, bHash, bIndex, bHashAlt, bIndexAlt;
     uint32_t *bHashCur = nullptr, *bIndexCur = nullptr;
-    // IISPH
+    // the solvers' buffers (BufName, nrs_host_solver.h: which solver allocates which, and what the shared ones hold on each)
     DevBuf densAdv, densCorr, P_l, P_l2, aii, velAdv, forcesAdv, forcesP, diiF, diiB, sumDij, diiSum;
     DevBuf redPartial, redOut;
-    // PCISPH (nrs_kernels_pcisph.h): the two predicted-position buffers (xsCur = the newest) and the density errors the exit test
-    // takes the max of; velAdv, forcesAdv, forcesP, densCorr (rho*) and P_l (p) are shared with the IISPH names
     DevBuf posPred, posPred2, pciErr;
-    PciSettings pciS;
-    bool pciDeltaValid = false; // pciDelta belongs to the current parameters and settings
-    R pciDelta = (R)0;
-    double pciLastErr = -1.0; // max e_i after the last iteration of the last solve (< 0: no solve yet)
-    // PBF (nrs_kernels_pbf.h) shares all of these: posPred / posPred2, pciErr, velAdv, forcesAdv, densCorr (rho*), P_l (lambda), forcesP
-    // (the last correction dx) and pciLastErr
-    PbfSettings pbfS;
-    bool pbfEpsValid = false; // pbfEps belongs to the current parameters and settings
-    R pbfEps = (R)0;
-    uint32_t pbfErrPending = 0; // fixed-count solve: max e over this many particles is formed on request (get_stat), not in the step
-    // PBF tensile correction and vorticity confinement (pbfS); pbfVort holds (omega, |omega|), allocated when confinement is first enabled
-    bool pbfWqValid = false; // pbfWq belongs to the current parameters and dq
-    R pbfWq = (R)0;
-    DevBuf pbfVort;
-    bool pbfVortValid = false; // pbfVort holds the omega of a step
-    // DFSPH (nrs_kernels_dfsph.h; DESIGN.md "DFSPH") shares velAdv, forcesAdv, forcesP (0), densCorr (rho_adv), P_l (kappa), posPred
-    // (the advection launch's x*, unused), pciErr (e of the density solve) and PBF's prototype kernel.  K lives in presA / presB, as
-    // IISPH's warm-start pressure does; Kv in its own pair (dfKvA: slot order of posA, dfKvB: sorted), alpha and the divergence
-    // solve's e in their own buffers.
     DevBuf dfAlpha, dfKvA, dfKvB, dfErrV;
-    DfsphSettings dfS;
-    bool dfThrValid = false; // dfThr belongs to the current parameters
-    R dfThr = (R)0;
-    bool dfAlphaValid = false, dfKvValid = false; // NRS_ARR_DFSPH_ALPHA / _KAPPA_V hold a step's values
-    uint32_t dfDenN = 0, dfDivN = 0; // particles whose e of the last density / divergence iteration pciErr / dfErrV hold (0: none)
-    uint32_t dfDivIters = 0;          // divergence iterations of the last step
-    // Akinci surface tension and adhesion (nrs_kernels_akinci.h; PCISPH, PBF, DFSPH): gamma = beta_a = 0 is off; akNormals holds the
-    // records (n_i, rho_i), allocated when gamma is first set above 0
-    AkinciSettings akS;
-    DevBuf akNormals;
-    bool akNormalsValid = false; // akNormals holds the records of a step
+    DevBuf pbfVort, akNormals; // allocated when confinement is first enabled / gamma is first set above 0
+    // per solver: settings, derived constants, what the last step left (nrs_host_solver.h).  PBF shares pciSt.xs and pciSt.lastErr.
+    PciState<R> pciSt;   // nrs_kernels_pcisph.h
+    PbfState<R> pbfSt;   // nrs_kernels_pbf.h
+    DfsphState<R> dfSt;  // nrs_kernels_dfsph.h; DESIGN.md "DFSPH"
+    AkinciState akSt;    // nrs_kernels_akinci.h; PCISPH, PBF, DFSPH
+    DevBuf *devbuf(BufName b)
+    {
+        switch (b) {
+        case BUF_POS_A: return &posA; case BUF_POS_B: return &posB; case BUF_VEL_A: return &velA; case BUF_VEL_B: return &velB;
+        case BUF_PRES_A: return &presA; case BUF_PRES_B: return &presB; case BUF_DENS: return &dens; case BUF_FORCES: return &forces;
+        case BUF_CELL_START: return &cellStart; case BUF_CELL_END: return &cellEnd; case BUF_B_CELL_START: return &bCellStart;
+        case BUF_B_CELL_END: return &bCellEnd; case BUF_B_SORTED: return &bSorted; case BUF_BD_BODY_SORTED: return &bdBodySorted;
+        case BUF_INV: return &inv; case BUF_DENS_ADV: return &densAdv; case BUF_P_L2: return &P_l2; case BUF_AII: return &aii;
+        case BUF_DII_F: return &diiF; case BUF_DII_B: return &diiB; case BUF_SUM_DIJ: return &sumDij; case BUF_DII_SUM: return &diiSum;
+        case BUF_VEL_ADV: return &velAdv; case BUF_FORCES_ADV: return &forcesAdv; case BUF_FORCES_P: return &forcesP;
+        case BUF_DENS_CORR: return &densCorr; case BUF_P_L: return &P_l; case BUF_POS_PRED: return &posPred; case BUF_POS_PRED2: return &posPred2;
+        case BUF_PCI_ERR: return &pciErr; case BUF_DF_ALPHA: return &dfAlpha; case BUF_DF_KV_A: return &dfKvA; case BUF_DF_KV_B: return &dfKvB;
+        case BUF_DF_ERR_V: return &dfErrV; case BUF_PBF_VORT: return &pbfVort; case BUF_AK_NORMALS: return &akNormals;
+        // no default: -Wswitch names a BufName that is missing here.  The sorted keys / values are pointers into a pair (buf_ptr).
+        case BUF_NONE: case BUF_HASH_CUR: case BUF_INDEX_CUR: case BUF_B_HASH_CUR: case BUF_B_INDEX_CUR: case BUF_COUNT: break;
+        }
+        return nullptr;
+    }
+    void *buf_ptr(BufName b)
+    {
+        switch (b) {
+        case BUF_HASH_CUR: return hashCur; case BUF_INDEX_CUR: return indexCur; case BUF_B_HASH_CUR: return bHashCur; case BUF_B_INDEX_CUR: return bIndexCur;
+        default: { DevBuf *d = devbuf(b); return d ? d->p : nullptr; }
+        }
+    }
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
     HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
@@ -319,29 +321,19 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         HIPCHK(hipMemsetAsync(presB.p, 0, s, stream));
         HIPCHK(hipMemsetAsync(dens.p, 0, s, stream));
         HIPCHK(hipMemsetAsync(forces.p, 0, v, stream));
-        if (iisph()) {
-            NRSCHK(inv.alloc(u));
-            NRSCHK(densAdv.alloc(s)); NRSCHK(densCorr.alloc(s)); NRSCHK(P_l.alloc(s)); NRSCHK(P_l2.alloc(s));
-            NRSCHK(aii.alloc(s));
-            NRSCHK(velAdv.alloc(v)); NRSCHK(forcesAdv.alloc(v)); NRSCHK(forcesP.alloc(v));
-            NRSCHK(diiF.alloc(v)); NRSCHK(diiB.alloc(v)); NRSCHK(sumDij.alloc(v)); NRSCHK(diiSum.alloc(v));
-            DevBuf *z[] = {&densAdv, &densCorr, &P_l, &P_l2, &aii, &velAdv, &forcesAdv, &forcesP, &diiF, &diiB, &sumDij};
-            for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
+        const SolverBufferList own = solver_buffers(cfg.solver);
+        for (const SolverBuffer &b : own) {
+            size_t bytes = 0;
+            switch (b.unit) { // (the table's contract: per-particle units, sized by the capacity)
+            case UNIT_VEC4_N: bytes = v; break;
+            case UNIT_SCALAR_N: bytes = s; break;
+            case UNIT_U32_N: bytes = u; break;
+            case UNIT_U32_CELLS: case UNIT_VEC4_NB: case UNIT_U32_NB: return fail(NRS_E_STATE, "solver_buffers lists a buffer that is not per particle");
+            }
+            NRSCHK(devbuf(b.buf)->alloc(bytes));
         }
-        if (pcisph() || pbf()) { // (no dii / a_ii / sum d_ij p_j, no inverse slot table: the loop skips j == i by sorted slot)
-            NRSCHK(velAdv.alloc(v)); NRSCHK(forcesAdv.alloc(v)); NRSCHK(forcesP.alloc(v));
-            NRSCHK(densCorr.alloc(s)); NRSCHK(P_l.alloc(s));
-            NRSCHK(posPred.alloc(v)); NRSCHK(posPred2.alloc(v)); NRSCHK(pciErr.alloc(s));
-            DevBuf *z[] = {&velAdv, &forcesAdv, &forcesP, &densCorr, &P_l, &posPred, &posPred2, &pciErr};
-            for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
-        }
-        if (dfsph()) { // PCISPH's advection buffers (one predicted-position buffer), and DFSPH's own
-            NRSCHK(velAdv.alloc(v)); NRSCHK(forcesAdv.alloc(v)); NRSCHK(forcesP.alloc(v));
-            NRSCHK(densCorr.alloc(s)); NRSCHK(P_l.alloc(s)); NRSCHK(posPred.alloc(v)); NRSCHK(pciErr.alloc(s));
-            NRSCHK(dfAlpha.alloc(s)); NRSCHK(dfKvA.alloc(s)); NRSCHK(dfKvB.alloc(s)); NRSCHK(dfErrV.alloc(s));
-            DevBuf *z[] = {&velAdv, &forcesAdv, &forcesP, &densCorr, &P_l, &posPred, &pciErr, &dfAlpha, &dfKvA, &dfKvB, &dfErrV};
-            for (DevBuf *b : z) HIPCHK(hipMemsetAsync(b->p, 0, b->bytes, stream));
-        }
+        for (const SolverBuffer &b : own)
+            if (b.zero) HIPCHK(hipMemsetAsync(devbuf(b.buf)->p, 0, devbuf(b.buf)->bytes, stream));
         const Features ft = features();
         if (ft.lists) {
             NRSCHK(hitBuf.alloc((size_t)HIT_CAP * cap * 4));
@@ -419,18 +411,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                               std::memcmp(PU.cellSize, q.cellSize, sizeof(PU.cellSize)) == 0;
         if (!sameGrid) NRSCHK(invalidate_grid_state());
         const uint32_t cellsBefore = P.numCells;
-        // delta (pcisph_prepare) depends on these alone; the host classes set the parameters every step
-        if (q.timestep != PU.timestep || q.particleMass != PU.particleMass || q.restDensity != PU.restDensity ||
-            q.interactionRadius != PU.interactionRadius || q.kpoly_grad != PU.kpoly_grad)
-            pciDeltaValid = false;
-        // ... and eps (pbf_prepare) and DFSPH's threshold (dfsph_prepare) on these
-        if (q.particleMass != PU.particleMass || q.restDensity != PU.restDensity || q.interactionRadius != PU.interactionRadius ||
-            q.kpress_grad != PU.kpress_grad) {
-            pbfEpsValid = false;
-            dfThrValid = false;
-        }
-        // ... and W_q of the tensile correction on these
-        if (q.interactionRadius != PU.interactionRadius || q.kpoly != PU.kpoly) pbfWqValid = false;
+        const StaleConstants stale = stale_after_params(params_key(PU), params_key(q)); // (the host classes set the parameters every step)
+        pciSt.params_changed(stale);
+        pbfSt.params_changed(stale);
+        dfSt.params_changed(stale);
         PU = q;
         if (!sameGrid && slabOn) sx.choose_window(PU.gridSize, slab.lo, slab.hi, slab.halo, true);
         derive_kernel_params();
@@ -448,6 +432,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         st.grid_changed();
         cellsClean = false;
         return NRS_OK;
+    }
+    static ParamsKey params_key(const Params<R> &p)
+    {
+        return ParamsKey{(double)p.timestep, (double)p.particleMass, (double)p.restDensity, (double)p.interactionRadius, (double)p.kpoly,
+                         (double)p.kpoly_grad, (double)p.kpress_grad};
     }
     int get_params(void *params) override
     {
@@ -806,7 +795,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (dfsph()) { // the warm-start inputs of the step, K_prev and Kv_prev, into sorted order
             hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, presA.as<R>(), indexCur, presB.as<R>(), N);
             hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, dfKvA.as<R>(), indexCur, dfKvB.as<R>(), N);
-            dfKvValid = true;
+            dfSt.kvValid = true;
         }
         NRSCHK(ev_end());
         return NRS_OK;
@@ -1199,8 +1188,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
 
     // ---- PCISPH step (nrs_kernels_pcisph.h; DESIGN.md "PCISPH") -------------------------------------------------------------------
-    int pciXs = 0; // which of posPred / posPred2 holds the newest predicted positions
-    void *pci_xs_current() const { return pciXs ? posPred2.p : posPred.p; }
+    void *pci_xs_current() const { return pciSt.xs ? posPred2.p : posPred.p; }
     PciArrays<R> pci_view(int in, int out) const
     {
         PciArrays<R> A;
@@ -1208,34 +1196,28 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         A.densPred = densCorr.as<R>(); A.pres = P_l.as<R>(); A.err = pciErr.as<R>();
         A.xsIn = (in ? posPred2 : posPred).as<T4>();
         A.xsOut = (out ? posPred2 : posPred).as<T4>();
-        A.delta = pciDelta;
+        A.delta = pciSt.delta();
         return A;
     }
     int pcisph_configure(double eta, uint32_t minIters, double spacing, double delta) override
     {
         if (!pcisph()) return fail(NRS_E_STATE, "nrs_pcisph_configure on a context that is not PCISPH");
-        NRSCHK(pciS.set(eta, minIters, spacing, delta));
-        pciDeltaValid = false;
+        NRSCHK(pciSt.s.set(eta, minIters, spacing, delta));
+        pciSt.settings_changed();
         return NRS_OK;
     }
-    // delta = -1 / (beta (-sum g . sum g - sum g . g)), beta = 2 (dt m / rho0)^2, over the prototype's lattice neighbours (k_pci_prototype,
-    // the solver's own W_grad on the device); once per parameter or settings change
+    // delta from the prototype's sums (k_pci_prototype, the solver's own W_grad on the device; pci_delta) unless it was given; once per
+    // parameter or settings change
     int pcisph_prepare()
     {
-        if (pciDeltaValid) return NRS_OK;
-        if (pciS.deltaGiven > 0.0) {
-            pciDelta = (R)pciS.deltaGiven;
-            pciDeltaValid = true;
-            return NRS_OK;
-        }
-        const double m = (double)PU.particleMass, rd = (double)PU.restDensity, dt = (double)PU.timestep;
-        double o[5];
-        NRSCHK(prototype_sums(true, pciS.spacing > 0.0 ? pciS.spacing : std::cbrt(m / rd), "PCISPH", "pressure scale delta", o));
-        const double q = dt * m / rd, beta = 2.0 * q * q;
-        const double d = -1.0 / (beta * (-(o[0] * o[0] + o[1] * o[1] + o[2] * o[2]) - o[3]));
-        if (!std::isfinite(d)) return fail(NRS_E_INVALID, "PCISPH: the prototype gives no finite pressure scale delta");
-        pciDelta = (R)d;
-        pciDeltaValid = true;
+        if (pciSt.delta_valid()) return NRS_OK;
+        const double m = (double)PU.particleMass, rd = (double)PU.restDensity, given = pciSt.s.deltaGiven;
+        double o[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        if (!(given > 0.0))
+            NRSCHK(prototype_sums(true, pciSt.s.spacing > 0.0 ? pciSt.s.spacing : prototype_default_spacing(m, rd), "PCISPH", "pressure scale delta", o));
+        R d;
+        NRSCHK(pci_delta(given, o, (double)PU.timestep, m, rd, &d));
+        pciSt.set_delta(d);
         return NRS_OK;
     }
     int set_surface_akinci(double gamma, double beta) override
@@ -1244,7 +1226,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         AkinciSettings a;
         NRSCHK(a.set(gamma, beta));
         if (gamma > 0.0) NRSCHK(akNormals.alloc(sizeof(T4) * cap));
-        akS = a;
+        akSt.s = a;
         return NRS_OK;
     }
     // the advection launch with the Akinci model on (nrs_kernels_akinci.h); SURF_EFF: the context's fsurf term, off while gamma > 0
@@ -1274,18 +1256,18 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (stop == NRS_STAGE_DENSITY) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_P_ADVECT));
         if (dfsph()) { // the divergence solve on the sorted velocities: the advection reads divergence-free ones
-            dfDivIters = 0;
-            if (dfS.minItersV) NRSCHK((dfsph_solve<HAS_B, false>(velB.as<T4>(), dfKvB.as<R>(), dfErrV.as<R>(), dfS.minItersV, dfS.etaV, &dfDivIters)));
-            dfDivN = dfS.minItersV ? N : 0u;
+            dfSt.divIters = 0;
+            if (dfSt.s.minItersV) NRSCHK((dfsph_solve<HAS_B, false>(velB.as<T4>(), dfKvB.as<R>(), dfErrV.as<R>(), dfSt.s.minItersV, dfSt.s.etaV, &dfSt.divIters)));
+            dfSt.divN = dfSt.s.minItersV ? N : 0u;
         }
-        pciXs = 0;
+        pciSt.xs = 0;
         const PciArrays<R> A0 = pci_view(0, 0);
-        const bool cohesion = akS.gamma > 0.0;
-        if (cohesion || (HAS_B && akS.beta > 0.0)) { // the Akinci model: the normals launch, then the advection launch with its walk
-            const AkinciView<R> K{cohesion ? akNormals.as<T4>() : (T4 *)nullptr, (R)akS.gamma, (R)akS.beta};
+        const bool cohesion = akSt.s.gamma > 0.0;
+        if (cohesion || (HAS_B && akSt.s.beta > 0.0)) { // the Akinci model: the normals launch, then the advection launch with its walk
+            const AkinciView<R> K{cohesion ? akNormals.as<T4>() : (T4 *)nullptr, (R)akSt.s.gamma, (R)akSt.s.beta};
             if (cohesion) {
                 launch_pass<HAS_B>(AkinciNormalsPass<R, KSET>{P, dens.as<R>(), K.normals});
-                akNormalsValid = true;
+                akSt.normalsValid = true;
             }
             if (SURF && !cohesion) akinci_advect<HAS_B, SURF>(A0, K);
             else akinci_advect<HAS_B, false>(A0, K);
@@ -1312,20 +1294,20 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         uint32_t l = 0;
         double err = -1.0;
         NRSCHK(solve_loop(
-            false, pciS.minIters, maxIters ? maxIters : 50u, pciS.eta,
+            false, pciSt.s.minIters, maxIters ? maxIters : 50u, pciSt.s.eta,
             [&](uint32_t) {
-                const PciArrays<R> A = pci_view(pciXs, pciXs ^ 1);
+                const PciArrays<R> A = pci_view(pciSt.xs, pciSt.xs ^ 1);
                 launch_pass<HAS_B>(PciDensityPass<R, KSET>{P, A});
                 if (!plan.lists) // (hand-written, nrs_kernels_pcisph.h)
                     hipLaunchKernelGGL((k_pci_pforce_ref<R, KSET, HAS_B>), g, b, 0, stream, P, grid_view(), A, posB.as<T4>(), N);
                 else if constexpr (KSET == KS_MULLER)
                     launch_listed(k_pci_pforce_lists<R, KSET, HAS_B, true>, k_pci_pforce_lists<R, KSET, HAS_B>, g.x, P, grid_view(), A, hit_buffer(),
                                   posB.as<T4>(), N);
-                pciXs ^= 1;
+                pciSt.xs ^= 1;
             },
             [&](double *e) { return max_of<false>(pciErr.p, N, e); }, &l, &err));
         lastIters = l;
-        pciLastErr = err;
+        pciSt.lastErr = err;
         HIPCHK(hipMemcpyAsync(presB.p, P_l.p, sizeof(R) * N, hipMemcpyDeviceToDevice, stream)); // (the step's pressures, NRS_ARR_PRES)
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
@@ -1340,14 +1322,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         A.dx = forcesP.as<T4>();
         A.xsIn = (in ? posPred2 : posPred).as<T4>();
         A.xsOut = (out ? posPred2 : posPred).as<T4>();
-        A.eps = pbfEps;
+        A.eps = pbfSt.eps();
         return A;
     }
     int pbf_configure(double eta, uint32_t minIters, double relaxation, double xsph) override
     {
         if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_configure on a context that is not PBF");
-        NRSCHK(pbfS.set(eta, minIters, relaxation, xsph));
-        pbfEpsValid = false;
+        NRSCHK(pbfSt.s.set(eta, minIters, relaxation, xsph));
+        pbfSt.settings_changed();
         return NRS_OK;
     }
     // W_q = W((dq h, 0, 0)) on the device (k_pbf_wq), with the current parameters
@@ -1365,71 +1347,60 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int pbf_set_tensile(double k, double dq) override
     {
         if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_set_tensile on a context that is not PBF");
-        PbfSettings t = pbfS;
+        PbfSettings t = pbfSt.s;
         NRSCHK(t.set_tensile(k, dq));
         R wq;
         NRSCHK(pbf_eval_wq(dq, &wq));
-        pbfS = t; pbfWq = wq;
-        pbfWqValid = true;
+        pbfSt.s = t;
+        pbfSt.set_wq(wq);
         return NRS_OK;
     }
     int pbf_set_vorticity(double epsV) override
     {
         if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_set_vorticity on a context that is not PBF");
-        PbfSettings t = pbfS;
+        PbfSettings t = pbfSt.s;
         NRSCHK(t.set_vorticity(epsV));
         if (epsV > 0.0) NRSCHK(pbfVort.alloc(sizeof(T4) * cap));
-        pbfS = t;
+        pbfSt.s = t;
         return NRS_OK;
     }
-    // eps = relaxation * D_proto, D = |sum g|^2 + sum |g|^2 over the neighbours of a prototype particle on the cubic lattice of spacing
-    // cbrt(m / rho0) (k_pbf_prototype, the solver's own gradient on the device); once per parameter or settings change.  W_q likewise.
-    // D_proto = |sum g|^2 + sum |g|^2 of the prototype particle (k_pbf_prototype); `who` and `what` name the caller and its result in
-    // the errors
-    // The five prototype sums (k_pci_prototype: g = W_grad, or k_pbf_prototype: g = (m / rho0) grad W_spiky) of a particle on the cubic
-    // lattice of the given spacing: o[0..2] = sum g, o[3] = sum g . g, o[4] = neighbours (at least one, or an error)
+    // The five prototype sums (nrs_host_solver.h "the derived constants") of a particle on the cubic lattice of the given spacing, by
+    // k_pci_prototype or k_pbf_prototype: the solver's own gradient on the device.  At least one neighbour, or an error.
     int prototype_sums(bool pci, double spacing, const char *who, const char *what, double *o)
     {
         const double h = (double)PU.interactionRadius;
         const R sp = (R)spacing;
-        char buf[200];
-        if (!(sp > (R)0) || !std::isfinite((double)sp) || !(h > 0.0) || h / (double)sp > 64.0) {
-            snprintf(buf, sizeof(buf), "%s: the prototype spacing (default cbrt(m / rho0)) must be positive and at least h / 64", who);
-            return fail(NRS_E_INVALID, buf);
-        }
-        const int kmax = (int)std::ceil(h / (double)sp) + 1;
+        int kmax;
+        NRSCHK(prototype_lattice((double)sp, h, who, &kmax));
         if (pci) hipLaunchKernelGGL((k_pci_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
         else hipLaunchKernelGGL((k_pbf_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(o, redPartial.p, 5 * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        if (o[4] == 0.0) {
-            snprintf(buf, sizeof(buf), "%s: the prototype particle (lattice spacing %g, h %g) has no neighbour within h: no %s", who, (double)sp, h,
-                     what);
-            return fail(NRS_E_INVALID, buf);
-        }
-        return NRS_OK;
+        return prototype_has_neighbours(o, (double)sp, h, who, what);
     }
+    // D of PBF's prototype on the default lattice (eps = relaxation * D, DFSPH's threshold = 1e-6 D)
     int pbf_prototype_d(const char *who, const char *what, double *d)
     {
         double o[5];
-        NRSCHK(prototype_sums(false, std::cbrt((double)PU.particleMass / (double)PU.restDensity), who, what, o));
-        *d = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3];
+        NRSCHK(prototype_sums(false, prototype_default_spacing((double)PU.particleMass, (double)PU.restDensity), who, what, o));
+        *d = prototype_d(o);
         return NRS_OK;
     }
+    // W_q and eps, each once per change of the parameters or settings it depends on
     int pbf_prepare()
     {
-        if (pbfS.tensK > 0.0 && !pbfWqValid) {
-            NRSCHK(pbf_eval_wq(pbfS.tensDq, &pbfWq));
-            pbfWqValid = true;
+        if (pbfSt.s.tensK > 0.0 && !pbfSt.wq_valid()) {
+            R wq;
+            NRSCHK(pbf_eval_wq(pbfSt.s.tensDq, &wq));
+            pbfSt.set_wq(wq);
         }
-        if (pbfEpsValid) return NRS_OK;
+        if (pbfSt.eps_valid()) return NRS_OK;
         double d;
         NRSCHK(pbf_prototype_d("PBF", "eps", &d));
-        const double e = pbfS.relax * d;
-        if (!(e > 0.0) || !std::isfinite(e)) return fail(NRS_E_INVALID, "PBF: the prototype gives no finite positive eps");
-        pbfEps = (R)e;
-        pbfEpsValid = true;
+        R e;
+        NRSCHK(pbf_eps(pbfSt.s.relax, d, &e));
+        pbfSt.set_eps(e);
         return NRS_OK;
     }
     template <bool HAS_B> int pbf_tail(int stop)
@@ -1442,25 +1413,25 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // Jacobi projection: with eta > 0 stop after the iteration l with l >= min_iters and max e <= eta, or at the cap, the max not
         // formed (nor read back) before min_iters; with eta = 0 exactly min_iters iterations and no read-back at all
         NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
-        const bool fixed = pbfS.eta == 0.0;
-        const uint32_t cap = fixed ? pbfS.minIters : (maxIters ? maxIters : 50u);
-        const bool tens = pbfS.tensK > 0.0;
-        const PbfTensile<R> T{(R)pbfS.tensK, pbfWq};
+        const bool fixed = pbfSt.s.eta == 0.0;
+        const uint32_t cap = fixed ? pbfSt.s.minIters : (maxIters ? maxIters : 50u);
+        const bool tens = pbfSt.s.tensK > 0.0;
+        const PbfTensile<R> T{(R)pbfSt.s.tensK, pbfSt.wq()};
         uint32_t l = 0;
         double err = -1.0;
         NRSCHK(solve_loop(
-            fixed, pbfS.minIters, cap, pbfS.eta,
+            fixed, pbfSt.s.minIters, cap, pbfSt.s.eta,
             [&](uint32_t) {
-                const PbfArrays<R> A = pbf_view(pciXs, pciXs ^ 1);
+                const PbfArrays<R> A = pbf_view(pciSt.xs, pciSt.xs ^ 1);
                 launch_pass<HAS_B>(PbfLambdaPass<R, KSET>{P, A});
                 if (tens) launch_pass<HAS_B>(PbfCorrectPass<R, KSET, true>{P, A, T});
                 else launch_pass<HAS_B>(PbfCorrectPass<R, KSET, false>{P, A, {}});
-                pciXs ^= 1;
+                pciSt.xs ^= 1;
             },
             [&](double *e) { return max_of<false>(pciErr.p, N, e); }, &l, &err));
         lastIters = l;
-        pciLastErr = err;
-        pbfErrPending = fixed ? N : 0u;
+        pciSt.lastErr = err;
+        pbfSt.errPending = fixed ? N : 0u;
         HIPCHK(hipMemcpyAsync(presB.p, P_l.p, sizeof(R) * N, hipMemcpyDeviceToDevice, stream)); // (lambda, NRS_ARR_PRES)
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
@@ -1468,15 +1439,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         // and k_pbf_integrate, which overwrites x, follows it.
         NRSCHK(ev_begin(NRS_STAGE_P_INTEGRATE));
         const T4 *xs = (const T4 *)pci_xs_current();
-        const bool xsph = pbfS.xsph > 0.0, vort = pbfS.vortEps > 0.0;
-        if (xsph) launch_pass<HAS_B>(PbfXsphPass<R, KSET>{{}, P, xs, velB.as<T4>(), (R)pbfS.xsph});
+        const bool xsph = pbfSt.s.xsph > 0.0, vort = pbfSt.s.vortEps > 0.0;
+        if (xsph) launch_pass<HAS_B>(PbfXsphPass<R, KSET>{{}, P, xs, velB.as<T4>(), (R)pbfSt.s.xsph});
         // vorticity confinement: omega from u = (x* - x) / dt, then the confinement on the velocity XSPH left (or u); both read x_j
         if (vort) {
             T4 *om = pbfVort.as<T4>();
             const int given = xsph ? 1 : 0;
             launch_pass<HAS_B>(PbfVorticityPass<R, KSET>{{}, P, xs, om});
-            launch_pass<HAS_B>(PbfConfinePass<R, KSET>{{}, P, xs, (const T4 *)om, velB.as<T4>(), given, (R)pbfS.vortEps});
-            pbfVortValid = true;
+            launch_pass<HAS_B>(PbfConfinePass<R, KSET>{{}, P, xs, (const T4 *)om, velB.as<T4>(), given, (R)pbfSt.s.vortEps});
+            pbfSt.vortValid = true;
         }
         return launch_last([&](uint32_t *nh, uint32_t *ni, const uint32_t *prevHash, uint32_t *tileMovers) {
             hipLaunchKernelGGL((k_pbf_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), xs, (xsph || vort) ? 1 : 0, N, nh, ni,
@@ -1491,30 +1462,30 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         DfsphArrays<R> A;
         A.u = u; A.dens = dens.as<R>(); A.alpha = dfAlpha.as<R>(); A.kappa = P_l.as<R>(); A.K = K; A.err = err;
-        A.rhoAdv = densCorr.as<R>(); A.thr = dfThr;
+        A.rhoAdv = densCorr.as<R>(); A.thr = dfSt.threshold();
         return A;
     }
     int dfsph_configure(double eta, uint32_t minIters, double etaV, uint32_t minItersV, int warm) override
     {
         if (!dfsph()) return fail(NRS_E_STATE, "nrs_dfsph_configure on a context that is not DFSPH");
-        NRSCHK(dfS.set(eta, minIters, etaV, minItersV, warm));
+        NRSCHK(dfSt.s.set(eta, minIters, etaV, minItersV, warm));
         return NRS_OK;
     }
     // thr = 1e-6 D_proto, D_proto = |sum g|^2 + sum |g|^2 of PBF's prototype (k_pbf_prototype); once per parameter change
     int dfsph_prepare()
     {
-        if (dfThrValid) return NRS_OK;
+        if (dfSt.threshold_valid()) return NRS_OK;
         double d;
         NRSCHK(pbf_prototype_d("DFSPH", "D_proto", &d));
-        if (!(d > 0.0) || !std::isfinite(d)) return fail(NRS_E_INVALID, "DFSPH: the prototype gives no finite positive D_proto");
-        dfThr = (R)(1e-6 * d);
-        dfThrValid = true;
+        R thr;
+        NRSCHK(dfsph_threshold(d, &thr));
+        dfSt.set_threshold(thr);
         return NRS_OK;
     }
     template <bool HAS_B> void dfsph_factor()
     {
         launch_pass<HAS_B>(DfsphFactorPass<R, KSET>{{P, dfsph_view(nullptr, nullptr, nullptr)}});
-        dfAlphaValid = true;
+        dfSt.alphaValid = true;
     }
     // one A/B pair on u
     template <bool HAS_B, bool DENS> void dfsph_pair(const DfsphArrays<R> &A, int phase)
@@ -1542,10 +1513,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const DfsphArrays<R> A = dfsph_view(u, K, err);
         const bool fixed = eta == 0.0;
         const uint32_t cap = fixed ? minIters : (maxIters ? maxIters : 100u);
-        if (dfS.warm) dfsph_pair<HAS_B, DENS>(A, DFSPH_PHASE_WARM);
+        if (dfSt.s.warm) dfsph_pair<HAS_B, DENS>(A, DFSPH_PHASE_WARM);
         double avg = 0.0;
         return solve_loop(
-            fixed, minIters, cap, eta, [&](uint32_t l) { dfsph_pair<HAS_B, DENS>(A, (l || dfS.warm) ? DFSPH_PHASE_MORE : DFSPH_PHASE_FIRST); },
+            fixed, minIters, cap, eta, [&](uint32_t l) { dfsph_pair<HAS_B, DENS>(A, (l || dfSt.s.warm) ? DFSPH_PHASE_MORE : DFSPH_PHASE_FIRST); },
             [&](double *e) {
                 double acc = 0.0;
                 NRSCHK(reduce_sum(err, N, &acc));
@@ -1562,9 +1533,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!more) return NRS_OK;
         NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
         uint32_t l = 0;
-        NRSCHK((dfsph_solve<HAS_B, true>(velAdv.as<T4>(), presB.as<R>(), pciErr.as<R>(), dfS.minIters, dfS.eta, &l)));
+        NRSCHK((dfsph_solve<HAS_B, true>(velAdv.as<T4>(), presB.as<R>(), pciErr.as<R>(), dfSt.s.minIters, dfSt.s.eta, &l)));
         lastIters = l;
-        dfDenN = N;
+        dfSt.denN = N;
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
         return integrate_adv(NRS_STAGE_P_INTEGRATE);
@@ -1866,48 +1837,40 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (steps) *steps = rs.steps;
         if (fallbacks) *fallbacks = rs.fallbacks;
     }
+    // which statistic an id means on this context, or its refusal: route_stat (nrs_host_solver.h); the device work is here
+    StatFacts stat_facts() const
+    {
+        return StatFacts{cfg.solver, sx.packed, pbfSt.errPending != 0, !(pciSt.lastErr < 0.0), dfSt.denN, dfSt.divN, hitCounts.p != nullptr, n != 0, midStep};
+    }
     int get_stat(int which, double *out) override
     {
-        if (which == NRS_STAT_MOVERS) { *out = rs.lastMovers; return NRS_OK; }
-        if (which == NRS_STAT_SLAB_PARTITION) {
-            if (!sx.packed) return fail(NRS_E_STATE, "no nrs_slab_pack yet");
-            *out = (int)sx.form;
-            return NRS_OK;
+        StatRoute r;
+        NRSCHK(route_stat(which, stat_facts(), r));
+        if (r.formMaxFirst) {
+            NRSCHK(max_of<false>(pciErr.p, pbfSt.errPending, &pciSt.lastErr));
+            pbfSt.errPending = 0;
+            NRSCHK(route_stat(which, stat_facts(), r)); // again, on the maximum just formed: "no PBF solve yet" is tested on that value
         }
-        if (pbf() && (which == NRS_STAT_DENSITY_ERROR || which == NRS_STAT_PBF_EPSILON)) {
-            if (pbfErrPending) { // (fixed-count mode: pciErr still holds the e_i of the last iteration)
-                NRSCHK(max_of<false>(pciErr.p, pbfErrPending, &pciLastErr));
-                pbfErrPending = 0;
-            }
-            if (pciLastErr < 0.0) return fail(NRS_E_STATE, "no PBF solve yet");
-            *out = which == NRS_STAT_DENSITY_ERROR ? pciLastErr : (double)pbfEps;
-            return NRS_OK;
-        }
-        if (which == NRS_STAT_DFSPH_DENSITY_AVG || which == NRS_STAT_DFSPH_DIVERGENCE_AVG || which == NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS ||
-            (dfsph() && which == NRS_STAT_DENSITY_ERROR)) {
-            if (!dfsph()) return fail(NRS_E_STATE, "DFSPH statistic requested from another context");
-            if (which == NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS) { *out = (double)dfDivIters; return NRS_OK; }
-            // formed on request from the e_i the last iteration of the solve left (deterministic: the exit test's own reductions)
-            const bool div = which == NRS_STAT_DFSPH_DIVERGENCE_AVG;
-            const uint32_t cnt = div ? dfDivN : dfDenN;
-            if (!cnt) return fail(NRS_E_STATE, div ? "no DFSPH divergence solve yet (or it is off)" : "no DFSPH density solve yet");
-            void *e = div ? dfErrV.p : pciErr.p;
-            if (which == NRS_STAT_DENSITY_ERROR) return max_of<false>(e, cnt, out);
+        switch (r.kind) {
+        case STAT_MOVER_COUNT: *out = rs.lastMovers; return NRS_OK;
+        case STAT_SLAB_FORM: *out = (int)sx.form; return NRS_OK;
+        case STAT_PBF_ERROR:
+        case STAT_PCI_ERROR: *out = pciSt.lastErr; return NRS_OK;
+        case STAT_PBF_EPS: *out = (double)pbfSt.eps(); return NRS_OK;
+        case STAT_PCI_DELTA: *out = (double)pciSt.delta(); return NRS_OK;
+        case STAT_DFSPH_DIV_ITERS: *out = (double)dfSt.divIters; return NRS_OK;
+        case STAT_DFSPH_MAX: return max_of<false>(r.divergence ? dfErrV.p : pciErr.p, r.count, out);
+        case STAT_DFSPH_AVG: {
             double acc = 0.0;
-            NRSCHK(reduce_sum((const R *)e, cnt, &acc));
-            *out = acc / (double)cnt;
+            NRSCHK(reduce_sum((const R *)(r.divergence ? dfErrV.p : pciErr.p), r.count, &acc));
+            *out = acc / (double)r.count;
             return NRS_OK;
         }
-        if (which == NRS_STAT_DENSITY_ERROR || which == NRS_STAT_PCISPH_DELTA) {
-            if (!pcisph()) return fail(NRS_E_STATE, "PCISPH statistic requested from another context");
-            if (pciLastErr < 0.0) return fail(NRS_E_STATE, "no PCISPH solve yet");
-            *out = which == NRS_STAT_DENSITY_ERROR ? pciLastErr : (double)pciDelta;
-            return NRS_OK;
+        case STAT_HIT_OVERFLOW:
+        case STAT_HIT_MEAN:
+        case STAT_HIT_MAX:
+        case STAT_HIT_UNSTAGED: break;
         }
-        if (which == NRS_STAT_PBF_EPSILON) return fail(NRS_E_STATE, "PBF statistic requested from another context");
-        if (which != NRS_STAT_HIT_OVERFLOW && which != NRS_STAT_HIT_MEAN && which != NRS_STAT_HIT_MAX && which != NRS_STAT_UNSTAGED)
-            return fail(NRS_E_INVALID, "unknown statistic");
-        if (!hitCounts.p || !n || midStep) return fail(NRS_E_STATE, "no shared hit lists (reference-order kernels, or no step yet)");
         const uint32_t N = (uint32_t)n;
         HIPCHK(hipMemsetAsync(redPartial.p, 0, 4 * sizeof(unsigned long long), stream));
         hipLaunchKernelGGL(k_hit_stats, dim3(std::min<uint32_t>(1024u, nblocks(N))), dim3(BLOCK), 0, stream, hitCounts.as<uint32_t>(),
@@ -1915,7 +1878,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         unsigned long long h[4] = {0, 0, 0, 0};
         HIPCHK(hipMemcpyAsync(h, redPartial.p, sizeof(h), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        *out = which == NRS_STAT_HIT_OVERFLOW ? (double)h[0] : (which == NRS_STAT_HIT_MEAN ? (double)h[1] / (double)N : (which == NRS_STAT_HIT_MAX ? (double)h[2] : (double)h[3]));
+        *out = r.kind == STAT_HIT_OVERFLOW ? (double)h[0] : (r.kind == STAT_HIT_MEAN ? (double)h[1] / (double)N : (r.kind == STAT_HIT_MAX ? (double)h[2] : (double)h[3]));
         return NRS_OK;
     }
     // bookkeeping at the end of a completed step (cell-table undo, buffer swaps)
@@ -1933,7 +1896,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             std::swap(posA.p, posB.p);
             std::swap(velA.p, velB.p);
         }
-        if (iisph() || pcisph() || pbf() || dfsph()) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB, PBF its lambda, DFSPH K)
+        if (pressure_swaps(cfg.solver)) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB, PBF its lambda, DFSPH K)
         if (dfsph()) std::swap(dfKvA.p, dfKvB.p);
         return NRS_OK;
     }
@@ -1942,9 +1905,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (iisphPhase) return fail(NRS_E_STATE, "a host-driven IISPH step is in progress (nrs_iisph_finish first)");
         NRSCHK(validate("nrs_step"));
         if (midStep) return fail(NRS_E_STATE, "state is mid-update after nrs_step_partial; upload particles first");
-        const char *const predictive = predictive_solver_name(cfg.solver);
-        if (predictive && stop && !(stop <= NRS_STAGE_DENSITY || (stop >= NRS_STAGE_P_ADVECT && stop <= NRS_STAGE_P_INTEGRATE)))
-            return fail(NRS_E_INVALID, std::string("stage not part of a ") + predictive + " step (HASH .. DENSITY, P_ADVECT .. P_INTEGRATE)");
+        NRSCHK(stage_allowed(cfg.solver, stop));
         if (n == 0) return NRS_OK;
         if (pcisph()) NRSCHK(pcisph_prepare());
         if (pbf()) NRSCHK(pbf_prepare());
@@ -2010,79 +1971,17 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         HIPCHK(hipStreamSynchronize(stream));
         return check_device_error();
     }
+    // which buffer an id means on this context, or its refusal: route_array (nrs_host_solver.h)
     int array(int which, void **dptr, uint64_t *bytes) override
     {
         if (which == NRS_ARR_POS || which == NRS_ARR_VEL) NRSCHK(compact_holes());
-        const uint64_t v = sizeof(T4) * n, s = sizeof(R) * n, u = 4 * n, c = 4ull * P.numCells;
-        void *p = nullptr;
-        uint64_t sz = 0;
-        // after a completed step the sorted arrays ARE the current arrays (buffers were swapped)
-        const bool sortedIsCurrent = !midStep;
-        switch (which) {
-        case NRS_ARR_POS: p = posA.p; sz = v; break;
-        case NRS_ARR_VEL: p = velA.p; sz = v; break;
-        case NRS_ARR_PRESSURE: p = presA.p; sz = s; break;
-        case NRS_ARR_HASH: p = hashCur; sz = u; break;
-        case NRS_ARR_INDEX: p = indexCur; sz = u; break;
-        case NRS_ARR_CELL_START: p = cellStart.p; sz = c; break;
-        case NRS_ARR_CELL_END: p = cellEnd.p; sz = c; break;
-        case NRS_ARR_SORTED_POS: p = sortedIsCurrent ? posA.p : posB.p; sz = v; break;
-        case NRS_ARR_SORTED_VEL: p = sortedIsCurrent ? velA.p : velB.p; sz = v; break;
-        case NRS_ARR_DENS: p = dens.p; sz = s; break;
-        case NRS_ARR_PRES: p = ((iisph() || pcisph() || pbf() || dfsph()) && sortedIsCurrent) ? presA.p : presB.p; sz = s; break;
-        case NRS_ARR_FORCES: p = forces.p; sz = v; break;
-        case NRS_ARR_B_HASH: p = bHashCur; sz = 4 * nb; break;
-        case NRS_ARR_B_INDEX: p = bIndexCur; sz = 4 * nb; break;
-        case NRS_ARR_B_CELL_START: p = nb ? bCellStart.p : nullptr; sz = nb ? c : 0; break;
-        case NRS_ARR_B_CELL_END: p = nb ? bCellEnd.p : nullptr; sz = nb ? c : 0; break;
-        case NRS_ARR_B_SORTED: p = bSorted.p; sz = sizeof(T4) * nb; break;
-        case NRS_ARR_DENS_ADV: p = densAdv.p; sz = s; break;
-        case NRS_ARR_DENS_CORR: p = densCorr.p; sz = s; break;
-        case NRS_ARR_P_L: p = P_l.p; sz = s; break;
-        case NRS_ARR_AII: p = aii.p; sz = s; break;
-        case NRS_ARR_VEL_ADV: p = velAdv.p; sz = v; break;
-        case NRS_ARR_FORCES_ADV: p = forcesAdv.p; sz = v; break;
-        case NRS_ARR_FORCES_P: p = forcesP.p; sz = v; break;
-        case NRS_ARR_DII_FLUID: p = diiF.p; sz = v; break;
-        case NRS_ARR_DII_BOUNDARY: p = diiB.p; sz = v; break;
-        case NRS_ARR_SUM_DIJ: p = sumDij.p; sz = v; break;
-        case NRS_ARR_POS_PRED: p = pci_xs_current(); sz = v; break;
-        case NRS_ARR_VORTICITY:
-            if (!pbf()) return fail(NRS_E_STATE, "PBF array requested from another context");
-            if (!pbfVortValid) return fail(NRS_E_STATE, "no PBF step with vorticity confinement yet");
-            p = pbfVort.p; sz = v; break;
-        case NRS_ARR_NORMALS:
-            if (!pcisph() && !pbf() && !dfsph()) return fail(NRS_E_STATE, "Akinci array requested from a SESPH or IISPH context");
-            if (!akNormalsValid) return fail(NRS_E_STATE, "no step with Akinci surface tension (gamma > 0) yet");
-            p = akNormals.p; sz = v; break;
-        case NRS_ARR_B_BODY:
-            if (!bodies.n) return fail(NRS_E_STATE, "no boundary body assignment (nrs_set_boundary_bodies)");
-            *dptr = bdBodySorted.p; *bytes = 4 * nb; // (not a solver array: none of the per-solver refusals below apply)
-            return NRS_OK;
-        case NRS_ARR_DFSPH_ALPHA:
-        case NRS_ARR_DFSPH_KAPPA_V:
-            if (!dfsph()) return fail(NRS_E_STATE, "DFSPH array requested from another context");
-            if (which == NRS_ARR_DFSPH_ALPHA) {
-                if (!dfAlphaValid) return fail(NRS_E_STATE, "no DFSPH factor launch yet");
-                p = dfAlpha.p;
-            } else {
-                if (!dfKvValid) return fail(NRS_E_STATE, "no DFSPH step yet");
-                p = sortedIsCurrent ? dfKvA.p : dfKvB.p;
-            }
-            sz = s; break;
-        default: return fail(NRS_E_INVALID, "unknown array id");
-        }
-        if (which == NRS_ARR_POS_PRED && !pcisph() && !pbf()) return fail(NRS_E_STATE, "PCISPH / PBF array requested from another context");
-        const bool pciArray = which == NRS_ARR_VEL_ADV || which == NRS_ARR_FORCES_ADV || which == NRS_ARR_FORCES_P ||
-                              which == NRS_ARR_DENS_CORR || which == NRS_ARR_P_L || which == NRS_ARR_POS_PRED || which == NRS_ARR_VORTICITY || which == NRS_ARR_NORMALS;
-        if (pcisph() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PCISPH context");
-        if (pbf() && which >= NRS_ARR_DENS_ADV && !pciArray) return fail(NRS_E_STATE, "IISPH array requested from a PBF context");
-        const bool dfArray = which == NRS_ARR_VEL_ADV || which == NRS_ARR_FORCES_ADV || which == NRS_ARR_FORCES_P || which == NRS_ARR_DENS_CORR ||
-                             which == NRS_ARR_P_L || which == NRS_ARR_DFSPH_ALPHA || which == NRS_ARR_DFSPH_KAPPA_V || which == NRS_ARR_NORMALS;
-        if (dfsph() && which >= NRS_ARR_DENS_ADV && !dfArray) return fail(NRS_E_STATE, "IISPH / PCISPH / PBF array requested from a DFSPH context");
-        if (which >= NRS_ARR_DENS_ADV && sesph()) return fail(NRS_E_STATE, "IISPH array requested from a SESPH context");
-        *dptr = p;
-        *bytes = p ? sz : 0;
+        ArrayRoute r;
+        NRSCHK(route_array(which, ArrayRouteFacts{cfg.solver, midStep, nb != 0, bodies.n != 0, pbfSt.vortValid, akSt.normalsValid, dfSt.alphaValid,
+                                                  dfSt.kvValid, pciSt.xs}, r));
+        const uint64_t count = (r.unit == UNIT_U32_CELLS) ? P.numCells : (r.unit == UNIT_VEC4_NB || r.unit == UNIT_U32_NB) ? nb : n;
+        const uint64_t elem = (r.unit == UNIT_VEC4_N || r.unit == UNIT_VEC4_NB) ? sizeof(T4) : r.unit == UNIT_SCALAR_N ? sizeof(R) : 4;
+        *dptr = buf_ptr(r.buf);
+        *bytes = (*dptr || which == NRS_ARR_B_BODY) ? elem * count : 0;
         return NRS_OK;
     }
 };

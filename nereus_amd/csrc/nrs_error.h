@@ -1,6 +1,6 @@
 // nrs_error.h — the error plumbing of the library without a HIP include: the NRS_* codes, the thread's last error text, fail() and
 // NRSCHK.  nrs_ctx_base.h adds HIPCHK on top; the host components (nrs_host_bodies.h, nrs_host_settings.h, nrs_host_slab.h,
-// nrs_host_state.h, nrs_host_plan.h) need only this, so a plain host compiler builds them.
+// nrs_host_state.h, nrs_host_plan.h, nrs_host_solver.h) need only this, so a plain host compiler builds them.
 #pragma once
 #include <string>
 

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "nrs_error.h"
+#include "nrs_host_solver.h"
 
 namespace nrs {
 
@@ -18,12 +19,6 @@ static inline uint32_t next_pow2(uint32_t v) // sph/sph.cpp:300-311
     v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16;
     v++;
     return v;
-}
-
-// PCISPH, PBF and DFSPH share the stage range of a step (nrs_step_partial) and have no slab decomposition; null for the others
-static inline const char *predictive_solver_name(int solver)
-{
-    return solver == NRS_SOLVER_PCISPH ? "PCISPH" : solver == NRS_SOLVER_PBF ? "PBF" : solver == NRS_SOLVER_DFSPH ? "DFSPH" : nullptr;
 }
 
 // The argument refusals of nrs_slab_configure.  IISPH: every solver iteration consumes two cells of halo validity, the predict stages

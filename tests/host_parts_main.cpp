@@ -1,8 +1,8 @@
 // host_parts_main.cpp — stand-alone driver of the library's HIP-free host components (nrs_host_bodies.h, nrs_host_settings.h,
-// nrs_host_slab.h, nrs_host_state.h, nrs_host_plan.h) for tests/test_host_parts_cpu.py and tests/test_host_state_cpu.py: one command
-// per line on stdin, one answer per line on stdout (the commands that enumerate a cross product themselves answer with one word per
-// case, in the order stated at the command).  Doubles travel as C99 hex floats (or nan / inf), so nothing is rounded on the way.
-// Built by the test with the host compiler, plain and under the sanitizers.
+// nrs_host_slab.h, nrs_host_state.h, nrs_host_plan.h, nrs_host_solver.h) for tests/test_host_parts_cpu.py, tests/test_host_state_cpu.py
+// and tests/test_host_solver_cpu.py: one command per line on stdin, one answer per line on stdout (the commands that enumerate a cross
+// product themselves answer with one word or line per case, in the order stated at the command).  Doubles travel as C99 hex floats (or
+// nan / inf), so nothing is rounded on the way.  Built by the test with the host compiler, plain and under the sanitizers.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -14,6 +14,7 @@
 #include "nrs_host_plan.h"
 #include "nrs_host_settings.h"
 #include "nrs_host_slab.h"
+#include "nrs_host_solver.h"
 #include "nrs_host_state.h"
 
 namespace nrs {
@@ -57,6 +58,48 @@ static unsigned field_bits(const ArrayFields &f)
 {
     return (f.hashReady ? 1u : 0u) | (f.rsPending ? 2u : 0u) | (f.rsCountKnown ? 4u : 0u) | (f.slotOrderValid ? 8u : 0u) | (f.classifiedValid ? 16u : 0u) |
            (f.holesPending ? 32u : 0u) | (f.packedHashValid ? 64u : 0u);
+}
+
+// nrs_host_solver.h: the buffers by the names the context gives them, the units as v / s / u (x n), c (u32 x numCells), vb / ub (x nb)
+static const char *buf_name(BufName b)
+{
+    static const char *const names[] = {
+        "none", "posA", "posB", "velA", "velB", "presA", "presB", "dens", "forces", "hashCur", "indexCur", "cellStart", "cellEnd", "bHashCur",
+        "bIndexCur", "bCellStart", "bCellEnd", "bSorted", "bdBodySorted", "inv", "densAdv", "P_l2", "aii", "diiF", "diiB", "sumDij", "diiSum",
+        "velAdv", "forcesAdv", "forcesP", "densCorr", "P_l", "posPred", "posPred2", "pciErr", "dfAlpha", "dfKvA", "dfKvB", "dfErrV", "pbfVort",
+        "akNormals"};
+    static_assert(sizeof(names) / sizeof(names[0]) == BUF_COUNT, "one name per BufName");
+    return names[b];
+}
+static const char *unit_name(ArrayUnit u)
+{
+    static const char *const names[] = {"v", "s", "u", "c", "vb", "ub"};
+    return names[u];
+}
+static const char *stat_name(StatKind k)
+{
+    static const char *const names[] = {"movers", "slabForm", "pbfError", "pbfEps", "dfDivIters", "dfMax", "dfAvg", "pciError", "pciDelta",
+                                        "hitOverflow", "hitMean", "hitMax", "unstaged"};
+    static_assert(sizeof(names) / sizeof(names[0]) == STAT_HIT_UNSTAGED + 1, "one name per StatKind");
+    return names[k];
+}
+// delta / eps / thr in the context's precision: the neighbour test of the prototype's sums, then the formula
+template <typename R> static void derived(const std::string &cmd, const std::vector<double> &a)
+{
+    int rc;
+    R out = (R)0;
+    if (cmd == "delta") { // delta prec given o0 .. o4 sp h dt m rho0
+        rc = a[1] > 0.0 ? (int)NRS_OK : prototype_has_neighbours(&a[2], a[7], a[8], "PCISPH", "pressure scale delta");
+        if (rc == NRS_OK) rc = pci_delta<R>(a[1], &a[2], a[9], a[10], a[11], &out);
+    } else if (cmd == "eps") { // eps prec relax o0 .. o4 sp h
+        rc = prototype_has_neighbours(&a[2], a[7], a[8], "PBF", "eps");
+        if (rc == NRS_OK) rc = pbf_eps<R>(a[1], prototype_d(&a[2]), &out);
+    } else { // thr prec o0 .. o4 sp h
+        rc = prototype_has_neighbours(&a[1], a[6], a[7], "DFSPH", "D_proto");
+        if (rc == NRS_OK) rc = dfsph_threshold<R>(prototype_d(&a[1]), &out);
+    }
+    if (rc == NRS_OK) printf("rc 0 %a\n", (double)out);
+    else answer(rc);
 }
 
 int main()
@@ -296,6 +339,65 @@ int main()
             printf("loop %u %u %a %d", iterates, iters, err, ordered ? 1 : 0);
             for (uint32_t l : measured) printf(" %u", l);
             printf("\n");
+        } else if (cmd == "stage") { // stage solver stop
+            need(2);
+            answer(stage_allowed((int)a[0], (int)a[1]));
+        } else if (cmd == "stale") { // stale old*7 new*7, each: timestep particleMass restDensity interactionRadius kpoly kpoly_grad kpress_grad
+            need(14);
+            const StaleConstants st = stale_after_params(ParamsKey{a[0], a[1], a[2], a[3], a[4], a[5], a[6]}, ParamsKey{a[7], a[8], a[9], a[10], a[11], a[12], a[13]});
+            printf("stale %d %d %d %d\n", st.delta ? 1 : 0, st.eps ? 1 : 0, st.threshold ? 1 : 0, st.wq ? 1 : 0);
+        } else if (cmd == "delta" || cmd == "eps" || cmd == "thr") {
+            need(cmd == "delta" ? 12 : cmd == "eps" ? 9 : 8);
+            if (a[0] == 64.0) derived<double>(cmd, a);
+            else derived<float>(cmd, a);
+        } else if (cmd == "spacing") { // spacing prec sp h who: the spacing is rounded to the precision first, as the context does
+            need(4);
+            static const char *const who[] = {"PCISPH", "PBF", "DFSPH"};
+            const double sp = a[0] == 64.0 ? a[1] : (double)(float)a[1];
+            int kmax = 0;
+            const int rc = prototype_lattice(sp, a[2], who[(int)a[3]], &kmax);
+            if (rc == NRS_OK) printf("rc 0 %d\n", kmax);
+            else answer(rc);
+        } else if (cmd == "buffers") { // buffers solver: name:unit:zeroed in the order of allocation
+            need(1);
+            printf("buffers");
+            for (const SolverBuffer &b : solver_buffers((int)a[0])) printf(" %s:%s:%d", buf_name(b.buf), unit_name(b.unit), b.zero ? 1 : 0);
+            printf("\n");
+        } else if (cmd == "array") {
+            // array solver: one line "rc buffer unit | message" per case, the loops nested in this order (outermost first): id -1 .. 40,
+            // midStep, walls, bodies, the mask of vortValid normalsValid alphaValid kvValid (bit 0..3), pciXs
+            need(1);
+            for (int which = -1; which <= 40; ++which)
+                for (int mid = 0; mid < 2; ++mid)
+                    for (int walls = 0; walls < 2; ++walls)
+                        for (int bd = 0; bd < 2; ++bd)
+                            for (unsigned m = 0; m < 16u; ++m)
+                                for (int xs = 0; xs < 2; ++xs) {
+                                    ArrayRoute r = {BUF_NONE, UNIT_VEC4_N};
+                                    const int rc = route_array(which, ArrayRouteFacts{(int)a[0], mid != 0, walls != 0, bd != 0, (m & 1u) != 0, (m & 2u) != 0,
+                                                                                      (m & 4u) != 0, (m & 8u) != 0, xs}, r);
+                                    if (rc != NRS_OK) printf("%d - - | %s\n", rc, g_err.c_str());
+                                    else printf("0 %s %s |\n", buf_name(r.buf), r.buf == BUF_NONE ? "0" : unit_name(r.unit));
+                                }
+            printf("array done\n");
+        } else if (cmd == "stat") {
+            // stat solver: one line "rc kind divergence count formMaxFirst | message" per case, the loops nested in this order (outermost first): id
+            // -1 .. 13, packed, pbfErrPending, solved, dfDenN in {0, 7}, dfDivN in {0, 7}, the mask of hitCounts particles midStep (bit 0..2)
+            need(1);
+            for (int which = -1; which <= 13; ++which)
+                for (int packed = 0; packed < 2; ++packed)
+                    for (int pend = 0; pend < 2; ++pend)
+                        for (int solved = 0; solved < 2; ++solved)
+                            for (uint32_t den = 0; den <= 7u; den += 7u)
+                                for (uint32_t dv = 0; dv <= 7u; dv += 7u)
+                                    for (unsigned m = 0; m < 8u; ++m) {
+                                        StatRoute r;
+                                        const int rc = route_stat(which, StatFacts{(int)a[0], packed != 0, pend != 0, solved != 0, den, dv, (m & 1u) != 0,
+                                                                                  (m & 2u) != 0, (m & 4u) != 0}, r);
+                                        if (rc != NRS_OK) printf("%d - 0 0 0 | %s\n", rc, g_err.c_str());
+                                        else printf("0 %s %d %u %d |\n", stat_name(r.kind), r.divergence ? 1 : 0, r.count, r.formMaxFirst ? 1 : 0);
+                                    }
+            printf("stat done\n");
         } else {
             fprintf(stderr, "host_parts_main: unknown command '%s'\n", cmd.c_str());
             return 2;
