@@ -7,18 +7,20 @@
 // the reference obtains by copying sorted→host→device.
 //
 // Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the sort stage's launches, the solver tails,
-// the slab code.  Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure
-// functions it calls: the body poses (nrs_host_bodies.h), the stage timer (nrs_host_profile.h), the snapshot ring
-// (nrs_host_snapshot.h), the solver settings and their validation (nrs_host_settings.h), the decisions of the slab exchange — window,
-// partition form, stream totals, unpack offsets — (nrs_host_slab.h), the state of the particle arrays with its transitions and the
-// sort stage's choice (nrs_host_state.h), the step plan and the exit rule of the solver loops (nrs_host_plan.h), what differs by solver
-// — stages, stale and derived constants, buffers, what an array or statistic id means — with one state struct per solver
-// (nrs_host_solver.h).  Every buffer, pinned landing and event frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only
-// synchronises.
+// the slab code.  The boundary particles, their tables and bodies depend on the precision alone and live in one member, bt
+// (BoundaryTables<R>, nrs_boundary_tables.h), which launches its own builds; the per-step wall list, sized by the fluid, stays here.
+// Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure functions it calls:
+// the stage timer (nrs_host_profile.h), the snapshot ring (nrs_host_snapshot.h), the solver settings and their validation
+// (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
+// form, stream totals, unpack offsets — (nrs_host_slab.h), the state of the particle arrays with its transitions and the sort stage's
+// choice (nrs_host_state.h), the step plan and the exit rule of the solver loops (nrs_host_plan.h), what differs by solver — stages,
+// stale and derived constants, buffers, what an array or statistic id means — with one state struct per solver (nrs_host_solver.h).
+// Every buffer, pinned landing and event frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
 #pragma once
 #include <sched.h>
 #include "nrs_ctx_base.h"
-#include "nrs_host_bodies.h"
+#include "nrs_boundary_tables.h"
+#include "nrs_host_grid.h"
 #include "nrs_host_plan.h"
 #include "nrs_host_profile.h"
 #include "nrs_host_settings.h"
@@ -43,8 +45,6 @@
 #include <climits>
 
 namespace nrs {
-
-static inline uint32_t nblocks(uint64_t n) { return (uint32_t)((n + BLOCK - 1) / BLOCK); }
 
 // Radix sort of (hash, index) pairs.  rocPRIM's onesweep sorts 8 key bits per pass by default, so the 25-27-bit
 // hashes of the dam-break grids take 4 passes; with 9 bits per pass they take 3.
@@ -118,7 +118,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     DevBuf gatherPos; // (x, y, z, p / rho^2), (vx, vy, vz, m / rho) side by side per sorted slot: density kernel -> force kernel of the same step (HitBuffer)
     DevBuf qpos; // one word per sorted slot (+ 4 slots of padding), written by the reorder kernels
     nrs_config cfg;
-    uint64_t cap = 0, n = 0, nb = 0;
+    uint64_t cap = 0, n = 0;
     bool midStep = false; // a partial step left the state mid-update
     // particle state: A = current ("unsorted" input of the next step), B = sorted work arrays
     DevBuf posA, posB, velA, velB, presA, presB, dens, forces;
@@ -127,11 +127,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint32_t *hashNext = nullptr, *indexNext = nullptr; // the next step's keys/values, once the fused force kernel wrote them (st: hashReady)
     // the buffer of the pair (a, b) that cur is not: where a sort or the next step's keys / values go
     static uint32_t *other(const DevBuf &a, const DevBuf &b, const uint32_t *cur) { return cur == a.as<uint32_t>() ? b.as<uint32_t>() : a.as<uint32_t>(); }
-    DevBuf cellStart, cellEnd, bCellStart, bCellEnd;
+    DevBuf cellStart, cellEnd;
     uint32_t cellsAllocated = 0;
-    // boundaries
-    DevBuf bSorted, bHash, bIndex, bHashAlt, bIndexAlt;
-    uint32_t *bHashCur = nullptr, *bIndexCur = nullptr;
+    BoundaryTables<R> bt; // the boundary particles, their tables and bodies (nrs_boundary_tables.h)
     // the solvers' buffers (BufName, nrs_host_solver.h: which solver allocates which, and what the shared ones hold on each)
     DevBuf densAdv, densCorr, P_l, P_l2, aii, velAdv, forcesAdv, forcesP, diiF, diiB, sumDij, diiSum;
     DevBuf redPartial, redOut;
@@ -148,33 +146,47 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         switch (b) {
         case BUF_POS_A: return &posA; case BUF_POS_B: return &posB; case BUF_VEL_A: return &velA; case BUF_VEL_B: return &velB;
         case BUF_PRES_A: return &presA; case BUF_PRES_B: return &presB; case BUF_DENS: return &dens; case BUF_FORCES: return &forces;
-        case BUF_CELL_START: return &cellStart; case BUF_CELL_END: return &cellEnd; case BUF_B_CELL_START: return &bCellStart;
-        case BUF_B_CELL_END: return &bCellEnd; case BUF_B_SORTED: return &bSorted; case BUF_BD_BODY_SORTED: return &bdBodySorted;
+        case BUF_CELL_START: return &cellStart; case BUF_CELL_END: return &cellEnd;
         case BUF_INV: return &inv; case BUF_DENS_ADV: return &densAdv; case BUF_P_L2: return &P_l2; case BUF_AII: return &aii;
         case BUF_DII_F: return &diiF; case BUF_DII_B: return &diiB; case BUF_SUM_DIJ: return &sumDij; case BUF_DII_SUM: return &diiSum;
         case BUF_VEL_ADV: return &velAdv; case BUF_FORCES_ADV: return &forcesAdv; case BUF_FORCES_P: return &forcesP;
         case BUF_DENS_CORR: return &densCorr; case BUF_P_L: return &P_l; case BUF_POS_PRED: return &posPred; case BUF_POS_PRED2: return &posPred2;
         case BUF_PCI_ERR: return &pciErr; case BUF_DF_ALPHA: return &dfAlpha; case BUF_DF_KV_A: return &dfKvA; case BUF_DF_KV_B: return &dfKvB;
         case BUF_DF_ERR_V: return &dfErrV; case BUF_PBF_VORT: return &pbfVort; case BUF_AK_NORMALS: return &akNormals;
-        // no default: -Wswitch names a BufName that is missing here.  The sorted keys / values are pointers into a pair (buf_ptr).
-        case BUF_NONE: case BUF_HASH_CUR: case BUF_INDEX_CUR: case BUF_B_HASH_CUR: case BUF_B_INDEX_CUR: case BUF_COUNT: break;
+        // no default: -Wswitch names a BufName that is missing here.  The sorted keys / values are pointers into a pair, the boundary's
+        // arrays live in bt (buf_ptr).
+        case BUF_NONE: case BUF_HASH_CUR: case BUF_INDEX_CUR: case BUF_COUNT: break;
+        case BUF_B_HASH_CUR: case BUF_B_INDEX_CUR: case BUF_B_CELL_START: case BUF_B_CELL_END: case BUF_B_SORTED: case BUF_BD_BODY_SORTED: break;
         }
         return nullptr;
     }
     void *buf_ptr(BufName b)
     {
+        void *p = nullptr;
+        size_t bytes = 0;
+        if (bt.buffer(b, &p, &bytes)) return p;
         switch (b) {
-        case BUF_HASH_CUR: return hashCur; case BUF_INDEX_CUR: return indexCur; case BUF_B_HASH_CUR: return bHashCur; case BUF_B_INDEX_CUR: return bIndexCur;
+        case BUF_HASH_CUR: return hashCur; case BUF_INDEX_CUR: return indexCur;
         default: { DevBuf *d = devbuf(b); return d ? d->p : nullptr; }
         }
     }
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
     HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
-    // wall-particle deferral (nrs_kernels_tiled.h): static near-boundary bit per cell, this step's wall list
-    DevBuf nearBits, wallList, wallTile, wallTileOffset, wallGroupTotal, wallGroupPrefix, wallScalars, wallMask;
-    bool nearBitsValid = false; // the wall buffers exist and nearBits describes the current grid (rebuild_boundary_tables)
-    WallList wall_view() const { return WallList{nearBits.as<uint32_t>(), hashCur, wallList.as<uint32_t>(), wallScalars.as<uint32_t>() + 1, wallMask.as<unsigned long long>()}; }
+    // wall-particle deferral (nrs_kernels_tiled.h): this step's wall list, from the near-boundary bit per cell that bt keeps
+    DevBuf wallList, wallTile, wallTileOffset, wallGroupTotal, wallGroupPrefix, wallScalars, wallMask;
+    // sized by the fluid capacity; a rest build of the boundary tables calls it where the near bits become valid
+    int ensure_wall_list()
+    {
+        const size_t nTiles = (cap + BLOCK - 1) / BLOCK, nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
+        NRSCHK(wallList.alloc((size_t)cap * 4));
+        NRSCHK(wallTile.alloc(nTiles * 4)); NRSCHK(wallTileOffset.alloc(nTiles * 4));
+        NRSCHK(wallMask.alloc(nTiles * 4 * 8));
+        NRSCHK(wallGroupTotal.alloc(nGroups * 4)); NRSCHK(wallGroupPrefix.alloc(nGroups * 4)); NRSCHK(wallScalars.alloc(16));
+        HIPCHK(hipMemsetAsync(wallScalars.p, 0, 16, stream));
+        return NRS_OK;
+    }
+    WallList wall_view() const { return WallList{bt.near_bits(), hashCur, wallList.as<uint32_t>(), wallScalars.as<uint32_t>() + 1, wallMask.as<unsigned long long>()}; }
     // this step's wall list: tile counts (reorder kernel) -> two-level scan (the re-sort's scan kernel) -> stable compaction
     int build_wall_list(uint32_t N)
     {
@@ -270,7 +282,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // ---- which kernels a step launches (nrs_host_plan.h) -----------------------------------------------------------------------
     PlanFacts plan_facts() const
     {
-        return PlanFacts{cfg.flags, cfg.solver, KSET == KS_MULLER, std::is_same<R, float>::value, cap, n, qOk, pow2_grid(), nearBitsValid, nb != 0,
+        return PlanFacts{cfg.flags, cfg.solver, KSET == KS_MULLER, std::is_same<R, float>::value, cap, n, qOk, pow2_grid(), bt.near_bits_valid(), bt.count() != 0,
                          slabOn, P.numCells};
     }
     Features features() const { return plan_features(plan_facts()); }
@@ -293,14 +305,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (C == 0 || C > (1ull << 31)) return fail(NRS_E_INVALID, "numCells out of range");
         NRSCHK(cellStart.alloc(C * 4));
         NRSCHK(cellEnd.alloc(C * 4));
-        if (nb) {
-            NRSCHK(bCellStart.alloc(C * 4));
-            NRSCHK(bCellEnd.alloc(C * 4));
-        }
+        NRSCHK(bt.alloc_cells(C));
         if (cellsAllocated != C) {
             cellsClean = false;
             HIPCHK(hipMemsetAsync(cellEnd.p, 0, C * 4, stream));
-            if (nb) HIPCHK(hipMemsetAsync(bCellEnd.p, 0, C * 4, stream));
+            NRSCHK(bt.zero_cell_ends(C, stream));
             cellsAllocated = (uint32_t)C;
         }
         return NRS_OK;
@@ -420,7 +429,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         derive_kernel_params();
         const bool regrid = P.numCells != cellsBefore;
         if (regrid) NRSCHK(alloc_cells());
-        if (!sameGrid && nb) NRSCHK(rebuild_boundary_tables()); // the boundary hashes / cell table depend on origin, cell size and extents
+        if (!sameGrid) NRSCHK(rebuild_boundary_tables()); // the boundary hashes / cell table depend on origin, cell size and extents
         return NRS_OK;
     }
     // The grid (origin, cell size or extents) is about to change: every key computed for the old grid is void — the
@@ -479,201 +488,48 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
     uint64_t get_n() override { return n; }
 
-    // ---- boundaries: SPH::updateGpuBoundaries / updateGrid (sph/sph.cpp:313-337, 391-432) ----------
-    std::vector<T4> hostBi;
-    std::vector<R> hostVbi;
-
-    uint32_t sort_end_bit() const
+    // ---- boundaries: the state and the builds live in bt (nrs_boundary_tables.h); here: what the context tells it, and the grid rule ---
+    uint32_t sort_end_bit() const { return sort_key_bits(P.numCells); }
+    BoundaryGrid<R> boundary_grid()
     {
-        uint32_t bits = 1;
-        while (bits < 32 && (1ull << bits) < (uint64_t)P.numCells) ++bits;
-        return bits;
+        return BoundaryGrid<R>{P, sort_end_bit(), features().listKernels && pow2_grid(), stream, [this] { return ensure_wall_list(); }};
     }
-
+    // the tables at the uploaded positions, on the current grid (the boundary hashes / cell table depend on origin, cell size and extents)
     int rebuild_boundary_tables()
     {
-        if (!nb) return NRS_OK;
+        if (!bt.count()) return NRS_OK;
         NRSCHK(alloc_cells());
-        DevBuf dBi, dVbi;
-        NRSCHK(dBi.alloc(sizeof(T4) * nb));
-        NRSCHK(dVbi.alloc(sizeof(R) * nb));
-        HIPCHK(hipMemcpyAsync(dBi.p, hostBi.data(), sizeof(T4) * nb, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(dVbi.p, hostVbi.data(), sizeof(R) * nb, hipMemcpyHostToDevice, stream));
-        NRSCHK(bHash.alloc(4 * nb)); NRSCHK(bIndex.alloc(4 * nb)); NRSCHK(bHashAlt.alloc(4 * nb)); NRSCHK(bIndexAlt.alloc(4 * nb));
-        NRSCHK(bSorted.alloc(sizeof(T4) * nb));
-        hipLaunchKernelGGL((k_hash<R>), dim3(nblocks(nb)), dim3(BLOCK), 0, stream, P, dBi.as<T4>(), bHash.as<uint32_t>(),
-                           bIndex.as<uint32_t>(), (uint32_t)nb);
-        size_t tmp = 0;
-        rocprim::double_buffer<uint32_t> k(bHash.as<uint32_t>(), bHashAlt.as<uint32_t>());
-        rocprim::double_buffer<uint32_t> v(bIndex.as<uint32_t>(), bIndexAlt.as<uint32_t>());
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, k, v, (size_t)nb, 0u, sort_end_bit(), stream));
-        DevBuf t;
-        NRSCHK(t.alloc(tmp));
-        HIPCHK(rocprim::radix_sort_pairs(t.p, tmp, k, v, (size_t)nb, 0u, sort_end_bit(), stream));
-        bHashCur = k.current();
-        bIndexCur = v.current();
-        HIPCHK(hipMemsetAsync(bCellStart.p, 0xff, (size_t)P.numCells * 4, stream));
-        hipLaunchKernelGGL((k_reorder_boundary<R>), dim3(nblocks(nb)), dim3(BLOCK), 0, stream, bHashCur, bIndexCur,
-                           dBi.as<T4>(), dVbi.as<R>(), bSorted.as<T4>(), bCellStart.as<uint32_t>(),
-                           bCellEnd.as<uint32_t>(), (uint32_t)nb);
-        nearBitsValid = false;
-        if (features().listKernels && pow2_grid()) {
-            const size_t words = ((size_t)P.numCells + 31) / 32;
-            NRSCHK(nearBits.alloc(words * 4));
-            const size_t nTiles = (cap + BLOCK - 1) / BLOCK, nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
-            NRSCHK(wallList.alloc((size_t)cap * 4));
-            NRSCHK(wallTile.alloc(nTiles * 4)); NRSCHK(wallTileOffset.alloc(nTiles * 4));
-            NRSCHK(wallMask.alloc(nTiles * 4 * 8));
-            NRSCHK(wallGroupTotal.alloc(nGroups * 4)); NRSCHK(wallGroupPrefix.alloc(nGroups * 4)); NRSCHK(wallScalars.alloc(16));
-            HIPCHK(hipMemsetAsync(wallScalars.p, 0, 16, stream));
-            HIPCHK(hipMemsetAsync(nearBits.p, 0, words * 4, stream));
-            hipLaunchKernelGGL((k_mark_near_boundary<R>), dim3(nblocks(nb)), dim3(BLOCK), 0, stream, P, bHashCur, (uint32_t)nb, nearBits.as<uint32_t>());
-            nearBitsValid = true;
-        }
-        if (bodies.n) { // the tables above hold the REST poses: sorted ids for them, and a rebuild at the poses before the next step
-            hipLaunchKernelGGL(k_gather_body, dim3(nblocks(nb)), dim3(BLOCK), 0, stream, bIndexCur, bdBodyOf.as<uint32_t>(), bdBodySorted.as<uint32_t>(),
-                               (uint32_t)nb);
-            HIPCHK(hipMemsetAsync(bdVel.p, 0, sizeof(T4) * nb, stream));
-            bodies.dirty = bodies.displaced();
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream));
-        return NRS_OK;
-    }
-
-    // ---- kinematic boundary bodies (nrs_kernels_bodies.h; DESIGN.md "Kinematic boundary bodies") ------------------------------------
-    // The poses live in `bodies` (host, double: nrs_host_bodies.h); only while it is moving does a step touch the boundary tables.
-    BodyPoses bodies;
-    bool movingStep = false; // this step rebuilt the tables: DFSPH's A launches take the wall velocities
-    DevBuf bdRest, bdVbi, bdBodyOf, bdWorld, bdBodySorted, bdVel, bdSortTmp;
-    void clear_bodies() { bodies.clear(); movingStep = false; }
-    size_t body_sort_bytes(unsigned bits)
-    {
-        size_t tmp = 0;
-        rocprim::double_buffer<uint32_t> k(bHash.as<uint32_t>(), bHashAlt.as<uint32_t>());
-        rocprim::double_buffer<uint32_t> v(bIndex.as<uint32_t>(), bIndexAlt.as<uint32_t>());
-        if (rocprim::radix_sort_pairs(nullptr, tmp, k, v, (size_t)nb, 0u, bits, stream) != hipSuccess) return 0;
-        return tmp;
+        return bt.build_at_rest(boundary_grid());
     }
     int set_boundary_bodies(const uint32_t *bodyOf, uint64_t nbGiven, uint32_t nbodies) override
     {
         NRSCHK(refuse_mid_iisph("nrs_set_boundary_bodies"));
-        if (!nb) return fail(NRS_E_STATE, "nrs_set_boundary_bodies before nrs_set_boundaries");
-        if (!bodyOf || nbodies <= 1) { // clear: the walls return to the uploaded positions
-            const bool had = bodies.n != 0;
-            const bool displaced = had && (bodies.displaced() || bodies.dirty);
-            clear_bodies();
-            if (displaced) NRSCHK(rebuild_boundary_tables());
-            return NRS_OK;
-        }
-        if (slabOn) return fail(NRS_E_INVALID, "slab contexts have no boundary bodies");
-        if (nbGiven != nb) return fail(NRS_E_INVALID, "nb differs from the context's boundary particle count");
-        if (nbodies > (uint32_t)NRS_MAX_BODIES) return fail(NRS_E_INVALID, "more than NRS_MAX_BODIES bodies");
-        double sum[NRS_MAX_BODIES][3] = {{0.0}};
-        uint64_t cnt[NRS_MAX_BODIES] = {0};
-        for (uint64_t i = 0; i < nb; ++i) {
-            const uint32_t k = bodyOf[i];
-            if (k >= nbodies) return fail(NRS_E_INVALID, "body id >= nbodies");
-            sum[k][0] += (double)hostBi[i].x; sum[k][1] += (double)hostBi[i].y; sum[k][2] += (double)hostBi[i].z;
-            ++cnt[k];
-        }
-        const bool displaced = bodies.n && (bodies.displaced() || bodies.dirty);
-        clear_bodies();
-        if (displaced) NRSCHK(rebuild_boundary_tables()); // (a new assignment starts from the rest poses)
-        NRSCHK(bdRest.alloc(sizeof(T4) * nb)); NRSCHK(bdVbi.alloc(sizeof(R) * nb)); NRSCHK(bdBodyOf.alloc(4 * nb));
-        NRSCHK(bdWorld.alloc(sizeof(T4) * nb)); NRSCHK(bdBodySorted.alloc(4 * nb)); NRSCHK(bdVel.alloc(sizeof(T4) * nb));
-        const size_t tmp = std::max(body_sort_bytes(sort_end_bit()), body_sort_bytes(32u));
-        if (!tmp) return fail(NRS_E_HIP, "rocprim::radix_sort_pairs: no temporary storage size for the boundary sort");
-        NRSCHK(bdSortTmp.alloc(tmp));
-        HIPCHK(hipMemcpyAsync(bdRest.p, hostBi.data(), sizeof(T4) * nb, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(bdVbi.p, hostVbi.data(), sizeof(R) * nb, hipMemcpyHostToDevice, stream));
-        HIPCHK(hipMemcpyAsync(bdBodyOf.p, bodyOf, 4 * nb, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_gather_body, dim3(nblocks(nb)), dim3(BLOCK), 0, stream, bIndexCur, bdBodyOf.as<uint32_t>(), bdBodySorted.as<uint32_t>(),
-                           (uint32_t)nb);
-        HIPCHK(hipMemsetAsync(bdVel.p, 0, sizeof(T4) * nb, stream));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(stream)); // the caller may reuse body_of on return
-        bodies.init(nbodies, sum, cnt);
-        return NRS_OK;
+        return bt.set_bodies(bodyOf, nbGiven, nbodies, slabOn, boundary_grid());
     }
-    int set_body_velocity(uint32_t body, const double *v, const double *omega) override { return bodies.set_velocity(body, v, omega); }
-    int set_body_pose(uint32_t body, const double *x, const double *q) override { return bodies.set_pose(body, x, q); }
-    int get_body_pose(uint32_t body, double *x, double *q) override { return bodies.get_pose(body, x, q); }
-    // Start of a step of a moving context: advance the poses (host, double), round the table to SReal, rebuild the boundary tables on
-    // the stream.  No synchronisation, no allocation, no read-back.  Timed as NRS_STAGE_HASH.
-    int advance_bodies_and_rebuild()
-    {
-        movingStep = bodies.moving();
-        if (!movingStep) return NRS_OK;
-        bodies.advance((double)PU.timestep);
-        BodyTable<R> T;
-        std::memset(&T, 0, sizeof(T));
-        for (uint32_t k = 1; k < bodies.n; ++k) {
-            const BodyPoses::Body &b = bodies.b[k];
-            double rot[9];
-            bodies.rotation(k, rot);
-            BodyPose<R> &o = T.b[k];
-            for (int a = 0; a < 9; ++a) o.rot[a] = (R)rot[a];
-            for (int a = 0; a < 3; ++a) { o.x[a] = (R)b.x[a]; o.c[a] = (R)b.c[a]; o.v[a] = (R)b.v[a]; o.w[a] = (R)b.w[a]; }
-        }
-        const uint32_t NB = (uint32_t)nb;
-        const unsigned bits = sort_end_bit();
-        if (body_sort_bytes(bits) > bdSortTmp.bytes || (size_t)P.numCells * 4 > bCellStart.bytes)
-            return fail(NRS_E_STATE, "boundary bodies: the grid outgrew the storage sized at nrs_set_boundary_bodies (assign the bodies again)");
-        NRSCHK(ev_begin(NRS_STAGE_HASH));
-        hipLaunchKernelGGL((k_boundary_pose_hash<R>), dim3(nblocks(NB)), dim3(BLOCK), 0, stream, P, T, bdRest.as<T4>(), bdVbi.as<R>(),
-                           bdBodyOf.as<uint32_t>(), bdWorld.as<T4>(), bHash.as<uint32_t>(), bIndex.as<uint32_t>(), NB);
-        rocprim::double_buffer<uint32_t> k(bHash.as<uint32_t>(), bHashAlt.as<uint32_t>());
-        rocprim::double_buffer<uint32_t> v(bIndex.as<uint32_t>(), bIndexAlt.as<uint32_t>());
-        size_t tmp = bdSortTmp.bytes;
-        HIPCHK(rocprim::radix_sort_pairs(bdSortTmp.p, tmp, k, v, (size_t)NB, 0u, bits, stream));
-        bHashCur = k.current();
-        bIndexCur = v.current();
-        HIPCHK(hipMemsetAsync(bCellStart.p, 0xff, (size_t)P.numCells * 4, stream));
-        hipLaunchKernelGGL((k_reorder_boundary_bodies<R>), dim3(nblocks(NB)), dim3(BLOCK), 0, stream, bHashCur, bIndexCur, T, bdWorld.as<T4>(),
-                           bdBodyOf.as<uint32_t>(), bSorted.as<T4>(), bdBodySorted.as<uint32_t>(), bdVel.as<T4>(), bCellStart.as<uint32_t>(),
-                           bCellEnd.as<uint32_t>(), NB);
-        if (nearBitsValid) {
-            HIPCHK(hipMemsetAsync(nearBits.p, 0, (((size_t)P.numCells + 31) / 32) * 4, stream));
-            hipLaunchKernelGGL((k_mark_near_boundary<R>), dim3(nblocks(NB)), dim3(BLOCK), 0, stream, P, bHashCur, NB, nearBits.as<uint32_t>());
-        }
-        HIPCHK(hipGetLastError());
-        NRSCHK(ev_end());
-        bodies.dirty = false;
-        return NRS_OK;
-    }
+    int set_body_velocity(uint32_t body, const double *v, const double *omega) override { return bt.set_body_velocity(body, v, omega); }
+    int set_body_pose(uint32_t body, const double *x, const double *q) override { return bt.set_body_pose(body, x, q); }
+    int get_body_pose(uint32_t body, double *x, double *q) override { return bt.get_body_pose(body, x, q); }
+    int advance_bodies_and_rebuild() { return bt.advance_and_rebuild(P, (double)PU.timestep, sort_end_bit(), timer, profMask, stream); }
 
+    // Everything that can be refused is decided from the incoming arrays before anything is stored: a refused call changes nothing.
     int set_boundaries(const void *bi4, const void *vbi, uint64_t nbNew, int update_grid) override
     {
         NRSCHK(refuse_mid_iisph("nrs_set_boundaries"));
         if (nbNew > (uint64_t)HIT_INDEX) return fail(NRS_E_INVALID, "too many boundary particles (max 2^27-1)");
         if (nbNew && (!bi4 || !vbi)) return fail(NRS_E_INVALID, "bi4/vbi is NULL");
-        nb = nbNew;
-        clear_bodies(); // (a new set of boundary particles has no body assignment)
-        hostBi.assign((const T4 *)bi4, (const T4 *)bi4 + nb);
-        hostVbi.assign((const R *)vbi, (const R *)vbi + nb);
-        if (!nb) { nearBitsValid = false; return NRS_OK; }
-        if (update_grid) {
+        const bool regrid = nbNew && update_grid;
+        AabbGrid<R> g;
+        if (regrid) { // BBMin/BBMax (sph_cuda.cu:461-505) + SPH::updateGrid (sph.cpp:313-337): nrs_host_grid.h
+            R mn[3], mx[3];
+            aabb_of_points((const R *)bi4, nbNew, mn, mx);
+            NRSCHK(grid_from_aabb(mn, mx, PU.interactionRadius, g));
+        }
+        bt.set_particles(bi4, vbi, nbNew); // (a new set of boundary particles has no body assignment)
+        if (!nbNew) return NRS_OK;
+        if (regrid) {
             NRSCHK(invalidate_grid_state());
-            // BBMin/BBMax (sph_cuda.cu:461-505) + SPH::updateGrid (sph.cpp:313-337)
-            R mn[3] = {hostBi[0].x, hostBi[0].y, hostBi[0].z}, mx[3] = {hostBi[0].x, hostBi[0].y, hostBi[0].z};
-            for (uint64_t i = 1; i < nb; ++i) {
-                const R c[3] = {hostBi[i].x, hostBi[i].y, hostBi[i].z};
-                for (int a = 0; a < 3; ++a) {
-                    if (c[a] < mn[a]) mn[a] = c[a];
-                    if (mx[a] < c[a]) mx[a] = c[a];
-                }
-            }
-            uint32_t g[3];
-            for (int a = 0; a < 3; ++a) {
-                PU.worldOrigin[a] = (R)(mn[a] - 0.1);
-                const uint32_t sz = (uint32_t)std::ceil((mx[a] - mn[a] + 0.1) / PU.interactionRadius);
-                g[a] = next_pow2(sz);
-            }
-            const uint64_t C = (uint64_t)g[0] * g[1] * g[2];
-            if (C > (1ull << 31)) return fail(NRS_E_INVALID, "grid from boundary AABB exceeds 2^31 cells");
-            PU.gridSize[0] = g[0]; PU.gridSize[1] = g[1]; PU.gridSize[2] = g[2];
-            PU.numCells = (uint32_t)C;
+            for (int a = 0; a < 3; ++a) { PU.worldOrigin[a] = g.origin[a]; PU.gridSize[a] = g.size[a]; }
+            PU.numCells = g.numCells;
             if (slabOn) sx.choose_window(PU.gridSize, slab.lo, slab.hi, slab.halo, true);
             derive_kernel_params();
         }
@@ -695,8 +551,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         GridView<R> G;
         G.cellStart = cellStart.as<uint32_t>(); G.cellEnd = cellEnd.as<uint32_t>();
-        G.bCellStart = bCellStart.as<uint32_t>(); G.bCellEnd = bCellEnd.as<uint32_t>();
-        G.sB = bSorted.as<T4>();
+        G.bCellStart = bt.cell_start(); G.bCellEnd = bt.cell_end();
+        G.sB = bt.sorted();
         G.actLo = INT_MIN;
         G.actHi = INT_MAX;
         G.nSorted = (uint32_t)n;
@@ -778,7 +634,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!cellsClean) HIPCHK(hipMemsetAsync(cellStart.p, 0xff, (size_t)P.numCells * 4, stream));
         cellsClean = false;
         st.holes_consumed(); // the gather below reads only live slots
-        const uint32_t *nearB = plan.wallTiles ? nearBits.as<uint32_t>() : (const uint32_t *)nullptr;
+        const uint32_t *nearB = plan.wallTiles ? bt.near_bits() : (const uint32_t *)nullptr;
         qword_t *qp = plan.quant ? qpos.as<qword_t>() : (qword_t *)nullptr;
         if (merged)
             hipLaunchKernelGGL((k_reorder_merged<R>), g, b, 0, stream, merged, hashCur, indexCur, posA.as<T4>(), velA.as<T4>(),
@@ -1491,9 +1347,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     template <bool HAS_B, bool DENS> void dfsph_pair(const DfsphArrays<R> &A, int phase)
     {
         const DfsphPassBase<R, KSET> base{P, A};
-        const bool moving = HAS_B && movingStep; // A with the wall velocities (DfsphDivPass's MOVING); B is unchanged
+        const bool moving = HAS_B && bt.moving_step(); // A with the wall velocities (DfsphDivPass's MOVING); B is unchanged
         if constexpr (HAS_B) {
-            if (moving) launch_pass<HAS_B>(DfsphDivPass<R, KSET, DENS, true>{base, bdVel.as<T4>(), phase});
+            if (moving) launch_pass<HAS_B>(DfsphDivPass<R, KSET, DENS, true>{base, bt.wall_velocities(), phase});
         }
         if (!moving) launch_pass<HAS_B>(DfsphDivPass<R, KSET, DENS>{base, {}, phase});
         const uint32_t N = (uint32_t)n; // B: hand-written (nrs_kernels_dfsph.h)
@@ -1553,7 +1409,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             plan = plan_step(0);
             NRSCHK(advance_bodies_and_rebuild());
             NRSCHK(stage_prefix(0));
-            if (nb) NRSCHK(iisph_predict<true>(0)); else NRSCHK(iisph_predict<false>(0));
+            if (bt.count()) NRSCHK(iisph_predict<true>(0)); else NRSCHK(iisph_predict<false>(0));
             iisphPhase = 1;
             return NRS_OK;
         }
@@ -1561,7 +1417,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (phase == 1) { // one iteration + the density-error sum over the particles this rank owns
             if (slabOn && (int)iisphIter >= slabMaxIters())
                 return fail(NRS_E_STATE, "IISPH slab run: more solver iterations than the halo width supports (halo >= 2 * iterations + 4 cells)");
-            if (nb) NRSCHK(iisph_iteration<true>()); else NRSCHK(iisph_iteration<false>());
+            if (bt.count()) NRSCHK(iisph_iteration<true>()); else NRSCHK(iisph_iteration<false>());
             const uint32_t N = (uint32_t)n, nbk = std::min<uint32_t>(1024u, nblocks(N));
             unsigned long long *cnt = (unsigned long long *)((char *)redOut.p); // redOut: [double sum][u64 count]
             HIPCHK(hipMemsetAsync(redOut.p, 0, 16, stream));
@@ -1580,7 +1436,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         // finish
         if (iisphIter == 0) return fail(NRS_E_STATE, "nrs_iisph_iterate at least once before nrs_iisph_finish");
-        if (nb) NRSCHK(iisph_finish<true>(0)); else NRSCHK(iisph_finish<false>(0));
+        if (bt.count()) NRSCHK(iisph_finish<true>(0)); else NRSCHK(iisph_finish<false>(0));
         HIPCHK(hipGetLastError());
         NRSCHK(end_of_step());
         iisphPhase = 0;
@@ -1592,7 +1448,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int slab_configure(int lo, int hi, int halo) override
     {
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
-        NRSCHK(slab_refuse_configure(cfg.solver, bodies.n != 0, lo, hi, halo));
+        NRSCHK(slab_refuse_configure(cfg.solver, bt.has_bodies(), lo, hi, halo));
         // the last force kernel classified (and marked dead keys) for the old cuts: partition the slow way once
         if (st.fields().classifiedValid && (slab.lo != lo || slab.hi != hi || slab.halo != halo)) st.cuts_changed();
         slab.lo = lo; slab.hi = hi; slab.halo = halo;
@@ -1606,7 +1462,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             if (P.numCells != cellsBefore || P.numBodies != baseBefore) {
                 cellsAllocated = 0; // (same size, other columns: the tables still have to be reset)
                 NRSCHK(alloc_cells());
-                if (nb) NRSCHK(rebuild_boundary_tables());
+                NRSCHK(rebuild_boundary_tables());
             }
         }
         return NRS_OK;
@@ -1917,11 +1773,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(advance_bodies_and_rebuild());
             NRSCHK(stage_prefix(stop));
             if (stop && stop <= NRS_STAGE_REORDER) { midStep = true; break; }
-            if (iisph()) { if (nb) NRSCHK(iisph_tail<true>(stop)); else NRSCHK(iisph_tail<false>(stop)); }
-            else if (pcisph()) { if (nb) NRSCHK(pcisph_tail<true>(stop)); else NRSCHK(pcisph_tail<false>(stop)); }
-            else if (pbf()) { if (nb) NRSCHK(pbf_tail<true>(stop)); else NRSCHK(pbf_tail<false>(stop)); }
-            else if (dfsph()) { if (nb) NRSCHK(dfsph_tail<true>(stop)); else NRSCHK(dfsph_tail<false>(stop)); }
-            else { if (nb) NRSCHK(sesph_tail<true>(stop)); else NRSCHK(sesph_tail<false>(stop)); }
+            if (iisph()) { if (bt.count()) NRSCHK(iisph_tail<true>(stop)); else NRSCHK(iisph_tail<false>(stop)); }
+            else if (pcisph()) { if (bt.count()) NRSCHK(pcisph_tail<true>(stop)); else NRSCHK(pcisph_tail<false>(stop)); }
+            else if (pbf()) { if (bt.count()) NRSCHK(pbf_tail<true>(stop)); else NRSCHK(pbf_tail<false>(stop)); }
+            else if (dfsph()) { if (bt.count()) NRSCHK(dfsph_tail<true>(stop)); else NRSCHK(dfsph_tail<false>(stop)); }
+            else { if (bt.count()) NRSCHK(sesph_tail<true>(stop)); else NRSCHK(sesph_tail<false>(stop)); }
             HIPCHK(hipGetLastError());
             if (stop) { midStep = true; break; }
             NRSCHK(end_of_step());
@@ -1976,9 +1832,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         if (which == NRS_ARR_POS || which == NRS_ARR_VEL) NRSCHK(compact_holes());
         ArrayRoute r;
-        NRSCHK(route_array(which, ArrayRouteFacts{cfg.solver, midStep, nb != 0, bodies.n != 0, pbfSt.vortValid, akSt.normalsValid, dfSt.alphaValid,
+        NRSCHK(route_array(which, ArrayRouteFacts{cfg.solver, midStep, bt.count() != 0, bt.has_bodies(), pbfSt.vortValid, akSt.normalsValid, dfSt.alphaValid,
                                                   dfSt.kvValid, pciSt.xs}, r));
-        const uint64_t count = (r.unit == UNIT_U32_CELLS) ? P.numCells : (r.unit == UNIT_VEC4_NB || r.unit == UNIT_U32_NB) ? nb : n;
+        const uint64_t count = (r.unit == UNIT_U32_CELLS) ? P.numCells : (r.unit == UNIT_VEC4_NB || r.unit == UNIT_U32_NB) ? bt.count() : n;
         const uint64_t elem = (r.unit == UNIT_VEC4_N || r.unit == UNIT_VEC4_NB) ? sizeof(T4) : r.unit == UNIT_SCALAR_N ? sizeof(R) : 4;
         *dptr = buf_ptr(r.buf);
         *bytes = (*dptr || which == NRS_ARR_B_BODY) ? elem * count : 0;

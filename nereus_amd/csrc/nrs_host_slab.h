@@ -9,17 +9,10 @@
 #include <string>
 
 #include "nrs_error.h"
+#include "nrs_host_grid.h"
 #include "nrs_host_solver.h"
 
 namespace nrs {
-
-static inline uint32_t next_pow2(uint32_t v) // sph/sph.cpp:300-311
-{
-    v--;
-    v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16;
-    v++;
-    return v;
-}
 
 // The argument refusals of nrs_slab_configure.  IISPH: every solver iteration consumes two cells of halo validity, the predict stages
 // three and the pressure force one: 2 iterations — the reference's minimum — need 8 cells.

@@ -163,6 +163,7 @@ struct AkinciState { // gamma = beta_a = 0 is off
 enum BufName {
     BUF_NONE, // a null pointer
     BUF_POS_A, BUF_POS_B, BUF_VEL_A, BUF_VEL_B, BUF_PRES_A, BUF_PRES_B, BUF_DENS, BUF_FORCES, BUF_HASH_CUR, BUF_INDEX_CUR, BUF_CELL_START, BUF_CELL_END,
+    // the boundary's: owned by BoundaryTables (nrs_boundary_tables.h), which maps these six names to pointers itself (buffer())
     BUF_B_HASH_CUR, BUF_B_INDEX_CUR, BUF_B_CELL_START, BUF_B_CELL_END, BUF_B_SORTED, BUF_BD_BODY_SORTED,
     // IISPH only
     BUF_INV, BUF_DENS_ADV, BUF_P_L2, BUF_AII, BUF_DII_F, BUF_DII_B, BUF_SUM_DIJ, BUF_DII_SUM,

@@ -54,6 +54,7 @@ template <typename R> NRS_DEV bool slab_active(const Params<R> &P, const GridVie
 }
 
 constexpr int BLOCK = 256;
+static inline uint32_t nblocks(uint64_t n) { return (uint32_t)((n + BLOCK - 1) / BLOCK); } // workgroups of BLOCK threads over n items
 
 // ---- calcHashD (sph_kernel_impl.cuh:127-145) -------------------------------------------------------
 template <typename R>

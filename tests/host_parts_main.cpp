@@ -1,5 +1,5 @@
 // host_parts_main.cpp — stand-alone driver of the library's HIP-free host components (nrs_host_bodies.h, nrs_host_settings.h,
-// nrs_host_slab.h, nrs_host_state.h, nrs_host_plan.h, nrs_host_solver.h) for tests/test_host_parts_cpu.py, tests/test_host_state_cpu.py
+// nrs_host_slab.h, nrs_host_state.h, nrs_host_plan.h, nrs_host_solver.h, nrs_host_grid.h) for tests/test_host_parts_cpu.py, tests/test_host_state_cpu.py
 // and tests/test_host_solver_cpu.py: one command per line on stdin, one answer per line on stdout (the commands that enumerate a cross
 // product themselves answer with one word or line per case, in the order stated at the command).  Doubles travel as C99 hex floats (or
 // nan / inf), so nothing is rounded on the way.  Built by the test with the host compiler, plain and under the sanitizers.
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "nrs_host_bodies.h"
+#include "nrs_host_grid.h"
 #include "nrs_host_plan.h"
 #include "nrs_host_settings.h"
 #include "nrs_host_slab.h"
@@ -100,6 +101,21 @@ template <typename R> static void derived(const std::string &cmd, const std::vec
     }
     if (rc == NRS_OK) printf("rc 0 %a\n", (double)out);
     else answer(rc);
+}
+
+// grid prec h n x y z ...: the bounding box of the n points and the grid it asks for, in the context's precision (the numbers given are
+// values of that precision).  Answers rc, then origin, extents and cell count: of a grid holding 7 everywhere if the call refused
+template <typename R> static void grid(const std::vector<double> &a)
+{
+    const uint64_t n = (uint64_t)a[2];
+    std::vector<R> p4(4 * n, (R)1);
+    for (uint64_t i = 0; i < n; ++i)
+        for (int c = 0; c < 3; ++c) p4[4 * i + c] = (R)a[3 + 3 * i + c];
+    R mn[3], mx[3];
+    aabb_of_points(p4.data(), n, mn, mx);
+    AabbGrid<R> g = {{(R)7, (R)7, (R)7}, {7u, 7u, 7u}, 7u};
+    answer(grid_from_aabb(mn, mx, (R)a[1], g));
+    printf("grid %a %a %a %u %u %u %u\n", (double)g.origin[0], (double)g.origin[1], (double)g.origin[2], g.size[0], g.size[1], g.size[2], g.numCells);
 }
 
 int main()
@@ -312,6 +328,13 @@ int main()
             SortKind kind;
             answer(choose_sort((uint64_t)a[0], (uint64_t)a[1], rs, kind));
             printf("sortc %d %llu %llu %a\n", (int)kind, (unsigned long long)rs.steps, (unsigned long long)rs.fallbacks, rs.lastMovers);
+        } else if (cmd == "grid") {
+            if (a.size() < 6 || a[2] < 1.0 || a.size() != 3 + 3 * (size_t)a[2]) { fprintf(stderr, "host_parts_main: grid prec h n (x y z) * n\n"); return 2; }
+            if (a[0] == 64.0) grid<double>(a);
+            else grid<float>(a);
+        } else if (cmd == "keybits") { // keybits numCells
+            need(1);
+            printf("keybits %u\n", sort_key_bits((uint32_t)a[0]));
         } else if (cmd == "sparse") { // sparse numCells n
             need(2);
             printf("sparse %d\n", sparse_cell_table((uint64_t)a[0], (uint64_t)a[1]) ? 1 : 0);

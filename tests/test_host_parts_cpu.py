@@ -14,6 +14,10 @@ program (tests/host_parts_main.cpp) built with the host compiler, -ffp-contract=
     overflow after storing) and the arithmetic of the unpack (header and capacity refusals at the limit and one over, piece offsets,
     n and n_owned).  The expectations restate the rule of the commit before the header existed (its nrs_ctx_impl.h: choose_window,
     slab_configure, slab_pack, finish_pack, slab_unpack); nothing is read from the code under test.
+  * the grid nrs_set_boundaries makes from the boundary particles' bounding box (nrs_host_grid.h), in both precisions, hex-float
+    exact against the rule of the commit before the header existed (its nrs_ctx_impl.h, set_boundaries) restated here: a single
+    point, extents that are whole multiples of h and one ulp to either side, extents whose cell count lands on a power of two and
+    just over it, negative coordinates, exactly 2^31 cells (accepted) and 2^32 (refused, with the text, and nothing written).
   * the same program once more under -fsanitize=address,undefined (a host program of its own: nothing is preloaded).
 """
 import os
@@ -448,6 +452,91 @@ def check_slab_unpack(exe):
     assert unpack(exe, INPLACE, 5, (3, 4), (2, 6), 92, 102, 1, 10, 121) == ((E_CAPACITY, T_CONTEXT), None)
 
 
+# ---- the grid from the boundary AABB (nrs_host_grid.h) ----------------------------------------------------------------------------
+T_GRID = "grid from boundary AABB exceeds 2^31 cells"
+
+
+def grid_model(real, pts, h):
+    """set_boundaries of the commit before: SReal min / max, origin = (SReal)(min - 0.1), extent = next_pow2((uint32)ceil((max - min
+    + 0.1) / h)) with max - min in SReal and the rest in double; None beyond 2^31 cells"""
+    pts = np.asarray(pts, real).reshape(-1, 3)
+    mn, mx = pts.min(axis=0), pts.max(axis=0)
+    origin = (mn.astype(np.float64) - 0.1).astype(real)
+    size = []
+    for a in range(3):
+        sz = int(np.ceil((np.float64(real(mx[a] - mn[a])) + 0.1) / np.float64(real(h))))
+        v = (sz - 1) & 0xFFFFFFFF
+        for k in (1, 2, 4, 8, 16):
+            v |= v >> k
+        size.append((v + 1) & 0xFFFFFFFF)
+    cells = size[0] * size[1] * size[2]
+    return None if cells > 2 ** 31 else (origin, size, cells)
+
+
+def straddle(real, k, h):
+    """the two neighbouring SReal extents e0 < e1 with ceil((e0 + 0.1) / h) = k and ceil((e1 + 0.1) / h) = k + 1"""
+    q = lambda e: int(np.ceil((np.float64(e) + 0.1) / np.float64(real(h))))
+    e = real(k * np.float64(real(h)) - 0.1)
+    while q(e) > k:
+        e = np.nextafter(e, real(-np.inf))
+    while q(np.nextafter(e, real(np.inf))) <= k:
+        e = np.nextafter(e, real(np.inf))
+    return e, np.nextafter(e, real(np.inf))
+
+
+def grid_cases(real):
+    h = 0.0457
+    up, dn = (lambda v: np.nextafter(real(v), real(np.inf))), (lambda v: np.nextafter(real(v), real(-np.inf)))
+    cases = [(h, [(1.0, 2.0, 3.0)]),                                               # a single point: ceil(0.1 / h) = 3 -> 4 cells
+             (h, [(-3.25, -0.5, -7.0), (-1.0, -0.25, -6.5), (-2.0, -0.4, -6.75)]),  # negative coordinates, min and max in different points
+             (0.125, [(0.0, 0.0, 0.0), (1.0, 2.0, 4.0)])]                          # extents 8 h, 16 h, 32 h exactly: (e + 0.1) / h = 8.8, 16.8, 32.8
+    cases += [(0.125, [(0.0, 0.0, 0.0), (f(1.0), f(2.0), f(4.0))]) for f in (up, dn)]  # ... and one ulp to either side
+    for k in (16, 64):                                                             # ceil = 2^m: that many cells; one ulp more: twice as many
+        e0, e1 = straddle(real, k, h)
+        cases += [(h, [(0.5, -1.0, 0.0), (0.5 + 0.0, -1.0, e)]) for e in (e0, e1)]
+        cases += [(h, [(0.0, 0.0, 0.0), (e, 1.0, 1.0)]) for e in (e0, e1)]
+    cases += [(1.0, [(-700.0, 0.0, 0.0), (800.0, 900.0, 900.0)]),                  # 2048 x 1024 x 1024 = 2^31 cells: accepted
+              (1.0, [(-700.0, 0.0, 0.0), (800.0, 1100.0, 900.0)]),                 # 2048 x 2048 x 1024 = 2^32: refused
+              (0.0457, [(0.0, 0.0, 0.0), (5773.5, 5773.5, 5773.5)])]               # 2^17 cells on every axis: refused
+    return cases
+
+
+def check_grid(exe):
+    for real, prec in ((np.float32, 32), (np.float64, 64)):
+        cases = grid_cases(real)
+        lines = [cmd("grid", prec, real(h), len(pts), np.asarray(pts, real)) for h, pts in cases]
+        ans = run(exe, lines)
+        seen = []
+        for i, (h, pts) in enumerate(cases):
+            want = grid_model(real, pts, h)
+            got = ans[2 * i + 1][1].split()
+            if want is None:
+                assert refusal(ans[2 * i]) == (E_INVALID, T_GRID), (prec, pts, ans[2 * i])
+                assert [float.fromhex(t) for t in got[:3]] == [7.0] * 3 and got[3:] == ["7"] * 4, (prec, pts, got)   # nothing was written
+                seen.append(None)
+                continue
+            assert refusal(ans[2 * i]) == (0, ""), (prec, pts, ans[2 * i])
+            origin, size, cells = want
+            assert [float.fromhex(t) for t in got[:3]] == [float(v) for v in origin], (prec, h, pts, got, want)   # (exact: hex floats)
+            assert got[3:] == [str(v) for v in size] + [str(cells)], (prec, h, pts, got, want)
+            seen.append(size)
+        # written out by hand: what the cases are there to show
+        assert seen[0] == [4, 4, 4] and seen[2] == [16, 32, 64] and seen[3] == [16, 32, 64] and seen[4] == [16, 32, 64]
+        assert [s[2] for s in seen[5:7]] == [16, 32] and [s[0] for s in seen[7:9]] == [16, 32]
+        assert [s[2] for s in seen[9:11]] == [64, 128] and [s[0] for s in seen[11:13]] == [64, 128]
+        assert seen[13] == [2048, 1024, 1024] and seen[14] is None and seen[15] is None
+        first = floats(ans[1][1])[:3]
+        assert np.array_equal(first, (np.asarray([1.0, 2.0, 3.0], real).astype(np.float64) - 0.1).astype(real).astype(np.float64))
+    # the key width of the sorts: the bits of numCells - 1, at least 1
+    cells = [1, 2, 3, 4, 5, 2 ** 24, 2 ** 24 + 1, 2 ** 27, 2 ** 31]
+    ans = run(exe, [cmd("keybits", c) for c in cells])
+    assert [ints(a, "keybits")[0] for a in ans] == [1, 1, 2, 2, 3, 24, 25, 27, 31]
+
+
+def test_grid_from_boundary_box(plain):
+    check_grid(plain)
+
+
 def test_slab_window(plain):
     check_slab_window(plain)
 
@@ -469,6 +558,7 @@ def test_slab_unpack_arithmetic(plain):
 
 
 def test_under_sanitizers(sanitized):
+    check_grid(sanitized)
     check_slab_window(sanitized)
     check_slab_form(sanitized)
     check_slab_configure(sanitized)
