@@ -6,10 +6,10 @@
 // this boundary, by nature.  Definition (Akinci et al. 2012, eq. 4): Vb_i = 1 / sum_k W_poly6(|x_i - x_k|, h) over all boundary
 // particles k with |x_i - x_k| < h, i itself included.
 //
-// Same machinery as the solver's own neighbour search: grid hash -> rocPRIM radix sort -> cell ranges -> 27-cell gather, on a
+// Same machinery as the solver's own neighbour search: grid hash -> radix sort (sort_pairs_plain, nrs_sort.h) -> cell ranges -> 27-cell gather, on a
 // private grid (origin = AABB minimum, cell = h, one thread per sorted particle, sums in double).
 #include "nrs_ctx_base.h"
-#include <rocprim/rocprim.hpp>
+#include "nrs_sort.h"
 
 namespace nrs {
 
@@ -113,13 +113,13 @@ template <typename R, typename T4> static int boundary_volumes(const void *bi4, 
     hipLaunchKernelGGL((k_bvol_hash<R, T4>), dim3(nbk), dim3(256), 0, st, g, dBi.as<T4>(), dKey.as<uint32_t>(), dVal.as<uint32_t>(), n);
     unsigned bits = 1;
     while (bits < 32 && (1ull << bits) < cells) ++bits;
-    rocprim::double_buffer<uint32_t> k(dKey.as<uint32_t>(), dKey2.as<uint32_t>()), v(dVal.as<uint32_t>(), dVal2.as<uint32_t>());
+    PairBuffers kv{dKey.as<uint32_t>(), dKey2.as<uint32_t>(), dVal.as<uint32_t>(), dVal2.as<uint32_t>()};
     size_t tmp = 0;
-    BHIP(rocprim::radix_sort_pairs(nullptr, tmp, k, v, (size_t)n, 0u, bits, st));
+    BHIP(sort_pairs_plain(nullptr, tmp, kv, (size_t)n, bits, st));
     BCHK(dTmp.alloc(tmp));
-    BHIP(rocprim::radix_sort_pairs(dTmp.p, tmp, k, v, (size_t)n, 0u, bits, st));
-    hipLaunchKernelGGL(k_bvol_ranges, dim3(nbk), dim3(256), 0, st, k.current(), dStart.as<uint32_t>(), dEnd.as<uint32_t>(), n);
-    hipLaunchKernelGGL((k_bvol_gather<R, T4>), dim3(nbk), dim3(256), 0, st, g, kpoly, dBi.as<T4>(), v.current(), dStart.as<uint32_t>(),
+    BHIP(sort_pairs_plain(dTmp.p, tmp, kv, (size_t)n, bits, st));
+    hipLaunchKernelGGL(k_bvol_ranges, dim3(nbk), dim3(256), 0, st, kv.key, dStart.as<uint32_t>(), dEnd.as<uint32_t>(), n);
+    hipLaunchKernelGGL((k_bvol_gather<R, T4>), dim3(nbk), dim3(256), 0, st, g, kpoly, dBi.as<T4>(), kv.val, dStart.as<uint32_t>(),
                        dEnd.as<uint32_t>(), dOut.as<R>(), n);
     BHIP(hipGetLastError());
     BHIP(hipMemcpyAsync(out, dOut.p, sizeof(R) * nb, hipMemcpyDeviceToHost, st));

@@ -12,8 +12,6 @@
 #include <functional>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
 #include "nrs_ctx_base.h"
 #include "nrs_host_bodies.h"
 #include "nrs_host_profile.h"
@@ -21,6 +19,7 @@
 #include "nrs_kernels_ref.h"
 #include "nrs_kernels_tiled.h"
 #include "nrs_kernels_bodies.h"
+#include "nrs_sort.h"
 
 namespace nrs {
 
@@ -227,28 +226,23 @@ private:
         HIPCHK(hipMemsetAsync(bdVel.p, 0, sizeof(T4) * nb, stream));
         return NRS_OK;
     }
-    struct Pairs { rocprim::double_buffer<uint32_t> k, v; };
-    Pairs pairs() const
-    {
-        return Pairs{rocprim::double_buffer<uint32_t>(bHash.as<uint32_t>(), bHashAlt.as<uint32_t>()),
-                     rocprim::double_buffer<uint32_t>(bIndex.as<uint32_t>(), bIndexAlt.as<uint32_t>())};
-    }
-    // temporary storage of the sort below; 0: rocPRIM gave none
+    PairBuffers pairs() const { return PairBuffers{bHash.as<uint32_t>(), bHashAlt.as<uint32_t>(), bIndex.as<uint32_t>(), bIndexAlt.as<uint32_t>()}; }
+    // temporary storage of the sort below (sort_pairs_plain, nrs_sort.h); 0: the sort gave none
     size_t sort_bytes(unsigned bits, hipStream_t stream) const
     {
         size_t tmp = 0;
-        Pairs p = pairs();
-        if (rocprim::radix_sort_pairs(nullptr, tmp, p.k, p.v, (size_t)nb, 0u, bits, stream) != hipSuccess) return 0;
+        PairBuffers p = pairs();
+        if (sort_pairs_plain(nullptr, tmp, p, (size_t)nb, bits, stream) != hipSuccess) return 0;
         return tmp;
     }
     // the middle of both builds: the pairs a front kernel left in bHash / bIndex sorted by hash, and an empty cell table for the reorder
     // kernel to fill
     int sort_and_reset_cells(const Params<R> &P, unsigned bits, void *tmp, size_t tmpBytes, hipStream_t stream)
     {
-        Pairs p = pairs();
-        HIPCHK(rocprim::radix_sort_pairs(tmp, tmpBytes, p.k, p.v, (size_t)nb, 0u, bits, stream));
-        bHashCur = p.k.current();
-        bIndexCur = p.v.current();
+        PairBuffers p = pairs();
+        HIPCHK(sort_pairs_plain(tmp, tmpBytes, p, (size_t)nb, bits, stream));
+        bHashCur = p.key;
+        bIndexCur = p.val;
         HIPCHK(hipMemsetAsync(bCellStart.p, 0xff, (size_t)P.numCells * 4, stream));
         return NRS_OK;
     }

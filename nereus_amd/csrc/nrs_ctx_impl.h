@@ -6,9 +6,14 @@
 // "unsorted" arrays of step t+1 are the integrated sorted arrays of step t (buffer swap), which is what
 // the reference obtains by copying sorted→host→device.
 //
-// Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the sort stage's launches, the solver tails,
-// the slab code.  The boundary particles, their tables and bodies depend on the precision alone and live in one member, bt
-// (BoundaryTables<R>, nrs_boundary_tables.h), which launches its own builds; the per-step wall list, sized by the fluid, stays here.
+// Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the hash and reorder launches of the sort
+// stage, the solver tails, the slab code.  The boundary particles, their tables and bodies depend on the precision alone and live in one
+// member, bt (BoundaryTables<R>, nrs_boundary_tables.h), which launches its own builds; the per-step wall list, sized by the fluid,
+// stays here.  The sort stage's state depends on none of the three and lives in one member, sort (SortStage, nrs_sort.h; compiled once,
+// in nrs_sort.hip, with the radix sorts and the merge): the (hash, index) pairs and which of each is current, prepared or a pack
+// target, the sort's workspace, the buffers of the coherent re-sort, its mover-count word and statistics.  The context reads views of
+// it (sort.hash(), sort.index(), sort.prepared(), the tile counts the fused and the slab kernels write) and calls its operations
+// (sort_keys, scan_movers, split, scan_holes, the pack targets); no pointer of it is assigned here.
 // Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure functions it calls:
 // the stage timer (nrs_host_profile.h), the snapshot ring (nrs_host_snapshot.h), the solver settings and their validation
 // (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
@@ -17,7 +22,6 @@
 // stale and derived constants, buffers, what an array or statistic id means — with one state struct per solver (nrs_host_solver.h).
 // Every buffer, pinned landing and event frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
 #pragma once
-#include <sched.h>
 #include "nrs_ctx_base.h"
 #include "nrs_boundary_tables.h"
 #include "nrs_host_grid.h"
@@ -28,7 +32,7 @@
 #include "nrs_host_snapshot.h"
 #include "nrs_host_solver.h"
 #include "nrs_host_state.h"
-#include <rocprim/rocprim.hpp>
+#include "nrs_sort.h"
 
 #include "nrs_kernels_ref.h"
 #include "nrs_kernels_tiled.h"
@@ -45,36 +49,6 @@
 #include <climits>
 
 namespace nrs {
-
-// Radix sort of (hash, index) pairs.  rocPRIM's onesweep sorts 8 key bits per pass by default, so the 25-27-bit
-// hashes of the dam-break grids take 4 passes; with 9 bits per pass they take 3.
-using SortCfg9 = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                            rocprim::radix_sort_onesweep_config<rocprim::kernel_config<512, 12>, rocprim::kernel_config<512, 12>, 9,
-                                                                                rocprim::block_radix_rank_algorithm::match>>;
-using SortCfg10 = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                             rocprim::radix_sort_onesweep_config<rocprim::kernel_config<512, 12>, rocprim::kernel_config<512, 12>, 10,
-                                                                                 rocprim::block_radix_rank_algorithm::match>>;
-static inline hipError_t sort_pairs(void *tmp, size_t &bytes, rocprim::double_buffer<uint32_t> &k, rocprim::double_buffer<uint32_t> &v,
-                                    size_t n, unsigned bits, hipStream_t stream)
-{
-    if (bits > 24 && bits <= 27) return rocprim::radix_sort_pairs<SortCfg9>(tmp, bytes, k, v, n, 0u, bits, stream);
-    if (bits > 27 && bits <= 30) return rocprim::radix_sort_pairs<SortCfg10>(tmp, bytes, k, v, n, 0u, bits, stream);
-    return rocprim::radix_sort_pairs(tmp, bytes, k, v, n, 0u, bits, stream);
-}
-
-// Radix sort of the movers of the coherent re-sort (nrs_kernels_resort.h): u64 keys "hash << 32 | slot", only the hash
-// bits are sorted (the slots are already ascending and the sort is stable).  A few hundred thousand keys: onesweep
-// from 8192 keys on (rocPRIM's default switches to its merge sort below 1 M keys: measured 104 vs 66 us at 300 k).
-template <unsigned BITS>
-using MoverSortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                                rocprim::radix_sort_onesweep_config<rocprim::kernel_config<512, 12>, rocprim::kernel_config<512, 12>, BITS,
-                                                                                    rocprim::block_radix_rank_algorithm::match>, 8192>;
-static inline hipError_t sort_movers(void *tmp, size_t &bytes, rocprim::double_buffer<uint64_t> &k, size_t m, unsigned bits, hipStream_t stream)
-{
-    if (bits > 24 && bits <= 27) return rocprim::radix_sort_keys<MoverSortCfg<9>>(tmp, bytes, k, m, 32u, 32u + bits, stream);
-    if (bits > 27 && bits <= 30) return rocprim::radix_sort_keys<MoverSortCfg<10>>(tmp, bytes, k, m, 32u, 32u + bits, stream);
-    return rocprim::radix_sort_keys<MoverSortCfg<8>>(tmp, bytes, k, m, 32u, 32u + bits, stream);
-}
 
 static_assert(SLT_STAY == ST_STAY && SLT_MIG_L == ST_MIG_L && SLT_HALO_L == ST_HALO_L && SLT_MIG_R == ST_MIG_R && SLT_HALO_R == ST_HALO_R &&
               SLT_GHOST == ST_GHOST && SLT_COUNT == ST_COUNT && SLT_CHANGED == ST_CHANGED && SLT_TOTALS == ST_TOTALS,
@@ -122,11 +96,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool midStep = false; // a partial step left the state mid-update
     // particle state: A = current ("unsorted" input of the next step), B = sorted work arrays
     DevBuf posA, posB, velA, velB, presA, presB, dens, forces;
-    DevBuf hashA, hashB, indexA, indexB, inv, sortTmp;
-    uint32_t *hashCur = nullptr, *indexCur = nullptr; // sorted keys/values after the sort stage
-    uint32_t *hashNext = nullptr, *indexNext = nullptr; // the next step's keys/values, once the fused force kernel wrote them (st: hashReady)
-    // the buffer of the pair (a, b) that cur is not: where a sort or the next step's keys / values go
-    static uint32_t *other(const DevBuf &a, const DevBuf &b, const uint32_t *cur) { return cur == a.as<uint32_t>() ? b.as<uint32_t>() : a.as<uint32_t>(); }
+    DevBuf inv;
+    SortStage sort; // the (hash, index) pairs, the sort's workspace, the coherent re-sort and its statistics (nrs_sort.h)
     DevBuf cellStart, cellEnd;
     uint32_t cellsAllocated = 0;
     BoundaryTables<R> bt; // the boundary particles, their tables and bodies (nrs_boundary_tables.h)
@@ -166,7 +137,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         size_t bytes = 0;
         if (bt.buffer(b, &p, &bytes)) return p;
         switch (b) {
-        case BUF_HASH_CUR: return hashCur; case BUF_INDEX_CUR: return indexCur;
+        case BUF_HASH_CUR: return sort.hash(); case BUF_INDEX_CUR: return sort.index();
         default: { DevBuf *d = devbuf(b); return d ? d->p : nullptr; }
         }
     }
@@ -186,30 +157,22 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         HIPCHK(hipMemsetAsync(wallScalars.p, 0, 16, stream));
         return NRS_OK;
     }
-    WallList wall_view() const { return WallList{bt.near_bits(), hashCur, wallList.as<uint32_t>(), wallScalars.as<uint32_t>() + 1, wallMask.as<unsigned long long>()}; }
+    WallList wall_view() const { return WallList{bt.near_bits(), sort.hash(), wallList.as<uint32_t>(), wallScalars.as<uint32_t>() + 1, wallMask.as<unsigned long long>()}; }
     // this step's wall list: tile counts (reorder kernel) -> two-level scan (the re-sort's scan kernel) -> stable compaction
     int build_wall_list(uint32_t N)
     {
-        const uint32_t nTiles = nblocks(N), nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
+        const uint32_t nTiles = nblocks(N);
         const WallList wl = wall_view(); // (the tile counts were left by the reorder kernel of this step)
         uint32_t *sc = wallScalars.as<uint32_t>();
         const ResortScan a = {wallTile.as<uint32_t>(), wallTileOffset.as<uint32_t>(), wallGroupTotal.as<uint32_t>(), wallGroupPrefix.as<uint32_t>(), sc + 1};
-        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, a, ResortScan{}, sc, (volatile uint64_t *)nullptr, 0u, nTiles);
+        NRSCHK(sort.scan_tiles(a, sc, nTiles));
         hipLaunchKernelGGL(k_wall_compact, dim3(nTiles), dim3(BLOCK), 0, stream, wl, wallTileOffset.as<uint32_t>(), wallGroupPrefix.as<uint32_t>(),
                            (uint32_t)RESORT_GROUP, wallList.as<uint32_t>(), N);
         HIPCHK(hipGetLastError());
         return NRS_OK;
     }
     DevBuf fastQ;             // NRS_FLAG_FAST_ARITH: (p/rho^2, 1/rho) per sorted slot, density kernel -> force kernel
-    // coherent re-sort (nrs_kernels_resort.h)
-    DevBuf rsMovers, rsMoversAlt, rsStayers, rsMerged, rsTileMovers, rsTileOffset, rsGroupTotal, rsGroupPrefix, rsScalars, rsPrevPacked;
-    uint32_t *packKeys = nullptr, *packVals = nullptr; // where slab_pack / slab_unpack write the next step's keys / values
-    PinnedBuf<uint64_t> rsHostTotal; // (launch number << 32 | mover count), written by k_resort_scan_tiles into pinned, mapped host
-    uint64_t *rsHostTotalDev = nullptr; // memory through this device pointer
-    uint32_t rsSeq = 0;
-    Event rsEvent;
-    bool splitClearedCells = false; // this step's k_resort_split also reset the cell table
-    ResortStats rs; // steps, fallbacks, mover count of the last coherent re-sort (nrs_host_state.h)
+    bool splitClearedCells = false; // this step's split of the coherent re-sort also reset the cell table
     // slab decomposition
     bool slabOn = false;
     SlabCfg slab = {INT_MIN / 2, INT_MAX / 2, 2};
@@ -217,12 +180,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint64_t nOwned = 0;
     bool cellsClean = false; // cellStart is all-EMPTY
     DevBuf slabFlags; // fused classification: the force kernel's stream flags (st: classifiedValid, classifiedN)
-    // slab runs, in-place partition: the owned particles are not compacted; dead slots carry the key 0xffffffff
-    DevBuf rsTileDead, rsTileDeadOffset, rsGroupDeadTotal, rsGroupDeadPrefix;
     // page-locked landing place (HT_WORDS words) of what the host reads in an exchange, and the event behind the pack's part of it
     enum { HT_TOTALS = 0,              // the ST_TOTALS stream totals of the pack
-           HT_SCAN = 8,                // pre-classified form: rsScalars, of which ...
-           HT_SCAN_CHANGED = HT_SCAN + 1, HT_SCAN_DEAD = HT_SCAN + 2, // ... the cell changers and the dead slots (scan_movers(), scan_dead())
+           HT_SCAN = 8,                // pre-classified form: sort.scan_scalars(), of which ...
+           HT_SCAN_CHANGED = HT_SCAN + 1, HT_SCAN_DEAD = HT_SCAN + 2, // ... the cell changers and the dead slots
            HT_HEADER_L = 16, HT_HEADER_R = 20, // the 16-byte headers of the received messages
            HT_WORDS = 32 };
     PinnedBuf<uint32_t> slabHostTotals;
@@ -237,16 +198,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!packEvent) HIPCHK(hipEventCreateWithFlags(&packEvent.e, hipEventDisableTiming));
         return NRS_OK;
     }
-    bool rsTilesDirty = false; // rsTileMovers holds counts no scan has consumed
-    int clean_tile_counts()
-    {
-        if (rsTilesDirty) {
-            HIPCHK(hipMemsetAsync(rsTileMovers.p, 0, rsTileMovers.bytes, stream));
-            HIPCHK(hipMemsetAsync(rsTileDead.p, 0, rsTileDead.bytes, stream));
-        }
-        rsTilesDirty = false;
-        return NRS_OK;
-    }
     bool fusedThisStep = false;
     StageTimer timer; // profiling (nrs_host_profile.h)
 
@@ -256,10 +207,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     ArrayTracker st;
     ArrayState array_state() const
     {
-        return nrs::array_state(st.fields(), ArrayFacts{n, cap, nOwned, slabOn, sx.inplace(), hashNext != nullptr, indexNext != nullptr,
-                                                        hashCur != nullptr, rsMovers.p != nullptr});
+        return nrs::array_state(st.fields(), ArrayFacts{n, cap, nOwned, slabOn, sx.inplace(), sort.prepared().hash != nullptr,
+                                                        sort.prepared().index != nullptr, sort.hash() != nullptr, sort.has_resort()});
     }
-    void keys_ready(uint32_t *h, uint32_t *i) { hashNext = h; indexNext = i; st.keys_ready(); } // -> AS_KEYS_READY
+    void keys_ready() { sort.keys_written(); st.keys_ready(); } // -> AS_KEYS_READY
     int validate(const char *where) const
     {
         if (array_state() != AS_INVALID) return NRS_OK;
@@ -325,7 +276,6 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const size_t v = sizeof(T4) * cap, s = sizeof(R) * cap, u = 4 * cap;
         NRSCHK(posA.alloc(v)); NRSCHK(posB.alloc(v)); NRSCHK(velA.alloc(v)); NRSCHK(velB.alloc(v));
         NRSCHK(presA.alloc(s)); NRSCHK(presB.alloc(s)); NRSCHK(dens.alloc(s)); NRSCHK(forces.alloc(v));
-        NRSCHK(hashA.alloc(u)); NRSCHK(hashB.alloc(u)); NRSCHK(indexA.alloc(u)); NRSCHK(indexB.alloc(u));
         HIPCHK(hipMemsetAsync(presA.p, 0, s, stream));
         HIPCHK(hipMemsetAsync(presB.p, 0, s, stream));
         HIPCHK(hipMemsetAsync(dens.p, 0, s, stream));
@@ -355,45 +305,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         HIPCHK(hipMemsetAsync(errWord.p, 0, 8, stream));
         NRSCHK(redPartial.alloc(sizeof(double) * 1024));
         NRSCHK(redOut.alloc(2 * sizeof(double)));
-        // radix sort workspace for the largest problem
-        size_t tmp = 0;
-        rocprim::double_buffer<uint32_t> k(hashA.as<uint32_t>(), hashB.as<uint32_t>());
-        rocprim::double_buffer<uint32_t> vv(indexA.as<uint32_t>(), indexB.as<uint32_t>());
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp, k, vv, (size_t)cap, 0u, 32u, stream));
-        size_t tmp9 = 0;
-        HIPCHK(rocprim::radix_sort_pairs<SortCfg9>(nullptr, tmp9, k, vv, (size_t)cap, 0u, 27u, stream));
-        size_t tmp10 = 0;
-        HIPCHK(rocprim::radix_sort_pairs<SortCfg10>(nullptr, tmp10, k, vv, (size_t)cap, 0u, 30u, stream));
-        size_t tmpAll = std::max(tmp, std::max(tmp9, tmp10));
-        // coherent re-sort: SESPH steps on the production kernels re-use the previous step's order
-        if (ft.resort) {
-            const size_t nTiles = (cap + BLOCK - 1) / BLOCK, nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
-            const size_t mcap = cap; // any share of the particles may be movers (see rsMaxPct)
-            NRSCHK(rsMovers.alloc(8 * cap)); NRSCHK(rsMoversAlt.alloc(8 * mcap)); NRSCHK(rsStayers.alloc(8 * cap)); NRSCHK(rsMerged.alloc(8 * cap));
-            NRSCHK(rsTileMovers.alloc(4 * nTiles)); NRSCHK(rsTileOffset.alloc(4 * nTiles));
-            NRSCHK(rsGroupTotal.alloc(4 * nGroups)); NRSCHK(rsGroupPrefix.alloc(4 * nGroups)); NRSCHK(rsScalars.alloc(16));
-            NRSCHK(rsPrevPacked.alloc(4 * cap));
-            NRSCHK(rsTileDead.alloc(4 * nTiles)); NRSCHK(rsTileDeadOffset.alloc(4 * nTiles));
-            NRSCHK(rsGroupDeadTotal.alloc(4 * nGroups)); NRSCHK(rsGroupDeadPrefix.alloc(4 * nGroups));
-            HIPCHK(hipMemsetAsync(rsTileDead.p, 0, 4 * nTiles, stream));
-            HIPCHK(hipMemsetAsync(rsTileMovers.p, 0, 4 * nTiles, stream));
-            HIPCHK(hipMemsetAsync(rsScalars.p, 0, 16, stream));
-            HIPCHK(hipHostMalloc((void **)&rsHostTotal.p, 64, hipHostMallocMapped));
-            std::memset(rsHostTotal, 0, 64);
-            HIPCHK(hipHostGetDevicePointer((void **)&rsHostTotalDev, rsHostTotal, 0));
-            HIPCHK(hipEventCreateWithFlags(&rsEvent.e, hipEventDisableTiming));
-            rocprim::double_buffer<uint64_t> mk(rsMovers.as<uint64_t>(), rsMoversAlt.as<uint64_t>());
-            for (unsigned bits : {24u, 27u, 30u}) {
-                size_t t = 0;
-                HIPCHK(sort_movers(nullptr, t, mk, mcap, bits, stream));
-                tmpAll = std::max(tmpAll, t);
-            }
-            size_t t = 0;
-            HIPCHK(rocprim::merge(nullptr, t, rsStayers.as<uint64_t>(), rsMovers.as<uint64_t>(), rsMerged.as<uint64_t>(), (size_t)cap, mcap,
-                                  rocprim::less<uint64_t>(), stream));
-            tmpAll = std::max(tmpAll, t);
-        }
-        NRSCHK(sortTmp.alloc(tmpAll));
+        NRSCHK(sort.init(cap, ft.resort, stream));
         NRSCHK(alloc_cells());
         return NRS_OK;
     }
@@ -580,53 +492,22 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const uint32_t N = (uint32_t)n;
         const dim3 g(nblocks(N)), b(BLOCK);
         // which of merge, full sort or compact-first this step takes (nrs_host_state.h); the launches below read the choice
-        const SortPrefix c = choose_sort_prefix(st.fields(), stop, n, rs);
+        const SortPrefix c = sort.choose_prefix(st.fields(), stop, n);
         if (c.compactFirst) NRSCHK(compact_holes()); // also drops the prepared keys: hash and sort from scratch below
-        uint32_t *kIn = hashA.as<uint32_t>(), *kAlt = hashB.as<uint32_t>();
-        uint32_t *vIn = indexA.as<uint32_t>(), *vAlt = indexB.as<uint32_t>();
         if (c.useKeys) { // keys/values of this step were produced by the previous step's fused force kernel
-            kIn = hashNext; vIn = indexNext;
-            kAlt = other(hashA, hashB, kIn); vAlt = other(indexA, indexB, vIn);
+            sort.take_prepared();
         } else {
+            sort.take_fresh();
             NRSCHK(ev_begin(NRS_STAGE_HASH));
-            hipLaunchKernelGGL((k_hash<R>), g, b, 0, stream, P, posA.as<T4>(), kIn, vIn, N);
+            hipLaunchKernelGGL((k_hash<R>), g, b, 0, stream, P, posA.as<T4>(), sort.hash(), sort.index(), N);
             NRSCHK(ev_end());
         }
         st.drop_prepared_keys(); // (consumed by this step)
-        hashCur = kIn; indexCur = vIn;
         if (stop == NRS_STAGE_HASH) return NRS_OK;
 
-        const uint64_t *merged = nullptr;
+        const uint64_t *merged = nullptr; // the u64 pairs of the coherent re-sort, or null after the full sort
         NRSCHK(ev_begin(NRS_STAGE_SORT, c.resort));
-        if (c.resort) {
-            // the split of these keys into movers / stayers was queued behind the force kernel; its mover count sizes
-            // the mover sort and the merge (see nrs_kernels_resort.h)
-            uint32_t M = c.knownCount; // (slab runs: the host already has the mover count)
-            if (!c.countKnown) NRSCHK(wait_mover_count(&M));
-            SortKind kind;
-            NRSCHK(choose_sort(M, N, rs, kind));
-            if (kind == SortKind::MERGE_STAYERS) {
-                merged = rsStayers.as<uint64_t>();
-            } else if (kind == SortKind::MERGE_MOVERS) {
-                rocprim::double_buffer<uint64_t> mk(rsMovers.as<uint64_t>(), rsMoversAlt.as<uint64_t>());
-                size_t tmp = sortTmp.bytes;
-                HIPCHK(sort_movers(sortTmp.p, tmp, mk, (size_t)M, sort_end_bit(), stream));
-                tmp = sortTmp.bytes;
-                HIPCHK(rocprim::merge(sortTmp.p, tmp, rsStayers.as<uint64_t>(), mk.current(), rsMerged.as<uint64_t>(), (size_t)(N - M),
-                                      (size_t)M, rocprim::less<uint64_t>(), stream));
-                merged = rsMerged.as<uint64_t>();
-            }
-        }
-        if (!merged) {
-            if (!c.resort) rs.lastMovers = -1.0;
-            rocprim::double_buffer<uint32_t> k(kIn, kAlt);
-            rocprim::double_buffer<uint32_t> v(vIn, vAlt);
-            size_t tmp = sortTmp.bytes;
-            HIPCHK(sort_pairs(sortTmp.p, tmp, k, v, (size_t)N, sort_end_bit(), stream));
-            hashCur = k.current(); indexCur = v.current();
-        } else {
-            hashCur = kAlt; indexCur = vAlt; // plain sorted arrays, written by k_reorder_merged below
-        }
+        NRSCHK(sort.sort_keys(c, N, sort_end_bit(), &merged));
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_SORT) return NRS_OK;
 
@@ -637,46 +518,26 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const uint32_t *nearB = plan.wallTiles ? bt.near_bits() : (const uint32_t *)nullptr;
         qword_t *qp = plan.quant ? qpos.as<qword_t>() : (qword_t *)nullptr;
         if (merged)
-            hipLaunchKernelGGL((k_reorder_merged<R>), g, b, 0, stream, merged, hashCur, indexCur, posA.as<T4>(), velA.as<T4>(),
+            hipLaunchKernelGGL((k_reorder_merged<R>), g, b, 0, stream, merged, sort.hash(), sort.index(), posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
                                cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
                                nearB, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc, qp);
         else
-            hipLaunchKernelGGL((k_reorder<R>), g, b, 0, stream, hashCur, indexCur, posA.as<T4>(), velA.as<T4>(),
+            hipLaunchKernelGGL((k_reorder<R>), g, b, 0, stream, sort.hash(), sort.index(), posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
                                cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
                                nearB, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc, qp);
         if (iisph() && (cfg.flags & NRS_FLAG_IISPH_SELF_BY_SLOT)) // Q5 off: the pressure kernels skip j == own slot
             hipLaunchKernelGGL(k_identity, g, b, 0, stream, inv.as<uint32_t>(), N);
         if (dfsph()) { // the warm-start inputs of the step, K_prev and Kv_prev, into sorted order
-            hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, presA.as<R>(), indexCur, presB.as<R>(), N);
-            hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, dfKvA.as<R>(), indexCur, dfKvB.as<R>(), N);
+            hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, presA.as<R>(), sort.index(), presB.as<R>(), N);
+            hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, dfKvA.as<R>(), sort.index(), dfKvB.as<R>(), N);
             dfSt.kvValid = true;
         }
         NRSCHK(ev_end());
         return NRS_OK;
     }
 
-    ResortScan scan_movers() const
-    {
-        uint32_t *sc = rsScalars.as<uint32_t>();
-        return ResortScan{rsTileMovers.as<uint32_t>(), rsTileOffset.as<uint32_t>(), rsGroupTotal.as<uint32_t>(), rsGroupPrefix.as<uint32_t>(), sc + 1};
-    }
-    ResortScan scan_dead() const
-    {
-        uint32_t *sc = rsScalars.as<uint32_t>();
-        return ResortScan{rsTileDead.as<uint32_t>(), rsTileDeadOffset.as<uint32_t>(), rsGroupDeadTotal.as<uint32_t>(), rsGroupDeadPrefix.as<uint32_t>(), sc + 2};
-    }
-    ResortOffsets offsets_movers() const { return ResortOffsets{rsTileOffset.as<uint32_t>(), rsGroupPrefix.as<uint32_t>()}; }
-    ResortOffsets offsets_dead() const { return ResortOffsets{rsTileDeadOffset.as<uint32_t>(), rsGroupDeadPrefix.as<uint32_t>()}; }
-    int launch_resort_scan(uint32_t nTiles, bool withDead)
-    {
-        const uint32_t nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
-        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, scan_movers(), withDead ? scan_dead() : ResortScan{},
-                           rsScalars.as<uint32_t>(), (volatile uint64_t *)rsHostTotalDev, ++rsSeq, nTiles);
-        HIPCHK(hipEventRecord(rsEvent, stream));
-        return NRS_OK;
-    }
     // Somebody wants to look at (or re-partition) the particle arrays while they still have the holes of an in-place slab
     // partition: compact them now (stable) and forget the prepared re-sort; the next step hashes and sorts from scratch.
     int compact_holes()
@@ -685,12 +546,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const uint32_t NP = st.fields().physN, nTiles = nblocks(NP);
         st.holes_compacted();
         if (!NP) return NRS_OK;
-        NRSCHK(clean_tile_counts());
-        hipLaunchKernelGGL(k_holes_count, dim3(nTiles), dim3(BLOCK), 0, stream, hashNext, rsTileDead.as<uint32_t>(), NP);
-        const uint32_t nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
-        hipLaunchKernelGGL(k_resort_scan_tiles, dim3(nGroups), dim3(RESORT_GROUP), 0, stream, scan_dead(), ResortScan{}, rsScalars.as<uint32_t>(),
-                           (volatile uint64_t *)nullptr, 0u, nTiles);
-        hipLaunchKernelGGL((k_holes_compact<R>), dim3(nTiles), dim3(BLOCK), 0, stream, hashNext, offsets_dead(), posA.as<T4>(), velA.as<T4>(),
+        NRSCHK(sort.scan_holes(NP));
+        hipLaunchKernelGGL((k_holes_compact<R>), dim3(nTiles), dim3(BLOCK), 0, stream, sort.prepared().hash, sort.offsets_dead(), posA.as<T4>(), velA.as<T4>(),
                            posB.as<T4>(), velB.as<T4>(), NP);
         HIPCHK(hipGetLastError());
         std::swap(posA.p, posB.p);
@@ -698,16 +555,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return NRS_OK;
     }
 
-    // first half of the next step's sort, queued right behind the kernel that produced the keys in hashNext and counted
+    // first half of the next step's sort, queued right behind the kernel that produced the prepared keys and counted
     // the movers per tile: scan of the tile counts (total to the host) + stable split into movers / stayers
     int queue_resort_split(uint32_t N)
     {
         NRSCHK(ev_begin(NRS_STAGE_SORT));
-        const uint32_t nTiles = nblocks(N);
-        NRSCHK(launch_resort_scan(nTiles, false));
+        NRSCHK(sort.scan_movers(nblocks(N), false));
         const bool clear = sparse_cell_table(P.numCells, n); // the step's cell-table reset rides along (see step())
-        hipLaunchKernelGGL((k_resort_split<false>), dim3(nTiles), dim3(BLOCK), 0, stream, hashCur, hashNext, offsets_movers(), offsets_movers(),
-                           rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, clear ? cellStart.as<uint32_t>() : (uint32_t *)nullptr);
+        NRSCHK(sort.split(SplitFrom::SORTED, N, clear ? cellStart.as<uint32_t>() : (uint32_t *)nullptr));
         splitClearedCells = clear;
         st.split_queued();
         NRSCHK(ev_end());
@@ -751,12 +606,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         FusedOut<R> fo{};
         if (plan.keys) {
             fo.newPos = posA.as<T4>(); fo.newVel = velA.as<T4>();
-            fo.hash = other(hashA, hashB, hashCur); fo.index = other(indexA, indexB, indexCur);
+            fo.hash = sort.next_keys().hash; fo.index = sort.next_keys().index;
             fo.slab = slab;
             if (plan.resort || plan.classify) {
-                NRSCHK(clean_tile_counts());
-                fo.prevHash = hashCur;
-                fo.tileMovers = rsTileMovers.as<uint32_t>();
+                NRSCHK(sort.clean_tile_counts());
+                fo.prevHash = sort.hash();
+                fo.tileMovers = sort.tile_movers();
             }
             st.classification_dropped();
             if (plan.classify) {
@@ -767,9 +622,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                 fo.slabFlags = slabFlags.as<uint8_t>();
                 fo.slabBlockCounts = slabCounts.as<uint32_t>();
                 fo.slabBlocks = nbk;
-                fo.tileDead = rsTileDead.as<uint32_t>();
+                fo.tileDead = sort.tile_dead();
                 st.classified(N);
-                rsTilesDirty = true; // until a pack's scan consumes the tile counts
+                sort.tile_counts_written(); // until a pack's scan consumes the tile counts
             }
         }
         const FusedOut<R> *fused = plan.keys ? &fo : nullptr;
@@ -786,8 +641,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                                                       fused, N, walls);
         }
         if (plan.keys) {
-            if (!slabOn) keys_ready(fo.hash, fo.index);
-            else { hashNext = fo.hash; indexNext = fo.index; } // a slab run re-partitions the arrays before the next step (AS_SLOT_ORDER)
+            if (!slabOn) keys_ready();
+            else sort.keys_written(); // a slab run re-partitions the arrays before the next step (AS_SLOT_ORDER)
             fusedThisStep = true;
         }
         NRSCHK(ev_end());
@@ -885,11 +740,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // tileMovers) gets where those go, or nulls; the stage ends behind it, the keys are ready and the split is queued.
     template <typename Launch> int launch_last(Launch &&launch)
     {
-        uint32_t *nh = plan.keys ? other(hashA, hashB, hashCur) : nullptr, *ni = plan.keys ? other(indexA, indexB, indexCur) : nullptr;
-        if (plan.resort) NRSCHK(clean_tile_counts());
-        launch(nh, ni, plan.resort ? (const uint32_t *)hashCur : (const uint32_t *)nullptr, plan.resort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr);
+        const KeyPair next = plan.keys ? sort.next_keys() : KeyPair{nullptr, nullptr};
+        if (plan.resort) NRSCHK(sort.clean_tile_counts());
+        launch(next.hash, next.index, plan.resort ? (const uint32_t *)sort.hash() : (const uint32_t *)nullptr, plan.resort ? sort.tile_movers() : (uint32_t *)nullptr);
         NRSCHK(ev_end());
-        if (plan.keys) keys_ready(nh, ni);
+        if (plan.keys) keys_ready();
         if (plan.resort) NRSCHK(queue_resort_split((uint32_t)n));
         return NRS_OK;
     }
@@ -985,7 +840,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const StepPlan chosen = plan;
         plan = plan_step(stop, true);
         ++iisphRestarts;
-        hipLaunchKernelGGL((k_gather_scalar<R>), dim3(nblocks((uint32_t)n)), dim3(BLOCK), 0, stream, presA.as<R>(), indexCur, presB.as<R>(), (uint32_t)n);
+        hipLaunchKernelGGL((k_gather_scalar<R>), dim3(nblocks((uint32_t)n)), dim3(BLOCK), 0, stream, presA.as<R>(), sort.index(), presB.as<R>(), (uint32_t)n);
         const int rc = iisph_tail_once<HAS_B>(stop);
         plan = chosen;
         return rc;
@@ -1489,7 +1344,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int totals_to_host(bool withScan)
     {
         HIPCHK(hipMemcpyAsync(slabHostTotals + HT_TOTALS, slabTotals.p, ST_TOTALS * 4, hipMemcpyDeviceToHost, stream));
-        if (withScan) HIPCHK(hipMemcpyAsync(slabHostTotals + HT_SCAN, rsScalars.p, 16, hipMemcpyDeviceToHost, stream));
+        if (withScan) HIPCHK(hipMemcpyAsync(slabHostTotals + HT_SCAN, sort.scan_scalars(), 16, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipEventRecord(packEvent, stream));
         return NRS_OK;
     }
@@ -1512,8 +1367,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ghostVel.alloc(sizeof(T4) * mcap));
         NRSCHK(ensure_host_totals());
         NRSCHK(ensure_pack_event());
-        const SlabChoice ch = choose_form(SlabFacts{st.fields().classifiedValid, st.fields().slotOrderValid, rsMovers.p != nullptr, hashCur != nullptr,
-                                                    hashNext != nullptr, hashNext != hashCur, st.fields().classifiedN, N, RESORT_MIN_PARTICLES});
+        const SlabChoice ch = choose_form(SlabFacts{st.fields().classifiedValid, st.fields().slotOrderValid, sort.has_resort(), sort.hash() != nullptr,
+                                                    sort.prepared().hash != nullptr, sort.prepared().hash != sort.hash(), st.fields().classifiedN, N, RESORT_MIN_PARTICLES});
         const bool inplace = ch.form != SlabForm::COMPACT, pre = ch.form == SlabForm::PRECLASSIFIED;
         if (N) {
             // pre-classified: the force kernel of the last step classified every slot for these cuts (flags, stream populations per
@@ -1521,27 +1376,26 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             // of the message and ghost streams, and split
             if (!pre)
                 hipLaunchKernelGGL((k_slab_count<R>), dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(), N,
-                                   slabCounts.as<uint32_t>(), nbk, ch.resort ? hashCur : (const uint32_t *)nullptr,
-                                   ch.resort ? hashNext : (const uint32_t *)nullptr);
+                                   slabCounts.as<uint32_t>(), nbk, ch.resort ? sort.hash() : (const uint32_t *)nullptr,
+                                   ch.resort ? sort.prepared().hash : (const uint32_t *)nullptr);
             hipLaunchKernelGGL(k_slab_scan, dim3(ST_TOTALS), dim3(SLAB_BLOCK), 0, stream, slabCounts.as<uint32_t>(), nbk, slabTotals.as<uint32_t>());
             // in place, the fused kernel's keys / slot numbers stay where they are; the compacting form does the hash pass of the next
             // step here, into the key buffers the last sort did not end in
-            packKeys = inplace ? hashNext : other(hashA, hashB, hashCur);
-            packVals = inplace ? indexNext : other(indexA, indexB, indexCur);
+            const KeyPair target = sort.pack_targets(inplace);
             SlabOut<R> out;
             out.stayPos = posB.as<T4>(); out.stayVel = velB.as<T4>();
-            out.hash = packKeys; out.index = packVals;
-            out.prevHash = ch.resort ? hashCur : nullptr;
-            out.prevPacked = (ch.resort && !inplace) ? rsPrevPacked.as<uint32_t>() : nullptr;
-            out.tileMovers = ch.resort ? rsTileMovers.as<uint32_t>() : nullptr;
-            out.tileDead = inplace ? rsTileDead.as<uint32_t>() : nullptr;
+            out.hash = target.hash; out.index = target.index;
+            out.prevHash = ch.resort ? sort.hash() : nullptr;
+            out.prevPacked = (ch.resort && !inplace) ? sort.prev_packed() : nullptr;
+            out.tileMovers = ch.resort ? sort.tile_movers() : nullptr;
+            out.tileDead = inplace ? sort.tile_dead() : nullptr;
             out.flags = pre ? slabFlags.as<uint8_t>() : nullptr;
             out.ghostPos = ghostPos.as<T4>(); out.ghostVel = ghostVel.as<T4>();
             out.sendL = (unsigned char *)sendL; out.sendR = (unsigned char *)sendR;
             out.cap = (uint32_t)mcap;
             if (ch.resort && !pre) { // the scatter counts per tile (pre-classified: the force kernel did, and its counts are still there)
-                NRSCHK(clean_tile_counts());
-                rsTilesDirty = true; // (never clear it here: the counts of an unused classification may still be in the arrays)
+                NRSCHK(sort.clean_tile_counts());
+                sort.tile_counts_written(); // (and stay marked until a scan: the counts of an unused classification may still be in the arrays)
             }
             const auto scatter = pre ? k_slab_scatter<R, true, true> : inplace ? k_slab_scatter<R, true> : k_slab_scatter<R, false>;
             hipLaunchKernelGGL(scatter, dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(), velA.as<T4>(), N, slabCounts.as<uint32_t>(),
@@ -1558,13 +1412,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const uint32_t nTiles = nblocks(N);
         if (!N) HIPCHK(hipEventRecord(packEvent, stream));
         else if (!pre) NRSCHK(totals_to_host(false));
-        if (inplace) NRSCHK(launch_resort_scan(nTiles, true));
+        if (inplace) NRSCHK(sort.scan_movers(nTiles, true));
         if (pre) NRSCHK(totals_to_host(true));
         if (inplace) {
-            hipLaunchKernelGGL((k_resort_split<true>), dim3(nTiles), dim3(BLOCK), 0, stream, hashCur, hashNext, offsets_movers(), offsets_dead(),
-                               rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, (uint32_t *)nullptr);
+            NRSCHK(sort.split(SplitFrom::SORTED_HOLES, N, nullptr));
             HIPCHK(hipGetLastError());
-            rsTilesDirty = false; // the scan resets the counts it reads
         }
         // Nothing above waits.  The messages are complete in stream order, so the caller can enqueue its sends right behind this call;
         // the stream totals (how many stay, leave, ghost) are read back by finish_pack() — in nrs_slab_unpack, together with the
@@ -1588,12 +1440,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!f.stored) return rc;
         st.to_fresh();
         if (f.form != SlabForm::COMPACT) {
-            // hashNext / indexNext hold key and slot of every live slot, 0xffffffff marks the dead ones; arrivals are added to the mover
+            // the prepared keys / values hold key and slot of every live slot, 0xffffffff marks the dead ones; arrivals are added to the mover
             // count by nrs_slab_unpack
             st.to_holes(sx.N, f.movers);
         } else {
             if (sx.N) { std::swap(posA.p, posB.p); std::swap(velA.p, velB.p); }
-            else { packKeys = hashA.as<uint32_t>(); packVals = indexA.as<uint32_t>(); }
+            else sort.pack_targets_empty();
             st.pack_hashed(sx.N != 0); // k_slab_scatter hashed the particles that stay (with the current parameters)
         }
         n = f.n;
@@ -1639,59 +1491,34 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const bool compactResort = sx.form == SlabForm::COMPACT && sx.resort;
         if (A.start[5])
             hipLaunchKernelGGL((k_slab_append<R>), dim3((A.start[5] + SLAB_BLOCK - 1) / SLAB_BLOCK), dim3(SLAB_BLOCK), 0, stream, P, A,
-                               posA.as<T4>(), velA.as<T4>(), packKeys, packVals,
-                               compactResort ? rsPrevPacked.as<uint32_t>() : (uint32_t *)nullptr,
-                               compactResort ? rsTileMovers.as<uint32_t>() : (uint32_t *)nullptr, (uint32_t)ar.base,
-                               ar.inplace ? rsMovers.as<uint64_t>() : (uint64_t *)nullptr, ar.inplace ? st.fields().rsKnownCount : 0u);
+                               posA.as<T4>(), velA.as<T4>(), sort.pack_keys().hash, sort.pack_keys().index,
+                               compactResort ? sort.prev_packed() : (uint32_t *)nullptr,
+                               compactResort ? sort.tile_movers() : (uint32_t *)nullptr, (uint32_t)ar.base,
+                               ar.inplace ? sort.movers() : (uint64_t *)nullptr, ar.inplace ? st.fields().rsKnownCount : 0u);
         HIPCHK(hipGetLastError());
         nOwned = ar.nOwned;
         n = ar.n;
         if (iisph() && n)
             hipLaunchKernelGGL((k_velw_to_pressure<R>), dim3(nblocks(n)), dim3(BLOCK), 0, stream, velA.as<T4>(), presA.as<R>(), (uint32_t)n);
         // pack + unpack have written the radix keys/values of every local particle
-        hashNext = packKeys; indexNext = packVals;
+        sort.pack_wrote_every_key();
         st.arrivals_appended(ar.inplace, (uint32_t)ar.arrivals);
         if (!ar.inplace && st.fields().hashReady && compactResort && n >= RESORT_MIN_PARTICLES) {
             // coherent re-sort: the owned particles that stayed in their cell are still in sorted order
             // (the partition and the append have counted the movers of every tile of the new arrays)
-            const uint32_t N = (uint32_t)n, nTiles = nblocks(N);
-            NRSCHK(launch_resort_scan(nTiles, false));
-            hipLaunchKernelGGL((k_resort_split<false>), dim3(nTiles), dim3(BLOCK), 0, stream, rsPrevPacked.as<uint32_t>(), hashNext,
-                               offsets_movers(), offsets_movers(), rsMovers.as<uint64_t>(), rsStayers.as<uint64_t>(), N, (uint32_t *)nullptr);
+            const uint32_t N = (uint32_t)n;
+            NRSCHK(sort.scan_movers(nblocks(N), false));
+            NRSCHK(sort.split(SplitFrom::PACKED, N, nullptr));
             st.split_queued_known(sx.totals[ST_CHANGED] + A.start[5]); // everything appended is a mover, and the partition counted the cell changers
-            rsTilesDirty = false; // the scan resets the counts it reads
         }
         sx.resort = false;
         return NRS_OK;
     }
 
-    // The scan kernel stores (launch number, count) straight into mapped host memory; polling that word costs a PCIe
-    // write latency, where hipEventSynchronize on an otherwise idle host thread was measured to cost ~0.1 ms per step.
-    int wait_mover_count(uint32_t *M)
-    {
-        volatile uint64_t *w = (volatile uint64_t *)rsHostTotal;
-        {
-            for (uint64_t spins = 0;; ++spins) {
-                const uint64_t v = *w;
-                if ((uint32_t)(v >> 32) == rsSeq) { *M = (uint32_t)v; return NRS_OK; }
-                // polite spin: on a host with fewer free cores than ranks (8 ranks on a 16-CPU share) the poller hands its
-                // time slice to whoever is runnable; with an idle core the yield returns at once and costs no latency
-                if ((spins & 63u) == 63u) sched_yield();
-                if ((spins & 0xfffff) == 0xfffff) { // every ~1 M polls: has the stream failed or finished without us seeing it?
-                    const hipError_t e = hipEventQuery(rsEvent);
-                    if (e == hipSuccess) break;
-                    if (e != hipErrorNotReady) HIPCHK(e);
-                }
-            }
-        }
-        HIPCHK(hipEventSynchronize(rsEvent));
-        *M = (uint32_t)*w;
-        return NRS_OK;
-    }
     void resort_stats(uint64_t *steps, uint64_t *fallbacks) override
     {
-        if (steps) *steps = rs.steps;
-        if (fallbacks) *fallbacks = rs.fallbacks;
+        if (steps) *steps = sort.stats().steps;
+        if (fallbacks) *fallbacks = sort.stats().fallbacks;
     }
     // which statistic an id means on this context, or its refusal: route_stat (nrs_host_solver.h); the device work is here
     StatFacts stat_facts() const
@@ -1708,7 +1535,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(route_stat(which, stat_facts(), r)); // again, on the maximum just formed: "no PBF solve yet" is tested on that value
         }
         switch (r.kind) {
-        case STAT_MOVER_COUNT: *out = rs.lastMovers; return NRS_OK;
+        case STAT_MOVER_COUNT: *out = sort.stats().lastMovers; return NRS_OK;
         case STAT_SLAB_FORM: *out = (int)sx.form; return NRS_OK;
         case STAT_PBF_ERROR:
         case STAT_PCI_ERROR: *out = pciSt.lastErr; return NRS_OK;
@@ -1742,12 +1569,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         if (sparse_cell_table(P.numCells, n)) { // big, mostly empty table: undo only the touched cells
             if (!splitClearedCells)
-                hipLaunchKernelGGL(k_clear_cells, dim3(nblocks(n)), dim3(BLOCK), 0, stream, hashCur, cellStart.as<uint32_t>(), (uint32_t)n);
+                hipLaunchKernelGGL(k_clear_cells, dim3(nblocks(n)), dim3(BLOCK), 0, stream, sort.hash(), cellStart.as<uint32_t>(), (uint32_t)n);
             cellsClean = true;
         }
         // the integrated sorted arrays become the next step's input (replaces D2H + H2D)
         ++stepsDone;
-        st.step_ended(fusedThisStep); // fused: A holds the new state in the slot order of hashCur
+        st.step_ended(fusedThisStep); // fused: A holds the new state in the slot order of sort.hash()
         if (!fusedThisStep) { // the fused kernel already wrote the new state into A
             std::swap(posA.p, posB.p);
             std::swap(velA.p, velB.p);

@@ -1,6 +1,7 @@
 // nrs_host_state.h — the state of the particle arrays and of the keys prepared for the next step, and what the sort stage makes of it.
-// No HIP: bools and counts in, a state or a choice out.  The context (nrs_ctx_impl.h) holds one ArrayTracker and the device pointers
-// the fields speak about (hashNext / indexNext, hashCur / indexCur, packKeys / packVals); it launches, then names what happened.
+// No HIP: bools and counts in, a state or a choice out.  The context (nrs_ctx_impl.h) holds one ArrayTracker; the device pointers
+// the fields speak about (hashNext / indexNext, hashCur / indexCur, packKeys / packVals) are SortStage's (nrs_sort.h).  The context
+// launches, then names what happened.
 #pragma once
 #include <cstdint>
 
@@ -73,7 +74,7 @@ struct ArrayTracker {
     const ArrayFields &fields() const { return f; }
     void drop_prepared_keys() { f.hashReady = false; f.rsPending = false; f.rsCountKnown = false; }   // the keys were consumed, or are void
     void to_fresh() { drop_prepared_keys(); f.slotOrderValid = false; f.classifiedValid = false; }   // -> AS_FRESH: compact arrays, any order
-    void keys_ready() { f.hashReady = true; }                                                        // -> AS_KEYS_READY (Ctx::keys_ready sets the pointers)
+    void keys_ready() { f.hashReady = true; }                                                        // -> AS_KEYS_READY (Ctx::keys_ready: SortStage::keys_written first)
     void split_queued() { f.rsPending = true; }                                                      // -> AS_SPLIT_QUEUED, count still on the device
     void split_queued_known(uint32_t movers) { f.rsPending = true; f.rsCountKnown = true; f.rsKnownCount = movers; } // ..., count on the host
     void to_holes(uint32_t extent, uint32_t movers)                                                  // -> AS_HOLES (in-place slab partition)

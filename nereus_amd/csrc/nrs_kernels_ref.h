@@ -53,9 +53,6 @@ template <typename R> NRS_DEV bool slab_active(const Params<R> &P, const GridVie
     return cx >= (long long)G.actLo && cx < (long long)G.actHi;
 }
 
-constexpr int BLOCK = 256;
-static inline uint32_t nblocks(uint64_t n) { return (uint32_t)((n + BLOCK - 1) / BLOCK); } // workgroups of BLOCK threads over n items
-
 // ---- calcHashD (sph_kernel_impl.cuh:127-145) -------------------------------------------------------
 template <typename R>
 __global__ __launch_bounds__(BLOCK) void k_hash(Params<R> P, const typename Vec4T<R>::type *__restrict__ pos,

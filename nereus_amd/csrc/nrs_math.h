@@ -316,6 +316,8 @@ template <typename R> NRS_DEV uint32_t calcGridHash(const Params<R> &P, int gx, 
 }
 
 static constexpr uint32_t CELL_EMPTY = 0xffffffffu;
+constexpr int BLOCK = 256;
+static inline uint32_t nblocks(uint64_t n) { return (uint32_t)((n + BLOCK - 1) / BLOCK); } // workgroups of BLOCK threads over n items
 
 // ---- compact scan candidates (the neighbour scan of the interior workgroups, nrs_kernels_tiled.h) -----------------------------
 // A quantised copy of every sorted position, written by the reorder kernels next to the exact one: the position modulo FOUR

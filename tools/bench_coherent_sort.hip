@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
-#include "../nereus_amd/csrc/nrs_kernels_resort.h"
+#include "../nereus_amd/csrc/nrs_kernels_sort.h"
 
 #include <algorithm>
 #include <cstdint>
