@@ -440,6 +440,49 @@ enum { NRS_STAT_MOVERS = 0, NRS_STAT_HIT_OVERFLOW = 1, NRS_STAT_HIT_MEAN = 2, NR
        NRS_STAT_DFSPH_DIVERGENCE_AVG = 9, NRS_STAT_DFSPH_DIVERGENCE_ITERATIONS = 10, NRS_STAT_SLAB_PARTITION = 11 };
 int nrs_get_stat(nrs_ctx *ctx, int which, double *out);
 
+/* ---- field sampling (DESIGN.md "Field sampling"; came after nrs_version() 0.3 without a version change) -------------------------------
+ * Evaluates the SPH fields of the CURRENT particle state (what nrs_download would return now) at positions that are not particles: at
+ * caller-supplied points, or on the nodes of a regular lattice.  Read-only: a context that samples steps bit-identically to one that
+ * never did.  Every solver, both precisions, both kernel sets; not on a slab context (NRS_E_INVALID: its arrays hold halo copies).
+ *
+ * With h = interactionRadius, m = particleMass and the neighbours j of a position x those fluid particles with length(x - x_j) < h
+ * (difference in SReal, the float length() of the kernels):
+ *   NRS_FIELD_DENSITY   SReal[M]      rho(x) = sum_j m W(x - x_j), W the density kernel of the context's kernel set; with
+ *                                     NRS_FIELD_WALLS also sum_b (restDensity V_b) W(x - x_b) over the boundary particles within h, at
+ *                                     the walls' current pose
+ *   NRS_FIELD_GRADIENT  SVec4[M]      grad rho(x) = sum_j m grad W(x - x_j), fluid only, w = 0; a neighbour AT x contributes nothing
+ *   NRS_FIELD_VELOCITY  SVec4[M]      Shepard average (sum_j (m W_j) v_j) / (sum_j m W_j), w = the fluid-only denominator; all four
+ *                                     components 0 where the denominator is 0
+ *   NRS_FIELD_COUNT     uint32_t[M]   number of fluid neighbours
+ *   NRS_FIELD_WALLS     modifier of NRS_FIELD_DENSITY only; ignored on a context without boundary particles
+ * One accumulator per output component; the cells of the position's 3x3x3 neighbourhood are visited z, y, x ascending, the sorted
+ * particles of a cell ascending, a cell's boundary particles after its fluid particles: results are deterministic and do not depend
+ * on the entry point.  A position with a non-finite coordinate gets zeros and count 0.
+ *
+ * nrs_sample_points: m positions (HOST SVec4[m], w ignored).  nrs_sample_lattice: node (i, j, k) of the lattice is at
+ * (SReal)(origin[a] + idx[a] * spacing[a]) (formed in double, rounded once) and has the linear index (k * dims[1] + j) * dims[0] + i.
+ * Both enqueue on the context's stream and do not wait for the device (nrs_sample_points returns once its points are copied).
+ * nrs_sample_result copies a field of the LAST sample call to the host and waits, as nrs_get_array does (dst NULL: only the size);
+ * nrs_sample_device_ptr gives its device address, as nrs_device_ptr does.  Both stay valid until the next sample call,
+ * nrs_sample_release (frees every sampler buffer; the next sample call allocates again) or nrs_destroy.  The sampler keeps its own
+ * sorted copy of the particles and its own cell table; they are rebuilt only when the particles, the grid or the boundaries changed
+ * since the last sample call; nrs_sample_builds gives the number of builds since nrs_create (read-only, does not touch the device).
+ *
+ * NRS_E_STATE: mid-update after nrs_step_partial; a host-driven IISPH step in progress; a result or pointer of a field the last
+ * sample call did not compute (or before any).  NRS_E_INVALID: fields without an output flag or with unknown bits; points4 NULL with
+ * m > 0; m >= 2^31; a spacing that is not finite or <= 0, an origin that is not finite, a dim of 0 or more than 2^31 nodes; a slab
+ * context; a grid whose cellSize is below h in some axis (the 27-cell walk is then incomplete), whose gridSize is below 4 in some axis
+ * or is not a power of two (the hash's wrap then aliases cells of one row and a neighbour would be counted twice).  m == 0 succeeds
+ * with empty results; a context without particles gives zeros. */
+enum { NRS_FIELD_DENSITY = 1, NRS_FIELD_GRADIENT = 2, NRS_FIELD_VELOCITY = 4, NRS_FIELD_COUNT = 8, NRS_FIELD_WALLS = 16 };
+typedef struct nrs_lattice { double origin[3]; double spacing[3]; uint32_t dims[3]; uint32_t reserved; } nrs_lattice;
+int nrs_sample_points(nrs_ctx *ctx, const void *points4, uint64_t m, uint32_t fields);
+int nrs_sample_lattice(nrs_ctx *ctx, const nrs_lattice *lattice, uint32_t fields);
+int nrs_sample_result(nrs_ctx *ctx, uint32_t field, void *dst, uint64_t dst_bytes, uint64_t *out_bytes);
+int nrs_sample_device_ptr(nrs_ctx *ctx, uint32_t field, void **dptr, uint64_t *bytes);
+int nrs_sample_release(nrs_ctx *ctx);
+int nrs_sample_builds(nrs_ctx *ctx, uint64_t *builds);
+
 /* Akinci boundary volumes on the device (no context needed): vbi[i] = 1 / sum_k W_poly6(|x_i - x_k|, h) over the boundary
  * particles k within h of i, i included — what the reference takes from its un-vendored submodule
  * (sample_spheres::boundary_forces::getVbi, main.cpp:546; own implementation, parity unpinned).  bi4: nb xyzw particles of

@@ -30,6 +30,8 @@ STAT_MOVERS, STAT_HIT_OVERFLOW, STAT_HIT_MEAN, STAT_HIT_MAX, STAT_UNSTAGED = 0, 
 STAT_DENSITY_ERROR, STAT_PCISPH_DELTA, STAT_PBF_EPSILON = 5, 6, 7
 STAT_DFSPH_DENSITY_AVG, STAT_DFSPH_DIVERGENCE_AVG, STAT_DFSPH_DIVERGENCE_ITERATIONS = 8, 9, 10
 STAT_SLAB_PARTITION = 11   # kind of the last slab_pack: 0 compacting, 1 in place, 2 in place from the force kernel's classification
+# NRS_FIELD_*: the outputs of the field sampler, and the modifier that adds the wall term to the density
+FIELD_DENSITY, FIELD_GRADIENT, FIELD_VELOCITY, FIELD_COUNT, FIELD_WALLS = 1, 2, 4, 8, 16
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
@@ -64,6 +66,8 @@ EXPORTS = [
     "nrs_slab_last_counts", "nrs_pcisph_configure", "nrs_pbf_configure", "nrs_pbf_set_tensile",
     "nrs_pbf_set_vorticity", "nrs_dfsph_configure", "nrs_set_surface_akinci",
     "nrs_set_boundary_bodies", "nrs_set_body_velocity", "nrs_set_body_pose", "nrs_get_body_pose",
+    "nrs_sample_points", "nrs_sample_lattice", "nrs_sample_result", "nrs_sample_device_ptr", "nrs_sample_release",
+    "nrs_sample_builds",
 ]
 
 
@@ -73,6 +77,10 @@ class NrsConfig(C.Structure):
         ("kernel_set", C.c_int32), ("surface_tension", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
         ("capacity", C.c_uint64), ("stream", C.c_void_p),
     ]
+
+
+class NrsLattice(C.Structure):
+    _fields_ = [("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("dims", C.c_uint32 * 3), ("reserved", C.c_uint32)]
 
 
 class NereusError(RuntimeError):
@@ -147,6 +155,12 @@ def load_library(path=None):
     lib.nrs_boundary_volumes.argtypes = [i32, i32, vp, u64, C.c_double, vp]
     lib.nrs_snapshot_begin.argtypes = [vp, i32]
     lib.nrs_snapshot_wait.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+    lib.nrs_sample_points.argtypes = [vp, vp, u64, C.c_uint32]
+    lib.nrs_sample_lattice.argtypes = [vp, C.POINTER(NrsLattice), C.c_uint32]
+    lib.nrs_sample_result.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(u64)]
+    lib.nrs_sample_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
+    lib.nrs_sample_release.argtypes = [vp]
+    lib.nrs_sample_builds.argtypes = [vp, C.POINTER(u64)]
     _lib = lib
     return lib
 
@@ -439,6 +453,45 @@ class Solver:
         v = C.c_double()
         self._chk(self.lib.nrs_get_stat(self.h, int(which), C.byref(v)))
         return v.value
+
+    # ---- field sampling -----------------------------------------------------------------------------
+    def sample_points(self, points4, fields):
+        """evaluate `fields` (FIELD_* flags) at the rows of points4 (m, 4), w ignored (nrs_sample_points); does not wait for the device"""
+        pts = np.ascontiguousarray(points4, dtype=self.real).reshape(-1, 4)
+        self._chk(self.lib.nrs_sample_points(self.h, _ptr(pts) if len(pts) else None, pts.shape[0], int(fields)))
+
+    def sample_lattice(self, origin, spacing, dims, fields):
+        """evaluate `fields` on the dims[0] x dims[1] x dims[2] nodes origin + idx * spacing (nrs_sample_lattice); spacing: a number
+        or one per axis"""
+        L = NrsLattice()
+        sp = np.broadcast_to(np.asarray(spacing, np.float64), (3,))
+        for a in range(3):
+            L.origin[a], L.spacing[a], L.dims[a] = float(origin[a]), float(sp[a]), int(dims[a])
+        self._chk(self.lib.nrs_sample_lattice(self.h, C.byref(L), int(fields)))
+
+    def sample_result(self, field):
+        """one field of the last sample call on the host: (m,) SReal density, (m, 4) gradient / velocity, (m,) uint32 count"""
+        nbytes = C.c_uint64(0)
+        self._chk(self.lib.nrs_sample_result(self.h, int(field), None, 0, C.byref(nbytes)))
+        dt = np.uint32 if field == FIELD_COUNT else self.real
+        a = np.empty(nbytes.value // np.dtype(dt).itemsize, dtype=dt)
+        if nbytes.value:
+            self._chk(self.lib.nrs_sample_result(self.h, int(field), _ptr(a), nbytes.value, None))
+        return a.reshape(-1, 4) if field in (FIELD_GRADIENT, FIELD_VELOCITY) else a
+
+    def sample_device_ptr(self, field):
+        p, b = C.c_void_p(), C.c_uint64()
+        self._chk(self.lib.nrs_sample_device_ptr(self.h, int(field), C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def sample_builds(self):
+        """how many times the sampler built its particle grid since the context was created (nrs_sample_builds)"""
+        b = C.c_uint64(0)
+        self._chk(self.lib.nrs_sample_builds(self.h, C.byref(b)))
+        return int(b.value)
+
+    def sample_release(self):
+        self._chk(self.lib.nrs_sample_release(self.h))
 
     @property
     def n_owned(self):

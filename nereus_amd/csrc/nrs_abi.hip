@@ -417,6 +417,39 @@ int nrs_get_stat(nrs_ctx *ctx, int which, double *out)
     if (!out) return fail(NRS_E_INVALID, "NULL argument");
     return ctx->impl->get_stat(which, out);
 }
+int nrs_sample_points(nrs_ctx *ctx, const void *points4, uint64_t m, uint32_t fields)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->sample_points(points4, m, fields);
+}
+int nrs_sample_lattice(nrs_ctx *ctx, const nrs_lattice *lattice, uint32_t fields)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->sample_lattice(lattice, fields);
+}
+int nrs_sample_result(nrs_ctx *ctx, uint32_t field, void *dst, uint64_t dst_bytes, uint64_t *out_bytes)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->sample_result(field, dst, dst_bytes, out_bytes);
+}
+int nrs_sample_device_ptr(nrs_ctx *ctx, uint32_t field, void **dptr, uint64_t *bytes)
+{
+    CTX_GUARD(ctx);
+    if (!dptr || !bytes) return fail(NRS_E_INVALID, "NULL argument");
+    return ctx->impl->sample_device_ptr(field, dptr, bytes);
+}
+int nrs_sample_release(nrs_ctx *ctx)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->sample_release();
+}
+int nrs_sample_builds(nrs_ctx *ctx, uint64_t *builds)
+{
+    CTX_GUARD(ctx);
+    if (!builds) return fail(NRS_E_INVALID, "NULL argument");
+    *builds = ctx->impl->sample_builds();
+    return NRS_OK;
+}
 uint64_t nrs_slab_message_bytes(uint64_t capacity, int precision) { return 16 + capacity * 2 * (precision == 64 ? 32 : 16); }
 
 int nrs_max_density(nrs_ctx *ctx, double *out)

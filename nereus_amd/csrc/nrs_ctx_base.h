@@ -133,6 +133,13 @@ struct CtxBase {
     virtual int settle() = 0;                           // finish host bookkeeping a previous call deferred (nrs_slab_pack's totals)
     virtual int slab_last_counts(uint32_t *counts) = 0; // stream populations of the last nrs_slab_pack
     virtual int set_profiling(uint32_t mask) = 0;
+    // field sampling (nrs_kernels_sample.h; the host decisions: nrs_host_sample.h)
+    virtual int sample_points(const void *points4, uint64_t m, uint32_t fields) = 0;
+    virtual int sample_lattice(const nrs_lattice *lattice, uint32_t fields) = 0;
+    virtual int sample_result(uint32_t field, void *dst, uint64_t dstBytes, uint64_t *outBytes) = 0;
+    virtual int sample_device_ptr(uint32_t field, void **dptr, uint64_t *bytes) = 0;
+    virtual int sample_release() = 0;
+    virtual uint64_t sample_builds() = 0;
     hipStream_t stream = nullptr;
     bool ownStream = false;
     int device = 0;

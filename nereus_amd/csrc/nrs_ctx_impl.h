@@ -45,6 +45,7 @@
 #include "nrs_kernels_akinci.h"
 #include "nrs_kernels_bodies.h"
 #include "nrs_kernels_slab.h"
+#include "nrs_field_sampler.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
 
@@ -352,6 +353,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(compact_holes());
         st.grid_changed();
         cellsClean = false;
+        ++gridGen;
         return NRS_OK;
     }
     static ParamsKey params_key(const Params<R> &p)
@@ -381,6 +383,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             HIPCHK(hipStreamSynchronize(stream)); // the caller may reuse its host buffers on return
         }
         if (first + count > n) n = first + count;
+        ++particleGen;
         if (slabOn) nOwned = n; // (until the next partition says otherwise)
         midStep = false;
         iisphPhase = 0; iisphIter = 0; // new particles abandon a host-driven IISPH step that was in progress
@@ -393,6 +396,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (nn > cap) return fail(NRS_E_CAPACITY, "n exceeds capacity");
         NRSCHK(compact_holes());
         if (nn != n) st.to_fresh();
+        if (nn != n) ++particleGen;
         if (nn != n) { iisphPhase = 0; iisphIter = 0; } // (the hit lists of a predicted step belong to the old particle set)
         n = nn;
         if (slabOn) nOwned = n;
@@ -416,6 +420,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int set_boundary_bodies(const uint32_t *bodyOf, uint64_t nbGiven, uint32_t nbodies) override
     {
         NRSCHK(refuse_mid_iisph("nrs_set_boundary_bodies"));
+        ++boundaryGen;
         return bt.set_bodies(bodyOf, nbGiven, nbodies, slabOn, boundary_grid());
     }
     int set_body_velocity(uint32_t body, const double *v, const double *omega) override { return bt.set_body_velocity(body, v, omega); }
@@ -437,6 +442,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(grid_from_aabb(mn, mx, PU.interactionRadius, g));
         }
         bt.set_particles(bi4, vbi, nbNew); // (a new set of boundary particles has no body assignment)
+        ++boundaryGen;
         if (!nbNew) return NRS_OK;
         if (regrid) {
             NRSCHK(invalidate_grid_state());
@@ -1665,6 +1671,105 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const uint64_t elem = (r.unit == UNIT_VEC4_N || r.unit == UNIT_VEC4_NB) ? sizeof(T4) : r.unit == UNIT_SCALAR_N ? sizeof(R) : 4;
         *dptr = buf_ptr(r.buf);
         *bytes = (*dptr || which == NRS_ARR_B_BODY) ? elem * count : 0;
+        return NRS_OK;
+    }
+
+    // ---- field sampling (include/nereus_hip.h; DESIGN.md "Field sampling") ----------------------------------------------------------------
+    // The sampler owns its buffers and its grid (sm, nrs_field_sampler.h) and reads posA / velA, P and, for walls, bt's sorted array and
+    // cell table; the refusals, sizes and the cache rule are nrs_host_sample.h's.  Nothing a step owns is written.
+    FieldSampler sm;
+    uint64_t particleGen = 0, gridGen = 0, boundaryGen = 0; // uploads / nrs_set_num_particles, grid changes, boundary sets / body assignments
+    SampleFacts sample_facts() const
+    {
+        return SampleFacts{midStep, iisphPhase != 0, slabOn, {P.gridSize[0], P.gridSize[1], P.gridSize[2]},
+                           {(double)P.cellSize[0], (double)P.cellSize[1], (double)P.cellSize[2]}, (double)P.interactionRadius};
+    }
+    // points (device, m of them) or, null, the m nodes of L
+    int sample_run(const T4 *points, const SampleLattice &L, uint64_t m, uint32_t fields)
+    {
+        const SampleKey key{stepsDone, particleGen, gridGen, boundaryGen};
+        if (sm.cache.needs_build(key)) {
+            NRSCHK(sm.template build_grid<R>(P, posA.as<T4>(), velA.as<T4>(), n, stream));
+            sm.cache.built(key);
+        }
+        NRSCHK(sm.ensure_results(fields, m, sizeof(R)));
+        GridView<R> G;
+        std::memset(&G, 0, sizeof(G));
+        G.cellStart = sm.cell_start(); G.cellEnd = sm.cell_end();
+        G.nSorted = sm.sorted_count();
+        G.err = sm.err_word();
+        G.actLo = INT_MIN; G.actHi = INT_MAX;
+        const bool walls = (fields & NRS_FIELD_WALLS) && bt.count();
+        if (walls) { G.bCellStart = bt.cell_start(); G.bCellEnd = bt.cell_end(); G.sB = bt.sorted(); }
+        const SampleOut<R> O{(fields & NRS_FIELD_DENSITY) ? (R *)sm.result(NRS_FIELD_DENSITY) : nullptr,
+                             (fields & NRS_FIELD_GRADIENT) ? (T4 *)sm.result(NRS_FIELD_GRADIENT) : nullptr,
+                             (fields & NRS_FIELD_VELOCITY) ? (T4 *)sm.result(NRS_FIELD_VELOCITY) : nullptr,
+                             (fields & NRS_FIELD_COUNT) ? (uint32_t *)sm.result(NRS_FIELD_COUNT) : nullptr};
+        const dim3 g(nblocks(m)), b(BLOCK);
+        const T4 *sP = sm.template sorted_pos<T4>(), *sV = sm.template sorted_vel<T4>();
+        if (walls) hipLaunchKernelGGL((k_sample_points<R, KSET, true>), g, b, 0, stream, P, G, sP, sV, points, L, O, fields, (uint32_t)m);
+        else hipLaunchKernelGGL((k_sample_points<R, KSET, false>), g, b, 0, stream, P, G, sP, sV, points, L, O, fields, (uint32_t)m);
+        HIPCHK(hipGetLastError());
+        return NRS_OK;
+    }
+    int sample_begin(uint32_t fields)
+    {
+        NRSCHK(validate("nrs_sample_*"));
+        NRSCHK(sample_check_fields(fields));
+        return sample_refusal(sample_facts());
+    }
+    int sample_points(const void *points4, uint64_t m, uint32_t fields) override
+    {
+        NRSCHK(sample_begin(fields));
+        NRSCHK(sample_check_points(points4, m));
+        sm.last = SampleLast();
+        if (m) {
+            NRSCHK(sm.upload_points(points4, m, sizeof(T4), stream));
+            NRSCHK(sample_run(sm.template query_points<T4>(), SampleLattice(), m, fields));
+        }
+        sm.last = SampleLast{true, fields, m};
+        return NRS_OK;
+    }
+    int sample_lattice(const nrs_lattice *lattice, uint32_t fields) override
+    {
+        NRSCHK(sample_begin(fields));
+        uint64_t m = 0;
+        NRSCHK(sample_check_lattice(lattice, &m));
+        SampleLattice L;
+        for (int a = 0; a < 3; ++a) { L.origin[a] = lattice->origin[a]; L.spacing[a] = lattice->spacing[a]; L.dims[a] = lattice->dims[a]; }
+        sm.last = SampleLast();
+        NRSCHK(sample_run(nullptr, L, m, fields));
+        sm.last = SampleLast{true, fields, m};
+        return NRS_OK;
+    }
+    int sample_device_ptr(uint32_t field, void **dptr, uint64_t *bytes) override
+    {
+        NRSCHK(sample_route_result(sm.last, field, (int)(8 * sizeof(R)), bytes));
+        *dptr = *bytes ? sm.result(field) : nullptr;
+        return NRS_OK;
+    }
+    int sample_result(uint32_t field, void *dst, uint64_t dstBytes, uint64_t *outBytes) override
+    {
+        void *p = nullptr;
+        uint64_t sz = 0;
+        NRSCHK(sample_device_ptr(field, &p, &sz));
+        if (outBytes) *outBytes = sz;
+        if (!dst) return NRS_OK;
+        if (dstBytes < sz) return fail(NRS_E_INVALID, "destination too small");
+        if (!sz) return NRS_OK;
+        uint32_t e = 0;
+        HIPCHK(hipMemcpyAsync(dst, p, sz, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(&e, sm.err_word(), 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (!e) return NRS_OK;
+        HIPCHK(hipMemsetAsync(sm.err_word(), 0, 4, stream));
+        return fail(NRS_E_STATE, "field sampling: a cell range of the sampler's table lies outside its sorted particles; the gather skipped it, the results are invalid");
+    }
+    uint64_t sample_builds() override { return sm.cache.builds; }
+    int sample_release() override
+    {
+        HIPCHK(hipStreamSynchronize(stream)); // a queued gather may still read the buffers
+        sm.release();
         return NRS_OK;
     }
 };

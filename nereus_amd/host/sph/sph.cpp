@@ -240,6 +240,63 @@ void SPH::getBodyPose(SUint body, double x[3], double q[4])
     if (nrs_get_body_pose(m_ctx, body, x, q) != NRS_OK) fatal("nrs_get_body_pose");
 }
 
+// ---- field sampling --------------------------------------------------------------------------------------------------------------
+void SPH::sampleLattice(const double origin[3], const double spacing[3], const SUint dims[3], SUint fields)
+{
+    ensureContext();
+    pushHostToDevice();
+    nrs_lattice L;
+    std::memset(&L, 0, sizeof(L));
+    for (int a = 0; a < 3; ++a) { L.origin[a] = origin[a]; L.spacing[a] = spacing[a]; L.dims[a] = dims[a]; }
+    if (nrs_sample_lattice(m_ctx, &L, fields) != NRS_OK) fatal("nrs_sample_lattice");
+}
+void SPH::samplePoints(const SVec4 *points, SUint n, SUint fields)
+{
+    ensureContext();
+    pushHostToDevice();
+    if (nrs_sample_points(m_ctx, points, n, fields) != NRS_OK) fatal("nrs_sample_points");
+}
+template <typename T> static void fetchInto(nrs_ctx *ctx, SUint field, std::vector<T> &v, bool &ok)
+{
+    uint64_t bytes = 0;
+    ok = nrs_sample_result(ctx, field, nullptr, 0, &bytes) == NRS_OK;
+    if (!ok) return;
+    v.resize((size_t)(bytes / sizeof(T)));
+    if (bytes) ok = nrs_sample_result(ctx, field, v.data(), bytes, nullptr) == NRS_OK;
+}
+const std::vector<SReal> &SPH::getSampledDensity()
+{
+    bool ok = false;
+    ensureContext();
+    fetchInto(m_ctx, NRS_FIELD_DENSITY, m_sampledDensity, ok);
+    if (!ok) fatal("nrs_sample_result");
+    return m_sampledDensity;
+}
+const std::vector<SVec4> &SPH::getSampledGradient()
+{
+    bool ok = false;
+    ensureContext();
+    fetchInto(m_ctx, NRS_FIELD_GRADIENT, m_sampledGradient, ok);
+    if (!ok) fatal("nrs_sample_result");
+    return m_sampledGradient;
+}
+const std::vector<SVec4> &SPH::getSampledVelocity()
+{
+    bool ok = false;
+    ensureContext();
+    fetchInto(m_ctx, NRS_FIELD_VELOCITY, m_sampledVelocity, ok);
+    if (!ok) fatal("nrs_sample_result");
+    return m_sampledVelocity;
+}
+const std::vector<SUint> &SPH::getSampledCount()
+{
+    bool ok = false;
+    ensureContext();
+    fetchInto(m_ctx, NRS_FIELD_COUNT, m_sampledCount, ok);
+    if (!ok) fatal("nrs_sample_result");
+    return m_sampledCount;
+}
+
 nrs_ctx *SPH::deviceContext()
 {
     ensureContext();

@@ -96,6 +96,17 @@ public:
     void setBodyVelocity(SUint body, const double v[3], const double omega[3]);
     void setBodyPose(SUint body, const double x[3], const double q[4]);
     void getBodyPose(SUint body, double x[3], double q[4]);
+    // Field sampling (nrs_sample_*, DESIGN.md "Field sampling"): the SPH fields of the current state — density, its gradient, the
+    // Shepard-averaged velocity, the neighbour count (NRS_FIELD_* flags in `fields`, NRS_FIELD_WALLS adds the wall term to the density)
+    // — at n points, or on the dims[0] x dims[1] x dims[2] nodes origin + idx * spacing (node (i, j, k) at (k * dims[1] + j) * dims[0] + i).
+    // Both enqueue and return; the getters wait and return the field of the LAST sample call in a host array the solver owns, valid
+    // until the next getter call for that field.  Read-only: the simulation does not notice.
+    void sampleLattice(const double origin[3], const double spacing[3], const SUint dims[3], SUint fields);
+    void samplePoints(const SVec4 *points, SUint n, SUint fields);
+    const std::vector<SReal> &getSampledDensity();
+    const std::vector<SVec4> &getSampledGradient();
+    const std::vector<SVec4> &getSampledVelocity();
+    const std::vector<SUint> &getSampledCount();
     void reserveParticles(SUint capacity);        // grow host+device storage up front
     void setEagerSync(bool on) { m_eagerSync = on; } // true: D2H at the end of every update() like the reference
     const SphSimParams &getParams() const { return m_params; }
@@ -159,6 +170,9 @@ protected:
     mutable unsigned long long m_frameStep;
     mutable bool m_frameIsCurrent;       // m_frame shows the state after the last update()
     void collectFrames(bool waitForAll) const;
+    std::vector<SReal> m_sampledDensity; // host copies of the last sample call's results, fetched by the getters
+    std::vector<SVec4> m_sampledGradient, m_sampledVelocity;
+    std::vector<SUint> m_sampledCount;
 };
 
 NEREUS_NAMESPACE_END

@@ -18,6 +18,10 @@
 //                                                               wall, a plate of boundary particles behind the fluid that is body 1
 //                                                               and moves at 1 m/s along +x (setBoundaryBodies / setBodyVelocity);
 //                                                               the dumped bi are the rest positions, the plate last
+//   headless lattice <solver> <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <out.lat>
+//                                                               as run, then the density (fluid only) on the dx x dy x dz nodes
+//                                                               origin + idx * spacing (SPH::sampleLattice / getSampledDensity)
+//                                                               out.lat: u32 dx, dy, dz, u32 precision (32 | 64), SReal[dx * dy * dz]
 // in.bin : u32 n, u32 nb, then pos4[n], vel4[n], bi4[nb], vbi[nb] (SReal)
 // out.bin: u32 n, u32 nb, u32 iters, u32 sizeof(params), params, pos4[n], vel4[n], pressure[n], bi4[nb], vbi[nb]
 #include <cstdio>
@@ -27,6 +31,7 @@
 #include <vector>
 
 #include "common.h"
+#include "nereus_hip.h"
 #include "iisph/iisph.h"
 #include "dfsph/dfsph.h"
 #include "pbf/pbf.h"
@@ -97,8 +102,9 @@ int main(int argc, char **argv)
     unsigned iters = 0;
     if (mode == "params") {
         dump(argv[3], sim, 0, bi, vbi);
-    } else if (mode == "run" || mode == "frames") {
+    } else if (mode == "run" || mode == "frames" || mode == "lattice") {
         if (argc < 6) die("run needs <in.bin> <steps> <out.bin>");
+        if (mode == "lattice" && argc < 13) die("lattice needs <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <out.lat>");
         FILE *f = std::fopen(argv[3], "rb");
         if (!f) die("cannot open input");
         unsigned n = 0, nb = 0;
@@ -135,7 +141,22 @@ int main(int argc, char **argv)
         if (pcisphSolve) iters = static_cast<Nereus::PCISPH *>(sim)->getLastIterations();
         if (pbf) iters = static_cast<Nereus::PBF *>(sim)->getLastIterations();
         if (dfsph) iters = static_cast<Nereus::DFSPH *>(sim)->getLastIterations();
-        dump(argv[5], sim, iters, bi, vbi);
+        if (mode == "lattice") {
+            const double h = std::strtod(argv[8], nullptr);
+            const double origin[3] = {std::strtod(argv[5], nullptr), std::strtod(argv[6], nullptr), std::strtod(argv[7], nullptr)}, spacing[3] = {h, h, h};
+            const SUint dims[3] = {(SUint)std::strtoul(argv[9], nullptr, 10), (SUint)std::strtoul(argv[10], nullptr, 10), (SUint)std::strtoul(argv[11], nullptr, 10)};
+            sim->sampleLattice(origin, spacing, dims, NRS_FIELD_DENSITY);
+            const std::vector<SReal> &rho = sim->getSampledDensity();
+            if (rho.size() != (size_t)dims[0] * dims[1] * dims[2]) die("getSampledDensity: wrong size");
+            FILE *o = std::fopen(argv[12], "wb");
+            if (!o) die("cannot open output");
+            const unsigned head[4] = {dims[0], dims[1], dims[2], (unsigned)(8 * sizeof(SReal))};
+            std::fwrite(head, 4, 4, o);
+            std::fwrite(rho.data(), sizeof(SReal), rho.size(), o);
+            std::fclose(o);
+        } else {
+            dump(argv[5], sim, iters, bi, vbi);
+        }
     } else if (mode == "resume" || mode == "cfl") {
         FILE *f = std::fopen(argv[3], "rb");
         if (!f) die("cannot open input");
