@@ -6,14 +6,19 @@
 // "unsorted" arrays of step t+1 are the integrated sorted arrays of step t (buffer swap), which is what
 // the reference obtains by copying sorted→host→device.
 //
-// Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the hash and reorder launches of the sort
-// stage, the solver tails, the slab code.  The boundary particles, their tables and bodies depend on the precision alone and live in one
-// member, bt (BoundaryTables<R>, nrs_boundary_tables.h), which launches its own builds; the per-step wall list, sized by the fluid,
-// stays here.  The sort stage's state depends on none of the three and lives in one member, sort (SortStage, nrs_sort.h; compiled once,
-// in nrs_sort.hip, with the radix sorts and the merge): the (hash, index) pairs and which of each is current, prepared or a pack
-// target, the sort's workspace, the buffers of the coherent re-sort, its mover-count word and statistics.  The context reads views of
-// it (sort.hash(), sort.index(), sort.prepared(), the tile counts the fused and the slab kernels write) and calls its operations
-// (sort_keys, scan_movers, split, scan_holes, the pack targets); no pointer of it is assigned here.
+// Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the particle arrays, the solvers' buffers,
+// the cell table and the hit lists, the hash and reorder launches of the sort stage, the solver tails.  Everything else has one owner
+// outside it, held as one member, read through views and driven through named operations; no buffer of theirs is assigned here.
+// The boundary particles, their tables and bodies depend on the precision alone: bt (BoundaryTables<R>, nrs_boundary_tables.h), which
+// launches its own builds.  So does the slab exchange: exch (SlabExchange<R>, nrs_slab_exchange.h) has the cuts, the window, the last
+// pack, the ghost streams, block counts, totals and flags of the partition, the pinned landing and the pack's event, and launches the
+// slab kernels; the context decides the refusals and applies what a pack or unpack means to n, nOwned and the array state.  The
+// step's wall list, sized by the fluid, is templated on nothing: wlist (WallLists, nrs_wall_list.h).  Nor is the sort stage's state:
+// sort (SortStage, nrs_sort.h; compiled once, in nrs_sort.hip, with the radix sorts and the merge) has the (hash, index) pairs and
+// which of each is current, prepared or a pack target, the sort's workspace, the buffers of the coherent re-sort, its mover-count
+// word and statistics.  The context reads views of it (sort.hash(), sort.index(), sort.prepared(), the tile counts the fused and the
+// slab kernels write) and calls its operations (sort_keys, scan_movers, split, scan_holes, the pack targets).  The field sampler's
+// buffers: sm (FieldSampler, nrs_field_sampler.h).
 // Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure functions it calls:
 // the stage timer (nrs_host_profile.h), the snapshot ring (nrs_host_snapshot.h), the solver settings and their validation
 // (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
@@ -33,6 +38,7 @@
 #include "nrs_host_solver.h"
 #include "nrs_host_state.h"
 #include "nrs_sort.h"
+#include "nrs_wall_list.h"
 
 #include "nrs_kernels_ref.h"
 #include "nrs_kernels_tiled.h"
@@ -44,16 +50,12 @@
 #include "nrs_kernels_dfsph.h"
 #include "nrs_kernels_akinci.h"
 #include "nrs_kernels_bodies.h"
-#include "nrs_kernels_slab.h"
+#include "nrs_slab_exchange.h"
 #include "nrs_field_sampler.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
 
 namespace nrs {
-
-static_assert(SLT_STAY == ST_STAY && SLT_MIG_L == ST_MIG_L && SLT_HALO_L == ST_HALO_L && SLT_MIG_R == ST_MIG_R && SLT_HALO_R == ST_HALO_R &&
-              SLT_GHOST == ST_GHOST && SLT_COUNT == ST_COUNT && SLT_CHANGED == ST_CHANGED && SLT_TOTALS == ST_TOTALS,
-              "nrs_host_slab.h numbers the stream totals as nrs_kernels_slab.h does");
 
 template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     typedef typename Vec4T<R>::type T4;
@@ -63,15 +65,16 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // width) stop growing with the number of ranks.  Cell coordinates stay global (calcGridPos is unchanged), only the hash
     // rebases x: the sort order, and with it every per-particle result, is the one of the global grid.
     Params<R> PU, P;
-    SlabHost sx; // the window, the last pack and its totals (nrs_host_slab.h)
+    SlabExchange<R> exch; // the cuts, the window, the last pack and its totals, the exchange's buffers and launches (nrs_slab_exchange.h)
     void derive_kernel_params()
     {
         P = PU;
         P.numBodies = 0;
-        if (sx.winW && sx.winW < PU.gridSize[0]) {
-            P.numBodies = (uint32_t)sx.winBase;
-            P.gridSize[0] = sx.winW;
-            P.numCells = sx.winW * PU.gridSize[1] * PU.gridSize[2];
+        const SlabHost &w = exch.host();
+        if (w.winW && w.winW < PU.gridSize[0]) {
+            P.numBodies = (uint32_t)w.winBase;
+            P.gridSize[0] = w.winW;
+            P.numCells = w.winW * PU.gridSize[1] * PU.gridSize[2];
         }
         // compact scan candidates (nrs_math.h): quanta per metre, threshold of the superset test, and whether the geometry allows
         // it at all (a pair inside the interaction radius must be less than two cells apart on every axis)
@@ -146,59 +149,13 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     DevBuf hitBuf, hitCounts; // hit lists shared by the density and force kernels of a step
     HitBuffer hit_buffer() const { return HitBuffer{hitBuf.as<uint32_t>(), hitCounts.as<uint32_t>(), (uint32_t)cap}; }
     // wall-particle deferral (nrs_kernels_tiled.h): this step's wall list, from the near-boundary bit per cell that bt keeps
-    DevBuf wallList, wallTile, wallTileOffset, wallGroupTotal, wallGroupPrefix, wallScalars, wallMask;
-    // sized by the fluid capacity; a rest build of the boundary tables calls it where the near bits become valid
-    int ensure_wall_list()
-    {
-        const size_t nTiles = (cap + BLOCK - 1) / BLOCK, nGroups = (nTiles + RESORT_GROUP - 1) / RESORT_GROUP;
-        NRSCHK(wallList.alloc((size_t)cap * 4));
-        NRSCHK(wallTile.alloc(nTiles * 4)); NRSCHK(wallTileOffset.alloc(nTiles * 4));
-        NRSCHK(wallMask.alloc(nTiles * 4 * 8));
-        NRSCHK(wallGroupTotal.alloc(nGroups * 4)); NRSCHK(wallGroupPrefix.alloc(nGroups * 4)); NRSCHK(wallScalars.alloc(16));
-        HIPCHK(hipMemsetAsync(wallScalars.p, 0, 16, stream));
-        return NRS_OK;
-    }
-    WallList wall_view() const { return WallList{bt.near_bits(), sort.hash(), wallList.as<uint32_t>(), wallScalars.as<uint32_t>() + 1, wallMask.as<unsigned long long>()}; }
-    // this step's wall list: tile counts (reorder kernel) -> two-level scan (the re-sort's scan kernel) -> stable compaction
-    int build_wall_list(uint32_t N)
-    {
-        const uint32_t nTiles = nblocks(N);
-        const WallList wl = wall_view(); // (the tile counts were left by the reorder kernel of this step)
-        uint32_t *sc = wallScalars.as<uint32_t>();
-        const ResortScan a = {wallTile.as<uint32_t>(), wallTileOffset.as<uint32_t>(), wallGroupTotal.as<uint32_t>(), wallGroupPrefix.as<uint32_t>(), sc + 1};
-        NRSCHK(sort.scan_tiles(a, sc, nTiles));
-        hipLaunchKernelGGL(k_wall_compact, dim3(nTiles), dim3(BLOCK), 0, stream, wl, wallTileOffset.as<uint32_t>(), wallGroupPrefix.as<uint32_t>(),
-                           (uint32_t)RESORT_GROUP, wallList.as<uint32_t>(), N);
-        HIPCHK(hipGetLastError());
-        return NRS_OK;
-    }
+    WallLists wlist; // its buffers, the scan and the compaction (nrs_wall_list.h)
+    WallList wall_view() const { return wlist.view(bt.near_bits(), sort.hash()); }
+    int build_wall_list(uint32_t N) { return wlist.build(N, sort, stream, bt.near_bits(), sort.hash()); }
     DevBuf fastQ;             // NRS_FLAG_FAST_ARITH: (p/rho^2, 1/rho) per sorted slot, density kernel -> force kernel
     bool splitClearedCells = false; // this step's split of the coherent re-sort also reset the cell table
-    // slab decomposition
-    bool slabOn = false;
-    SlabCfg slab = {INT_MIN / 2, INT_MAX / 2, 2};
-    DevBuf ghostPos, ghostVel, slabCounts, slabTotals;
-    uint64_t nOwned = 0;
+    uint64_t nOwned = 0;     // slab decomposition: of the n particles, those this rank owns (the rest are halo copies)
     bool cellsClean = false; // cellStart is all-EMPTY
-    DevBuf slabFlags; // fused classification: the force kernel's stream flags (st: classifiedValid, classifiedN)
-    // page-locked landing place (HT_WORDS words) of what the host reads in an exchange, and the event behind the pack's part of it
-    enum { HT_TOTALS = 0,              // the ST_TOTALS stream totals of the pack
-           HT_SCAN = 8,                // pre-classified form: sort.scan_scalars(), of which ...
-           HT_SCAN_CHANGED = HT_SCAN + 1, HT_SCAN_DEAD = HT_SCAN + 2, // ... the cell changers and the dead slots
-           HT_HEADER_L = 16, HT_HEADER_R = 20, // the 16-byte headers of the received messages
-           HT_WORDS = 32 };
-    PinnedBuf<uint32_t> slabHostTotals;
-    Event packEvent;
-    int ensure_host_totals()
-    {
-        if (!slabHostTotals) HIPCHK(hipHostMalloc((void **)&slabHostTotals.p, HT_WORDS * 4, hipHostMallocDefault));
-        return NRS_OK;
-    }
-    int ensure_pack_event()
-    {
-        if (!packEvent) HIPCHK(hipEventCreateWithFlags(&packEvent.e, hipEventDisableTiming));
-        return NRS_OK;
-    }
     bool fusedThisStep = false;
     StageTimer timer; // profiling (nrs_host_profile.h)
 
@@ -208,7 +165,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     ArrayTracker st;
     ArrayState array_state() const
     {
-        return nrs::array_state(st.fields(), ArrayFacts{n, cap, nOwned, slabOn, sx.inplace(), sort.prepared().hash != nullptr,
+        return nrs::array_state(st.fields(), ArrayFacts{n, cap, nOwned, exch.on(), exch.host().inplace(), sort.prepared().hash != nullptr,
                                                         sort.prepared().index != nullptr, sort.hash() != nullptr, sort.has_resort()});
     }
     void keys_ready() { sort.keys_written(); st.keys_ready(); } // -> AS_KEYS_READY
@@ -219,8 +176,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         char buf[320];
         snprintf(buf, sizeof(buf), "internal state inconsistent at %s (n %llu cap %llu physN %u owned %llu | hashReady %d rsPending %d countKnown %d "
                  "known %u holes %d inplace %d classified %d slotOrder %d slab %d)", where, (unsigned long long)n, (unsigned long long)cap, f.physN,
-                 (unsigned long long)nOwned, f.hashReady, f.rsPending, f.rsCountKnown, f.rsKnownCount, f.holesPending, sx.inplace(),
-                 f.classifiedValid, f.slotOrderValid, slabOn);
+                 (unsigned long long)nOwned, f.hashReady, f.rsPending, f.rsCountKnown, f.rsKnownCount, f.holesPending, exch.host().inplace(),
+                 f.classifiedValid, f.slotOrderValid, exch.on());
         return fail(NRS_E_STATE, buf);
     }
 
@@ -235,7 +192,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     PlanFacts plan_facts() const
     {
         return PlanFacts{cfg.flags, cfg.solver, KSET == KS_MULLER, std::is_same<R, float>::value, cap, n, qOk, pow2_grid(), bt.near_bits_valid(), bt.count() != 0,
-                         slabOn, P.numCells};
+                         exch.on(), P.numCells};
     }
     Features features() const { return plan_features(plan_facts()); }
     // Chosen at the start of every step (step(), nrs_iisph_predict) and held until its end: a host-driven IISPH step spans three calls.
@@ -307,6 +264,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(redPartial.alloc(sizeof(double) * 1024));
         NRSCHK(redOut.alloc(2 * sizeof(double)));
         NRSCHK(sort.init(cap, ft.resort, stream));
+        exch.init(cap, stream);
         NRSCHK(alloc_cells());
         return NRS_OK;
     }
@@ -338,7 +296,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         pbfSt.params_changed(stale);
         dfSt.params_changed(stale);
         PU = q;
-        if (!sameGrid && slabOn) sx.choose_window(PU.gridSize, slab.lo, slab.hi, slab.halo, true);
+        if (!sameGrid && exch.on()) exch.choose_window(PU.gridSize, true);
         derive_kernel_params();
         const bool regrid = P.numCells != cellsBefore;
         if (regrid) NRSCHK(alloc_cells());
@@ -384,7 +342,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         if (first + count > n) n = first + count;
         ++particleGen;
-        if (slabOn) nOwned = n; // (until the next partition says otherwise)
+        if (exch.on()) nOwned = n; // (until the next partition says otherwise)
         midStep = false;
         iisphPhase = 0; iisphIter = 0; // new particles abandon a host-driven IISPH step that was in progress
         st.to_fresh();
@@ -399,7 +357,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (nn != n) ++particleGen;
         if (nn != n) { iisphPhase = 0; iisphIter = 0; } // (the hit lists of a predicted step belong to the old particle set)
         n = nn;
-        if (slabOn) nOwned = n;
+        if (exch.on()) nOwned = n;
         return NRS_OK;
     }
     uint64_t get_n() override { return n; }
@@ -408,7 +366,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint32_t sort_end_bit() const { return sort_key_bits(P.numCells); }
     BoundaryGrid<R> boundary_grid()
     {
-        return BoundaryGrid<R>{P, sort_end_bit(), features().listKernels && pow2_grid(), stream, [this] { return ensure_wall_list(); }};
+        return BoundaryGrid<R>{P, sort_end_bit(), features().listKernels && pow2_grid(), stream, [this] { return wlist.ensure(cap, stream); }};
     }
     // the tables at the uploaded positions, on the current grid (the boundary hashes / cell table depend on origin, cell size and extents)
     int rebuild_boundary_tables()
@@ -421,7 +379,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         NRSCHK(refuse_mid_iisph("nrs_set_boundary_bodies"));
         ++boundaryGen;
-        return bt.set_bodies(bodyOf, nbGiven, nbodies, slabOn, boundary_grid());
+        return bt.set_bodies(bodyOf, nbGiven, nbodies, exch.on(), boundary_grid());
     }
     int set_body_velocity(uint32_t body, const double *v, const double *omega) override { return bt.set_body_velocity(body, v, omega); }
     int set_body_pose(uint32_t body, const double *x, const double *q) override { return bt.set_body_pose(body, x, q); }
@@ -448,7 +406,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(invalidate_grid_state());
             for (int a = 0; a < 3; ++a) { PU.worldOrigin[a] = g.origin[a]; PU.gridSize[a] = g.size[a]; }
             PU.numCells = g.numCells;
-            if (slabOn) sx.choose_window(PU.gridSize, slab.lo, slab.hi, slab.halo, true);
+            if (exch.on()) exch.choose_window(PU.gridSize, true);
             derive_kernel_params();
         }
         return rebuild_boundary_tables();
@@ -527,12 +485,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             hipLaunchKernelGGL((k_reorder_merged<R>), g, b, 0, stream, merged, sort.hash(), sort.index(), posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
                                cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
-                               nearB, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc, qp);
+                               nearB, wlist.tile_counts(), wlist.slot_masks(), qc, qp);
         else
             hipLaunchKernelGGL((k_reorder<R>), g, b, 0, stream, sort.hash(), sort.index(), posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
                                cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
-                               nearB, wallTile.as<uint32_t>(), wallMask.as<unsigned long long>(), qc, qp);
+                               nearB, wlist.tile_counts(), wlist.slot_masks(), qc, qp);
         if (iisph() && (cfg.flags & NRS_FLAG_IISPH_SELF_BY_SLOT)) // Q5 off: the pressure kernels skip j == own slot
             hipLaunchKernelGGL(k_identity, g, b, 0, stream, inv.as<uint32_t>(), N);
         if (dfsph()) { // the warm-start inputs of the step, K_prev and Kv_prev, into sorted order
@@ -580,7 +538,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         const uint32_t N = (uint32_t)n;
         const dim3 g(nblocks(N)), b(BLOCK);
         GridView<R> G = grid_view();
-        if (slabOn) { G.actLo = slab.lo - 1; G.actHi = slab.hi + 1; } // density is also needed one cell beyond the cuts
+        if (exch.on()) { G.actLo = exch.cuts().lo - 1; G.actHi = exch.cuts().hi + 1; } // density is also needed one cell beyond the cuts
         // the density kernel's hit lists are handed to the force kernel when both run in this call
         HitBuffer hb = hit_buffer();
         hb.gpos = gatherPos.p; hb.gvel = gatherPos.as<T4>() + 1; hb.svel = velB.p; // (the two records of a slot side by side: GATHER_STRIDE)
@@ -603,7 +561,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         } else {
             launch_density_tiled<R, KSET, HAS_B>(stream, P, G, share, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, walls);
         }
-        if (slabOn) { G.actLo = slab.lo; G.actHi = slab.hi; }
+        if (exch.on()) { G.actLo = exch.cuts().lo; G.actHi = exch.cuts().hi; }
         NRSCHK(ev_end());
         if (stop == NRS_STAGE_DENSITY) return NRS_OK;
         // A full step on the production kernels fuses forces + integrate + next-step hash into one launch that
@@ -613,7 +571,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (plan.keys) {
             fo.newPos = posA.as<T4>(); fo.newVel = velA.as<T4>();
             fo.hash = sort.next_keys().hash; fo.index = sort.next_keys().index;
-            fo.slab = slab;
+            fo.slab = exch.cuts();
             if (plan.resort || plan.classify) {
                 NRSCHK(sort.clean_tile_counts());
                 fo.prevHash = sort.hash();
@@ -621,13 +579,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             }
             st.classification_dropped();
             if (plan.classify) {
-                const uint32_t nbk = std::max<uint32_t>(1u, (N + SLAB_TILE - 1) / SLAB_TILE);
-                NRSCHK(slabFlags.alloc(cap));
-                NRSCHK(slabCounts.alloc((size_t)ST_TOTALS * ((cap_blocks() > nbk) ? cap_blocks() : nbk) * 4));
-                HIPCHK(hipMemsetAsync(slabCounts.p, 0, (size_t)ST_TOTALS * nbk * 4, stream));
-                fo.slabFlags = slabFlags.as<uint8_t>();
-                fo.slabBlockCounts = slabCounts.as<uint32_t>();
-                fo.slabBlocks = nbk;
+                SlabClassify sc;
+                NRSCHK(exch.classify_targets(N, sc));
+                fo.slabFlags = sc.flags;
+                fo.slabBlockCounts = sc.blockCounts;
+                fo.slabBlocks = sc.blocks;
                 fo.tileDead = sort.tile_dead();
                 st.classified(N);
                 sort.tile_counts_written(); // until a pack's scan consumes the tile counts
@@ -647,7 +603,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                                                       fused, N, walls);
         }
         if (plan.keys) {
-            if (!slabOn) keys_ready();
+            if (!exch.on()) keys_ready();
             else sort.keys_written(); // a slab run re-partitions the arrays before the next step (AS_SLOT_ORDER)
             fusedThisStep = true;
         }
@@ -831,7 +787,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ev_begin(stage));
         return launch_last([&](uint32_t *nh, uint32_t *ni, const uint32_t *prevHash, uint32_t *tileMovers) {
             hipLaunchKernelGGL((k_iisph_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), velAdv.as<T4>(), forcesP.as<T4>(), N,
-                               nh, ni, prevHash, tileMovers, slabOn ? 1 : 0);
+                               nh, ni, prevHash, tileMovers, exch.on() ? 1 : 0);
         });
     }
 
@@ -1276,14 +1232,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         if (!iisphPhase) return fail(NRS_E_STATE, "nrs_iisph_predict first");
         if (phase == 1) { // one iteration + the density-error sum over the particles this rank owns
-            if (slabOn && (int)iisphIter >= slabMaxIters())
+            if (exch.on() && (int)iisphIter >= exch.max_iters())
                 return fail(NRS_E_STATE, "IISPH slab run: more solver iterations than the halo width supports (halo >= 2 * iterations + 4 cells)");
             if (bt.count()) NRSCHK(iisph_iteration<true>()); else NRSCHK(iisph_iteration<false>());
             const uint32_t N = (uint32_t)n, nbk = std::min<uint32_t>(1024u, nblocks(N));
             unsigned long long *cnt = (unsigned long long *)((char *)redOut.p); // redOut: [double sum][u64 count]
             HIPCHK(hipMemsetAsync(redOut.p, 0, 16, stream));
             hipLaunchKernelGGL((k_sum_partial<R>), dim3(nbk), dim3(BLOCK), 0, stream, densCorr.as<R>(), redPartial.as<double>(), N,
-                               slabOn ? posB.as<T4>() : (const T4 *)nullptr, cnt + 1);
+                               exch.on() ? posB.as<T4>() : (const T4 *)nullptr, cnt + 1);
             hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(BLOCK), 0, stream, redPartial.as<double>(), redOut.as<double>(), nbk);
             double h[2] = {0, 0};
             HIPCHK(hipMemcpyAsync(h, redOut.p, 16, hipMemcpyDeviceToHost, stream));
@@ -1291,7 +1247,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             unsigned long long c;
             std::memcpy(&c, &h[1], 8);
             if (sum) *sum = h[0];
-            if (count) *count = slabOn ? (uint64_t)c : (uint64_t)N;
+            if (count) *count = exch.on() ? (uint64_t)c : (uint64_t)N;
             lastIters = iisphIter;
             return NRS_OK;
         }
@@ -1303,21 +1259,20 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         iisphPhase = 0;
         return NRS_OK;
     }
-    int slabMaxIters() const { return (slab.halo - 4) / 2; }
-
-    // ---- slab decomposition (nrs_kernels_slab.h; the host decisions: nrs_host_slab.h) ------------------------------------
+    // ---- slab decomposition: the exchange itself lives in exch (nrs_slab_exchange.h; its kernels: nrs_kernels_slab.h; the host
+    // decisions: nrs_host_slab.h); here: the refusals, and what a call does to n, nOwned and the state of the particle arrays ----------
     int slab_configure(int lo, int hi, int halo) override
     {
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
         NRSCHK(slab_refuse_configure(cfg.solver, bt.has_bodies(), lo, hi, halo));
+        bool cutsChanged = false;
+        exch.configure(lo, hi, halo, &cutsChanged);
         // the last force kernel classified (and marked dead keys) for the old cuts: partition the slow way once
-        if (st.fields().classifiedValid && (slab.lo != lo || slab.hi != hi || slab.halo != halo)) st.cuts_changed();
-        slab.lo = lo; slab.hi = hi; slab.halo = halo;
-        slabOn = true;
+        if (st.fields().classifiedValid && cutsChanged) st.cuts_changed();
         nOwned = n;
         // cell-table window of this rank (see PU / P): re-chosen only when the slab no longer fits the current one
         const uint32_t cellsBefore = P.numCells, baseBefore = P.numBodies;
-        if (sx.choose_window(PU.gridSize, lo, hi, halo, false)) {
+        if (exch.choose_window(PU.gridSize, false)) {
             NRSCHK(invalidate_grid_state());
             derive_kernel_params();
             if (P.numCells != cellsBefore || P.numBodies != baseBefore) {
@@ -1328,36 +1283,18 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         return NRS_OK;
     }
-    uint64_t num_owned() override { return slabOn ? nOwned : n; }
+    uint64_t num_owned() override { return exch.on() ? nOwned : n; }
     int slab_histogram(int lo0, uint32_t nbins, uint32_t *out) override
     {
         if (!nbins || !out) return fail(NRS_E_INVALID, "bad histogram request");
         NRSCHK(compact_holes());
-        DevBuf bins;
-        NRSCHK(bins.alloc((size_t)nbins * 4));
-        HIPCHK(hipMemsetAsync(bins.p, 0, (size_t)nbins * 4, stream));
-        if (n)
-            hipLaunchKernelGGL((k_slab_histogram<R>), dim3((uint32_t)((n + SLAB_BLOCK - 1) / SLAB_BLOCK)), dim3(SLAB_BLOCK), 0, stream, P,
-                               posA.as<T4>(), (uint32_t)n, lo0, nbins, bins.as<uint32_t>());
-        HIPCHK(hipMemcpyAsync(out, bins.p, (size_t)nbins * 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return NRS_OK;
+        return exch.histogram(P, posA.as<T4>(), n, lo0, nbins, out);
     }
 
-    // The stream totals (and, in the pre-classified form, the scalars of the re-sort's scan) on their way to the host, and the event
-    // finish_pack() waits for.  Page-locked destination: the copy is complete when the event behind it is (a pageable destination is
-    // only guaranteed after a stream synchronization, which would also wait for the split queued behind it).
-    int totals_to_host(bool withScan)
-    {
-        HIPCHK(hipMemcpyAsync(slabHostTotals + HT_TOTALS, slabTotals.p, ST_TOTALS * 4, hipMemcpyDeviceToHost, stream));
-        if (withScan) HIPCHK(hipMemcpyAsync(slabHostTotals + HT_SCAN, sort.scan_scalars(), 16, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipEventRecord(packEvent, stream));
-        return NRS_OK;
-    }
     int slab_pack(void *sendL, void *sendR, uint64_t mcap, uint32_t *counts) override
     {
         NRSCHK(validate("nrs_slab_pack"));
-        if (!slabOn) return fail(NRS_E_STATE, "nrs_slab_configure first");
+        if (!exch.on()) return fail(NRS_E_STATE, "nrs_slab_configure first");
         if (midStep) return fail(NRS_E_STATE, "state is mid-update");
         if (mcap == 0 || mcap > (uint64_t)HIT_INDEX) return fail(NRS_E_INVALID, "bad message capacity");
         NRSCHK(finish_pack());   // (a pack right behind a pack whose totals nobody has looked at yet)
@@ -1366,93 +1303,33 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (iisph() && n) // the warm-start pressure travels in vel.w (k_pressure_to_velw)
             hipLaunchKernelGGL((k_pressure_to_velw<R>), dim3(nblocks(n)), dim3(BLOCK), 0, stream, velA.as<T4>(), presA.as<R>(), (uint32_t)n);
         const uint32_t N = (uint32_t)n;
-        const uint32_t nbk = std::max<uint32_t>(1u, (N + SLAB_TILE - 1) / SLAB_TILE);
-        NRSCHK(slabCounts.alloc((size_t)ST_TOTALS * ((cap_blocks() > nbk) ? cap_blocks() : nbk) * 4));
-        NRSCHK(slabTotals.alloc(ST_TOTALS * 4));
-        NRSCHK(ghostPos.alloc(sizeof(T4) * mcap));
-        NRSCHK(ghostVel.alloc(sizeof(T4) * mcap));
-        NRSCHK(ensure_host_totals());
-        NRSCHK(ensure_pack_event());
         const SlabChoice ch = choose_form(SlabFacts{st.fields().classifiedValid, st.fields().slotOrderValid, sort.has_resort(), sort.hash() != nullptr,
                                                     sort.prepared().hash != nullptr, sort.prepared().hash != sort.hash(), st.fields().classifiedN, N, RESORT_MIN_PARTICLES});
-        const bool inplace = ch.form != SlabForm::COMPACT, pre = ch.form == SlabForm::PRECLASSIFIED;
-        if (N) {
-            // pre-classified: the force kernel of the last step classified every slot for these cuts (flags, stream populations per
-            // 2048 slots, dead marks in the keys, movers / dead per 256 slots); what is left is to scan, copy out the few particles
-            // of the message and ghost streams, and split
-            if (!pre)
-                hipLaunchKernelGGL((k_slab_count<R>), dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(), N,
-                                   slabCounts.as<uint32_t>(), nbk, ch.resort ? sort.hash() : (const uint32_t *)nullptr,
-                                   ch.resort ? sort.prepared().hash : (const uint32_t *)nullptr);
-            hipLaunchKernelGGL(k_slab_scan, dim3(ST_TOTALS), dim3(SLAB_BLOCK), 0, stream, slabCounts.as<uint32_t>(), nbk, slabTotals.as<uint32_t>());
-            // in place, the fused kernel's keys / slot numbers stay where they are; the compacting form does the hash pass of the next
-            // step here, into the key buffers the last sort did not end in
-            const KeyPair target = sort.pack_targets(inplace);
-            SlabOut<R> out;
-            out.stayPos = posB.as<T4>(); out.stayVel = velB.as<T4>();
-            out.hash = target.hash; out.index = target.index;
-            out.prevHash = ch.resort ? sort.hash() : nullptr;
-            out.prevPacked = (ch.resort && !inplace) ? sort.prev_packed() : nullptr;
-            out.tileMovers = ch.resort ? sort.tile_movers() : nullptr;
-            out.tileDead = inplace ? sort.tile_dead() : nullptr;
-            out.flags = pre ? slabFlags.as<uint8_t>() : nullptr;
-            out.ghostPos = ghostPos.as<T4>(); out.ghostVel = ghostVel.as<T4>();
-            out.sendL = (unsigned char *)sendL; out.sendR = (unsigned char *)sendR;
-            out.cap = (uint32_t)mcap;
-            if (ch.resort && !pre) { // the scatter counts per tile (pre-classified: the force kernel did, and its counts are still there)
-                NRSCHK(sort.clean_tile_counts());
-                sort.tile_counts_written(); // (and stay marked until a scan: the counts of an unused classification may still be in the arrays)
-            }
-            const auto scatter = pre ? k_slab_scatter<R, true, true> : inplace ? k_slab_scatter<R, true> : k_slab_scatter<R, false>;
-            hipLaunchKernelGGL(scatter, dim3(nbk), dim3(SLAB_BLOCK), 0, stream, P, slab, posA.as<T4>(), velA.as<T4>(), N, slabCounts.as<uint32_t>(),
-                               nbk, slabTotals.as<uint32_t>(), out);
-        } else {
-            HIPCHK(hipMemsetAsync(slabTotals.p, 0, ST_TOTALS * 4, stream));
-        }
-        hipLaunchKernelGGL(k_slab_headers, dim3(1), dim3(64), 0, stream, slabTotals.as<uint32_t>(), (unsigned char *)sendL, (unsigned char *)sendR);
-        HIPCHK(hipGetLastError());
-        // In place, the split of the slots we keep does not depend on what arrives: it is queued now, so that it runs while the
-        // messages travel.  Its scan also totals the cell changers and the dead slots, which in the pre-classified form nothing else
-        // has counted: there the scan comes before the copy and the event.  Otherwise the event comes first, and finish_pack() never
-        // waits for the scan.  (N == 0: the totals are zero and nobody reads the landing; only the event is needed.)
-        const uint32_t nTiles = nblocks(N);
-        if (!N) HIPCHK(hipEventRecord(packEvent, stream));
-        else if (!pre) NRSCHK(totals_to_host(false));
-        if (inplace) NRSCHK(sort.scan_movers(nTiles, true));
-        if (pre) NRSCHK(totals_to_host(true));
-        if (inplace) {
-            NRSCHK(sort.split(SplitFrom::SORTED_HOLES, N, nullptr));
-            HIPCHK(hipGetLastError());
-        }
-        // Nothing above waits.  The messages are complete in stream order, so the caller can enqueue its sends right behind this call;
-        // the stream totals (how many stay, leave, ghost) are read back by finish_pack() — in nrs_slab_unpack, together with the
-        // headers of the received messages: ONE host synchronisation per exchange instead of two — or by whichever entry point needs
-        // the particle count first (settle()).
-        sx.queue(ch, N, mcap);
+        // count -> scan -> scatter, the headers, the totals on their way to the host, in place the split; nothing waits: the totals
+        // are read back by finish_pack()
+        NRSCHK(exch.pack(P, posA.as<T4>(), velA.as<T4>(), posB.as<T4>(), velB.as<T4>(), N, sendL, sendR, mcap, ch, sort));
         if (counts) { // the caller wants the counts now: that is the synchronisation it asked for
             NRSCHK(finish_pack());
-            std::memcpy(counts, sx.totals, ST_COUNT * sizeof(uint32_t));
+            std::memcpy(counts, exch.host().totals, ST_COUNT * sizeof(uint32_t));
         }
         return NRS_OK;
     }
-    // ---- the host half of nrs_slab_pack, run when the stream totals are needed ---------------------------------------------
+    // ---- the host half of nrs_slab_pack, run when the stream totals are needed: what they mean for the arrays -----------------------
     int finish_pack()
     {
-        if (!sx.pending) return NRS_OK;
-        sx.pending = false; // (whatever the wait returns)
-        HIPCHK(hipEventSynchronize(packEvent));
         SlabFinish f;
-        const int rc = sx.finish(slabHostTotals + HT_TOTALS, slabHostTotals[HT_SCAN_CHANGED], slabHostTotals[HT_SCAN_DEAD], f);
+        const int rc = exch.finish(f); // (nothing pending, or the wait failed: nothing stored)
         if (!f.stored) return rc;
+        const uint32_t packedN = exch.host().N;
         st.to_fresh();
         if (f.form != SlabForm::COMPACT) {
             // the prepared keys / values hold key and slot of every live slot, 0xffffffff marks the dead ones; arrivals are added to the mover
             // count by nrs_slab_unpack
-            st.to_holes(sx.N, f.movers);
+            st.to_holes(packedN, f.movers);
         } else {
-            if (sx.N) { std::swap(posA.p, posB.p); std::swap(velA.p, velB.p); }
+            if (packedN) { std::swap(posA.p, posB.p); std::swap(velA.p, velB.p); }
             else sort.pack_targets_empty();
-            st.pack_hashed(sx.N != 0); // k_slab_scatter hashed the particles that stay (with the current parameters)
+            st.pack_hashed(packedN != 0); // k_slab_scatter hashed the particles that stay (with the current parameters)
         }
         n = f.n;
         nOwned = n;
@@ -1462,46 +1339,25 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int slab_last_counts(uint32_t *counts) override
     {
         NRSCHK(finish_pack());
-        std::memcpy(counts, sx.totals, ST_COUNT * sizeof(uint32_t));
+        std::memcpy(counts, exch.host().totals, ST_COUNT * sizeof(uint32_t));
         return NRS_OK;
     }
-    uint32_t cap_blocks() const { return (uint32_t)((cap + SLAB_TILE - 1) / SLAB_TILE); }
 
     int slab_unpack(const void *recvL, const void *recvR, uint64_t mcap) override
     {
         NRSCHK(validate("nrs_slab_unpack"));
         NRSCHK(refuse_mid_iisph("nrs_slab_unpack"));
-        if (!slabOn) return fail(NRS_E_STATE, "nrs_slab_configure first");
-        // ONE host synchronisation for the exchange: the headers of the received messages (how many migrants, how many halo copies)
-        // are copied to page-locked memory behind the receives, and the same wait covers the stream totals of the pack (finish_pack)
-        NRSCHK(ensure_host_totals());
-        uint32_t *hL = recvL ? slabHostTotals + HT_HEADER_L : nullptr, *hR = recvR ? slabHostTotals + HT_HEADER_R : nullptr;
-        if (hL) HIPCHK(hipMemcpyAsync(hL, recvL, 16, hipMemcpyDeviceToHost, stream));
-        if (hR) HIPCHK(hipMemcpyAsync(hR, recvR, 16, hipMemcpyDeviceToHost, stream));
-        if (hL || hR) HIPCHK(hipStreamSynchronize(stream));
+        if (!exch.on()) return fail(NRS_E_STATE, "nrs_slab_configure first");
+        // ONE host synchronisation for the exchange: the wait for the headers of the received messages also covers the stream totals
+        // of the pack (finish_pack)
+        const uint32_t *hL = nullptr, *hR = nullptr;
+        NRSCHK(exch.read_headers(recvL, recvR, &hL, &hR));
         NRSCHK(finish_pack());
         SlabArrivals ar;
-        NRSCHK(sx.unpack(hL, hR, n, st.fields().physN, st.fields().holesPending, mcap, cap, ar));
-        const unsigned char *bL = (const unsigned char *)recvL, *bR = (const unsigned char *)recvR;
-        auto mp = [&](const unsigned char *b) { return (const T4 *)(b + 16); };
-        auto mv = [&](const unsigned char *b) { return (const T4 *)(b + 16 + (size_t)mcap * sizeof(T4)); };
-        const uint32_t migL = hL ? hL[0] : 0u, migR = hR ? hR[0] : 0u;
-        AppendPieces<R> A;
-        A.srcPos[0] = bL ? mp(bL) : nullptr;           A.srcVel[0] = bL ? mv(bL) : nullptr;            // migrants from the left
-        A.srcPos[1] = bR ? mp(bR) : nullptr;           A.srcVel[1] = bR ? mv(bR) : nullptr;            // migrants from the right
-        A.srcPos[2] = ghostPos.as<T4>();               A.srcVel[2] = ghostVel.as<T4>();               // our ghosts
-        A.srcPos[3] = bL ? mp(bL) + migL : nullptr;    A.srcVel[3] = bL ? mv(bL) + migL : nullptr;     // halo from the left
-        A.srcPos[4] = bR ? mp(bR) + migR : nullptr;    A.srcVel[4] = bR ? mv(bR) + migR : nullptr;     // halo from the right
-        std::memcpy(A.start, ar.start, sizeof(A.start));
+        NRSCHK(exch.arrivals(hL, hR, n, st.fields().physN, st.fields().holesPending, mcap, ar));
         // compacting form with a re-sort: the append extends the compacted old keys and the tile counts of the scatter
-        const bool compactResort = sx.form == SlabForm::COMPACT && sx.resort;
-        if (A.start[5])
-            hipLaunchKernelGGL((k_slab_append<R>), dim3((A.start[5] + SLAB_BLOCK - 1) / SLAB_BLOCK), dim3(SLAB_BLOCK), 0, stream, P, A,
-                               posA.as<T4>(), velA.as<T4>(), sort.pack_keys().hash, sort.pack_keys().index,
-                               compactResort ? sort.prev_packed() : (uint32_t *)nullptr,
-                               compactResort ? sort.tile_movers() : (uint32_t *)nullptr, (uint32_t)ar.base,
-                               ar.inplace ? sort.movers() : (uint64_t *)nullptr, ar.inplace ? st.fields().rsKnownCount : 0u);
-        HIPCHK(hipGetLastError());
+        const bool compactResort = exch.host().form == SlabForm::COMPACT && exch.host().resort;
+        NRSCHK(exch.append(P, ar, recvL, recvR, mcap, posA.as<T4>(), velA.as<T4>(), sort, compactResort, ar.inplace ? st.fields().rsKnownCount : 0u));
         nOwned = ar.nOwned;
         n = ar.n;
         if (iisph() && n)
@@ -1515,9 +1371,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             const uint32_t N = (uint32_t)n;
             NRSCHK(sort.scan_movers(nblocks(N), false));
             NRSCHK(sort.split(SplitFrom::PACKED, N, nullptr));
-            st.split_queued_known(sx.totals[ST_CHANGED] + A.start[5]); // everything appended is a mover, and the partition counted the cell changers
+            st.split_queued_known(exch.host().totals[ST_CHANGED] + ar.start[5]); // everything appended is a mover, and the partition counted the cell changers
         }
-        sx.resort = false;
+        exch.unpack_done();
         return NRS_OK;
     }
 
@@ -1529,7 +1385,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // which statistic an id means on this context, or its refusal: route_stat (nrs_host_solver.h); the device work is here
     StatFacts stat_facts() const
     {
-        return StatFacts{cfg.solver, sx.packed, pbfSt.errPending != 0, !(pciSt.lastErr < 0.0), dfSt.denN, dfSt.divN, hitCounts.p != nullptr, n != 0, midStep};
+        return StatFacts{cfg.solver, exch.host().packed, pbfSt.errPending != 0, !(pciSt.lastErr < 0.0), dfSt.denN, dfSt.divN, hitCounts.p != nullptr, n != 0, midStep};
     }
     int get_stat(int which, double *out) override
     {
@@ -1542,7 +1398,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         switch (r.kind) {
         case STAT_MOVER_COUNT: *out = sort.stats().lastMovers; return NRS_OK;
-        case STAT_SLAB_FORM: *out = (int)sx.form; return NRS_OK;
+        case STAT_SLAB_FORM: *out = (int)exch.host().form; return NRS_OK;
         case STAT_PBF_ERROR:
         case STAT_PCI_ERROR: *out = pciSt.lastErr; return NRS_OK;
         case STAT_PBF_EPS: *out = (double)pbfSt.eps(); return NRS_OK;
@@ -1681,7 +1537,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint64_t particleGen = 0, gridGen = 0, boundaryGen = 0; // uploads / nrs_set_num_particles, grid changes, boundary sets / body assignments
     SampleFacts sample_facts() const
     {
-        return SampleFacts{midStep, iisphPhase != 0, slabOn, {P.gridSize[0], P.gridSize[1], P.gridSize[2]},
+        return SampleFacts{midStep, iisphPhase != 0, exch.on(), {P.gridSize[0], P.gridSize[1], P.gridSize[2]},
                            {(double)P.cellSize[0], (double)P.cellSize[1], (double)P.cellSize[2]}, (double)P.interactionRadius};
     }
     // points (device, m of them) or, null, the m nodes of L

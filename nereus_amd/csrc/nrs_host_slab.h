@@ -1,7 +1,8 @@
 // nrs_host_slab.h — the host decisions of the slab exchange (nrs_slab_configure / _pack / _unpack): which cell-table window a rank
 // keeps, which calls nrs_slab_configure refuses, which form the partition takes, what the stream totals of a pack mean and where the
-// pieces of an unpack go.  No HIP: plain integers and bools in, plain integers out.  The context (nrs_ctx_impl.h) holds one SlabHost,
-// launches the kernels and applies what these functions return to n, nOwned and the state of the particle arrays (array_state()).
+// pieces of an unpack go.  No HIP: plain integers and bools in, plain integers out.  The exchange's owner (SlabExchange<R>,
+// nrs_slab_exchange.h) holds one SlabHost and launches the kernels; the context (nrs_ctx_impl.h) reads it through that owner and applies
+// what these functions return to n, nOwned and the state of the particle arrays (array_state()).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -54,7 +55,7 @@ static inline SlabChoice choose_form(const SlabFacts &f)
     return {resort && (uint64_t)f.N >= f.resortMin ? SlabForm::INPLACE : SlabForm::COMPACT, resort};
 }
 
-// the stream totals of a pack, in the order of nrs_kernels_slab.h's ST_* (nrs_ctx_impl.h asserts that they agree)
+// the stream totals of a pack, in the order of nrs_kernels_slab.h's ST_* (nrs_slab_exchange.h asserts that they agree)
 enum { SLT_STAY = 0, SLT_MIG_L = 1, SLT_HALO_L = 2, SLT_MIG_R = 3, SLT_HALO_R = 4, SLT_GHOST = 5, SLT_COUNT = 6, SLT_CHANGED = 6, SLT_TOTALS = 7 };
 
 struct SlabFinish { // what SlabHost::finish hands the context; valid when `stored`

@@ -1,9 +1,12 @@
 // nrs_kernels_slab.h — device side of the multi-GPU slab decomposition (new: the reference is
 // single-GPU).  Each rank owns the particles whose global grid cell-x lies in [lo, hi).  Once per step, before
-// update(), every rank partitions its current particles into six streams with ONE stable multi-way
-// compaction (count → scan → scatter; deterministic, no atomics on the output order):
+// update(), every rank partitions its current particles into six streams (count → scan → scatter; deterministic,
+// no atomics on the output order), in one of three forms (SlabForm, nrs_host_slab.h; launched by nrs_slab_exchange.h):
+// COMPACT, ONE stable multi-way compaction that also moves the particles that stay to the front of the other arrays;
+// INPLACE, where they keep their slots, the slots that empty get the key 0xffffffff and only the message and ghost
+// streams are copied out; PRECLASSIFIED, in place with the count pass already done by the fused force kernel of the step.
 //
-//   STAY    cell-x in [lo,hi)                      → stays owned (compacted to the front of the local arrays)
+//   STAY    cell-x in [lo,hi)                      → stays owned (COMPACT: compacted to the front of the local arrays)
 //   MIG_L/R cell-x < lo / >= hi                    → ownership moves to the left / right neighbour
 //   HALO_L/R STAY particles within `halo` cells of the left / right cut → copied to that neighbour as read-only halo
 //   GHOST   migrants still within `halo` cells of our cut → we keep a read-only copy (they are the neighbour's now)
