@@ -20,7 +20,7 @@ import time
 
 import numpy as np
 
-from . import scene
+from . import capi, scene
 from .params import default_params, update_grid
 
 HALO_CELLS = 2
@@ -33,6 +33,13 @@ def iisph_halo_cells(max_iters):
     return 2 * max(2, int(max_iters)) + 4
 NO_CUT_LO = -(1 << 29)
 NO_CUT_HI = (1 << 29)
+
+
+def mean_density(total, count, real=np.float32):
+    """The mean corrected density that IISPH's exit test reads, from the sums of all ranks, in the solver's precision:
+    `rho_avg = (SReal)acc; rho_avg /= N` (sph_cuda.cu:818-819).  The one statement of that rule for SlabDriver.iisph_step,
+    tools/fuzz_slab.py and the tests' in-process ranks."""
+    return real(real(total) / real(count))
 
 
 def cell_of(x, origin_x, cell_x, real=np.float32):
@@ -88,13 +95,13 @@ class HipSlabEngine:
     """Product engine: particles live in an nrs_ctx on this rank's GPU; buffers are torch CUDA tensors."""
 
     def __init__(self, params, capacity, msg_capacity, cell_lo, cell_hi, device_index, halo=None, iisph=False, flags=0,
-                 iisph_max_iters=2):
+                 iisph_max_iters=2, double=False, kernel_set=capi.MULLER):
         """halo: cells exchanged per side; None = 2 for SESPH, iisph_halo_cells(iisph_max_iters) for IISPH.  An IISPH slab run can
         do at most (halo - 4) // 2 solver iterations per step (`max_iters`; SlabDriver.iisph_step stops there and counts the step
-        as truncated, like nrs_set_max_iterations on a single domain) — size the halo from the iteration budget."""
+        as truncated, like nrs_set_max_iterations on a single domain) — size the halo from the iteration budget.
+        double / kernel_set select the build of the context; SlabDriver.iisph_step forms its mean density in
+        float64 when `double` is set."""
         import torch
-
-        from . import capi
 
         self.torch = torch
         self.device = torch.device("cuda", device_index)
@@ -105,11 +112,13 @@ class HipSlabEngine:
         self.stream = torch.cuda.Stream(device=self.device)
         assert self.stream.cuda_stream != 0
         self.iisph = bool(iisph)
+        self.double = bool(double)
         if halo is None:
             halo = iisph_halo_cells(iisph_max_iters) if iisph else HALO_CELLS
         self.max_iters = (halo - 4) // 2 if iisph else None
         self.solver = capi.Solver(params, capacity, solver=capi.IISPH if iisph else capi.SESPH, device=device_index,
-                                  stream=self.stream.cuda_stream, flags=flags)
+                                  stream=self.stream.cuda_stream, flags=flags, double=self.double,
+                                  kernel_set=kernel_set)
         self.cell_lo, self.cell_hi, self.halo = cell_lo, cell_hi, halo
         self.msg_bytes = self.solver.message_bytes(self.msg_capacity)
         self._configured = False
@@ -266,7 +275,7 @@ class SlabDriver:
                 t = t.to(dev)
             dist.all_reduce(t, group=self.group)
             tot, cnt = (float(v) for v in t.cpu())
-            rho_avg = real(real(tot) / real(cnt))   # `rho_avg = (SReal)acc; rho_avg /= N` (sph_cuda.cu:818-819)
+            rho_avg = mean_density(tot, cnt, real)
             it += 1
         eng.iisph_finish()
         self.last_iterations = it

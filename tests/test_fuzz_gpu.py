@@ -34,6 +34,23 @@ def test_random_slab_runs_equal_single_domain(hip_lib):
     assert "12 seeds, 0 failures" in r.stdout and "'migrants': 0," not in r.stdout
 
 
+@pytest.mark.gpu
+def test_random_slab_runs_equal_single_domain_fp64(hip_lib):
+    """tools/fuzz_slab.py in the fp64 builds, every second seed Monaghan: the end state equals the single domain's within
+    TOL_STEPS_F64, after the oracle's run of each scene has shown no pair within 1e-11 m of the cut-off radius (a seed that fails this
+    is replaced by the next one, not counted)."""
+    import subprocess
+
+    from tests.test_parity_gpu import TOL_STEPS_F64
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_slab.py"), "6", "7100", "sesph", "f64", "alternate", repr(TOL_STEPS_F64)],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    print(r.stdout[-1500:])
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
+    assert "6 seeds, 0 failures, 0 skipped" in r.stdout and "'migrants': 0," not in r.stdout
+    assert "largest difference f64 muller" in r.stdout and "largest difference f64 monaghan" in r.stdout
+
+
 def _classes(seeds, solver):
     from fuzz_parity import make_scene
     c = dict(fp64=0, narrow_x=0, far=0, nonfinite=0, resort=0, walls=0, monaghan=0)

@@ -29,26 +29,34 @@ def _free_port():
     return port
 
 
-def _worker(rank, world, port, steps, use_hip, outdir, skew=0, rebalance_every=0, lattice=None):
+def _base_params(double, kset):
+    """constructor defaults in the build's precision (the kernel set changes none of them), as tools/fuzz_slab.py takes them"""
+    from nereus_amd.params import default_params
+
+    return default_params(0, double=double)
+
+
+def _worker(rank, world, port, steps, use_hip, outdir, skew=0, rebalance_every=0, lattice=None, double=False, kset=1):
     sys.path.insert(0, ROOT)
     import torch.distributed as dist
 
     from nereus_amd import scene, slab
-    from nereus_amd.params import default_params
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     lattice = lattice or LATTICE
-    p, cuts, pos, vel, bi, vbi, info = slab.rank_scene(lattice, rank, world, default_params(0))
+    real = np.float64 if double else np.float32
+    assert use_hip or real is np.float32   # (the checker engine is fp32 Muller)
+    p, cuts, pos, vel, bi, vbi, info = slab.rank_scene(lattice, rank, world, _base_params(double, kset), real=real)
     # particle id rides in vel.w (preserved by reorder/integrate/exchange): global lattice id
     nx, ny, nz = lattice
-    d = float(np.float32(p["interactionRadius"][0])) - 0.005
+    d = float(real(p["interactionRadius"][0])) - 0.005
     ix = np.rint(pos[:, 0] / d - 1).astype(np.int64)
     iy = np.rint(pos[:, 1] / d - 1).astype(np.int64)
     iz = np.rint(pos[:, 2] / d - 1).astype(np.int64)
-    vel[:, 3] = ((ix * ny + iy) * nz + iz).astype(np.float32)
-    vel[:, 0] = np.where((iy + iz) % 2 == 0, 2.5, -2.5).astype(np.float32)  # make particles cross the cuts
+    vel[:, 3] = ((ix * ny + iy) * nz + iz).astype(real)
+    vel[:, 0] = np.where((iy + iz) % 2 == 0, 2.5, -2.5).astype(real)  # make particles cross the cuts
     if skew:  # deliberately unbalanced cuts (every interior cut moved by `skew` cells) to exercise the re-cut
         cuts = [cuts[0]] + [c + skew for c in cuts[1:-1]] + [cuts[-1]]
         ox, cs = float(p["worldOrigin"][0][0]), float(p["cellSize"][0][0])
@@ -68,7 +76,7 @@ def _worker(rank, world, port, steps, use_hip, outdir, skew=0, rebalance_every=0
     if lattice != LATTICE:
         msg_cap, ctx_cap = slab.capacities(lattice, float(p["interactionRadius"][0]), len(pos))
     if use_hip:
-        eng = slab.HipSlabEngine(p, ctx_cap, msg_cap, cuts[rank], cuts[rank + 1], 0)
+        eng = slab.HipSlabEngine(p, ctx_cap, msg_cap, cuts[rank], cuts[rank + 1], 0, double=double, kernel_set=kset)
     else:
         from tests.slab_check_engine import OracleSlabEngine
 
@@ -97,15 +105,18 @@ def _worker(rank, world, port, steps, use_hip, outdir, skew=0, rebalance_every=0
     dist.destroy_process_group()
 
 
-def _run(world, steps, use_hip, tmp_path, skew=0, rebalance_every=0, lattice=None):
+def _run(world, steps, use_hip, tmp_path, skew=0, rebalance_every=0, lattice=None, double=False, kset=1, tol=1e-5, cut_off_margin=0.0):
+    """cut_off_margin > 0: before anything is compared, no pair of the oracle's run comes closer than that to the cut-off radius
+    (tests/slab_scenes.py cut_off_margin: the truncated Monaghan kernels jump there)"""
     from nereus_amd import scene
-    from nereus_amd.params import default_params, params_dtype
+    from nereus_amd.params import params_dtype
     from tests.common import rel_err
     from tests.oracle_lib import SESPH, Oracle
 
     lattice = lattice or LATTICE
-    mp.spawn(_worker, args=(world, _free_port(), steps, use_hip, str(tmp_path), skew, rebalance_every, lattice), nprocs=world,
-             join=True)
+    real = np.float64 if double else np.float32
+    mp.spawn(_worker, args=(world, _free_port(), steps, use_hip, str(tmp_path), skew, rebalance_every, lattice, double, kset),
+             nprocs=world, join=True)
     parts = [np.load(os.path.join(str(tmp_path), "rank%d.npz" % r)) for r in range(world)]
     pos = np.concatenate([q["pos"] for q in parts])
     vel = np.concatenate([q["vel"] for q in parts])
@@ -115,23 +126,35 @@ def _run(world, steps, use_hip, tmp_path, skew=0, rebalance_every=0, lattice=Non
     ids = vel[:, 3].astype(np.int64)
     assert np.array_equal(np.sort(ids), np.arange(n))
     # single-domain oracle on the union scene with the same global grid
-    p = parts[0]["params"].view(params_dtype(False)).copy()
+    p = parts[0]["params"].view(params_dtype(double)).copy()
     h = float(p["interactionRadius"][0])
-    full = scene.dam_break((nx * world, ny, nz), h=h, kpoly=float(p["kpoly"][0]))
+    full = scene.dam_break((nx * world, ny, nz), h=h, kpoly=float(p["kpoly"][0]), real=real)
     fvel = full["vel"].copy()
-    fvel[:, 3] = np.arange(n, dtype=np.float32)
+    fvel[:, 3] = np.arange(n, dtype=real)
     gid = np.arange(n)
-    fvel[:, 0] = np.where(((gid // nz) % ny + gid % nz) % 2 == 0, 2.5, -2.5).astype(np.float32)
-    o = Oracle(p, solver=SESPH, threads=min(16, os.cpu_count() or 1))
+    fvel[:, 0] = np.where(((gid // nz) % ny + gid % nz) % 2 == 0, 2.5, -2.5).astype(real)
+    o = Oracle(p, double, kset, SESPH, threads=min(16, os.cpu_count() or 1), tait="double7" if double else "powf")
     o.set_particles(full["pos"], fvel)
     o.set_boundaries(full["bi"], full["vbi"], update_grid=True)
     np.testing.assert_array_equal(o.params.view(np.uint8), p.view(np.uint8))  # same GLOBAL grid on every rank
-    o.step(steps)
+    if cut_off_margin:
+        from tests.slab_scenes import cut_off_margin as margin_of
+
+        states = [(full["pos"], fvel)]
+        for _ in range(steps):
+            o.step(1)
+            states.append((o.get("pos").copy(), None))
+        assert margin_of(states, h) >= cut_off_margin, margin_of(states, h)
+    else:
+        o.step(steps)
     rp, rv = o.get("pos"), o.get("vel")
     order_ref = np.argsort(rv[:, 3].astype(np.int64))
     order_got = np.argsort(ids)
-    assert rel_err(pos[order_got][:, :3], rp[order_ref][:, :3]) <= 1e-5
-    assert rel_err(vel[order_got][:, :3], rv[order_ref][:, :3]) <= 1e-5
+    e_p, e_v = rel_err(pos[order_got][:, :3], rp[order_ref][:, :3]), rel_err(vel[order_got][:, :3], rv[order_ref][:, :3])
+    print("slab gloo %s kset %d, %d ranks, %d steps against the oracle: pos %.3g vel %.3g (bar %.0e)"
+          % ("f64" if double else "f32", kset, world, steps, e_p, e_v, tol))
+    assert e_p <= tol
+    assert e_v <= tol
     _run.owned = [q["owned"] for q in parts]
     _run.resort = [tuple(int(v) for v in q["resort"]) for q in parts]
     return sum(int(q["moved"]) for q in parts)
@@ -145,6 +168,16 @@ def test_slab_protocol_gloo_cpu(tmp_path, world):
 @pytest.mark.gpu
 def test_slab_hip_engine_two_ranks_one_gpu(tmp_path, hip_lib):
     assert _run(2, 25, True, tmp_path) > 0
+
+
+@pytest.mark.gpu
+def test_slab_hip_engine_fp64_monaghan(tmp_path, hip_lib):
+    """the product driver and engine in the fp64 Monaghan build (HipSlabEngine(double=True, kernel_set=MONAGHAN)): 12 steps against
+    the fp64 Monaghan oracle at TOL_STEPS_F64, no pair within 1e-11 m of the cut-off radius during the oracle's run"""
+    from nereus_amd import capi
+    from tests.test_parity_gpu import TOL_STEPS_F64
+
+    assert _run(2, 12, True, tmp_path, double=True, kset=capi.MONAGHAN, tol=TOL_STEPS_F64, cut_off_margin=1e-11) > 0
 
 
 @pytest.mark.gpu
@@ -246,20 +279,21 @@ def test_slab_rebalance_hip_engine(tmp_path, hip_lib):
 IISPH_LATTICE = (22, 8, 8)
 
 
-def _iisph_scene():
+def _iisph_scene(double=False, kset=1):
     """A compressed block (so that the pressure solve has work) under the IISPH constructor defaults: global 128^3 grid."""
     from nereus_amd import scene
     from nereus_amd.params import default_params
 
-    p = default_params(1)
+    real = np.float64 if double else np.float32
+    p = default_params(1, double=double)   # (the kernel set changes none of the constructor defaults)
     h = float(p["interactionRadius"][0])
-    pos = scene.fluid_block(*IISPH_LATTICE, h, jitter=0.02, spacing=0.72 * h)
+    pos = scene.fluid_block(*IISPH_LATTICE, h, real=real, jitter=0.02, spacing=0.72 * h)
     vel = np.zeros_like(pos)
-    vel[:, 0] = np.where((np.arange(len(pos)) // IISPH_LATTICE[2]) % 2 == 0, 1.5, -1.5).astype(np.float32)  # cross the cut
+    vel[:, 0] = np.where((np.arange(len(pos)) // IISPH_LATTICE[2]) % 2 == 0, 1.5, -1.5).astype(real)  # cross the cut
     return p, pos, vel
 
 
-def _iisph_worker(rank, world, port, steps, use_hip, outdir, by_slot, force_iters=0, halo=None):
+def _iisph_worker(rank, world, port, steps, use_hip, outdir, by_slot, force_iters=0, halo=None, double=False, kset=1):
     sys.path.insert(0, ROOT)
     import torch.distributed as dist
 
@@ -268,18 +302,20 @@ def _iisph_worker(rank, world, port, steps, use_hip, outdir, by_slot, force_iter
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    p, pos, vel = _iisph_scene()
+    p, pos, vel = _iisph_scene(double, kset)
     ox, cs = float(p["worldOrigin"][0][0]), float(p["cellSize"][0][0])
-    cx = slab.cell_of(pos[:, 0], ox, cs)
+    cx = slab.cell_of(pos[:, 0], ox, cs, real=pos.dtype.type)
     cut = int(np.median(cx)) + 1
     cuts = [slab.NO_CUT_LO, cut, slab.NO_CUT_HI]
     mine = (cx >= cuts[rank]) & (cx < cuts[rank + 1])
     halo = halo or slab.IISPH_HALO_CELLS
     if use_hip:
         eng = slab.HipSlabEngine(p, 4 * len(pos), 2 * len(pos), cuts[rank], cuts[rank + 1], 0, halo=halo, iisph=True,
-                                 flags=capi.FLAG_IISPH_SELF_BY_SLOT if by_slot else 0)
+                                 flags=capi.FLAG_IISPH_SELF_BY_SLOT if by_slot else 0, double=double, kernel_set=kset)
     else:
         from tests.slab_check_engine import OracleSlabEngine
+
+        assert not double and kset == 1   # (the checker engine is fp32 Muller)
 
         eng = OracleSlabEngine(p, 2 * len(pos), cuts[rank], cuts[rank + 1], halo=halo, iisph=True, self_by_slot=by_slot)
     eng.load(pos[mine], vel[mine], None, None)
@@ -297,10 +333,10 @@ def _iisph_worker(rank, world, port, steps, use_hip, outdir, by_slot, force_iter
     dist.destroy_process_group()
 
 
-def _iisph_single(p, pos0, vel0, steps, by_slot, force_iters=0):
+def _iisph_single(p, pos0, vel0, steps, by_slot, force_iters=0, double=False, kset=1):
     from tests.oracle_lib import IISPH, Oracle
 
-    o = Oracle(p, solver=IISPH, self_by_slot=by_slot)
+    o = Oracle(p, double, kset, solver=IISPH, self_by_slot=by_slot, tait="double7" if double else "powf")
     o.set_particles(pos0, vel0)
     o.set_boundaries(None, None)
     iters = []
@@ -318,31 +354,36 @@ def _match(ref_pos, pos):
     return cKDTree(ref_pos[:, :3]).query(pos[:, :3])
 
 
-def _run_iisph(steps, use_hip, tmp_path, by_slot, force_iters=0, halo=None, single_iters=None):
-    mp.spawn(_iisph_worker, args=(2, _free_port(), steps, use_hip, str(tmp_path), by_slot, force_iters, halo), nprocs=2, join=True)
+def _run_iisph(steps, use_hip, tmp_path, by_slot, force_iters=0, halo=None, single_iters=None, double=False, kset=1):
+    mp.spawn(_iisph_worker, args=(2, _free_port(), steps, use_hip, str(tmp_path), by_slot, force_iters, halo, double, kset), nprocs=2,
+             join=True)
     parts = [np.load(os.path.join(str(tmp_path), "irank%d.npz" % r)) for r in range(2)]
     pos = np.concatenate([q["pos"] for q in parts])
     vel = np.concatenate([q["vel"] for q in parts])
-    p, pos0, vel0 = _iisph_scene()
+    p, pos0, vel0 = _iisph_scene(double, kset)
     assert len(pos) == len(pos0), "particles lost or duplicated by the exchange"
     assert sum(int(q["moved"]) for q in parts) > 0
-    rp, rv, ref_iters = _iisph_single(p, pos0, vel0, steps, by_slot, force_iters if single_iters is None else single_iters)
+    rp, rv, ref_iters = _iisph_single(p, pos0, vel0, steps, by_slot, force_iters if single_iters is None else single_iters, double, kset)
     assert list(parts[0]["iters"]) == ref_iters == list(parts[1]["iters"])   # the global exit test, same count on every rank
     _run_iisph.truncated = [int(q["truncated"]) for q in parts]
     d, idx = _match(rp, pos)
     return pos, vel, rp, rv, d, idx
 
 
-def _check_order_independent(steps, use_hip, tmp_path, force_iters=0, halo=None, single_iters=None):
+def _check_order_independent(steps, use_hip, tmp_path, force_iters=0, halo=None, single_iters=None, double=False, kset=1,
+                             tol=(1e-5, 1e-4)):
     """NRS_FLAG_IISPH_SELF_BY_SLOT (SURVEY Q5 off): the result no longer depends on the order of the arrays, so two slabs must
     reproduce the single-domain oracle particle for particle — this is the test of the halo width, of the pressure carried in
     vel.w and of the all-reduced exit test."""
     from tests.common import rel_err
 
-    pos, vel, rp, rv, d, idx = _run_iisph(steps, use_hip, tmp_path, True, force_iters, halo, single_iters)
+    pos, vel, rp, rv, d, idx = _run_iisph(steps, use_hip, tmp_path, True, force_iters, halo, single_iters, double, kset)
     assert len(np.unique(idx)) == len(pos) and d.max() < 1e-5
-    assert rel_err(pos[:, :3], rp[idx, :3]) <= 1e-5
-    assert rel_err(vel[:, :3], rv[idx, :3]) <= 1e-4
+    e_p, e_v = rel_err(pos[:, :3], rp[idx, :3]), rel_err(vel[:, :3], rv[idx, :3])
+    print("slab gloo iisph by slot %s kset %d, %d steps against the oracle: pos %.3g vel %.3g (bars %.0e / %.0e)"
+          % ("f64" if double else "f32", kset, steps, e_p, e_v, tol[0], tol[1]))
+    assert e_p <= tol[0]
+    assert e_v <= tol[1]
 
 
 def _check_reference_mode(steps, use_hip, tmp_path):
@@ -373,6 +414,16 @@ def test_iisph_slabs_reference_mode_gloo_cpu(tmp_path):
 @pytest.mark.gpu
 def test_iisph_slabs_hip_engine(tmp_path, hip_lib):
     _check_order_independent(6, True, tmp_path)
+
+
+@pytest.mark.gpu
+def test_iisph_slabs_hip_engine_fp64_muller(tmp_path, hip_lib):
+    """the fp64 Muller build through the product driver: SlabDriver.iisph_step forms its mean density in float64 (engine.double);
+    self-exclusion by slot, against the fp64 oracle at TOL_STEPS_F64"""
+    from nereus_amd import capi
+    from tests.test_parity_gpu import TOL_STEPS_F64
+
+    _check_order_independent(6, True, tmp_path, double=True, kset=capi.MULLER, tol=(TOL_STEPS_F64, TOL_STEPS_F64))
 
 
 @pytest.mark.gpu
