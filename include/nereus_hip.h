@@ -483,6 +483,50 @@ int nrs_sample_device_ptr(nrs_ctx *ctx, uint32_t field, void **dptr, uint64_t *b
 int nrs_sample_release(nrs_ctx *ctx);
 int nrs_sample_builds(nrs_ctx *ctx, uint64_t *builds);
 
+/* ---- surface extraction (DESIGN.md "Surface extraction"; came after nrs_version() 0.3 without a version change) ------------------------
+ * The iso-surface rho = iso of the sampled density as an indexed triangle mesh, by marching tetrahedra on the nodes of a lattice, all
+ * on the device.  nrs_surface_extract IS nrs_sample_lattice(ctx, lattice, DENSITY [| GRADIENT] [| VELOCITY] [| WALLS]) followed by the
+ * mesher: it writes the sampler's own result arrays (nrs_sample_result(ctx, NRS_FIELD_DENSITY, ...) afterwards returns exactly the
+ * lattice the mesh was cut from), every refusal and the cache rule of the sampler apply, nrs_sample_builds counts as for any sample
+ * call.  Read-only like the sampler.  Every output is bit-reproducible: nothing below depends on a launch geometry.
+ *
+ * Nodes.  Lattice, node positions and linear node index are nrs_sample_lattice's.  A node is INSIDE when rho(node) >= (SReal)iso.
+ * Cells.  The cube with low corner (i, j, k), i < dims[0] - 1, j < dims[1] - 1, k < dims[2] - 1, cells ordered by the linear index of
+ *   their low corner.  Each is split into the six Kuhn tetrahedra: for a permutation (a, b, c) of the axes the corners 000, +e_a,
+ *   +e_a+e_b, 111 (tet-local numbers 0..3), permutations in lexicographic order xyz, xzy, yxz, yzx, zxy, zyx.  All six share the body
+ *   diagonal and neighbouring cells agree on every face diagonal, so there are no ambiguous cases.
+ * Vertices.  Every node owns the seven lattice edges towards +, numbered (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1),
+ *   those whose far node exists.  An owned edge whose ends differ in inside-ness carries one vertex; vertices are numbered by owner
+ *   node ascending, then edge number ascending.  With p0, f0 position and density of the owner and p1, f1 of the far node, in SReal:
+ *   t = (iso - f0) / (f1 - f0), x = p0 + t * (p1 - p0) per component (the library is built without contraction: two roundings).  The
+ *   record is SVec4 (x, y, z, t).
+ * Triangles.  Three uint32_t vertex numbers; listed by cell ascending, then tet, then within the tet.  A tet with one corner inside,
+ *   or three, gives one triangle over its three crossing edges.  One with inside corners a < b and outside corners c < d gives the quad
+ *   ac, ad, bd, bc split along ac-bd into (ac, ad, bd) and (ac, bd, bc).  Every triangle is wound so that its right-hand normal points
+ *   from the inside corners to the outside ones (out of the fluid).  A surface that does not reach the lattice boundary is a closed,
+ *   consistently oriented manifold; one cut by the boundary is open there.
+ * Attributes (flags).  NRS_SURFACE_GRADIENT / NRS_SURFACE_VELOCITY: the sampler's gradient / velocity record at the two end nodes,
+ *   interpolated as g0 + t * (g1 - g0) on all four components, one SVec4 per vertex.  Not normalised: the outward normal is -g / |g|.
+ *   NRS_SURFACE_WALLS: the density includes the wall term (NRS_FIELD_WALLS).
+ *
+ * nrs_surface_extract needs the totals to size its outputs: it WAITS for the context's stream once (queued nrs_step work included) and
+ * reads back eight bytes.  *vertices / *triangles (either may be NULL) get V and T.  An empty surface is a success with V = T = 0 and
+ * zero-byte results.  nrs_surface_result copies ONE result (an NRS_MESH_* id) to the host and waits (dst NULL: only the size):
+ * SVec4[V] vertices / gradient / velocity, uint32_t[3 T] triangles; nrs_surface_device_ptr gives its device address (NULL for zero
+ * bytes).  The mesh buffers belong to the mesher: valid until the next extract, nrs_surface_release (frees only the mesher's buffers)
+ * or nrs_destroy; nrs_sample_* calls and nrs_sample_release do not touch them.  Nothing is allocated before the first extract.
+ *
+ * NRS_E_INVALID: iso not finite or <= 0; unknown flag bits; a lattice dim below 2; more than 2^27 nodes (7 vertices and 12 triangles
+ * per node then fit 32-bit offsets); a `which` that is not exactly one result id; everything nrs_sample_lattice refuses as invalid.
+ * NRS_E_STATE: a result or pointer before any extract or after nrs_surface_release, or of an attribute the last extract did not
+ * compute; mid-update after nrs_step_partial; a host-driven IISPH step in progress. */
+enum { NRS_SURFACE_GRADIENT = 1, NRS_SURFACE_VELOCITY = 2, NRS_SURFACE_WALLS = 4 };
+enum { NRS_MESH_VERTICES = 1, NRS_MESH_TRIANGLES = 2, NRS_MESH_GRADIENT = 4, NRS_MESH_VELOCITY = 8 };
+int nrs_surface_extract(nrs_ctx *ctx, const nrs_lattice *lattice, double iso, uint32_t flags, uint64_t *vertices, uint64_t *triangles);
+int nrs_surface_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_bytes, uint64_t *out_bytes);
+int nrs_surface_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes);
+int nrs_surface_release(nrs_ctx *ctx);
+
 /* Akinci boundary volumes on the device (no context needed): vbi[i] = 1 / sum_k W_poly6(|x_i - x_k|, h) over the boundary
  * particles k within h of i, i included — what the reference takes from its un-vendored submodule
  * (sample_spheres::boundary_forces::getVbi, main.cpp:546; own implementation, parity unpinned).  bi4: nb xyzw particles of

@@ -32,6 +32,9 @@ STAT_DFSPH_DENSITY_AVG, STAT_DFSPH_DIVERGENCE_AVG, STAT_DFSPH_DIVERGENCE_ITERATI
 STAT_SLAB_PARTITION = 11   # kind of the last slab_pack: 0 compacting, 1 in place, 2 in place from the force kernel's classification
 # NRS_FIELD_*: the outputs of the field sampler, and the modifier that adds the wall term to the density
 FIELD_DENSITY, FIELD_GRADIENT, FIELD_VELOCITY, FIELD_COUNT, FIELD_WALLS = 1, 2, 4, 8, 16
+# NRS_SURFACE_*: the flags of a surface extract (per-vertex attributes, the wall term in the density); NRS_MESH_*: one of its results
+SURFACE_GRADIENT, SURFACE_VELOCITY, SURFACE_WALLS = 1, 2, 4
+MESH_VERTICES, MESH_TRIANGLES, MESH_GRADIENT, MESH_VELOCITY = 1, 2, 4, 8
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
@@ -68,6 +71,7 @@ EXPORTS = [
     "nrs_set_boundary_bodies", "nrs_set_body_velocity", "nrs_set_body_pose", "nrs_get_body_pose",
     "nrs_sample_points", "nrs_sample_lattice", "nrs_sample_result", "nrs_sample_device_ptr", "nrs_sample_release",
     "nrs_sample_builds",
+    "nrs_surface_extract", "nrs_surface_result", "nrs_surface_device_ptr", "nrs_surface_release",
 ]
 
 
@@ -161,6 +165,10 @@ def load_library(path=None):
     lib.nrs_sample_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
     lib.nrs_sample_release.argtypes = [vp]
     lib.nrs_sample_builds.argtypes = [vp, C.POINTER(u64)]
+    lib.nrs_surface_extract.argtypes = [vp, C.POINTER(NrsLattice), C.c_double, C.c_uint32, C.POINTER(u64), C.POINTER(u64)]
+    lib.nrs_surface_result.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(u64)]
+    lib.nrs_surface_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
+    lib.nrs_surface_release.argtypes = [vp]
     _lib = lib
     return lib
 
@@ -460,13 +468,18 @@ class Solver:
         pts = np.ascontiguousarray(points4, dtype=self.real).reshape(-1, 4)
         self._chk(self.lib.nrs_sample_points(self.h, _ptr(pts) if len(pts) else None, pts.shape[0], int(fields)))
 
-    def sample_lattice(self, origin, spacing, dims, fields):
-        """evaluate `fields` on the dims[0] x dims[1] x dims[2] nodes origin + idx * spacing (nrs_sample_lattice); spacing: a number
-        or one per axis"""
+    @staticmethod
+    def _lattice(origin, spacing, dims):
         L = NrsLattice()
         sp = np.broadcast_to(np.asarray(spacing, np.float64), (3,))
         for a in range(3):
             L.origin[a], L.spacing[a], L.dims[a] = float(origin[a]), float(sp[a]), int(dims[a])
+        return L
+
+    def sample_lattice(self, origin, spacing, dims, fields):
+        """evaluate `fields` on the dims[0] x dims[1] x dims[2] nodes origin + idx * spacing (nrs_sample_lattice); spacing: a number
+        or one per axis"""
+        L = self._lattice(origin, spacing, dims)
         self._chk(self.lib.nrs_sample_lattice(self.h, C.byref(L), int(fields)))
 
     def sample_result(self, field):
@@ -492,6 +505,33 @@ class Solver:
 
     def sample_release(self):
         self._chk(self.lib.nrs_sample_release(self.h))
+
+    # ---- surface extraction ---------------------------------------------------------------------------
+    def surface_extract(self, origin, spacing, dims, iso, flags=0):
+        """the iso-surface rho = iso on the lattice as a triangle mesh on the device (nrs_surface_extract): samples the lattice
+        (sample_result(FIELD_DENSITY) afterwards is the lattice the mesh was cut from), meshes it, waits for the totals; -> (V, T)"""
+        L = self._lattice(origin, spacing, dims)
+        v, t = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.nrs_surface_extract(self.h, C.byref(L), float(iso), int(flags), C.byref(v), C.byref(t)))
+        return int(v.value), int(t.value)
+
+    def surface_result(self, which):
+        """one result of the last extract on the host: (V, 4) SReal vertices (x, y, z, t) / gradient / velocity, (T, 3) uint32 triangles"""
+        nbytes = C.c_uint64(0)
+        self._chk(self.lib.nrs_surface_result(self.h, int(which), None, 0, C.byref(nbytes)))
+        dt = np.uint32 if which == MESH_TRIANGLES else self.real
+        a = np.empty(nbytes.value // np.dtype(dt).itemsize, dtype=dt)
+        if nbytes.value:
+            self._chk(self.lib.nrs_surface_result(self.h, int(which), _ptr(a), nbytes.value, None))
+        return a.reshape(-1, 3) if which == MESH_TRIANGLES else a.reshape(-1, 4)
+
+    def surface_device_ptr(self, which):
+        p, b = C.c_void_p(), C.c_uint64()
+        self._chk(self.lib.nrs_surface_device_ptr(self.h, int(which), C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def surface_release(self):
+        self._chk(self.lib.nrs_surface_release(self.h))
 
     @property
     def n_owned(self):

@@ -450,6 +450,27 @@ int nrs_sample_builds(nrs_ctx *ctx, uint64_t *builds)
     *builds = ctx->impl->sample_builds();
     return NRS_OK;
 }
+int nrs_surface_extract(nrs_ctx *ctx, const nrs_lattice *lattice, double iso, uint32_t flags, uint64_t *vertices, uint64_t *triangles)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->surface_extract(lattice, iso, flags, vertices, triangles);
+}
+int nrs_surface_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_bytes, uint64_t *out_bytes)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->surface_result(which, dst, dst_bytes, out_bytes);
+}
+int nrs_surface_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes)
+{
+    CTX_GUARD(ctx);
+    if (!dptr || !bytes) return fail(NRS_E_INVALID, "NULL argument");
+    return ctx->impl->surface_device_ptr(which, dptr, bytes);
+}
+int nrs_surface_release(nrs_ctx *ctx)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->surface_release();
+}
 uint64_t nrs_slab_message_bytes(uint64_t capacity, int precision) { return 16 + capacity * 2 * (precision == 64 ? 32 : 16); }
 
 int nrs_max_density(nrs_ctx *ctx, double *out)

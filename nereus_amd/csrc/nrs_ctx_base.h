@@ -140,6 +140,11 @@ struct CtxBase {
     virtual int sample_device_ptr(uint32_t field, void **dptr, uint64_t *bytes) = 0;
     virtual int sample_release() = 0;
     virtual uint64_t sample_builds() = 0;
+    // surface extraction (nrs_kernels_surface.h; the host decisions: nrs_host_surface.h)
+    virtual int surface_extract(const nrs_lattice *lattice, double iso, uint32_t flags, uint64_t *vertices, uint64_t *triangles) = 0;
+    virtual int surface_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) = 0;
+    virtual int surface_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) = 0;
+    virtual int surface_release() = 0;
     hipStream_t stream = nullptr;
     bool ownStream = false;
     int device = 0;

@@ -18,7 +18,7 @@
 // which of each is current, prepared or a pack target, the sort's workspace, the buffers of the coherent re-sort, its mover-count
 // word and statistics.  The context reads views of it (sort.hash(), sort.index(), sort.prepared(), the tile counts the fused and the
 // slab kernels write) and calls its operations (sort_keys, scan_movers, split, scan_holes, the pack targets).  The field sampler's
-// buffers: sm (FieldSampler, nrs_field_sampler.h).
+// buffers: sm (FieldSampler, nrs_field_sampler.h); the surface mesh's: sf (SurfaceMesher, nrs_surface_mesher.h).
 // Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure functions it calls:
 // the stage timer (nrs_host_profile.h), the snapshot ring (nrs_host_snapshot.h), the solver settings and their validation
 // (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
@@ -52,6 +52,7 @@
 #include "nrs_kernels_bodies.h"
 #include "nrs_slab_exchange.h"
 #include "nrs_field_sampler.h"
+#include "nrs_surface_mesher.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
 
@@ -1626,6 +1627,67 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         HIPCHK(hipStreamSynchronize(stream)); // a queued gather may still read the buffers
         sm.release();
+        return NRS_OK;
+    }
+
+    // ---- surface extraction (include/nereus_hip.h; DESIGN.md "Surface extraction") ---------------------------------------------------------
+    // A sample call on the lattice path above (sm's result arrays, refusals and cache rule), then the mesher (sf, nrs_surface_mesher.h) on
+    // sm's result pointers.  The mesh buffers are sf's: no sample call touches them.  Nothing a step owns is written.
+    SurfaceMesher sf;
+    int surface_extract(const nrs_lattice *lattice, double iso, uint32_t flags, uint64_t *vertices, uint64_t *triangles) override
+    {
+        NRSCHK(surface_check_call(iso, flags));
+        const uint32_t fields = surface_sample_fields(flags);
+        NRSCHK(sample_begin(fields));
+        uint64_t m = 0;
+        NRSCHK(surface_check_lattice(lattice, &m));
+        SampleLattice L;
+        SurfaceInput in;
+        for (int a = 0; a < 3; ++a) {
+            in.L.origin[a] = L.origin[a] = lattice->origin[a];
+            in.L.spacing[a] = L.spacing[a] = lattice->spacing[a];
+            in.L.dims[a] = L.dims[a] = lattice->dims[a];
+        }
+        sm.last = SampleLast();
+        NRSCHK(sample_run(nullptr, L, m, fields));
+        sm.last = SampleLast{true, fields, m};
+        in.nodes = m;
+        in.iso = iso;
+        in.precision = (int)(8 * sizeof(R));
+        in.dens = sm.result(NRS_FIELD_DENSITY);
+        in.grad = (flags & NRS_SURFACE_GRADIENT) ? sm.result(NRS_FIELD_GRADIENT) : nullptr;
+        in.vel = (flags & NRS_SURFACE_VELOCITY) ? sm.result(NRS_FIELD_VELOCITY) : nullptr;
+        sf.last = SurfaceLast();
+        uint64_t V = 0, T = 0;
+        NRSCHK(sf.extract(in, stream, &V, &T));
+        sf.last = SurfaceLast{true, flags, V, T};
+        if (vertices) *vertices = V;
+        if (triangles) *triangles = T;
+        return NRS_OK;
+    }
+    int surface_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override
+    {
+        NRSCHK(surface_route_result(sf.last, which, (int)(8 * sizeof(R)), bytes));
+        *dptr = *bytes ? sf.result(which) : nullptr;
+        return NRS_OK;
+    }
+    int surface_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override
+    {
+        void *p = nullptr;
+        uint64_t sz = 0;
+        NRSCHK(surface_device_ptr(which, &p, &sz));
+        if (outBytes) *outBytes = sz;
+        if (!dst) return NRS_OK;
+        if (dstBytes < sz) return fail(NRS_E_INVALID, "destination too small");
+        if (!sz) return NRS_OK;
+        HIPCHK(hipMemcpyAsync(dst, p, sz, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return NRS_OK;
+    }
+    int surface_release() override
+    {
+        HIPCHK(hipStreamSynchronize(stream)); // a queued emit may still write the buffers
+        sf.release();
         return NRS_OK;
     }
 };

@@ -297,6 +297,60 @@ const std::vector<SUint> &SPH::getSampledCount()
     return m_sampledCount;
 }
 
+// ---- surface extraction -----------------------------------------------------------------------------------------------------------
+void SPH::extractSurface(const double origin[3], const double spacing[3], const SUint dims[3], double iso, SUint flags)
+{
+    ensureContext();
+    pushHostToDevice();
+    nrs_lattice L;
+    std::memset(&L, 0, sizeof(L));
+    for (int a = 0; a < 3; ++a) { L.origin[a] = origin[a]; L.spacing[a] = spacing[a]; L.dims[a] = dims[a]; }
+    uint64_t V = 0, T = 0;
+    if (nrs_surface_extract(m_ctx, &L, iso, flags, &V, &T) != NRS_OK) fatal("nrs_surface_extract");
+    m_surfaceV = (SUint)V;
+    m_surfaceT = (SUint)T;
+}
+template <typename T> static void fetchMesh(nrs_ctx *ctx, SUint which, std::vector<T> &v, bool &ok)
+{
+    uint64_t bytes = 0;
+    ok = nrs_surface_result(ctx, which, nullptr, 0, &bytes) == NRS_OK;
+    if (!ok) return;
+    v.resize((size_t)(bytes / sizeof(T)));
+    if (bytes) ok = nrs_surface_result(ctx, which, v.data(), bytes, nullptr) == NRS_OK;
+}
+const std::vector<SVec4> &SPH::getSurfaceVertices()
+{
+    bool ok = false;
+    ensureContext();
+    fetchMesh(m_ctx, NRS_MESH_VERTICES, m_surfaceVertices, ok);
+    if (!ok) fatal("nrs_surface_result");
+    return m_surfaceVertices;
+}
+const std::vector<SUint> &SPH::getSurfaceTriangles()
+{
+    bool ok = false;
+    ensureContext();
+    fetchMesh(m_ctx, NRS_MESH_TRIANGLES, m_surfaceTriangles, ok);
+    if (!ok) fatal("nrs_surface_result");
+    return m_surfaceTriangles;
+}
+const std::vector<SVec4> &SPH::getSurfaceGradient()
+{
+    bool ok = false;
+    ensureContext();
+    fetchMesh(m_ctx, NRS_MESH_GRADIENT, m_surfaceGradient, ok);
+    if (!ok) fatal("nrs_surface_result");
+    return m_surfaceGradient;
+}
+const std::vector<SVec4> &SPH::getSurfaceVelocity()
+{
+    bool ok = false;
+    ensureContext();
+    fetchMesh(m_ctx, NRS_MESH_VELOCITY, m_surfaceVelocity, ok);
+    if (!ok) fatal("nrs_surface_result");
+    return m_surfaceVelocity;
+}
+
 nrs_ctx *SPH::deviceContext()
 {
     ensureContext();

@@ -107,6 +107,18 @@ public:
     const std::vector<SVec4> &getSampledGradient();
     const std::vector<SVec4> &getSampledVelocity();
     const std::vector<SUint> &getSampledCount();
+    // Surface extraction (nrs_surface_*, DESIGN.md "Surface extraction"): the iso-surface density = iso of the current state as an
+    // indexed triangle mesh, by marching tetrahedra on the lattice, on the device.  It IS sampleLattice (density, plus what the
+    // NRS_SURFACE_* flags ask for) followed by the mesher, so getSampledDensity() afterwards is the lattice the mesh was cut from.  Waits
+    // for the device once (the totals size the outputs).  The getters return one result of the LAST extract in a host array the solver
+    // owns: vertices (x, y, z, t), three vertex numbers per triangle, and the per-vertex gradient / velocity if asked for.
+    void extractSurface(const double origin[3], const double spacing[3], const SUint dims[3], double iso, SUint flags);
+    SUint getSurfaceNumVertices() const { return m_surfaceV; }
+    SUint getSurfaceNumTriangles() const { return m_surfaceT; }
+    const std::vector<SVec4> &getSurfaceVertices();
+    const std::vector<SUint> &getSurfaceTriangles();
+    const std::vector<SVec4> &getSurfaceGradient();
+    const std::vector<SVec4> &getSurfaceVelocity();
     void reserveParticles(SUint capacity);        // grow host+device storage up front
     void setEagerSync(bool on) { m_eagerSync = on; } // true: D2H at the end of every update() like the reference
     const SphSimParams &getParams() const { return m_params; }
@@ -173,6 +185,9 @@ protected:
     std::vector<SReal> m_sampledDensity; // host copies of the last sample call's results, fetched by the getters
     std::vector<SVec4> m_sampledGradient, m_sampledVelocity;
     std::vector<SUint> m_sampledCount;
+    std::vector<SVec4> m_surfaceVertices, m_surfaceGradient, m_surfaceVelocity; // ... and of the last surface extract
+    std::vector<SUint> m_surfaceTriangles;
+    SUint m_surfaceV = 0, m_surfaceT = 0;
 };
 
 NEREUS_NAMESPACE_END

@@ -22,6 +22,10 @@
 //                                                               as run, then the density (fluid only) on the dx x dy x dz nodes
 //                                                               origin + idx * spacing (SPH::sampleLattice / getSampledDensity)
 //                                                               out.lat: u32 dx, dy, dz, u32 precision (32 | 64), SReal[dx * dy * dz]
+//   headless surface <solver> <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <iso> <out.obj>
+//                                                               as run, then the surface density = iso on that lattice
+//                                                               (SPH::extractSurface) as a Wavefront OBJ: "v x y z" lines, then
+//                                                               "f a b c" lines with 1-based vertex numbers, wound outwards
 // in.bin : u32 n, u32 nb, then pos4[n], vel4[n], bi4[nb], vbi[nb] (SReal)
 // out.bin: u32 n, u32 nb, u32 iters, u32 sizeof(params), params, pos4[n], vel4[n], pressure[n], bi4[nb], vbi[nb]
 #include <cstdio>
@@ -102,9 +106,10 @@ int main(int argc, char **argv)
     unsigned iters = 0;
     if (mode == "params") {
         dump(argv[3], sim, 0, bi, vbi);
-    } else if (mode == "run" || mode == "frames" || mode == "lattice") {
+    } else if (mode == "run" || mode == "frames" || mode == "lattice" || mode == "surface") {
         if (argc < 6) die("run needs <in.bin> <steps> <out.bin>");
         if (mode == "lattice" && argc < 13) die("lattice needs <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <out.lat>");
+        if (mode == "surface" && argc < 14) die("surface needs <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <iso> <out.obj>");
         FILE *f = std::fopen(argv[3], "rb");
         if (!f) die("cannot open input");
         unsigned n = 0, nb = 0;
@@ -153,6 +158,21 @@ int main(int argc, char **argv)
             const unsigned head[4] = {dims[0], dims[1], dims[2], (unsigned)(8 * sizeof(SReal))};
             std::fwrite(head, 4, 4, o);
             std::fwrite(rho.data(), sizeof(SReal), rho.size(), o);
+            std::fclose(o);
+        } else if (mode == "surface") {
+            const double h = std::strtod(argv[8], nullptr);
+            const double origin[3] = {std::strtod(argv[5], nullptr), std::strtod(argv[6], nullptr), std::strtod(argv[7], nullptr)}, spacing[3] = {h, h, h};
+            const SUint dims[3] = {(SUint)std::strtoul(argv[9], nullptr, 10), (SUint)std::strtoul(argv[10], nullptr, 10), (SUint)std::strtoul(argv[11], nullptr, 10)};
+            sim->extractSurface(origin, spacing, dims, std::strtod(argv[12], nullptr), 0);
+            const std::vector<SVec4> &v = sim->getSurfaceVertices();
+            const std::vector<SUint> &t = sim->getSurfaceTriangles();
+            if (v.size() != sim->getSurfaceNumVertices() || t.size() != 3 * (size_t)sim->getSurfaceNumTriangles()) die("extractSurface: wrong sizes");
+            FILE *o = std::fopen(argv[13], "w");
+            if (!o) die("cannot open output");
+            std::fprintf(o, "# density = %s, %zu vertices, %zu triangles\n", argv[12], v.size(), t.size() / 3);
+            const int digits = sizeof(SReal) == 8 ? 17 : 9; // enough to read every coordinate back bit for bit
+            for (size_t i = 0; i < v.size(); ++i) std::fprintf(o, "v %.*g %.*g %.*g\n", digits, (double)v[i].x, digits, (double)v[i].y, digits, (double)v[i].z);
+            for (size_t i = 0; i + 2 < t.size(); i += 3) std::fprintf(o, "f %u %u %u\n", t[i] + 1, t[i + 1] + 1, t[i + 2] + 1);
             std::fclose(o);
         } else {
             dump(argv[5], sim, iters, bi, vbi);
