@@ -527,6 +527,71 @@ int nrs_surface_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_byt
 int nrs_surface_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes);
 int nrs_surface_release(nrs_ctx *ctx);
 
+/* ---- diffuse particles (DESIGN.md "Diffuse particles"; came after nrs_version() 0.3 without a version change) --------------------------
+ * Spray, foam and air bubbles after Ihmsen, Akinci, Akinci, Teschner (2012), "Unified spray, foam and air bubbles for particle-based
+ * fluids": a set of secondary particles that the context owns and nrs_diffuse_step advances, all on the device.  It never runs inside
+ * nrs_step.  It READS the current fluid state (what nrs_download would return now) through the field sampler's particle grid (the
+ * sampler's cache rule applies and nrs_sample_builds counts a rebuild; the sampler's result arrays are not touched) and writes only its
+ * own buffers: a context that uses it steps bit-identically to one that never did.  Every output is bit-reproducible: offsets come from
+ * scans, nothing depends on a launch geometry or on the order of atomics.  DESIGN.md states every formula and the order of every sum.
+ *
+ * One nrs_diffuse_step(ctx, dt) (dt == 0: the context's timestep), per fluid particle i in the sampler's SORTED order (cell hash
+ * ascending, ties by array index), every sum over the fluid neighbours j != i with length(x_i - x_j) < h, W_lin = 1 - |x_ij| / h:
+ *   normals     g_i = sum_j m grad W(x_i - x_j): the sampler's gradient at the particle (NRS_DIFFUSE_NORMALS holds g_i, the density
+ *               gradient, w = 0).  The unit normal the potentials use points OUT of the fluid: n_i = -g_i / |g_i|.
+ *   trapped air sum |v_ij| (1 - vhat_ij . xhat_ij) W_lin
+ *   wave crest  sum (1 - n_i . n_j) W_lin over the j with xhat_ji . n_i < 0, the whole sum gated by vhat_i . n_i >= 0.6
+ *   energy      1/2 m |v_i|^2
+ *   A zero-length vector has no direction: that term, or that gate, is 0.  Each potential x is clamped to
+ *   I = (min(x, tau_max) - min(x, tau_min)) / (tau_max - tau_min); rate = I_k (k_ta I_ta + k_wc I_wc) particles per second;
+ *   births_i = min(floor(rate dt + u), max_per_particle), u the particle's first uniform draw.
+ * Then the living diffuse particles are advected: the sampler's Shepard velocity vt and neighbour count n at the particle decide —
+ * n < spray_below: spray, ballistic under gravity; n > bubble_above: bubble, v += dt (-k_buoyancy g) + k_drag (vt - v); else foam,
+ * carried with vt and losing dt of its lifetime.  A particle dies when its lifetime is <= 0 or a coordinate is not finite or leaves
+ * the grid box [worldOrigin, worldOrigin + gridSize * cellSize).  Survivors are compacted in their order (oldest first); the births
+ * follow, ordered by fluid slot, then birth number, each on a random point of the cylinder of radius particleRadius and height
+ * dt |v_i| along v_i, with velocity v_i + the radial offset (NOT divided by dt) and a lifetime uniform in lifetime[].  Births that do
+ * not fit the capacity are the LAST in that order; they are counted in `dropped`.  New particles are not advected in their birth step;
+ * their kind is that of their parent's neighbour count (the parent included).  Uniforms: a counter-based integer hash of (seed,
+ * diffuse steps since configure, fluid slot, draw number), top 24 bits times 2^-24.  There are no collisions with boundary particles.
+ *
+ * nrs_diffuse_configure checks and stores the configuration and allocates nothing; it restarts the step counter and `dropped`, and
+ * keeps the living particles when the capacity is unchanged (drops them otherwise).  nrs_diffuse_step enqueues on the context's stream
+ * and does not wait; buffers are allocated by the first step or upload.  nrs_diffuse_count WAITS and gives the living count, the count
+ * per kind (0 spray, 1 foam, 2 bubble) and the births refused for capacity since configure (any pointer may be NULL).
+ * nrs_diffuse_result copies ONE result to the host and waits (dst NULL: only the size); nrs_diffuse_device_ptr gives its device address
+ * (NULL for zero bytes); both wait for the living count.  D: living diffuse particles; N: fluid particles of the last diffuse step:
+ *   NRS_DIFFUSE_POS        SVec4[D], w = remaining lifetime         NRS_DIFFUSE_POTENTIALS  SVec4[N] (I_ta, I_wc, I_k, births per second)
+ *   NRS_DIFFUSE_VEL        SVec4[D], w = 0                          NRS_DIFFUSE_BIRTHS      uint32_t[N]
+ *   NRS_DIFFUSE_KIND       uint32_t[D], as found by the last step   NRS_DIFFUSE_NORMALS     SVec4[N]
+ * (the three per-fluid arrays are in the sampler's sorted order; they are kept for tests and tuning).  nrs_diffuse_upload replaces the
+ * living set with n <= capacity particles (pos4.w = lifetime; listed as spray until a step classifies them) and waits.
+ * nrs_diffuse_release frees the buffers and empties the set; the configuration stays.
+ *
+ * NRS_E_INVALID: a NULL or wrongly sized config, capacity 0 or above 2^30, a tau range that is not finite with min < max, negative or
+ * non-finite k_ta / k_wc, lifetime not 0 <= min <= max, k_drag outside [0, 1], max_per_particle outside [1, 1024], reserved != 0; a
+ * NaN or negative dt; N * max_per_particle above 2^31; an upload above the capacity; a slab context and the sampler's grid conditions;
+ * an unknown result id.  NRS_E_STATE: anything before nrs_diffuse_configure; a per-fluid result before the first step; mid-update
+ * after nrs_step_partial; a host-driven IISPH step in progress.  What is wrong with an argument is named before the state. */
+typedef struct nrs_diffuse_config {
+    uint32_t struct_size, capacity;          /* max diffuse particles; 0 is invalid */
+    uint64_t seed;
+    double tau_ta[2], tau_wc[2], tau_k[2];   /* clamp ranges of the three potentials, min < max */
+    double k_ta, k_wc;                       /* particles per second at potential 1 */
+    double lifetime[2];                      /* foam lifetime drawn uniformly in [min, max] seconds */
+    double k_buoyancy, k_drag;               /* bubbles; k_drag in [0, 1] */
+    uint32_t spray_below, bubble_above;      /* kinds by fluid-neighbour count n: n < spray_below spray, n > bubble_above bubble, else foam */
+    uint32_t max_per_particle, reserved;     /* cap on births per fluid particle per step, >= 1 */
+} nrs_diffuse_config;
+enum { NRS_DIFFUSE_POS = 0, NRS_DIFFUSE_VEL = 1, NRS_DIFFUSE_KIND = 2, NRS_DIFFUSE_POTENTIALS = 3, NRS_DIFFUSE_BIRTHS = 4, NRS_DIFFUSE_NORMALS = 5 };
+int nrs_diffuse_configure(nrs_ctx *ctx, const nrs_diffuse_config *cfg);
+int nrs_diffuse_step(nrs_ctx *ctx, double dt);
+int nrs_diffuse_count(nrs_ctx *ctx, uint64_t *alive, uint64_t by_kind[3], uint64_t *dropped);
+int nrs_diffuse_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_bytes, uint64_t *out_bytes);
+int nrs_diffuse_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes);
+int nrs_diffuse_upload(nrs_ctx *ctx, const void *pos4, const void *vel4, uint64_t n);
+int nrs_diffuse_release(nrs_ctx *ctx);
+
 /* Akinci boundary volumes on the device (no context needed): vbi[i] = 1 / sum_k W_poly6(|x_i - x_k|, h) over the boundary
  * particles k within h of i, i included — what the reference takes from its un-vendored submodule
  * (sample_spheres::boundary_forces::getVbi, main.cpp:546; own implementation, parity unpinned).  bi4: nb xyzw particles of

@@ -35,6 +35,9 @@ FIELD_DENSITY, FIELD_GRADIENT, FIELD_VELOCITY, FIELD_COUNT, FIELD_WALLS = 1, 2, 
 # NRS_SURFACE_*: the flags of a surface extract (per-vertex attributes, the wall term in the density); NRS_MESH_*: one of its results
 SURFACE_GRADIENT, SURFACE_VELOCITY, SURFACE_WALLS = 1, 2, 4
 MESH_VERTICES, MESH_TRIANGLES, MESH_GRADIENT, MESH_VELOCITY = 1, 2, 4, 8
+# NRS_DIFFUSE_*: one result of the diffuse particles; the kinds of NRS_DIFFUSE_KIND
+DIFFUSE_POS, DIFFUSE_VEL, DIFFUSE_KIND, DIFFUSE_POTENTIALS, DIFFUSE_BIRTHS, DIFFUSE_NORMALS = 0, 1, 2, 3, 4, 5
+DIFFUSE_SPRAY, DIFFUSE_FOAM, DIFFUSE_BUBBLE = 0, 1, 2
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
@@ -72,7 +75,19 @@ EXPORTS = [
     "nrs_sample_points", "nrs_sample_lattice", "nrs_sample_result", "nrs_sample_device_ptr", "nrs_sample_release",
     "nrs_sample_builds",
     "nrs_surface_extract", "nrs_surface_result", "nrs_surface_device_ptr", "nrs_surface_release",
+    "nrs_diffuse_configure", "nrs_diffuse_step", "nrs_diffuse_count", "nrs_diffuse_result", "nrs_diffuse_device_ptr",
+    "nrs_diffuse_upload", "nrs_diffuse_release",
 ]
+
+
+class NrsDiffuseConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("capacity", C.c_uint32), ("seed", C.c_uint64),
+        ("tau_ta", C.c_double * 2), ("tau_wc", C.c_double * 2), ("tau_k", C.c_double * 2),
+        ("k_ta", C.c_double), ("k_wc", C.c_double), ("lifetime", C.c_double * 2),
+        ("k_buoyancy", C.c_double), ("k_drag", C.c_double),
+        ("spray_below", C.c_uint32), ("bubble_above", C.c_uint32), ("max_per_particle", C.c_uint32), ("reserved", C.c_uint32),
+    ]
 
 
 class NrsConfig(C.Structure):
@@ -169,6 +184,13 @@ def load_library(path=None):
     lib.nrs_surface_result.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(u64)]
     lib.nrs_surface_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
     lib.nrs_surface_release.argtypes = [vp]
+    lib.nrs_diffuse_configure.argtypes = [vp, C.POINTER(NrsDiffuseConfig)]
+    lib.nrs_diffuse_step.argtypes = [vp, C.c_double]
+    lib.nrs_diffuse_count.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    lib.nrs_diffuse_result.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(u64)]
+    lib.nrs_diffuse_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
+    lib.nrs_diffuse_upload.argtypes = [vp, vp, vp, u64]
+    lib.nrs_diffuse_release.argtypes = [vp]
     _lib = lib
     return lib
 
@@ -532,6 +554,60 @@ class Solver:
 
     def surface_release(self):
         self._chk(self.lib.nrs_surface_release(self.h))
+
+    # ---- diffuse particles ----------------------------------------------------------------------------
+    def diffuse_configure(self, capacity, seed=0, tau_ta=(5.0, 20.0), tau_wc=(2.0, 8.0), tau_k=(5.0, 50.0), k_ta=4000.0, k_wc=50000.0,
+                          lifetime=(2.0, 5.0), k_buoyancy=2.0, k_drag=0.8, spray_below=6, bubble_above=20, max_per_particle=8,
+                          struct_size=None, reserved=0):
+        """configure the context's diffuse particles (nrs_diffuse_configure): spray, foam and bubbles after Ihmsen et al. 2012; allocates
+        nothing, restarts the step counter and `dropped`, keeps the living set when the capacity is unchanged"""
+        c = NrsDiffuseConfig()
+        c.struct_size = C.sizeof(NrsDiffuseConfig) if struct_size is None else int(struct_size)
+        c.capacity, c.seed = int(capacity), int(seed)
+        c.tau_ta[:], c.tau_wc[:], c.tau_k[:] = [float(x) for x in tau_ta], [float(x) for x in tau_wc], [float(x) for x in tau_k]
+        c.k_ta, c.k_wc = float(k_ta), float(k_wc)
+        c.lifetime[:] = [float(x) for x in lifetime]
+        c.k_buoyancy, c.k_drag = float(k_buoyancy), float(k_drag)
+        c.spray_below, c.bubble_above, c.max_per_particle, c.reserved = int(spray_below), int(bubble_above), int(max_per_particle), int(reserved)
+        self._chk(self.lib.nrs_diffuse_configure(self.h, C.byref(c)))
+
+    def diffuse_step(self, dt=0.0):
+        """one step of the diffuse particles on the current fluid state (nrs_diffuse_step; dt 0: the context's timestep); enqueues"""
+        self._chk(self.lib.nrs_diffuse_step(self.h, float(dt)))
+
+    def diffuse_count(self):
+        """(alive, [spray, foam, bubble], dropped) of the diffuse set (nrs_diffuse_count; waits)"""
+        a, d = C.c_uint64(0), C.c_uint64(0)
+        k = (C.c_uint64 * 3)()
+        self._chk(self.lib.nrs_diffuse_count(self.h, C.byref(a), k, C.byref(d)))
+        return int(a.value), [int(x) for x in k], int(d.value)
+
+    def diffuse_result(self, which):
+        """one result on the host: (D, 4) SReal DIFFUSE_POS (w = lifetime) / DIFFUSE_VEL, (D,) uint32 DIFFUSE_KIND; per sorted fluid
+        particle of the last step (N, 4) DIFFUSE_POTENTIALS / DIFFUSE_NORMALS, (N,) uint32 DIFFUSE_BIRTHS"""
+        nbytes = C.c_uint64(0)
+        self._chk(self.lib.nrs_diffuse_result(self.h, int(which), None, 0, C.byref(nbytes)))
+        ints = which in (DIFFUSE_KIND, DIFFUSE_BIRTHS)
+        dt = np.uint32 if ints else self.real
+        a = np.empty(nbytes.value // np.dtype(dt).itemsize, dtype=dt)
+        if nbytes.value:
+            self._chk(self.lib.nrs_diffuse_result(self.h, int(which), _ptr(a), nbytes.value, None))
+        return a if ints else a.reshape(-1, 4)
+
+    def diffuse_device_ptr(self, which):
+        p, b = C.c_void_p(), C.c_uint64()
+        self._chk(self.lib.nrs_diffuse_device_ptr(self.h, int(which), C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def diffuse_upload(self, pos4, vel4):
+        """replace the living diffuse set (nrs_diffuse_upload): (n, 4) positions with the lifetime in w, (n, 4) velocities"""
+        pos4 = np.ascontiguousarray(pos4, dtype=self.real).reshape(-1, 4)
+        vel4 = np.ascontiguousarray(vel4, dtype=self.real).reshape(-1, 4)
+        assert len(pos4) == len(vel4)
+        self._chk(self.lib.nrs_diffuse_upload(self.h, _ptr(pos4), _ptr(vel4), len(pos4)))
+
+    def diffuse_release(self):
+        self._chk(self.lib.nrs_diffuse_release(self.h))
 
     @property
     def n_owned(self):

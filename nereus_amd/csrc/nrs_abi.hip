@@ -471,6 +471,42 @@ int nrs_surface_release(nrs_ctx *ctx)
     CTX_GUARD(ctx);
     return ctx->impl->surface_release();
 }
+int nrs_diffuse_configure(nrs_ctx *ctx, const nrs_diffuse_config *cfg)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->diffuse_configure(cfg);
+}
+int nrs_diffuse_step(nrs_ctx *ctx, double dt)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->diffuse_step(dt);
+}
+int nrs_diffuse_count(nrs_ctx *ctx, uint64_t *alive, uint64_t by_kind[3], uint64_t *dropped)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->diffuse_count(alive, by_kind, dropped);
+}
+int nrs_diffuse_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_bytes, uint64_t *out_bytes)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->diffuse_result(which, dst, dst_bytes, out_bytes);
+}
+int nrs_diffuse_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes)
+{
+    CTX_GUARD(ctx);
+    if (!dptr || !bytes) return fail(NRS_E_INVALID, "NULL argument");
+    return ctx->impl->diffuse_device_ptr(which, dptr, bytes);
+}
+int nrs_diffuse_upload(nrs_ctx *ctx, const void *pos4, const void *vel4, uint64_t n)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->diffuse_upload(pos4, vel4, n);
+}
+int nrs_diffuse_release(nrs_ctx *ctx)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->diffuse_release();
+}
 uint64_t nrs_slab_message_bytes(uint64_t capacity, int precision) { return 16 + capacity * 2 * (precision == 64 ? 32 : 16); }
 
 int nrs_max_density(nrs_ctx *ctx, double *out)

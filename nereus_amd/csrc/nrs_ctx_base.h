@@ -145,6 +145,14 @@ struct CtxBase {
     virtual int surface_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) = 0;
     virtual int surface_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) = 0;
     virtual int surface_release() = 0;
+    // diffuse particles (nrs_kernels_diffuse.h; the host decisions: nrs_host_diffuse.h)
+    virtual int diffuse_configure(const nrs_diffuse_config *cfg) = 0;
+    virtual int diffuse_step(double dt) = 0;
+    virtual int diffuse_count(uint64_t *alive, uint64_t *byKind, uint64_t *dropped) = 0;
+    virtual int diffuse_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) = 0;
+    virtual int diffuse_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) = 0;
+    virtual int diffuse_upload(const void *pos4, const void *vel4, uint64_t n) = 0;
+    virtual int diffuse_release() = 0;
     hipStream_t stream = nullptr;
     bool ownStream = false;
     int device = 0;

@@ -18,7 +18,8 @@
 // which of each is current, prepared or a pack target, the sort's workspace, the buffers of the coherent re-sort, its mover-count
 // word and statistics.  The context reads views of it (sort.hash(), sort.index(), sort.prepared(), the tile counts the fused and the
 // slab kernels write) and calls its operations (sort_keys, scan_movers, split, scan_holes, the pack targets).  The field sampler's
-// buffers: sm (FieldSampler, nrs_field_sampler.h); the surface mesh's: sf (SurfaceMesher, nrs_surface_mesher.h).
+// buffers: sm (FieldSampler, nrs_field_sampler.h); the surface mesh's: sf (SurfaceMesher, nrs_surface_mesher.h); the diffuse
+// particles': df (DiffuseSystem, nrs_diffuse.h).
 // Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure functions it calls:
 // the stage timer (nrs_host_profile.h), the snapshot ring (nrs_host_snapshot.h), the solver settings and their validation
 // (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
@@ -53,6 +54,7 @@
 #include "nrs_slab_exchange.h"
 #include "nrs_field_sampler.h"
 #include "nrs_surface_mesher.h"
+#include "nrs_diffuse.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
 
@@ -1688,6 +1690,87 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         HIPCHK(hipStreamSynchronize(stream)); // a queued emit may still write the buffers
         sf.release();
+        return NRS_OK;
+    }
+
+    // ---- diffuse particles (include/nereus_hip.h; DESIGN.md "Diffuse particles") -----------------------------------------------------------
+    // The sampler's particle grid (sm's sorted fluid and cell table, its cache rule and build count — its result arrays and `last` are not
+    // touched), then the launches of df (nrs_diffuse.h) on its views.  The set's buffers are df's.  Nothing a step owns is written.
+    DiffuseSystem df;
+    int diffuse_configure(const nrs_diffuse_config *c) override
+    {
+        NRSCHK(validate("nrs_diffuse_configure"));
+        NRSCHK(diffuse_check_config(c));
+        if (exch.on()) return fail(NRS_E_INVALID, "diffuse particles on a slab context (its arrays hold halo copies)");
+        df.configure(*c);
+        return NRS_OK;
+    }
+    int diffuse_step(double dt) override
+    {
+        NRSCHK(validate("nrs_diffuse_step"));
+        NRSCHK(diffuse_check_dt(dt));
+        NRSCHK(diffuse_refusal(sample_facts(), df.last.configured));
+        NRSCHK(diffuse_check_births(n, df.cfg.max_per_particle));
+        const SampleKey key{stepsDone, particleGen, gridGen, boundaryGen};
+        if (sm.cache.needs_build(key)) {
+            NRSCHK(sm.template build_grid<R>(P, posA.as<T4>(), velA.as<T4>(), n, stream));
+            sm.cache.built(key);
+        }
+        GridView<R> G;
+        std::memset(&G, 0, sizeof(G));
+        G.cellStart = sm.cell_start(); G.cellEnd = sm.cell_end();
+        G.nSorted = sm.sorted_count();
+        G.err = sm.err_word();
+        G.actLo = INT_MIN; G.actHi = INT_MAX;
+        return df.template step<R, KSET>(P, G, sm.template sorted_pos<T4>(), sm.template sorted_vel<T4>(), sm.sorted_count(),
+                                         dt == 0.0 ? P.timestep : (R)dt, stream);
+    }
+    int diffuse_count(uint64_t *alive, uint64_t *byKind, uint64_t *dropped) override
+    {
+        NRSCHK(validate("nrs_diffuse_count"));
+        if (!df.last.configured) return fail(NRS_E_STATE, "diffuse particles before nrs_diffuse_configure");
+        return df.count(stream, alive, byKind, dropped);
+    }
+    int diffuse_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override
+    {
+        NRSCHK(diffuse_route_check(df.last, which));
+        uint64_t alive = 0;
+        if (!diffuse_per_fluid(which)) NRSCHK(df.alive_now(stream, &alive));
+        NRSCHK(diffuse_route_result(df.last, which, alive, (int)(8 * sizeof(R)), bytes));
+        *dptr = *bytes ? df.result(which) : nullptr;
+        return NRS_OK;
+    }
+    int diffuse_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override
+    {
+        void *p = nullptr;
+        uint64_t sz = 0;
+        NRSCHK(diffuse_device_ptr(which, &p, &sz));
+        if (outBytes) *outBytes = sz;
+        if (!dst) return NRS_OK;
+        if (dstBytes < sz) return fail(NRS_E_INVALID, "destination too small");
+        if (!sz) return NRS_OK;
+        uint32_t e = 0;
+        HIPCHK(hipMemcpyAsync(dst, p, sz, hipMemcpyDeviceToHost, stream));
+        if (sm.err_word()) HIPCHK(hipMemcpyAsync(&e, sm.err_word(), 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (!e) return NRS_OK;
+        HIPCHK(hipMemsetAsync(sm.err_word(), 0, 4, stream));
+        return fail(NRS_E_STATE, "diffuse particles: a cell range of the sampler's table lies outside its sorted particles; the walks skipped it, the results are invalid");
+    }
+    int diffuse_upload(const void *pos4, const void *vel4, uint64_t count) override
+    {
+        NRSCHK(validate("nrs_diffuse_upload"));
+        if (!df.last.configured) {
+            if (exch.on()) return fail(NRS_E_INVALID, "diffuse particles on a slab context (its arrays hold halo copies)");
+            return fail(NRS_E_STATE, "diffuse particles before nrs_diffuse_configure");
+        }
+        NRSCHK(diffuse_check_upload(pos4, vel4, count, df.cfg.capacity));
+        return df.template upload<R>(pos4, vel4, count, stream);
+    }
+    int diffuse_release() override
+    {
+        HIPCHK(hipStreamSynchronize(stream)); // a queued step may still use the buffers
+        df.release();
         return NRS_OK;
     }
 };

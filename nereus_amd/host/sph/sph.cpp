@@ -351,6 +351,43 @@ const std::vector<SVec4> &SPH::getSurfaceVelocity()
     return m_surfaceVelocity;
 }
 
+// ---- diffuse particles -----------------------------------------------------------------------------------------------------------------
+void SPH::configureDiffuse(const nrs_diffuse_config &cfg)
+{
+    ensureContext();
+    nrs_diffuse_config c = cfg;
+    c.struct_size = (uint32_t)sizeof(c);
+    c.reserved = 0;
+    if (nrs_diffuse_configure(m_ctx, &c) != NRS_OK) fatal("nrs_diffuse_configure");
+}
+void SPH::stepDiffuse(double dt)
+{
+    ensureContext();
+    pushHostToDevice();
+    if (nrs_diffuse_step(m_ctx, dt) != NRS_OK) fatal("nrs_diffuse_step");
+}
+template <typename T> static void fetchDiffuse(nrs_ctx *ctx, SUint which, std::vector<T> &v, bool &ok)
+{
+    uint64_t bytes = 0;
+    ok = nrs_diffuse_result(ctx, which, nullptr, 0, &bytes) == NRS_OK;
+    if (!ok) return;
+    v.resize((size_t)(bytes / sizeof(T)));
+    if (bytes) ok = nrs_diffuse_result(ctx, which, v.data(), bytes, nullptr) == NRS_OK;
+}
+SUint SPH::getDiffuse(const SVec4 **positions, const SVec4 **velocities, const SUint **kinds)
+{
+    bool ok = false;
+    ensureContext();
+    fetchDiffuse(m_ctx, NRS_DIFFUSE_POS, m_diffusePositions, ok);
+    if (ok) fetchDiffuse(m_ctx, NRS_DIFFUSE_VEL, m_diffuseVelocities, ok);
+    if (ok) fetchDiffuse(m_ctx, NRS_DIFFUSE_KIND, m_diffuseKinds, ok);
+    if (!ok || m_diffuseVelocities.size() != m_diffusePositions.size() || m_diffuseKinds.size() != m_diffusePositions.size()) fatal("nrs_diffuse_result");
+    if (positions) *positions = m_diffusePositions.data();
+    if (velocities) *velocities = m_diffuseVelocities.data();
+    if (kinds) *kinds = m_diffuseKinds.data();
+    return (SUint)m_diffusePositions.size();
+}
+
 nrs_ctx *SPH::deviceContext()
 {
     ensureContext();

@@ -28,6 +28,7 @@
 #define MAX_PARTICLE_NUMBER 150000
 
 struct nrs_ctx;
+struct nrs_diffuse_config;
 
 NEREUS_NAMESPACE_BEGIN
 
@@ -119,6 +120,14 @@ public:
     const std::vector<SUint> &getSurfaceTriangles();
     const std::vector<SVec4> &getSurfaceGradient();
     const std::vector<SVec4> &getSurfaceVelocity();
+    // Diffuse particles (nrs_diffuse_*, DESIGN.md "Diffuse particles"): spray, foam and bubbles born from the fluid's trapped air, wave
+    // crests and kinetic energy, kept and advected on the device.  configureDiffuse stores the configuration (struct_size and reserved are
+    // filled in); stepDiffuse advances the set on the current state (dt 0: the timestep) and returns without waiting — call it after
+    // update(); getDiffuse waits and returns the living set in host arrays the solver owns (positions with the remaining lifetime in w,
+    // velocities, kinds 0 spray / 1 foam / 2 bubble), valid until the next call.  Read-only: the simulation does not notice.
+    void configureDiffuse(const nrs_diffuse_config &cfg);
+    void stepDiffuse(double dt = 0.0);
+    SUint getDiffuse(const SVec4 **positions, const SVec4 **velocities, const SUint **kinds);
     void reserveParticles(SUint capacity);        // grow host+device storage up front
     void setEagerSync(bool on) { m_eagerSync = on; } // true: D2H at the end of every update() like the reference
     const SphSimParams &getParams() const { return m_params; }
@@ -188,6 +197,8 @@ protected:
     std::vector<SVec4> m_surfaceVertices, m_surfaceGradient, m_surfaceVelocity; // ... and of the last surface extract
     std::vector<SUint> m_surfaceTriangles;
     SUint m_surfaceV = 0, m_surfaceT = 0;
+    std::vector<SVec4> m_diffusePositions, m_diffuseVelocities; // ... and the living diffuse set of the last getDiffuse
+    std::vector<SUint> m_diffuseKinds;
 };
 
 NEREUS_NAMESPACE_END

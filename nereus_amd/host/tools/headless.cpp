@@ -26,6 +26,10 @@
 //                                                               as run, then the surface density = iso on that lattice
 //                                                               (SPH::extractSurface) as a Wavefront OBJ: "v x y z" lines, then
 //                                                               "f a b c" lines with 1-based vertex numbers, wound outwards
+//   headless diffuse <solver> <in.bin> <steps> <out.dif>        as run with SPH::stepDiffuse after every update (capacity 2^20, seed 0,
+//                                                               the ranges below), then the living diffuse set (SPH::getDiffuse)
+//                                                               out.dif: u32 count, u32 precision (32 | 64), pos4[count] (w = lifetime),
+//                                                               vel4[count], u32 kind[count] (0 spray, 1 foam, 2 bubble)
 // in.bin : u32 n, u32 nb, then pos4[n], vel4[n], bi4[nb], vbi[nb] (SReal)
 // out.bin: u32 n, u32 nb, u32 iters, u32 sizeof(params), params, pos4[n], vel4[n], pressure[n], bi4[nb], vbi[nb]
 #include <cstdio>
@@ -106,7 +110,7 @@ int main(int argc, char **argv)
     unsigned iters = 0;
     if (mode == "params") {
         dump(argv[3], sim, 0, bi, vbi);
-    } else if (mode == "run" || mode == "frames" || mode == "lattice" || mode == "surface") {
+    } else if (mode == "run" || mode == "frames" || mode == "lattice" || mode == "surface" || mode == "diffuse") {
         if (argc < 6) die("run needs <in.bin> <steps> <out.bin>");
         if (mode == "lattice" && argc < 13) die("lattice needs <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <out.lat>");
         if (mode == "surface" && argc < 14) die("surface needs <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <iso> <out.obj>");
@@ -139,6 +143,23 @@ int main(int argc, char **argv)
                 if (fstep < last || fstep > (unsigned long long)(s + 1) || fstep + 2 < (unsigned long long)(s + 1)) die("latestFrame: stale or out of order");
                 last = fstep;
             }
+        } else if (mode == "diffuse") {
+            nrs_diffuse_config dc;
+            std::memset(&dc, 0, sizeof(dc));
+            dc.capacity = 1u << 20;
+            dc.tau_ta[0] = 0.1; dc.tau_ta[1] = 0.5;
+            dc.tau_wc[0] = 0.1; dc.tau_wc[1] = 1.0;
+            dc.tau_k[0] = 5e-4; dc.tau_k[1] = 4e-3;
+            dc.k_ta = dc.k_wc = 3000.0;
+            dc.lifetime[0] = 0.5; dc.lifetime[1] = 2.0;
+            dc.k_buoyancy = 2.0; dc.k_drag = 0.8;
+            dc.spray_below = 6; dc.bubble_above = 20;
+            dc.max_per_particle = 3;
+            sim->configureDiffuse(dc);
+            for (int s = 0; s < steps; ++s) {
+                sim->update();
+                sim->stepDiffuse();
+            }
         } else {
             for (int s = 0; s < steps; ++s) sim->update();
         }
@@ -159,6 +180,19 @@ int main(int argc, char **argv)
             std::fwrite(head, 4, 4, o);
             std::fwrite(rho.data(), sizeof(SReal), rho.size(), o);
             std::fclose(o);
+        } else if (mode == "diffuse") {
+            const SVec4 *dp = nullptr, *dv = nullptr;
+            const SUint *dk = nullptr;
+            const SUint count = sim->getDiffuse(&dp, &dv, &dk);
+            FILE *o = std::fopen(argv[5], "wb");
+            if (!o) die("cannot open output");
+            const unsigned head[2] = {count, (unsigned)(8 * sizeof(SReal))};
+            std::fwrite(head, sizeof(unsigned), 2, o);
+            std::fwrite(dp, sizeof(SVec4), count, o);
+            std::fwrite(dv, sizeof(SVec4), count, o);
+            std::fwrite(dk, sizeof(SUint), count, o);
+            std::fclose(o);
+            std::printf("diffuse: %u particles after %d steps\n", count, steps);
         } else if (mode == "surface") {
             const double h = std::strtod(argv[8], nullptr);
             const double origin[3] = {std::strtod(argv[5], nullptr), std::strtod(argv[6], nullptr), std::strtod(argv[7], nullptr)}, spacing[3] = {h, h, h};
