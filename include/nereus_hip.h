@@ -592,6 +592,69 @@ int nrs_diffuse_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *
 int nrs_diffuse_upload(nrs_ctx *ctx, const void *pos4, const void *vel4, uint64_t n);
 int nrs_diffuse_release(nrs_ctx *ctx);
 
+/* ---- sources and sinks (DESIGN.md "Sources and sinks"; came after nrs_version() 0.3 without a version change) ---------------------------
+ * Emitters append fluid particles on the device, kill volumes remove them; both change the particle count without a host round trip.
+ * The feature is opt-in: a context that never configures it allocates nothing new and launches nothing new.
+ *
+ * WHEN.  At the top of every step of nrs_step and of nrs_iisph_predict — before the bodies move, before the step's kernels are chosen,
+ * and, when an enabled emitter exists, also on an empty context (it steps from empty) — first the sinks cull, then the emitters emit.
+ * dt is the context's timestep.  A step in which the context is still empty afterwards does nothing else.
+ *
+ * EMITTERS.  Up to NRS_MAX_EMITTERS slots.  d = direction / |direction| (double).  Frame: e1 = normalised d x axis, axis the coordinate
+ * axis of d's smallest absolute component (the lowest on a tie), e2 = d x e1 (all double, in the order written).  s = spacing, or, for
+ * spacing 0, cbrt(particleMass / restDensity) of the parameters at nrs_emitter_set.  Sites of a layer: integer (i, j), j-major (j outer,
+ * i inner, both ascending); rect: |i| <= floor(half_extent[0] / s), |j| <= floor(half_extent[1] / s); disc: both within
+ * floor(r / s), r = half_extent[0], keeping (i s)^2 + (j s)^2 <= r^2.  Schedule per slot and step, on the host in double:
+ *   acc += speed * dt;  while (acc >= s) { acc -= s; emit a layer with origin o = center + acc * d; }
+ * The layers of a step are appended in that order, slots ascending.  A layer that does not fit capacity - n whole, or that would take
+ * the slot past max_particles, is not emitted: its sites are added to `dropped`, the accumulator still advances (no burst later).
+ * A site's position component a is (SReal)(o[a] + (i * s) * e1[a] + (j * s) * e2[a]), evaluated in double in the written order without
+ * contraction and rounded once (the lattice-node rule of nrs_sample_lattice; the same bits in all four builds); pos.w = 1;
+ * vel = (SReal)(speed * d[a]), w = 0; pressure 0; DFSPH Kv 0.  Emitting into occupied space is the caller's business.
+ * nrs_emitter_set(slot, NULL) removes a slot; every successful set restarts the slot's accumulator and counts.  nrs_emitter_get returns
+ * the emitter as stored (direction normalised, spacing as given) and its counts; any pointer may be NULL; an empty slot reads as zeros.
+ * nrs_emit_block appends the nodes of a lattice in its linear index order ((k * dims[1] + j) * dims[0] + i), positions by the lattice
+ * rule, all with velocity (SReal)vel[a]: all of them or, with NRS_E_CAPACITY, none.
+ *
+ * SINKS.  A particle is removed when a coordinate of its position is not finite; or, with NRS_SINK_DOMAIN, when a coordinate lies
+ * outside [worldOrigin, worldOrigin + gridSize * cellSize); or when it lies inside a box (min <= x < max on every axis).  The
+ * comparisons are in SReal against bounds rounded to SReal once (the domain's upper bound is formed in double from the parameters).
+ * Survivors keep their order; positions, velocities, pressures and DFSPH's Kv move together.  The cull before a step runs before step
+ * k = interval, 2 interval, ... counted from nrs_sinks_set (interval 0 = 1).  It reads the survivor count back: one wait on the stepping
+ * thread.  If nothing was removed nothing else happens: the step is bit-identical to that of a context without sinks.  nrs_cull runs
+ * one cull now with the current sinks (non-finite positions are removed even with none) and waits.  nrs_sinks_count: particles removed
+ * and culls run since nrs_sinks_set.
+ *
+ * After any emission or removal the arrays are in the state nrs_upload_particles leaves: the next step hashes and sorts in full, and
+ * the field sampler, the mesher and the diffuse particles rebuild their grid.
+ *
+ * NRS_E_INVALID: a slab context (and nrs_slab_configure on a context with sources or sinks); a slot >= NRS_MAX_EMITTERS; an unknown
+ * shape; a non-finite field; a zero direction; speed < 0; spacing < 0, or so small that a layer has more than 2^24 sites; a negative
+ * extent; nboxes > NRS_MAX_SINK_BOXES; unknown flags; reserved != 0; a box with min >= max on some axis; a bad lattice or a non-finite
+ * velocity for nrs_emit_block.  NRS_E_STATE: mid-update after nrs_step_partial; a host-driven IISPH step in progress (nrs_cull,
+ * nrs_emit_block).  NRS_E_CAPACITY: nrs_emit_block with more nodes than capacity - n.  A refused call changes nothing. */
+enum { NRS_MAX_EMITTERS = 16, NRS_MAX_SINK_BOXES = 16 };
+enum { NRS_EMITTER_RECT = 0, NRS_EMITTER_DISC = 1 };
+typedef struct nrs_emitter {
+    uint32_t shape, enabled;
+    double center[3], direction[3];   /* direction normalised by the library */
+    double half_extent[2];            /* rect: along e1, e2; disc: [0] = radius */
+    double speed, spacing;            /* spacing 0 = cbrt(particleMass / restDensity) */
+    uint64_t max_particles;           /* 0 = no limit */
+} nrs_emitter;
+int nrs_emitter_set(nrs_ctx *ctx, uint32_t slot, const nrs_emitter *e);
+int nrs_emitter_get(nrs_ctx *ctx, uint32_t slot, nrs_emitter *e, uint64_t *emitted, uint64_t *dropped);
+int nrs_emit_block(nrs_ctx *ctx, const nrs_lattice *sites, const double vel[3], uint64_t *added);
+
+enum { NRS_SINK_DOMAIN = 1 };
+typedef struct nrs_sink_config {
+    uint32_t flags, nboxes, interval, reserved;   /* interval 0 = 1: cull before every interval-th step */
+    double boxes[NRS_MAX_SINK_BOXES][6];          /* min xyz, max xyz; inside means min <= x < max */
+} nrs_sink_config;
+int nrs_sinks_set(nrs_ctx *ctx, const nrs_sink_config *cfg);   /* NULL clears */
+int nrs_cull(nrs_ctx *ctx, uint64_t *removed);
+int nrs_sinks_count(nrs_ctx *ctx, uint64_t *removed_total, uint64_t *culls);
+
 /* Akinci boundary volumes on the device (no context needed): vbi[i] = 1 / sum_k W_poly6(|x_i - x_k|, h) over the boundary
  * particles k within h of i, i included — what the reference takes from its un-vendored submodule
  * (sample_spheres::boundary_forces::getVbi, main.cpp:546; own implementation, parity unpinned).  bi4: nb xyzw particles of

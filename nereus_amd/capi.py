@@ -38,6 +38,10 @@ MESH_VERTICES, MESH_TRIANGLES, MESH_GRADIENT, MESH_VELOCITY = 1, 2, 4, 8
 # NRS_DIFFUSE_*: one result of the diffuse particles; the kinds of NRS_DIFFUSE_KIND
 DIFFUSE_POS, DIFFUSE_VEL, DIFFUSE_KIND, DIFFUSE_POTENTIALS, DIFFUSE_BIRTHS, DIFFUSE_NORMALS = 0, 1, 2, 3, 4, 5
 DIFFUSE_SPRAY, DIFFUSE_FOAM, DIFFUSE_BUBBLE = 0, 1, 2
+# sources and sinks: slot and box caps, NRS_EMITTER_* shapes, NRS_SINK_* flags
+MAX_EMITTERS, MAX_SINK_BOXES = 16, 16
+EMITTER_RECT, EMITTER_DISC = 0, 1
+SINK_DOMAIN = 1
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
@@ -77,7 +81,22 @@ EXPORTS = [
     "nrs_surface_extract", "nrs_surface_result", "nrs_surface_device_ptr", "nrs_surface_release",
     "nrs_diffuse_configure", "nrs_diffuse_step", "nrs_diffuse_count", "nrs_diffuse_result", "nrs_diffuse_device_ptr",
     "nrs_diffuse_upload", "nrs_diffuse_release",
+    "nrs_emitter_set", "nrs_emitter_get", "nrs_emit_block", "nrs_sinks_set", "nrs_cull", "nrs_sinks_count",
 ]
+
+
+class NrsEmitter(C.Structure):
+    _fields_ = [
+        ("shape", C.c_uint32), ("enabled", C.c_uint32), ("center", C.c_double * 3), ("direction", C.c_double * 3),
+        ("half_extent", C.c_double * 2), ("speed", C.c_double), ("spacing", C.c_double), ("max_particles", C.c_uint64),
+    ]
+
+
+class NrsSinkConfig(C.Structure):
+    _fields_ = [
+        ("flags", C.c_uint32), ("nboxes", C.c_uint32), ("interval", C.c_uint32), ("reserved", C.c_uint32),
+        ("boxes", (C.c_double * 6) * MAX_SINK_BOXES),
+    ]
 
 
 class NrsDiffuseConfig(C.Structure):
@@ -191,6 +210,12 @@ def load_library(path=None):
     lib.nrs_diffuse_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
     lib.nrs_diffuse_upload.argtypes = [vp, vp, vp, u64]
     lib.nrs_diffuse_release.argtypes = [vp]
+    lib.nrs_emitter_set.argtypes = [vp, C.c_uint32, C.POINTER(NrsEmitter)]
+    lib.nrs_emitter_get.argtypes = [vp, C.c_uint32, C.POINTER(NrsEmitter), C.POINTER(u64), C.POINTER(u64)]
+    lib.nrs_emit_block.argtypes = [vp, C.POINTER(NrsLattice), C.POINTER(C.c_double), C.POINTER(u64)]
+    lib.nrs_sinks_set.argtypes = [vp, C.POINTER(NrsSinkConfig)]
+    lib.nrs_cull.argtypes = [vp, C.POINTER(u64)]
+    lib.nrs_sinks_count.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     _lib = lib
     return lib
 
@@ -608,6 +633,64 @@ class Solver:
 
     def diffuse_release(self):
         self._chk(self.lib.nrs_diffuse_release(self.h))
+
+    # ---- sources and sinks ----------------------------------------------------------------------------
+    def emitter_set(self, slot, center=None, direction=None, half_extent=(0.0, 0.0), speed=0.0, spacing=0.0, shape=EMITTER_RECT,
+                    enabled=True, max_particles=0):
+        """store an emitter in `slot` (nrs_emitter_set), or remove it with center=None: layers of sites on a rectangle or disc through
+        `center`, normal to `direction`, moving with `speed`; a layer is appended at the top of a step whenever speed * dt has
+        accumulated one `spacing` (0: cbrt(particleMass / restDensity)); restarts the slot's accumulator and counts"""
+        if center is None:
+            self._chk(self.lib.nrs_emitter_set(self.h, int(slot), None))
+            return
+        e = NrsEmitter()
+        e.shape, e.enabled, e.max_particles = int(shape), int(bool(enabled)), int(max_particles)
+        he = list(np.broadcast_to(np.asarray(half_extent, np.float64), (2,)))
+        e.center[:], e.direction[:], e.half_extent[:] = [float(x) for x in center], [float(x) for x in direction], [float(x) for x in he]
+        e.speed, e.spacing = float(speed), float(spacing)
+        self._chk(self.lib.nrs_emitter_set(self.h, int(slot), C.byref(e)))
+
+    def emitter_get(self, slot):
+        """(emitter as stored — a dict, direction normalised —, emitted, dropped) of a slot (nrs_emitter_get)"""
+        e, a, d = NrsEmitter(), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.nrs_emitter_get(self.h, int(slot), C.byref(e), C.byref(a), C.byref(d)))
+        em = dict(shape=int(e.shape), enabled=bool(e.enabled), center=list(e.center), direction=list(e.direction),
+                  half_extent=list(e.half_extent), speed=e.speed, spacing=e.spacing, max_particles=int(e.max_particles))
+        return em, int(a.value), int(d.value)
+
+    def emit_block(self, origin, spacing, dims, vel=(0.0, 0.0, 0.0)):
+        """append the nodes of a lattice as fluid particles with velocity `vel` (nrs_emit_block): all or, above the capacity, none;
+        returns how many were added"""
+        L = self._lattice(origin, spacing, dims)
+        v, added = (C.c_double * 3)(*[float(a) for a in vel]), C.c_uint64(0)
+        self._chk(self.lib.nrs_emit_block(self.h, C.byref(L), v, C.byref(added)))
+        return int(added.value)
+
+    def sinks_set(self, boxes=(), domain=False, interval=1, flags=None, nboxes=None, reserved=0):
+        """kill volumes (nrs_sinks_set): boxes as rows (min xyz, max xyz), `domain`: also whatever leaves the grid box; culled before every
+        interval-th step.  boxes=None clears the sinks."""
+        if boxes is None:
+            self._chk(self.lib.nrs_sinks_set(self.h, None))
+            return
+        b = np.asarray(boxes, np.float64).reshape(-1, 6)
+        c = NrsSinkConfig()
+        c.flags = (SINK_DOMAIN if domain else 0) if flags is None else int(flags)
+        c.nboxes, c.interval, c.reserved = (len(b) if nboxes is None else int(nboxes)), int(interval), int(reserved)
+        for i in range(min(len(b), MAX_SINK_BOXES)):
+            c.boxes[i][:] = [float(x) for x in b[i]]
+        self._chk(self.lib.nrs_sinks_set(self.h, C.byref(c)))
+
+    def cull(self):
+        """one cull now with the current sinks (nrs_cull; waits); returns how many particles were removed"""
+        r = C.c_uint64(0)
+        self._chk(self.lib.nrs_cull(self.h, C.byref(r)))
+        return int(r.value)
+
+    def sinks_count(self):
+        """(particles removed, culls run) since the last sinks_set (nrs_sinks_count)"""
+        r, c = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.nrs_sinks_count(self.h, C.byref(r), C.byref(c)))
+        return int(r.value), int(c.value)
 
     @property
     def n_owned(self):

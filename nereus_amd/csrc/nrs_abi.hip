@@ -507,6 +507,36 @@ int nrs_diffuse_release(nrs_ctx *ctx)
     CTX_GUARD(ctx);
     return ctx->impl->diffuse_release();
 }
+int nrs_emitter_set(nrs_ctx *ctx, uint32_t slot, const nrs_emitter *e)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->emitter_set(slot, e);
+}
+int nrs_emitter_get(nrs_ctx *ctx, uint32_t slot, nrs_emitter *e, uint64_t *emitted, uint64_t *dropped)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->emitter_get(slot, e, emitted, dropped);
+}
+int nrs_emit_block(nrs_ctx *ctx, const nrs_lattice *sites, const double vel[3], uint64_t *added)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->emit_block(sites, vel, added);
+}
+int nrs_sinks_set(nrs_ctx *ctx, const nrs_sink_config *cfg)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->sinks_set(cfg);
+}
+int nrs_cull(nrs_ctx *ctx, uint64_t *removed)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->cull(removed);
+}
+int nrs_sinks_count(nrs_ctx *ctx, uint64_t *removed_total, uint64_t *culls)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->sinks_count(removed_total, culls);
+}
 uint64_t nrs_slab_message_bytes(uint64_t capacity, int precision) { return 16 + capacity * 2 * (precision == 64 ? 32 : 16); }
 
 int nrs_max_density(nrs_ctx *ctx, double *out)

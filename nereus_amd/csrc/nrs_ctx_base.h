@@ -153,6 +153,13 @@ struct CtxBase {
     virtual int diffuse_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) = 0;
     virtual int diffuse_upload(const void *pos4, const void *vel4, uint64_t n) = 0;
     virtual int diffuse_release() = 0;
+    // sources and sinks (nrs_kernels_inflow.h; the host decisions: nrs_host_inflow.h)
+    virtual int emitter_set(uint32_t slot, const nrs_emitter *e) = 0;
+    virtual int emitter_get(uint32_t slot, nrs_emitter *e, uint64_t *emitted, uint64_t *dropped) = 0;
+    virtual int emit_block(const nrs_lattice *lattice, const double *vel, uint64_t *added) = 0;
+    virtual int sinks_set(const nrs_sink_config *cfg) = 0;
+    virtual int cull(uint64_t *removed) = 0;
+    virtual int sinks_count(uint64_t *removedTotal, uint64_t *culls) = 0;
     hipStream_t stream = nullptr;
     bool ownStream = false;
     int device = 0;

@@ -19,7 +19,7 @@
 // word and statistics.  The context reads views of it (sort.hash(), sort.index(), sort.prepared(), the tile counts the fused and the
 // slab kernels write) and calls its operations (sort_keys, scan_movers, split, scan_holes, the pack targets).  The field sampler's
 // buffers: sm (FieldSampler, nrs_field_sampler.h); the surface mesh's: sf (SurfaceMesher, nrs_surface_mesher.h); the diffuse
-// particles': df (DiffuseSystem, nrs_diffuse.h).
+// particles': df (DiffuseSystem, nrs_diffuse.h); the sources' and sinks': inflow (InflowSystem, nrs_inflow.h).
 // Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure functions it calls:
 // the stage timer (nrs_host_profile.h), the snapshot ring (nrs_host_snapshot.h), the solver settings and their validation
 // (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
@@ -55,6 +55,7 @@
 #include "nrs_field_sampler.h"
 #include "nrs_surface_mesher.h"
 #include "nrs_diffuse.h"
+#include "nrs_inflow.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
 
@@ -1224,6 +1225,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(validate("nrs_iisph_*"));
         if (phase == 0) { // predict
             if (midStep || iisphPhase) return fail(NRS_E_STATE, "a step is already in progress");
+            if (inflow.active()) NRSCHK(apply_inflow());
             if (n == 0) return NRS_OK;
             fusedThisStep = false; splitClearedCells = false;
             plan = plan_step(0);
@@ -1268,6 +1270,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
         NRSCHK(slab_refuse_configure(cfg.solver, bt.has_bodies(), lo, hi, halo));
+        if (inflow.configured()) return inflow_refuse_slab();
         bool cutsChanged = false;
         exch.configure(lo, hi, halo, &cutsChanged);
         // the last force kernel classified (and marked dead keys) for the old cuts: partition the slow way once
@@ -1454,11 +1457,16 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(validate("nrs_step"));
         if (midStep) return fail(NRS_E_STATE, "state is mid-update after nrs_step_partial; upload particles first");
         NRSCHK(stage_allowed(cfg.solver, stop));
-        if (n == 0) return NRS_OK;
+        const bool sources = inflow.active(); // sinks, then emitters, at the top of every step; an enabled emitter steps from empty
+        if (n == 0 && !(sources && inflow.emitter_enabled())) return NRS_OK;
         if (pcisph()) NRSCHK(pcisph_prepare());
         if (pbf()) NRSCHK(pbf_prepare());
         if (dfsph()) NRSCHK(dfsph_prepare());
         for (int s = 0; s < nsteps; ++s) {
+            if (sources) {
+                NRSCHK(apply_inflow());
+                if (n == 0) continue; // (still empty: nothing to step)
+            }
             fusedThisStep = false;
             splitClearedCells = false;
             plan = plan_step(stop);
@@ -1771,6 +1779,127 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         HIPCHK(hipStreamSynchronize(stream)); // a queued step may still use the buffers
         df.release();
+        return NRS_OK;
+    }
+
+    // ---- sources and sinks (include/nereus_hip.h; DESIGN.md "Sources and sinks") ----------------------------------------------------------------
+    // The slots, the sink configuration, the counts and the cull's buffers are inflow's (nrs_inflow.h); the arrays, the count and the state
+    // transition are the context's.  Emission writes behind the living particles of the A arrays; a cull that removes something moves
+    // A -> B and swaps, as end_of_step does.  Both leave the state nrs_upload_particles leaves (particles_changed).
+    InflowSystem inflow;
+    int inflow_begin(const char *where, bool driven) const
+    {
+        NRSCHK(validate(where));
+        return inflow_refusal(exch.on(), midStep, iisphPhase != 0, driven);
+    }
+    void particles_changed()
+    {
+        ++particleGen;
+        st.to_fresh();
+    }
+    EmitOut<R> emit_out() { return EmitOut<R>{posA.as<T4>(), velA.as<T4>(), presA.as<R>(), dfsph() ? dfKvA.as<R>() : (R *)nullptr, (uint32_t)n}; }
+    int emitter_set(uint32_t slot, const nrs_emitter *e) override
+    {
+        NRSCHK(inflow_check_slot(slot));
+        EmitterSlot fresh;
+        if (e) NRSCHK(inflow_check_emitter(e, (double)PU.particleMass, (double)PU.restDensity, fresh));
+        NRSCHK(inflow_begin("nrs_emitter_set", false));
+        inflow.slots[slot] = std::move(fresh);
+        return NRS_OK;
+    }
+    int emitter_get(uint32_t slot, nrs_emitter *e, uint64_t *emitted, uint64_t *dropped) override
+    {
+        NRSCHK(inflow_check_slot(slot));
+        const EmitterSlot &sl = inflow.slots[slot];
+        if (e) *e = sl.e;
+        if (emitted) *emitted = sl.emitted;
+        if (dropped) *dropped = sl.dropped;
+        return NRS_OK;
+    }
+    int emit_block(const nrs_lattice *lattice, const double *vel, uint64_t *added) override
+    {
+        if (added) *added = 0;
+        NRSCHK(validate("nrs_emit_block"));
+        if (exch.on()) return inflow_refusal(true, false, false, true);
+        uint64_t m = 0;
+        NRSCHK(inflow_check_block(lattice, vel, n, cap, &m));
+        NRSCHK(inflow_refusal(false, midStep, iisphPhase != 0, true));
+        SampleLattice L;
+        for (int a = 0; a < 3; ++a) { L.origin[a] = lattice->origin[a]; L.spacing[a] = lattice->spacing[a]; L.dims[a] = lattice->dims[a]; }
+        NRSCHK(inflow.template emit_block<R>(L, vel, (uint32_t)m, emit_out(), stream));
+        n += m;
+        particles_changed();
+        if (added) *added = m;
+        return NRS_OK;
+    }
+    int sinks_set(const nrs_sink_config *c) override
+    {
+        if (c) NRSCHK(inflow_check_sinks(c));
+        NRSCHK(inflow_begin("nrs_sinks_set", false));
+        inflow.set_sinks(c);
+        return NRS_OK;
+    }
+    int sinks_count(uint64_t *removedTotal, uint64_t *culls) override
+    {
+        if (removedTotal) *removedTotal = inflow.removedTotal;
+        if (culls) *culls = inflow.culls;
+        return NRS_OK;
+    }
+    // one cull with the current sinks: count, scan, read the survivor count back (the wait); only when something goes: compact and swap
+    int cull_now(uint64_t *removed)
+    {
+        *removed = 0;
+        if (n) {
+            const CullBounds<R> B = inflow_bounds<R>(inflow.haveSinks ? &inflow.sinks : nullptr, PU.worldOrigin, PU.gridSize, PU.cellSize);
+            const uint32_t N = (uint32_t)n;
+            uint32_t keep = 0;
+            NRSCHK(inflow.template count<R>(posA.as<T4>(), B, N, stream, &keep));
+            if (keep > N) return fail(NRS_E_STATE, "cull: more survivors than particles");
+            if (keep < N) {
+                const CullArrays<R> A{posA.as<T4>(), velA.as<T4>(), presA.as<R>(), dfsph() ? dfKvA.as<R>() : (const R *)nullptr,
+                                      posB.as<T4>(), velB.as<T4>(), presB.as<R>(), dfsph() ? dfKvB.as<R>() : (R *)nullptr};
+                NRSCHK(inflow.template compact<R>(A, B, N, stream));
+                std::swap(posA.p, posB.p);
+                std::swap(velA.p, velB.p);
+                std::swap(presA.p, presB.p);
+                if (dfsph()) std::swap(dfKvA.p, dfKvB.p);
+                *removed = N - keep;
+                n = keep;
+                particles_changed();
+            }
+        }
+        inflow.culled(*removed);
+        return NRS_OK;
+    }
+    int cull(uint64_t *removed) override
+    {
+        uint64_t r = 0;
+        if (removed) *removed = 0;
+        NRSCHK(inflow_begin("nrs_cull", true));
+        NRSCHK(cull_now(&r));
+        if (removed) *removed = r;
+        return NRS_OK;
+    }
+    // the top of a step (step(), nrs_iisph_predict): the sinks, then the emitters' layers of this step, slots ascending
+    int apply_inflow()
+    {
+        if (inflow.cull_due()) {
+            uint64_t r = 0;
+            NRSCHK(cull_now(&r));
+        }
+        bool any = false;
+        std::vector<double> offsets;
+        for (uint32_t si = 0; si < (uint32_t)NRS_MAX_EMITTERS; ++si) {
+            uint64_t room = cap - n;
+            const uint64_t before = room;
+            offsets.clear();
+            inflow_schedule(inflow.slots[si], (double)PU.timestep, room, offsets);
+            if (offsets.empty()) continue;
+            NRSCHK(inflow.template emit<R>(si, offsets, emit_out(), stream));
+            n += before - room;
+            any = true;
+        }
+        if (any) particles_changed();
         return NRS_OK;
     }
 };

@@ -388,6 +388,67 @@ SUint SPH::getDiffuse(const SVec4 **positions, const SVec4 **velocities, const S
     return (SUint)m_diffusePositions.size();
 }
 
+// ---- sources and sinks -------------------------------------------------------------------------------------------------------------------
+void SPH::adoptDeviceCount()
+{
+    const SUint n = (SUint)nrs_num_particles(m_ctx);
+    growHost(n);
+    m_numParticles = n;
+    m_deviceNewer = true;
+    m_frameIsCurrent = false;
+}
+void SPH::setEmitter(SUint slot, const nrs_emitter *emitter)
+{
+    ensureContext();
+    if (nrs_emitter_set(m_ctx, slot, emitter) != NRS_OK) fatal("nrs_emitter_set");
+    m_inflow = true;
+}
+void SPH::getEmitter(SUint slot, nrs_emitter *emitter, unsigned long long *emitted, unsigned long long *dropped)
+{
+    ensureContext();
+    uint64_t a = 0, d = 0;
+    if (nrs_emitter_get(m_ctx, slot, emitter, &a, &d) != NRS_OK) fatal("nrs_emitter_get");
+    if (emitted) *emitted = a;
+    if (dropped) *dropped = d;
+}
+SUint SPH::emitBlock(const double origin[3], const double spacing[3], const SUint dims[3], const double vel[3])
+{
+    ensureContext();
+    pushHostToDevice();
+    nrs_lattice L;
+    std::memset(&L, 0, sizeof(L));
+    for (int a = 0; a < 3; ++a) { L.origin[a] = origin[a]; L.spacing[a] = spacing[a]; L.dims[a] = dims[a]; }
+    uint64_t added = 0;
+    const int rc = nrs_emit_block(m_ctx, &L, vel, &added);
+    if (rc == NRS_E_CAPACITY) return 0;
+    if (rc != NRS_OK) fatal("nrs_emit_block");
+    adoptDeviceCount();
+    return (SUint)added;
+}
+void SPH::setSinks(const nrs_sink_config *sinks)
+{
+    ensureContext();
+    if (nrs_sinks_set(m_ctx, sinks) != NRS_OK) fatal("nrs_sinks_set");
+    m_inflow = true;
+}
+SUint SPH::cull()
+{
+    ensureContext();
+    pushHostToDevice();
+    uint64_t removed = 0;
+    if (nrs_cull(m_ctx, &removed) != NRS_OK) fatal("nrs_cull");
+    if (removed) adoptDeviceCount();
+    return (SUint)removed;
+}
+void SPH::sinkCounts(unsigned long long *removedTotal, unsigned long long *culls)
+{
+    ensureContext();
+    uint64_t r = 0, c = 0;
+    if (nrs_sinks_count(m_ctx, &r, &c) != NRS_OK) fatal("nrs_sinks_count");
+    if (removedTotal) *removedTotal = r;
+    if (culls) *culls = c;
+}
+
 nrs_ctx *SPH::deviceContext()
 {
     ensureContext();
@@ -421,7 +482,7 @@ void SPH::synchronize() const
 
 void SPH::update()
 {
-    if (m_numParticles == 0) return;
+    if (m_numParticles == 0 && !m_inflow) return; // (an emitter steps from empty)
     ensureContext();
     pushHostToDevice();                                                   // only if the host side changed
     if (m_cfl) { // sph.cpp:217-231 (disabled there): newDeltat = lambda * (ir / |v|max)
@@ -433,6 +494,7 @@ void SPH::update()
     if (nrs_step(m_ctx, 1) != NRS_OK) fatal("nrs_step");
     m_deviceNewer = true;
     m_frameIsCurrent = false;
+    if (m_inflow) adoptDeviceCount(); // sources and sinks: the count is the device's
     if (m_asyncReadback) {
         if (m_framesInFlight == 2) collectFrames(false); // the library would wait for the oldest anyway: keep it
         if (nrs_snapshot_begin(m_ctx, 0) != NRS_OK) fatal("nrs_snapshot_begin");

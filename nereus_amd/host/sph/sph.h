@@ -29,6 +29,8 @@
 
 struct nrs_ctx;
 struct nrs_diffuse_config;
+struct nrs_emitter;
+struct nrs_sink_config;
 
 NEREUS_NAMESPACE_BEGIN
 
@@ -128,6 +130,19 @@ public:
     void configureDiffuse(const nrs_diffuse_config &cfg);
     void stepDiffuse(double dt = 0.0);
     SUint getDiffuse(const SVec4 **positions, const SVec4 **velocities, const SUint **kinds);
+    // Sources and sinks (nrs_emitter_* / nrs_sinks_* / nrs_cull / nrs_emit_block, DESIGN.md "Sources and sinks"): emitters append layers of
+    // particles at the top of every update(), kill volumes remove particles there, all on the device; update() then also runs on an empty
+    // solver, and getNumParticles() follows the device's count.  setEmitter(slot, nullptr) removes a slot, setSinks(nullptr) clears the
+    // sinks.  emitBlock appends the nodes of a lattice with one velocity and returns their number, 0 when they do not fit the capacity
+    // (reserveParticles first); cull runs one cull now and returns the number removed.  The device context holds the configuration:
+    // reserve the capacity BEFORE configuring (a context rebuilt to grow starts without emitters and sinks), and saveState / loadState
+    // do not hold emitters, sinks, accumulators or counts.
+    void setEmitter(SUint slot, const nrs_emitter *emitter);
+    void getEmitter(SUint slot, nrs_emitter *emitter, unsigned long long *emitted, unsigned long long *dropped);
+    SUint emitBlock(const double origin[3], const double spacing[3], const SUint dims[3], const double vel[3]);
+    void setSinks(const nrs_sink_config *sinks);
+    SUint cull();
+    void sinkCounts(unsigned long long *removedTotal, unsigned long long *culls);
     void reserveParticles(SUint capacity);        // grow host+device storage up front
     void setEagerSync(bool on) { m_eagerSync = on; } // true: D2H at the end of every update() like the reference
     const SphSimParams &getParams() const { return m_params; }
@@ -199,6 +214,8 @@ protected:
     SUint m_surfaceV = 0, m_surfaceT = 0;
     std::vector<SVec4> m_diffusePositions, m_diffuseVelocities; // ... and the living diffuse set of the last getDiffuse
     std::vector<SUint> m_diffuseKinds;
+    bool m_inflow = false; // emitters or sinks were configured: the device's particle count leads
+    void adoptDeviceCount();
 };
 
 NEREUS_NAMESPACE_END

@@ -30,8 +30,14 @@
 //                                                               the ranges below), then the living diffuse set (SPH::getDiffuse)
 //                                                               out.dif: u32 count, u32 precision (32 | 64), pos4[count] (w = lifetime),
 //                                                               vel4[count], u32 kind[count] (0 spray, 1 foam, 2 bubble)
+//   headless faucet <solver> <steps> <out.bin>                  no input: an empty solver with the constructor's parameters and no walls, a disc
+//                                                               emitter (SPH::setEmitter: centre (0, -0.9, 0), pointing down, radius 2.5
+//                                                               rest spacings, 4 m/s) and a domain sink (SPH::setSinks); <steps> updates,
+//                                                               then out.bin: u32 n, u32 precision (32 | 64), u64 emitted, u64 dropped,
+//                                                               u64 removed, u64 culls, pos4[n], vel4[n]
 // in.bin : u32 n, u32 nb, then pos4[n], vel4[n], bi4[nb], vbi[nb] (SReal)
 // out.bin: u32 n, u32 nb, u32 iters, u32 sizeof(params), params, pos4[n], vel4[n], pressure[n], bi4[nb], vbi[nb]
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -110,6 +116,36 @@ int main(int argc, char **argv)
     unsigned iters = 0;
     if (mode == "params") {
         dump(argv[3], sim, 0, bi, vbi);
+    } else if (mode == "faucet") {
+        if (argc < 5) die("faucet needs <steps> <out.bin>");
+        const int steps = std::atoi(argv[3]);
+        const SphSimParams &P = sim->getParams();
+        nrs_emitter em;
+        std::memset(&em, 0, sizeof(em));
+        em.shape = NRS_EMITTER_DISC; em.enabled = 1;
+        em.center[1] = -0.9; em.direction[1] = -1.0;
+        em.half_extent[0] = 2.5 * std::cbrt((double)P.particleMass / (double)P.restDensity);
+        em.speed = 4.0;
+        nrs_sink_config sk;
+        std::memset(&sk, 0, sizeof(sk));
+        sk.flags = NRS_SINK_DOMAIN;
+        sim->setEmitter(0, &em);
+        sim->setSinks(&sk);
+        for (int s = 0; s < steps; ++s) sim->update();
+        unsigned long long emitted = 0, dropped = 0, removed = 0, culls = 0;
+        sim->getEmitter(0, nullptr, &emitted, &dropped);
+        sim->sinkCounts(&removed, &culls);
+        const unsigned n = sim->getNumParticles();
+        FILE *o = std::fopen(argv[4], "wb");
+        if (!o) die("cannot open output");
+        const unsigned head[2] = {n, (unsigned)(8 * sizeof(SReal))};
+        const unsigned long long counts[4] = {emitted, dropped, removed, culls};
+        std::fwrite(head, sizeof(unsigned), 2, o);
+        std::fwrite(counts, sizeof(unsigned long long), 4, o);
+        std::fwrite(sim->getHostPos(), sizeof(SReal) * 4, n, o);
+        std::fwrite(sim->getHostVel(), sizeof(SReal) * 4, n, o);
+        std::fclose(o);
+        std::printf("faucet: %u particles after %d steps (%llu emitted, %llu removed)\n", n, steps, emitted, removed);
     } else if (mode == "run" || mode == "frames" || mode == "lattice" || mode == "surface" || mode == "diffuse") {
         if (argc < 6) die("run needs <in.bin> <steps> <out.bin>");
         if (mode == "lattice" && argc < 13) die("lattice needs <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <out.lat>");
