@@ -17,9 +17,10 @@
 // sort (SortStage, nrs_sort.h; compiled once, in nrs_sort.hip, with the radix sorts and the merge) has the (hash, index) pairs and
 // which of each is current, prepared or a pack target, the sort's workspace, the buffers of the coherent re-sort, its mover-count
 // word and statistics.  The context reads views of it (sort.hash(), sort.index(), sort.prepared(), the tile counts the fused and the
-// slab kernels write) and calls its operations (sort_keys, scan_movers, split, scan_holes, the pack targets).  The field sampler's
-// buffers: sm (FieldSampler, nrs_field_sampler.h); the surface mesh's: sf (SurfaceMesher, nrs_surface_mesher.h); the diffuse
-// particles': df (DiffuseSystem, nrs_diffuse.h); the sources' and sinks': inflow (InflowSystem, nrs_inflow.h).
+// slab kernels write) and calls its operations (sort_keys, scan_movers, split, scan_holes, the pack targets).  The add-ons that only
+// read the particle state — field sampling, surface extraction, diffuse particles — depend on the precision and the kernel set: rd
+// (FluidReaders<R, KSET>, nrs_readers.h) holds their buffers, launches on them and copies their results out; the context tells it per call
+// what the fluid is now (fluid_now).  The sources and sinks change n and the array state: their buffers are inflow's (InflowSystem, nrs_inflow.h).
 // Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure functions it calls:
 // the stage timer (nrs_host_profile.h), the snapshot ring (nrs_host_snapshot.h), the solver settings and their validation
 // (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
@@ -52,9 +53,7 @@
 #include "nrs_kernels_akinci.h"
 #include "nrs_kernels_bodies.h"
 #include "nrs_slab_exchange.h"
-#include "nrs_field_sampler.h"
-#include "nrs_surface_mesher.h"
-#include "nrs_diffuse.h"
+#include "nrs_readers.h"
 #include "nrs_inflow.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
@@ -1541,246 +1540,53 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return NRS_OK;
     }
 
-    // ---- field sampling (include/nereus_hip.h; DESIGN.md "Field sampling") ----------------------------------------------------------------
-    // The sampler owns its buffers and its grid (sm, nrs_field_sampler.h) and reads posA / velA, P and, for walls, bt's sorted array and
-    // cell table; the refusals, sizes and the cache rule are nrs_host_sample.h's.  Nothing a step owns is written.
-    FieldSampler sm;
+    // ---- field sampling, surface extraction, diffuse particles (include/nereus_hip.h; DESIGN.md under these names) ---------------------------
+    // The add-ons that only read the particle state have one owner: rd (nrs_readers.h) holds the sampler, the mesher and the diffuse set, launches,
+    // copies out and names what their results hold.  The context counts what the sampler's cache rule depends on, checks its own state and says what
+    // the fluid is now; every call below forwards.
+    FluidReaders<R, KSET> rd;
     uint64_t particleGen = 0, gridGen = 0, boundaryGen = 0; // uploads / nrs_set_num_particles, grid changes, boundary sets / body assignments
-    SampleFacts sample_facts() const
+    FluidNow<R> fluid_now() const
     {
-        return SampleFacts{midStep, iisphPhase != 0, exch.on(), {P.gridSize[0], P.gridSize[1], P.gridSize[2]},
-                           {(double)P.cellSize[0], (double)P.cellSize[1], (double)P.cellSize[2]}, (double)P.interactionRadius};
-    }
-    // points (device, m of them) or, null, the m nodes of L
-    int sample_run(const T4 *points, const SampleLattice &L, uint64_t m, uint32_t fields)
-    {
-        const SampleKey key{stepsDone, particleGen, gridGen, boundaryGen};
-        if (sm.cache.needs_build(key)) {
-            NRSCHK(sm.template build_grid<R>(P, posA.as<T4>(), velA.as<T4>(), n, stream));
-            sm.cache.built(key);
-        }
-        NRSCHK(sm.ensure_results(fields, m, sizeof(R)));
-        GridView<R> G;
-        std::memset(&G, 0, sizeof(G));
-        G.cellStart = sm.cell_start(); G.cellEnd = sm.cell_end();
-        G.nSorted = sm.sorted_count();
-        G.err = sm.err_word();
-        G.actLo = INT_MIN; G.actHi = INT_MAX;
-        const bool walls = (fields & NRS_FIELD_WALLS) && bt.count();
-        if (walls) { G.bCellStart = bt.cell_start(); G.bCellEnd = bt.cell_end(); G.sB = bt.sorted(); }
-        const SampleOut<R> O{(fields & NRS_FIELD_DENSITY) ? (R *)sm.result(NRS_FIELD_DENSITY) : nullptr,
-                             (fields & NRS_FIELD_GRADIENT) ? (T4 *)sm.result(NRS_FIELD_GRADIENT) : nullptr,
-                             (fields & NRS_FIELD_VELOCITY) ? (T4 *)sm.result(NRS_FIELD_VELOCITY) : nullptr,
-                             (fields & NRS_FIELD_COUNT) ? (uint32_t *)sm.result(NRS_FIELD_COUNT) : nullptr};
-        const dim3 g(nblocks(m)), b(BLOCK);
-        const T4 *sP = sm.template sorted_pos<T4>(), *sV = sm.template sorted_vel<T4>();
-        if (walls) hipLaunchKernelGGL((k_sample_points<R, KSET, true>), g, b, 0, stream, P, G, sP, sV, points, L, O, fields, (uint32_t)m);
-        else hipLaunchKernelGGL((k_sample_points<R, KSET, false>), g, b, 0, stream, P, G, sP, sV, points, L, O, fields, (uint32_t)m);
-        HIPCHK(hipGetLastError());
-        return NRS_OK;
-    }
-    int sample_begin(uint32_t fields)
-    {
-        NRSCHK(validate("nrs_sample_*"));
-        NRSCHK(sample_check_fields(fields));
-        return sample_refusal(sample_facts());
+        const SampleFacts facts{midStep, iisphPhase != 0, exch.on(), {P.gridSize[0], P.gridSize[1], P.gridSize[2]},
+                                {(double)P.cellSize[0], (double)P.cellSize[1], (double)P.cellSize[2]}, (double)P.interactionRadius};
+        return FluidNow<R>{P, posA.as<T4>(), velA.as<T4>(), n, SampleKey{stepsDone, particleGen, gridGen, boundaryGen}, facts,
+                           bt.cell_start(), bt.cell_end(), bt.sorted(), bt.count(), stream};
     }
     int sample_points(const void *points4, uint64_t m, uint32_t fields) override
     {
-        NRSCHK(sample_begin(fields));
-        NRSCHK(sample_check_points(points4, m));
-        sm.last = SampleLast();
-        if (m) {
-            NRSCHK(sm.upload_points(points4, m, sizeof(T4), stream));
-            NRSCHK(sample_run(sm.template query_points<T4>(), SampleLattice(), m, fields));
-        }
-        sm.last = SampleLast{true, fields, m};
-        return NRS_OK;
+        NRSCHK(validate("nrs_sample_*"));
+        return rd.sample_points(fluid_now(), points4, m, fields);
     }
-    int sample_lattice(const nrs_lattice *lattice, uint32_t fields) override
-    {
-        NRSCHK(sample_begin(fields));
-        uint64_t m = 0;
-        NRSCHK(sample_check_lattice(lattice, &m));
-        SampleLattice L;
-        for (int a = 0; a < 3; ++a) { L.origin[a] = lattice->origin[a]; L.spacing[a] = lattice->spacing[a]; L.dims[a] = lattice->dims[a]; }
-        sm.last = SampleLast();
-        NRSCHK(sample_run(nullptr, L, m, fields));
-        sm.last = SampleLast{true, fields, m};
-        return NRS_OK;
-    }
-    int sample_device_ptr(uint32_t field, void **dptr, uint64_t *bytes) override
-    {
-        NRSCHK(sample_route_result(sm.last, field, (int)(8 * sizeof(R)), bytes));
-        *dptr = *bytes ? sm.result(field) : nullptr;
-        return NRS_OK;
-    }
-    int sample_result(uint32_t field, void *dst, uint64_t dstBytes, uint64_t *outBytes) override
-    {
-        void *p = nullptr;
-        uint64_t sz = 0;
-        NRSCHK(sample_device_ptr(field, &p, &sz));
-        if (outBytes) *outBytes = sz;
-        if (!dst) return NRS_OK;
-        if (dstBytes < sz) return fail(NRS_E_INVALID, "destination too small");
-        if (!sz) return NRS_OK;
-        uint32_t e = 0;
-        HIPCHK(hipMemcpyAsync(dst, p, sz, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipMemcpyAsync(&e, sm.err_word(), 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (!e) return NRS_OK;
-        HIPCHK(hipMemsetAsync(sm.err_word(), 0, 4, stream));
-        return fail(NRS_E_STATE, "field sampling: a cell range of the sampler's table lies outside its sorted particles; the gather skipped it, the results are invalid");
-    }
-    uint64_t sample_builds() override { return sm.cache.builds; }
-    int sample_release() override
-    {
-        HIPCHK(hipStreamSynchronize(stream)); // a queued gather may still read the buffers
-        sm.release();
-        return NRS_OK;
-    }
-
-    // ---- surface extraction (include/nereus_hip.h; DESIGN.md "Surface extraction") ---------------------------------------------------------
-    // A sample call on the lattice path above (sm's result arrays, refusals and cache rule), then the mesher (sf, nrs_surface_mesher.h) on
-    // sm's result pointers.  The mesh buffers are sf's: no sample call touches them.  Nothing a step owns is written.
-    SurfaceMesher sf;
+    int sample_lattice(const nrs_lattice *lattice, uint32_t fields) override { NRSCHK(validate("nrs_sample_*")); return rd.sample_lattice(fluid_now(), lattice, fields); }
+    int sample_device_ptr(uint32_t field, void **dptr, uint64_t *bytes) override { return rd.sample_device_ptr(field, dptr, bytes); }
+    int sample_result(uint32_t field, void *dst, uint64_t dstBytes, uint64_t *outBytes) override { return rd.sample_result(field, dst, dstBytes, outBytes, stream); }
+    uint64_t sample_builds() override { return rd.sm.cache.builds; }
+    int sample_release() override { return rd.release(rd.sm, stream); }
     int surface_extract(const nrs_lattice *lattice, double iso, uint32_t flags, uint64_t *vertices, uint64_t *triangles) override
     {
-        NRSCHK(surface_check_call(iso, flags));
-        const uint32_t fields = surface_sample_fields(flags);
-        NRSCHK(sample_begin(fields));
-        uint64_t m = 0;
-        NRSCHK(surface_check_lattice(lattice, &m));
-        SampleLattice L;
-        SurfaceInput in;
-        for (int a = 0; a < 3; ++a) {
-            in.L.origin[a] = L.origin[a] = lattice->origin[a];
-            in.L.spacing[a] = L.spacing[a] = lattice->spacing[a];
-            in.L.dims[a] = L.dims[a] = lattice->dims[a];
-        }
-        sm.last = SampleLast();
-        NRSCHK(sample_run(nullptr, L, m, fields));
-        sm.last = SampleLast{true, fields, m};
-        in.nodes = m;
-        in.iso = iso;
-        in.precision = (int)(8 * sizeof(R));
-        in.dens = sm.result(NRS_FIELD_DENSITY);
-        in.grad = (flags & NRS_SURFACE_GRADIENT) ? sm.result(NRS_FIELD_GRADIENT) : nullptr;
-        in.vel = (flags & NRS_SURFACE_VELOCITY) ? sm.result(NRS_FIELD_VELOCITY) : nullptr;
-        sf.last = SurfaceLast();
-        uint64_t V = 0, T = 0;
-        NRSCHK(sf.extract(in, stream, &V, &T));
-        sf.last = SurfaceLast{true, flags, V, T};
-        if (vertices) *vertices = V;
-        if (triangles) *triangles = T;
-        return NRS_OK;
+        NRSCHK(surface_check_call(iso, flags)); // (its refusals come before the state check's)
+        NRSCHK(validate("nrs_sample_*"));
+        return rd.surface_extract(fluid_now(), lattice, iso, flags, vertices, triangles);
     }
-    int surface_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override
-    {
-        NRSCHK(surface_route_result(sf.last, which, (int)(8 * sizeof(R)), bytes));
-        *dptr = *bytes ? sf.result(which) : nullptr;
-        return NRS_OK;
-    }
-    int surface_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override
-    {
-        void *p = nullptr;
-        uint64_t sz = 0;
-        NRSCHK(surface_device_ptr(which, &p, &sz));
-        if (outBytes) *outBytes = sz;
-        if (!dst) return NRS_OK;
-        if (dstBytes < sz) return fail(NRS_E_INVALID, "destination too small");
-        if (!sz) return NRS_OK;
-        HIPCHK(hipMemcpyAsync(dst, p, sz, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return NRS_OK;
-    }
-    int surface_release() override
-    {
-        HIPCHK(hipStreamSynchronize(stream)); // a queued emit may still write the buffers
-        sf.release();
-        return NRS_OK;
-    }
-
-    // ---- diffuse particles (include/nereus_hip.h; DESIGN.md "Diffuse particles") -----------------------------------------------------------
-    // The sampler's particle grid (sm's sorted fluid and cell table, its cache rule and build count — its result arrays and `last` are not
-    // touched), then the launches of df (nrs_diffuse.h) on its views.  The set's buffers are df's.  Nothing a step owns is written.
-    DiffuseSystem df;
-    int diffuse_configure(const nrs_diffuse_config *c) override
-    {
-        NRSCHK(validate("nrs_diffuse_configure"));
-        NRSCHK(diffuse_check_config(c));
-        if (exch.on()) return fail(NRS_E_INVALID, "diffuse particles on a slab context (its arrays hold halo copies)");
-        df.configure(*c);
-        return NRS_OK;
-    }
-    int diffuse_step(double dt) override
-    {
-        NRSCHK(validate("nrs_diffuse_step"));
-        NRSCHK(diffuse_check_dt(dt));
-        NRSCHK(diffuse_refusal(sample_facts(), df.last.configured));
-        NRSCHK(diffuse_check_births(n, df.cfg.max_per_particle));
-        const SampleKey key{stepsDone, particleGen, gridGen, boundaryGen};
-        if (sm.cache.needs_build(key)) {
-            NRSCHK(sm.template build_grid<R>(P, posA.as<T4>(), velA.as<T4>(), n, stream));
-            sm.cache.built(key);
-        }
-        GridView<R> G;
-        std::memset(&G, 0, sizeof(G));
-        G.cellStart = sm.cell_start(); G.cellEnd = sm.cell_end();
-        G.nSorted = sm.sorted_count();
-        G.err = sm.err_word();
-        G.actLo = INT_MIN; G.actHi = INT_MAX;
-        return df.template step<R, KSET>(P, G, sm.template sorted_pos<T4>(), sm.template sorted_vel<T4>(), sm.sorted_count(),
-                                         dt == 0.0 ? P.timestep : (R)dt, stream);
-    }
+    int surface_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override { return rd.surface_device_ptr(which, dptr, bytes); }
+    int surface_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override { return rd.surface_result(which, dst, dstBytes, outBytes, stream); }
+    int surface_release() override { return rd.release(rd.sf, stream); }
+    int diffuse_configure(const nrs_diffuse_config *c) override { NRSCHK(validate("nrs_diffuse_configure")); return rd.diffuse_configure(fluid_now(), c); }
+    int diffuse_step(double dt) override { NRSCHK(validate("nrs_diffuse_step")); return rd.diffuse_step(fluid_now(), dt); }
     int diffuse_count(uint64_t *alive, uint64_t *byKind, uint64_t *dropped) override
     {
         NRSCHK(validate("nrs_diffuse_count"));
-        if (!df.last.configured) return fail(NRS_E_STATE, "diffuse particles before nrs_diffuse_configure");
-        return df.count(stream, alive, byKind, dropped);
+        return rd.diffuse_count(stream, alive, byKind, dropped);
     }
-    int diffuse_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override
-    {
-        NRSCHK(diffuse_route_check(df.last, which));
-        uint64_t alive = 0;
-        if (!diffuse_per_fluid(which)) NRSCHK(df.alive_now(stream, &alive));
-        NRSCHK(diffuse_route_result(df.last, which, alive, (int)(8 * sizeof(R)), bytes));
-        *dptr = *bytes ? df.result(which) : nullptr;
-        return NRS_OK;
-    }
-    int diffuse_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override
-    {
-        void *p = nullptr;
-        uint64_t sz = 0;
-        NRSCHK(diffuse_device_ptr(which, &p, &sz));
-        if (outBytes) *outBytes = sz;
-        if (!dst) return NRS_OK;
-        if (dstBytes < sz) return fail(NRS_E_INVALID, "destination too small");
-        if (!sz) return NRS_OK;
-        uint32_t e = 0;
-        HIPCHK(hipMemcpyAsync(dst, p, sz, hipMemcpyDeviceToHost, stream));
-        if (sm.err_word()) HIPCHK(hipMemcpyAsync(&e, sm.err_word(), 4, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (!e) return NRS_OK;
-        HIPCHK(hipMemsetAsync(sm.err_word(), 0, 4, stream));
-        return fail(NRS_E_STATE, "diffuse particles: a cell range of the sampler's table lies outside its sorted particles; the walks skipped it, the results are invalid");
-    }
+    int diffuse_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override { return rd.diffuse_device_ptr(which, dptr, bytes, stream); }
+    int diffuse_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override { return rd.diffuse_result(which, dst, dstBytes, outBytes, stream); }
     int diffuse_upload(const void *pos4, const void *vel4, uint64_t count) override
     {
         NRSCHK(validate("nrs_diffuse_upload"));
-        if (!df.last.configured) {
-            if (exch.on()) return fail(NRS_E_INVALID, "diffuse particles on a slab context (its arrays hold halo copies)");
-            return fail(NRS_E_STATE, "diffuse particles before nrs_diffuse_configure");
-        }
-        NRSCHK(diffuse_check_upload(pos4, vel4, count, df.cfg.capacity));
-        return df.template upload<R>(pos4, vel4, count, stream);
+        return rd.diffuse_upload(fluid_now(), pos4, vel4, count);
     }
-    int diffuse_release() override
-    {
-        HIPCHK(hipStreamSynchronize(stream)); // a queued step may still use the buffers
-        df.release();
-        return NRS_OK;
-    }
+    int diffuse_release() override { return rd.release(rd.df, stream); }
 
     // ---- sources and sinks (include/nereus_hip.h; DESIGN.md "Sources and sinks") ----------------------------------------------------------------
     // The slots, the sink configuration, the counts and the cull's buffers are inflow's (nrs_inflow.h); the arrays, the count and the state
@@ -1824,9 +1630,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         uint64_t m = 0;
         NRSCHK(inflow_check_block(lattice, vel, n, cap, &m));
         NRSCHK(inflow_refusal(false, midStep, iisphPhase != 0, true));
-        SampleLattice L;
-        for (int a = 0; a < 3; ++a) { L.origin[a] = lattice->origin[a]; L.spacing[a] = lattice->spacing[a]; L.dims[a] = lattice->dims[a]; }
-        NRSCHK(inflow.template emit_block<R>(L, vel, (uint32_t)m, emit_out(), stream));
+        NRSCHK(inflow.template emit_block<R>(lattice_from(*lattice), vel, (uint32_t)m, emit_out(), stream));
         n += m;
         particles_changed();
         if (added) *added = m;

@@ -2,7 +2,7 @@
 // the counters, the living set (positions with lifetimes, velocities, kinds), its staging copy and survivor flags, the workgroup totals of
 // the two scans, and the per-fluid arrays of the last step (density gradients, potentials, births, parents' kinds).  Nothing is allocated
 // before the first step or upload; nrs_diffuse_release frees everything.  It stands beside the FieldSampler (nrs_field_sampler.h): the
-// context (nrs_ctx_impl.h) refuses what has to be refused, has the sampler build its particle grid and hands its views to step().  The
+// holder of both (nrs_readers.h) refuses what has to be refused, has the sampler build its particle grid and hands its views to step().  The
 // host decisions — what is accepted, sizes, which result an id means, the per-particle rules — are in nrs_host_diffuse.h.
 #pragma once
 #include "nrs_ctx_base.h"
@@ -58,7 +58,7 @@ struct DiffuseSystem {
         DiffuseHeader h = {};
         if (hdr.p) {
             NRSCHK(flush(stream));
-            hipLaunchKernelGGL(k_diffuse_kinds, dim3(1), dim3(DIFF_SCAN_BLOCK), 0, stream, (const uint32_t *)kind.as<uint32_t>(), hdr.as<DiffuseHeader>());
+            hipLaunchKernelGGL(k_diffuse_kinds, dim3(1), dim3(SCAN_BLOCK), 0, stream, (const uint32_t *)kind.as<uint32_t>(), hdr.as<DiffuseHeader>());
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(&h, hdr.p, sizeof(h), hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
@@ -101,14 +101,14 @@ struct DiffuseSystem {
             NRSCHK(normals.alloc(sizeof(T4) * (size_t)N)); NRSCHK(potentials.alloc(sizeof(T4) * (size_t)N));
             NRSCHK(births.alloc(4 * (size_t)N)); NRSCHK(parentKind.alloc(4 * (size_t)N)); NRSCHK(birthTot.alloc(4 * (size_t)nbF));
             const SampleOut<R> O{nullptr, normals.as<T4>(), nullptr, nullptr};
-            hipLaunchKernelGGL((k_sample_points<R, KSET, false>), dim3(nbF), dim3(BLOCK), 0, stream, P, G, sP, sV, sP, SampleLattice(), O,
+            hipLaunchKernelGGL((k_sample_points<R, KSET, false>), dim3(nbF), dim3(BLOCK), 0, stream, P, G, sP, sV, sP, Lattice(), O,
                                (uint32_t)NRS_FIELD_GRADIENT, N);
             const DiffuseFluidOut<R> F{potentials.as<T4>(), births.as<uint32_t>(), parentKind.as<uint32_t>(), birthTot.as<uint32_t>()};
             hipLaunchKernelGGL((k_diffuse_potentials<R, KSET>), dim3(nbF), dim3(BLOCK), 0, stream, P, G, sP, sV, (const T4 *)normals.as<T4>(), C, steps, dt, F, N);
         }
         hipLaunchKernelGGL((k_diffuse_advect<R, KSET>), dim3(nbD), dim3(BLOCK), 0, stream, P, G, sP, sV, C, dt, (const DiffuseHeader *)H, cur, staged,
                            flag.as<uint32_t>(), keepTot.as<uint32_t>());
-        hipLaunchKernelGGL(k_diffuse_scan, dim3(1), dim3(DIFF_SCAN_BLOCK), 0, stream, keepTot.as<uint32_t>(), nbD, birthTot.as<uint32_t>(), N ? nbF : 0u, cap, H);
+        hipLaunchKernelGGL(k_diffuse_scan, dim3(1), dim3(SCAN_BLOCK), 0, stream, keepTot.as<uint32_t>(), nbD, birthTot.as<uint32_t>(), N ? nbF : 0u, cap, H);
         hipLaunchKernelGGL((k_diffuse_compact<R>), dim3(nbD), dim3(BLOCK), 0, stream, (const uint32_t *)flag.as<uint32_t>(),
                            (const uint32_t *)keepTot.as<uint32_t>(), staged, cur, cap);
         if (N)

@@ -1,7 +1,7 @@
 // nrs_field_sampler.h — the owner of everything the field sampler keeps on the device (DESIGN.md "Field sampling"): its (hash, index)
 // pairs and sort workspace, its sorted copy of the fluid's positions and velocities, its own fluid cell table, the uploaded query
 // points and the four result arrays.  Nothing is allocated before the first sample call; everything grows as needed and
-// nrs_sample_release frees it.  It depends on neither the solver nor the kernel set: the context (nrs_ctx_impl.h) holds one, tells it
+// nrs_sample_release frees it.  It depends on neither the solver nor the kernel set: FluidReaders (nrs_readers.h) holds one, tells it
 // the particle state to build from (build_grid) and launches the gather (nrs_kernels_sample.h) on its views.
 //
 // It READS the context's current positions and velocities and writes only its own buffers: the context's cell table, sort stage and

@@ -1,7 +1,7 @@
 // nrs_host_sample.h — the host decisions of the field sampler (include/nereus_hip.h "field sampling"; DESIGN.md "Field sampling"): which
 // flags and lattices are accepted, how many nodes a lattice has, how many bytes a result takes, when a context refuses to
 // sample, when the sampler's particle grid has to be rebuilt, and which result of the last call a field id means.  No HIP: plain facts
-// in, a size or a refusal out.  The owner of the device buffers (FieldSampler, nrs_field_sampler.h) and the context launch, then name
+// in, a size or a refusal out.  The owner of the device buffers (FieldSampler, nrs_field_sampler.h) and its holder (nrs_readers.h) launch, then name
 // what happened.
 #pragma once
 #include <cmath>
@@ -48,6 +48,17 @@ static inline int sample_check_lattice(const nrs_lattice *L, uint64_t *nodes)
     if (n > SAMPLE_MAX_QUERIES) return fail(NRS_E_INVALID, "lattice has more than 2^31 nodes");
     if (nodes) *nodes = n;
     return NRS_OK;
+}
+// a validated nrs_lattice as the kernels and the host routines of the sampler, the surface extraction and nrs_emit_block get it
+struct Lattice {
+    double origin[3], spacing[3];
+    uint32_t dims[3];
+};
+static inline Lattice lattice_from(const nrs_lattice &l)
+{
+    Lattice L;
+    for (int a = 0; a < 3; ++a) { L.origin[a] = l.origin[a]; L.spacing[a] = l.spacing[a]; L.dims[a] = l.dims[a]; }
+    return L;
 }
 
 // ---- bytes of a result: `field` is ONE output flag, m the queries of the call, precision 32 or 64; 0 for anything else ------------------

@@ -75,16 +75,12 @@ static inline int surface_route_result(const SurfaceLast &last, uint32_t which, 
     return NRS_OK;
 }
 
-// ---- the lattice as the routines get it (nrs_lattice, validated) --------------------------------------------------------------------------
-struct SurfLattice {
-    double origin[3], spacing[3];
-    uint32_t dims[3];
-};
+// ---- the lattice as the routines get it (Lattice, nrs_host_sample.h) ------------------------------------------------------------------------
 // coordinate `a` of the node with index idx on that axis: (R)(origin + idx * spacing), product and sum in double, one rounding to R
 // (the sampler's lattice_node)
-template <typename R> NRS_SURF_HD R surf_node_coord(const SurfLattice &L, int a, uint32_t idx) { return (R)(L.origin[a] + (double)idx * L.spacing[a]); }
+template <typename R> NRS_SURF_HD R surf_node_coord(const Lattice &L, int a, uint32_t idx) { return (R)(L.origin[a] + (double)idx * L.spacing[a]); }
 // which of the three + neighbours of node (i, j, k) exist: bit a set when idx[a] + 1 < dims[a]; 7: the node is the low corner of a cell
-NRS_SURF_HD uint32_t surf_have(const SurfLattice &L, uint32_t i, uint32_t j, uint32_t k)
+NRS_SURF_HD uint32_t surf_have(const Lattice &L, uint32_t i, uint32_t j, uint32_t k)
 {
     return (i + 1u < L.dims[0] ? 1u : 0u) | (j + 1u < L.dims[1] ? 2u : 0u) | (k + 1u < L.dims[2] ? 4u : 0u);
 }

@@ -1,8 +1,8 @@
 // nrs_inflow.h — the owner of what the sources and sinks keep (DESIGN.md "Sources and sinks"): the emitter slots with their
 // accumulators and counts, the sink configuration and its counts on the host; on the device the workgroup totals of the cull, its
-// header, and the row tables of disc emitters.  Nothing is allocated before the first cull or the first emission of a disc.  It stands
-// beside the FieldSampler and the DiffuseSystem: the context (nrs_ctx_impl.h) refuses what has to be refused, hands over its arrays
-// and applies what a call reports (the new count, the pointer swap, the state transition).  The host decisions are nrs_host_inflow.h's.
+// header, and the row tables of disc emitters.  Nothing is allocated before the first cull or the first emission of a disc.  Unlike
+// the add-ons that only read the particles (nrs_readers.h) it is the context's own member: the context (nrs_ctx_impl.h) refuses what has
+// to be refused, hands over its arrays and applies what a call reports (the new count, the pointer swap, the state transition).  The host decisions are nrs_host_inflow.h's.
 #pragma once
 #include "nrs_ctx_base.h"
 #include "nrs_host_inflow.h"
@@ -52,7 +52,7 @@ struct InflowSystem {
         NRSCHK(blockTot.alloc(4 * (size_t)nb));
         NRSCHK(hdr.alloc(sizeof(InflowHeader)));
         hipLaunchKernelGGL((k_cull_count<R>), dim3(nb), dim3(BLOCK), 0, stream, pos, B, n, blockTot.as<uint32_t>());
-        hipLaunchKernelGGL(k_cull_scan, dim3(1), dim3(DIFF_SCAN_BLOCK), 0, stream, blockTot.as<uint32_t>(), nb, hdr.as<InflowHeader>());
+        hipLaunchKernelGGL(k_cull_scan, dim3(1), dim3(SCAN_BLOCK), 0, stream, blockTot.as<uint32_t>(), nb, hdr.as<InflowHeader>());
         HIPCHK(hipGetLastError());
         InflowHeader h = {};
         HIPCHK(hipMemcpyAsync(&h, hdr.p, sizeof(h), hipMemcpyDeviceToHost, stream));
@@ -99,7 +99,7 @@ struct InflowSystem {
         return NRS_OK;
     }
     // nrs_emit_block: the m nodes of L behind O.first; enqueues
-    template <typename R> int emit_block(const SampleLattice &L, const double vel[3], uint32_t m, EmitOut<R> O, hipStream_t stream)
+    template <typename R> int emit_block(const Lattice &L, const double vel[3], uint32_t m, EmitOut<R> O, hipStream_t stream)
     {
         hipLaunchKernelGGL((k_inflow_block<R>), dim3(nblocks(m)), dim3(BLOCK), 0, stream, L, vel[0], vel[1], vel[2], m, O);
         HIPCHK(hipGetLastError());

@@ -14,6 +14,7 @@
 #pragma once
 #include "nrs_host_diffuse.h"
 #include "nrs_kernels_sample.h"
+#include "nrs_scan.h"
 
 namespace nrs {
 
@@ -26,38 +27,7 @@ struct DiffuseHeader {
     uint32_t pad;
 };
 
-constexpr int DIFF_SCAN_BLOCK = 1024; // threads of the one scanning workgroup
-
 template <typename R> NRS_DEV D3<R> d3(V3<R> a) { D3<R> d; d.x = a.x; d.y = a.y; d.z = a.z; return d; }
-
-// inclusive scan over the 64 lanes of a wave; exclusive scan over the BLOCK threads of a workgroup (wsum: BLOCK / 64 words of LDS; every
-// thread calls it); the sum over the workgroup in thread 0
-NRS_DEV uint32_t diff_wave_scan(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-template <int NT> NRS_DEV uint32_t diff_block_scan(uint32_t v, uint32_t *wsum, uint32_t *total)
-{
-    const uint32_t incl = diff_wave_scan(v), w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 63u) wsum[w] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < NT / 64; ++i) {
-        const uint32_t s = wsum[i];
-        before += i < w ? s : 0u;
-        all += s;
-    }
-    __syncthreads(); // (wsum may be used again)
-    if (total) *total = all;
-    return before + incl - v;
-}
 
 // ---- 1. potentials and births per sorted fluid particle ---------------------------------------------------------------------------------
 template <typename R> struct DiffuseFluidOut {
@@ -142,7 +112,7 @@ __global__ __launch_bounds__(BLOCK) void k_diffuse_potentials(Params<R> P, GridV
         O.parentKind[i] = diffuse_kind(cnt, C.sprayBelow, C.bubbleAbove);
     }
     uint32_t total;
-    diff_block_scan<BLOCK>(births, wsum, &total);
+    block_scan<BLOCK>(births, wsum, &total);
     if (threadIdx.x == 0) O.blockTot[blockIdx.x] = total;
 }
 
@@ -186,31 +156,17 @@ __global__ __launch_bounds__(BLOCK) void k_diffuse_advect(Params<R> P, GridView<
         flag[d] = keep;
     }
     uint32_t total;
-    diff_block_scan<BLOCK>(keep, wsum, &total);
+    block_scan<BLOCK>(keep, wsum, &total);
     if (threadIdx.x == 0) blockTot[blockIdx.x] = total;
 }
 
 // ---- 3. both scans and the header --------------------------------------------------------------------------------------------------------------
-// exclusive scan of tot[0 .. nb) in place by the whole workgroup; returns the total in every thread
-NRS_DEV uint32_t diff_scan_list(uint32_t *__restrict__ tot, uint32_t nb, uint32_t *wsum)
-{
-    uint32_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += DIFF_SCAN_BLOCK) {
-        const uint32_t idx = base + threadIdx.x;
-        const uint32_t v = idx < nb ? tot[idx] : 0u;
-        uint32_t all;
-        const uint32_t ex = diff_block_scan<DIFF_SCAN_BLOCK>(v, wsum, &all);
-        if (idx < nb) tot[idx] = carry + ex;
-        carry += all;
-    }
-    return carry;
-}
-static __global__ __launch_bounds__(DIFF_SCAN_BLOCK) void k_diffuse_scan(uint32_t *__restrict__ keepTot, uint32_t nbKeep, uint32_t *__restrict__ birthTot,
+static __global__ __launch_bounds__(SCAN_BLOCK) void k_diffuse_scan(uint32_t *__restrict__ keepTot, uint32_t nbKeep, uint32_t *__restrict__ birthTot,
                                                                   uint32_t nbBirth, uint32_t capacity, DiffuseHeader *__restrict__ hdr)
 {
-    __shared__ uint32_t wsum[DIFF_SCAN_BLOCK / 64];
-    const uint32_t S = diff_scan_list(keepTot, nbKeep, wsum);
-    const uint32_t B = diff_scan_list(birthTot, nbBirth, wsum);
+    __shared__ uint32_t wsum[SCAN_BLOCK / 64];
+    const uint32_t S = scan_list(keepTot, nbKeep, wsum);
+    const uint32_t B = scan_list(birthTot, nbBirth, wsum);
     if (threadIdx.x == 0) {
         const uint64_t all = (uint64_t)S + B;
         const uint32_t alive = all < capacity ? (uint32_t)all : capacity;
@@ -228,7 +184,7 @@ __global__ __launch_bounds__(BLOCK) void k_diffuse_compact(const uint32_t *__res
     __shared__ uint32_t wsum[BLOCK / 64];
     const uint32_t d = blockIdx.x * BLOCK + threadIdx.x;
     const uint32_t keep = d < capacity ? flag[d] : 0u;
-    const uint32_t to = blockOff[blockIdx.x] + diff_block_scan<BLOCK>(keep, wsum, nullptr);
+    const uint32_t to = blockOff[blockIdx.x] + block_scan<BLOCK>(keep, wsum);
     if (!keep) return;
     cur.pos[to] = staged.pos[d]; // (to <= d: the staging arrays are read, the set is written)
     cur.vel[to] = staged.vel[d];
@@ -246,7 +202,7 @@ __global__ __launch_bounds__(BLOCK) void k_diffuse_births(Params<R> P, const typ
     __shared__ uint32_t wsum[BLOCK / 64];
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     const uint32_t b = i < n ? births[i] : 0u;
-    const uint64_t first = (uint64_t)hdr->survivors + blockOff[blockIdx.x] + diff_block_scan<BLOCK>(b, wsum, nullptr);
+    const uint64_t first = (uint64_t)hdr->survivors + blockOff[blockIdx.x] + block_scan<BLOCK>(b, wsum);
     if (!b || first >= C.capacity) return;
     const D3<R> xi = d3<R>(xyz<R>(sPos[i])), vi = d3<R>(xyz<R>(sVel[i]));
     const uint32_t kind = parentKind[i];
@@ -267,17 +223,17 @@ static __global__ void k_diffuse_header(DiffuseHeader *hdr, uint32_t alive, int 
     if (clearDropped) hdr->dropped = 0ull;
 }
 // nrs_diffuse_count: the living particles per kind, one workgroup, integer sums
-static __global__ __launch_bounds__(DIFF_SCAN_BLOCK) void k_diffuse_kinds(const uint32_t *__restrict__ kind, DiffuseHeader *__restrict__ hdr)
+static __global__ __launch_bounds__(SCAN_BLOCK) void k_diffuse_kinds(const uint32_t *__restrict__ kind, DiffuseHeader *__restrict__ hdr)
 {
-    __shared__ uint32_t wsum[DIFF_SCAN_BLOCK / 64];
+    __shared__ uint32_t wsum[SCAN_BLOCK / 64];
     const uint32_t n = hdr->alive;
     uint32_t c[3] = {0u, 0u, 0u};
-    for (uint32_t d = threadIdx.x; d < n; d += DIFF_SCAN_BLOCK) {
+    for (uint32_t d = threadIdx.x; d < n; d += SCAN_BLOCK) {
         const uint32_t k = kind[d];
         c[0] += k == 0u; c[1] += k == 1u; c[2] += k == 2u;
     }
     uint32_t tot[3];
-    for (int a = 0; a < 3; ++a) diff_block_scan<DIFF_SCAN_BLOCK>(c[a], wsum, &tot[a]);
+    for (int a = 0; a < 3; ++a) block_scan<SCAN_BLOCK>(c[a], wsum, &tot[a]);
     if (threadIdx.x == 0) { hdr->byKind[0] = tot[0]; hdr->byKind[1] = tot[1]; hdr->byKind[2] = tot[2]; }
 }
 

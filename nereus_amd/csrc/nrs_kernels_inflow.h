@@ -5,7 +5,8 @@
 // workgroups: every offset comes from a scan, every output is bit-reproducible.
 #pragma once
 #include "nrs_host_inflow.h"
-#include "nrs_kernels_diffuse.h" // diff_block_scan, diff_scan_list
+#include "nrs_kernels_sample.h" // lattice_node
+#include "nrs_scan.h"
 
 namespace nrs {
 
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(BLOCK) void k_inflow_emit(EmitArgs A, const int32_t
     emit_store<R>(O, t, x[0], x[1], x[2], (R)A.v[0], (R)A.v[1], (R)A.v[2]);
 }
 // nrs_emit_block: one thread per node of L in its linear index order
-template <typename R> __global__ __launch_bounds__(BLOCK) void k_inflow_block(SampleLattice L, double vx, double vy, double vz, uint32_t m, EmitOut<R> O)
+template <typename R> __global__ __launch_bounds__(BLOCK) void k_inflow_block(Lattice L, double vx, double vy, double vz, uint32_t m, EmitOut<R> O)
 {
     const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
     if (q >= m) return;
@@ -84,10 +85,10 @@ __global__ __launch_bounds__(BLOCK) void k_cull_count(const typename Vec4T<R>::t
     }
 }
 // 2. one workgroup: the exclusive scan of the totals in place, the survivor count into the header
-static __global__ __launch_bounds__(DIFF_SCAN_BLOCK) void k_cull_scan(uint32_t *__restrict__ blockTot, uint32_t nb, InflowHeader *__restrict__ hdr)
+static __global__ __launch_bounds__(SCAN_BLOCK) void k_cull_scan(uint32_t *__restrict__ blockTot, uint32_t nb, InflowHeader *__restrict__ hdr)
 {
-    __shared__ uint32_t wsum[DIFF_SCAN_BLOCK / 64];
-    const uint32_t S = diff_scan_list(blockTot, nb, wsum);
+    __shared__ uint32_t wsum[SCAN_BLOCK / 64];
+    const uint32_t S = scan_list(blockTot, nb, wsum);
     if (threadIdx.x == 0) hdr->survivors = S;
 }
 // 3. the survivors move, in order: the predicate again, a scan inside the workgroup, the workgroup's offset from the scanned totals
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(BLOCK) void k_cull_compact(CullArrays<R> A, CullBou
         p = A.pos[i];
         keep = inflow_caught<R>(B, p.x, p.y, p.z) ? 0u : 1u;
     }
-    const uint32_t to = blockOff[blockIdx.x] + diff_block_scan<BLOCK>(keep, wsum, nullptr);
+    const uint32_t to = blockOff[blockIdx.x] + block_scan<BLOCK>(keep, wsum);
     if (!keep) return;
     A.posTo[to] = p; // (to <= i < n)
     A.velTo[to] = A.vel[i];

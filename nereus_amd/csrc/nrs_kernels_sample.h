@@ -8,17 +8,13 @@
 // unwrapped neighbourhood z, y, x ascending; in a cell the sorted slots ascending; with walls a cell's boundary particles after its
 // fluid particles.
 #pragma once
+#include "nrs_host_sample.h"
 #include "nrs_kernels_ref.h"
 
 namespace nrs {
 
-// a lattice as the kernels get it (nrs_lattice, validated by sample_check_lattice)
-struct SampleLattice {
-    double origin[3], spacing[3];
-    uint32_t dims[3];
-};
-// node (i, j, k): (R)(origin + idx * spacing), product and sum in double, one rounding to R
-template <typename R> NRS_DEV V3<R> lattice_node(const SampleLattice &L, uint32_t i, uint32_t j, uint32_t k)
+// node (i, j, k) of a lattice (Lattice, nrs_host_sample.h): (R)(origin + idx * spacing), product and sum in double, one rounding to R
+template <typename R> NRS_DEV V3<R> lattice_node(const Lattice &L, uint32_t i, uint32_t j, uint32_t k)
 {
     return mk3<R>((R)(L.origin[0] + (double)i * L.spacing[0]), (R)(L.origin[1] + (double)j * L.spacing[1]), (R)(L.origin[2] + (double)k * L.spacing[2]));
 }
@@ -126,7 +122,7 @@ template <typename R> NRS_DEV void sample_store(const SampleOut<R> &O, uint32_t 
 template <typename R, int KSET, bool HAS_B>
 __global__ __launch_bounds__(BLOCK) void k_sample_points(Params<R> P, GridView<R> G, const typename Vec4T<R>::type *__restrict__ sPos,
                                                          const typename Vec4T<R>::type *__restrict__ sVel,
-                                                         const typename Vec4T<R>::type *__restrict__ points, SampleLattice L,
+                                                         const typename Vec4T<R>::type *__restrict__ points, Lattice L,
                                                          SampleOut<R> O, uint32_t fields, uint32_t m)
 {
     const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;

@@ -11,11 +11,11 @@
 #include <hip/hip_runtime.h>
 
 #include "nrs_host_surface.h"
+#include "nrs_scan.h"
 
 namespace nrs {
 
-constexpr int SURF_BLOCK = 256;      // nodes per workgroup of the three lattice kernels (4 waves)
-constexpr int SURF_SCAN_BLOCK = 1024; // threads of the one scanning workgroup
+constexpr int SURF_BLOCK = 256; // nodes per workgroup of the three lattice kernels (4 waves)
 
 template <typename R> struct SurfVec4;
 template <> struct SurfVec4<float> { typedef float4 type; };
@@ -23,7 +23,7 @@ template <> struct SurfVec4<double> { typedef double4 type; };
 
 // node q of the lattice: indices, which + neighbours exist, and the eight densities of its cell's corners (only the existing ones are read)
 struct SurfNodeIdx { uint32_t i, j, k, have; };
-__device__ __forceinline__ SurfNodeIdx surf_node_idx(const SurfLattice &L, uint32_t q)
+__device__ __forceinline__ SurfNodeIdx surf_node_idx(const Lattice &L, uint32_t q)
 {
     SurfNodeIdx n;
     n.i = q % L.dims[0];
@@ -34,43 +34,19 @@ __device__ __forceinline__ SurfNodeIdx surf_node_idx(const SurfLattice &L, uint3
     return n;
 }
 // linear offset of the node at direction code d from a node
-__device__ __forceinline__ uint32_t surf_dir_offset(const SurfLattice &L, uint32_t d)
+__device__ __forceinline__ uint32_t surf_dir_offset(const Lattice &L, uint32_t d)
 {
     return (d & 1u) + ((d >> 1) & 1u) * L.dims[0] + ((d >> 2) & 1u) * L.dims[0] * L.dims[1];
 }
-template <typename R> __device__ __forceinline__ void surf_load(const R *__restrict__ dens, const SurfLattice &L, uint32_t q, uint32_t have, R f[8])
+template <typename R> __device__ __forceinline__ void surf_load(const R *__restrict__ dens, const Lattice &L, uint32_t q, uint32_t have, R f[8])
 {
 #pragma unroll
     for (uint32_t d = 0; d < 8; ++d) f[d] = (d & ~have) ? (R)0 : dens[q + surf_dir_offset(L, d)];
 }
 
-// inclusive scan over the 64 lanes of a wave
-__device__ __forceinline__ uint32_t surf_wave_scan(uint32_t v)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-// exclusive scan of v over the SURF_BLOCK threads of a workgroup (wsum: SURF_BLOCK / 64 words of LDS); every thread calls it
-__device__ __forceinline__ uint32_t surf_block_scan(uint32_t v, uint32_t *wsum)
-{
-    const uint32_t incl = surf_wave_scan(v), w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 63u) wsum[w] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < SURF_BLOCK / 64; ++i) before += i < w ? wsum[i] : 0u;
-    __syncthreads(); // (wsum may be used again)
-    return before + incl - v;
-}
-
 // ---- 1. mark and reduce ---------------------------------------------------------------------------------------------------------------------
 template <typename R>
-__global__ __launch_bounds__(SURF_BLOCK) void k_surf_count(const R *__restrict__ dens, SurfLattice L, R iso, uint32_t nodes, uint2 *__restrict__ blockTot)
+__global__ __launch_bounds__(SURF_BLOCK) void k_surf_count(const R *__restrict__ dens, Lattice L, R iso, uint32_t nodes, uint2 *__restrict__ blockTot)
 {
     __shared__ uint32_t wsum[SURF_BLOCK / 64];
     const uint32_t q = blockIdx.x * SURF_BLOCK + threadIdx.x;
@@ -96,29 +72,11 @@ __global__ __launch_bounds__(SURF_BLOCK) void k_surf_count(const R *__restrict__
 }
 
 // ---- 2. exclusive scan of the nb workgroup totals, in place; tot[nb] = (V, T) ------------------------------------------------------------------
-__global__ __launch_bounds__(SURF_SCAN_BLOCK) void k_surf_scan(uint2 *__restrict__ tot, uint32_t nb)
+__global__ __launch_bounds__(SCAN_BLOCK) void k_surf_scan(uint2 *__restrict__ tot, uint32_t nb)
 {
-    __shared__ uint2 wsum[SURF_SCAN_BLOCK / 64];
-    uint2 carry = make_uint2(0u, 0u); // the same in every thread
-    const uint32_t w = threadIdx.x >> 6;
-    for (uint32_t base = 0; base < nb; base += SURF_SCAN_BLOCK) {
-        const uint32_t idx = base + threadIdx.x;
-        const uint2 v = idx < nb ? tot[idx] : make_uint2(0u, 0u);
-        const uint2 incl = make_uint2(surf_wave_scan(v.x), surf_wave_scan(v.y));
-        if ((threadIdx.x & 63u) == 63u) wsum[w] = incl;
-        __syncthreads();
-        uint2 before = carry, all = carry;
-#pragma unroll
-        for (uint32_t i = 0; i < SURF_SCAN_BLOCK / 64; ++i) {
-            const uint2 s = wsum[i];
-            if (i < w) { before.x += s.x; before.y += s.y; }
-            all.x += s.x; all.y += s.y;
-        }
-        if (idx < nb) tot[idx] = make_uint2(before.x + incl.x - v.x, before.y + incl.y - v.y);
-        carry = all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tot[nb] = carry;
+    __shared__ uint2 wsum[SCAN_BLOCK / 64];
+    const uint2 all = scan_list(tot, nb, wsum);
+    if (threadIdx.x == 0) tot[nb] = all;
 }
 
 // ---- 3. vertex emit -------------------------------------------------------------------------------------------------------------------------------
@@ -136,7 +94,7 @@ template <typename T4, typename R> __device__ __forceinline__ T4 surf_lerp4(cons
 }
 template <typename R>
 __global__ __launch_bounds__(SURF_BLOCK) void k_surf_vertices(const R *__restrict__ dens, const typename SurfVec4<R>::type *__restrict__ sGrad,
-                                                              const typename SurfVec4<R>::type *__restrict__ sVel, SurfLattice L, R iso, uint32_t nodes,
+                                                              const typename SurfVec4<R>::type *__restrict__ sVel, Lattice L, R iso, uint32_t nodes,
                                                               const uint2 *__restrict__ blockOff, SurfVertexOut<R> O)
 {
     typedef typename SurfVec4<R>::type T4;
@@ -151,7 +109,7 @@ __global__ __launch_bounds__(SURF_BLOCK) void k_surf_vertices(const R *__restric
         surf_load<R>(dens, L, q, n.have, f);
         mask = surf_node_mask(surf_inside_bits<R>(f, iso, n.have), n.have);
     }
-    const uint32_t first = blockOff[blockIdx.x].x + surf_block_scan(surf_popcount(mask), wsum);
+    const uint32_t first = blockOff[blockIdx.x].x + block_scan<SURF_BLOCK>(surf_popcount(mask), wsum);
     if (!live) return;
     O.nodeOff[q] = first;
     O.nodeMask[q] = (uint8_t)mask;
@@ -179,7 +137,7 @@ __global__ __launch_bounds__(SURF_BLOCK) void k_surf_vertices(const R *__restric
 
 // ---- 4. triangle emit ---------------------------------------------------------------------------------------------------------------------------------
 template <typename R>
-__global__ __launch_bounds__(SURF_BLOCK) void k_surf_triangles(const R *__restrict__ dens, SurfLattice L, R iso, uint32_t nodes, const uint2 *__restrict__ blockOff,
+__global__ __launch_bounds__(SURF_BLOCK) void k_surf_triangles(const R *__restrict__ dens, Lattice L, R iso, uint32_t nodes, const uint2 *__restrict__ blockOff,
                                                                const uint32_t *__restrict__ nodeOff, const uint8_t *__restrict__ nodeMask, uint32_t *__restrict__ tri)
 {
     __shared__ uint32_t wsum[SURF_BLOCK / 64];
@@ -194,7 +152,7 @@ __global__ __launch_bounds__(SURF_BLOCK) void k_surf_triangles(const R *__restri
             count = surf_cell_count(bits);
         }
     }
-    const uint32_t first = blockOff[blockIdx.x].y + surf_block_scan(count, wsum);
+    const uint32_t first = blockOff[blockIdx.x].y + block_scan<SURF_BLOCK>(count, wsum);
     if (!count) return;
     // the vertex offsets and masks of the cell's eight corner nodes; corner 7 owns no edge of this cell
     uint32_t off[7], msk[7];

@@ -18,7 +18,7 @@ template <typename R> int SurfaceMesher::extract_t(const SurfaceInput &in, hipSt
     NRSCHK(nodeMask.alloc((size_t)nodes));
     uint2 *tot = blockTot.as<uint2>();
     hipLaunchKernelGGL((k_surf_count<R>), dim3(nb), dim3(SURF_BLOCK), 0, stream, dens, in.L, iso, nodes, tot);
-    hipLaunchKernelGGL(k_surf_scan, dim3(1), dim3(SURF_SCAN_BLOCK), 0, stream, tot, nb);
+    hipLaunchKernelGGL(k_surf_scan, dim3(1), dim3(SCAN_BLOCK), 0, stream, tot, nb);
     HIPCHK(hipGetLastError());
     uint32_t vt[2] = {0u, 0u};
     HIPCHK(hipMemcpyAsync(vt, tot + nb, sizeof(vt), hipMemcpyDeviceToHost, stream));

@@ -1,8 +1,8 @@
 // nrs_surface_mesher.h — the owner of everything the surface extraction keeps on the device (DESIGN.md "Surface extraction"): the
 // workgroup totals and their scan, the per-node vertex offsets and edge masks, and the mesh itself — vertices, triangles and the two
 // optional attribute arrays.  Nothing is allocated before the first extract; everything grows as needed and nrs_surface_release frees it.
-// It depends on neither the solver, the kernel set nor the sampler: the context (nrs_ctx_impl.h) holds one next to its FieldSampler
-// and hands it the device pointers of a sampled lattice.  nrs_surface.hip defines extract() and is the one translation unit that
+// It depends on neither the solver, the kernel set nor the sampler: the owner of the read-only add-ons (FluidReaders, nrs_readers.h) holds
+// one next to its FieldSampler and hands it the device pointers of a sampled lattice.  nrs_surface.hip defines extract() and is the one translation unit that
 // compiles the kernels (nrs_kernels_surface.h), for float and double; this header includes no kernel.  The host decisions — what is
 // accepted, sizes, which result an id means — are in nrs_host_surface.h.
 #pragma once
@@ -13,7 +13,7 @@ namespace nrs {
 
 // one sampled lattice on the device: SReal[nodes] density and, or null, SVec4[nodes] gradient / velocity (precision 32 or 64)
 struct SurfaceInput {
-    SurfLattice L;
+    Lattice L;
     uint64_t nodes;
     double iso;
     int precision;

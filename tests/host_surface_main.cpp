@@ -50,8 +50,7 @@ template <typename R> static int mesh(const nrs_lattice &lat, double isoD, std::
     uint64_t nodes64 = 0;
     const int rc = surface_check_lattice(&lat, &nodes64);
     if (rc != NRS_OK) { answer(rc); return 0; }
-    SurfLattice L;
-    for (int a = 0; a < 3; ++a) { L.origin[a] = lat.origin[a]; L.spacing[a] = lat.spacing[a]; L.dims[a] = lat.dims[a]; }
+    const Lattice L = lattice_from(lat);
     const uint32_t nodes = (uint32_t)nodes64, nx = L.dims[0], ny = L.dims[1];
     std::vector<R> dens(nodes);
     for (uint32_t q = 0; q < nodes; ++q) dens[q] = (R)num(in);

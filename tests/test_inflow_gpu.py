@@ -162,6 +162,48 @@ def test_compaction_shapes(double, ks):
     s.close()
 
 
+# 1026 workgroups of 256: the one scanning workgroup takes 1024 totals per pass, so its second pass starts from a carry
+N_CARRY = 1024 * 256 + 256 + 7
+CARRY_PATTERNS = {
+    "every_third": lambda i: i % 3 == 0,
+    "all_but_last": lambda i: i != N_CARRY - 1,
+    "workgroups_1023_1024": lambda i: (i >= 1023 * 256) & (i < 1025 * 256),  # the last of the first pass, the first of the second
+}
+
+
+@pytest.mark.parametrize("double,ks", BUILDS[::3], ids=BUILD_IDS[::3])
+def test_compaction_scan_carry(double, ks):
+    """test_compaction_shapes at a size whose workgroup totals need two passes of the scan; no step is taken"""
+    p, _ = small_dam_break((12, 10, 9), double=double, kernel_set=ks)
+    real = np.float64 if double else np.float32
+    idx = np.arange(N_CARRY)
+    rng = np.random.default_rng(5)
+    box = [0.5, 0.5, 0.5, 1.0, 1.0, 1.0]
+    s = capi.Solver(p, N_CARRY, double=double, kernel_set=ks)
+    s.sinks_set([box])
+    total, culls = 0, 0
+    for name, pat in CARRY_PATTERNS.items():
+        inside = pat(idx)
+        pos = np.ones((N_CARRY, 4), real)
+        pos[:, :3] = rng.uniform(0.0, 0.4, (N_CARRY, 3))
+        pos[inside, :3] = rng.uniform(0.5, 0.99, (int(inside.sum()), 3))
+        vel = rng.uniform(-1, 1, (N_CARRY, 4)).astype(real)
+        pres = rng.uniform(0, 1, N_CARRY).astype(real)
+        s.set_particles(pos, vel, pres)
+        gone = im.caught(p, pos, real, boxes=[box])
+        assert gone.sum() == inside.sum()
+        removed = s.cull()
+        want = im.compact(gone, pos, vel, pres)
+        got = s.download(pressure=True)
+        assert removed == int(gone.sum()) and s.n == N_CARRY - removed, (name, removed)
+        for a, b in zip(got, want):
+            assert a.tobytes() == b.tobytes(), name
+        total += removed
+        culls += 1
+        assert s.sinks_count() == (total, culls)
+    s.close()
+
+
 def test_compaction_moves_dfsph_kv():
     """after two DFSPH steps with the warm start, Kv is compacted like the positions"""
     p, sc = small_dam_break((12, 10, 9), solver=capi.DFSPH)

@@ -19,7 +19,7 @@ D, G, VEL = capi.FIELD_DENSITY, capi.FIELD_GRADIENT, capi.FIELD_VELOCITY
 ATTRS = capi.SURFACE_GRADIENT | capi.SURFACE_VELOCITY
 MESH = [capi.MESH_VERTICES, capi.MESH_TRIANGLES, capi.MESH_GRADIENT, capi.MESH_VELOCITY]
 NODES_PER_WORKGROUP = 256           # SURF_BLOCK of nrs_kernels_surface.h: the count, vertex and triangle kernels
-NODES_PER_SCAN_PASS = 1024 * 256    # SURF_SCAN_BLOCK workgroup totals per pass of the one scanning workgroup
+NODES_PER_SCAN_PASS = 1024 * 256    # SCAN_BLOCK workgroup totals per pass of the one scanning workgroup
 
 
 def fluid_lattice(pos, h, spacing, pad=2.0):
