@@ -674,6 +674,50 @@ int nrs_eval_smoothing(int precision, int which, uint64_t n, const void *r3, con
 int nrs_max_density(nrs_ctx *ctx, double *out);
 int nrs_max_velocity(nrs_ctx *ctx, double *out_speed);
 
+/* ---- anisotropic surface reconstruction (DESIGN.md "Anisotropic kernels"; Yu & Turk 2013; came without a version change) ------------------
+ * The raw SPH density of an under-dense scene dips below any usable iso value between the particles: its iso-surface is a foam of small
+ * closed surfaces.  Here the field the mesher is fed is a volume-normalised colour field (about 1 inside the fluid whatever the
+ * density) of kernels whose centres are smoothed towards the neighbourhood's weighted mean and which are stretched along the principal
+ * axes of the neighbourhood's covariance.  Geometry only: nothing depends on the kernel set, the particle mass or the rest density.
+ * Read-only for the simulation; it uses the sampler's particle grid (its cache rule, nrs_sample_builds) and the mesher unchanged.
+ * R is the build's real type, h = interactionRadius; r = (R)2 h, the largest centre shift is h / 2, the largest semi-axis 3 h / 2.
+ *
+ * Pass A, one record per fluid particle i in the sampler's sorted order.  Candidates: the fluid particles j of the 5 x 5 x 5 unwrapped
+ * cell neighbourhood of x_i (i included), cells z, y, x ascending, sorted slots ascending, one accumulator per component.  d = x_j - x_i
+ * per component in R, d2 = (dx dx + dy dy) + dz dz; j is a neighbour when d2 < r2 = r r; count = the neighbours.  w = 1 - (|d| / r)^3;
+ * Sw = sum w, M = sum w d, S = sum w d d^T, D = sum (r2 - d2)^3.  V_i = 1 / (k6 D), k6 = 315 / (64 pi r^9).  mu = M / Sw,
+ * delta = lambda mu, scaled to length h / 2 if longer; centre = x_i + delta.  C = S / Sw - mu mu^T = U diag(s1 >= s2 >= s3) U^T.  With
+ * count < n_eps or s1 not > 0 the semi-axes are a_k = k_n support; otherwise st_k = max(s_k, s1 / k_r) and
+ * a_k = support st_k / cbrt(st_1 st_2 st_3); then a_k = min(a_k, 3 h / 2).  G = U diag(1 / a_k) U^T, weight = (315 / (64 pi)) V_i /
+ * (a1 a2 a3), bound = max a_k.  A particle with a non-finite coordinate has count 0, weight 0, bound 0, G = 0.
+ *   NRS_ANISO_CENTER  SVec4[N]     centre, bound
+ *   NRS_ANISO_G       SVec4[2N]    (G00, G01, G02, G11), (G12, G22, weight, 0)
+ *   NRS_ANISO_COUNT   uint32_t[N]  neighbour count
+ *   NRS_ANISO_INDEX   uint32_t[N]  the particle's index in nrs_download order
+ * Pass B, the field at a lattice node x (the sampler's node rule): the same walk around x; d = x - centre_j, skipped unless
+ * d2 < bound_j^2; g = G_j d, q2 = g . g, skipped unless q2 < 1; p = 1 - q2.  phi = sum weight_j p^3; grad phi = sum -6 weight_j p^2 (G_j g);
+ * velocity = (sum (weight_j p^3) v_j) / phi with w = phi, all four components 0 where phi is 0.  A non-finite node gets zeros.
+ *
+ * nrs_aniso_config: NULL means support = h, lambda = 0.9, k_r = 4, k_n = 0.5, n_eps = 25; a support of 0 means h.
+ * nrs_aniso_build runs pass A (enqueues only; the records are recomputed on every call).  nrs_aniso_result copies ONE result to the
+ * host and waits (dst NULL: only the size); nrs_aniso_device_ptr gives its device address; the buffers are valid until the next build,
+ * nrs_aniso_release (frees only these buffers) or nrs_destroy.  nrs_surface_extract_aniso runs pass A, then pass B on the lattice INTO
+ * THE SAMPLER'S RESULT ARRAYS (NRS_FIELD_DENSITY holds phi; GRADIENT / VELOCITY with NRS_SURFACE_GRADIENT / _VELOCITY;
+ * nrs_sample_result afterwards returns exactly the lattice the mesh was cut from), then the mesher of nrs_surface_extract: the mesh
+ * comes back through nrs_surface_result / nrs_surface_device_ptr.  iso is a value of phi (0.5 is the usual choice).
+ *
+ * Refusals: everything nrs_sample_lattice and nrs_surface_extract refuse; NRS_E_INVALID for NRS_SURFACE_WALLS, a gridSize < 8 on some
+ * axis (the five cells of a row would alias through the wrap), support outside (0, 1.5 h], lambda outside [0, 1], k_r < 1, k_n outside
+ * (0, 1], a non-finite field, reserved != 0.  NRS_E_STATE: a result or pointer before any build or after nrs_aniso_release. */
+enum { NRS_ANISO_CENTER = 1, NRS_ANISO_G = 2, NRS_ANISO_COUNT = 4, NRS_ANISO_INDEX = 8 };
+typedef struct nrs_aniso_config { double support, lambda, k_r, k_n; uint32_t n_eps, reserved; } nrs_aniso_config;
+int nrs_aniso_build(nrs_ctx *ctx, const nrs_aniso_config *cfg);
+int nrs_aniso_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_bytes, uint64_t *out_bytes);
+int nrs_aniso_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes);
+int nrs_aniso_release(nrs_ctx *ctx);
+int nrs_surface_extract_aniso(nrs_ctx *ctx, const nrs_lattice *lattice, double iso, uint32_t flags, const nrs_aniso_config *cfg,
+                              uint64_t *vertices, uint64_t *triangles);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,8 @@ FIELD_DENSITY, FIELD_GRADIENT, FIELD_VELOCITY, FIELD_COUNT, FIELD_WALLS = 1, 2, 
 # NRS_SURFACE_*: the flags of a surface extract (per-vertex attributes, the wall term in the density); NRS_MESH_*: one of its results
 SURFACE_GRADIENT, SURFACE_VELOCITY, SURFACE_WALLS = 1, 2, 4
 MESH_VERTICES, MESH_TRIANGLES, MESH_GRADIENT, MESH_VELOCITY = 1, 2, 4, 8
+# NRS_ANISO_*: one result of the anisotropic kernels (nrs_aniso_build)
+ANISO_CENTER, ANISO_G, ANISO_COUNT, ANISO_INDEX = 1, 2, 4, 8
 # NRS_DIFFUSE_*: one result of the diffuse particles; the kinds of NRS_DIFFUSE_KIND
 DIFFUSE_POS, DIFFUSE_VEL, DIFFUSE_KIND, DIFFUSE_POTENTIALS, DIFFUSE_BIRTHS, DIFFUSE_NORMALS = 0, 1, 2, 3, 4, 5
 DIFFUSE_SPRAY, DIFFUSE_FOAM, DIFFUSE_BUBBLE = 0, 1, 2
@@ -79,10 +81,16 @@ EXPORTS = [
     "nrs_sample_points", "nrs_sample_lattice", "nrs_sample_result", "nrs_sample_device_ptr", "nrs_sample_release",
     "nrs_sample_builds",
     "nrs_surface_extract", "nrs_surface_result", "nrs_surface_device_ptr", "nrs_surface_release",
+    "nrs_aniso_build", "nrs_aniso_result", "nrs_aniso_device_ptr", "nrs_aniso_release", "nrs_surface_extract_aniso",
     "nrs_diffuse_configure", "nrs_diffuse_step", "nrs_diffuse_count", "nrs_diffuse_result", "nrs_diffuse_device_ptr",
     "nrs_diffuse_upload", "nrs_diffuse_release",
     "nrs_emitter_set", "nrs_emitter_get", "nrs_emit_block", "nrs_sinks_set", "nrs_cull", "nrs_sinks_count",
 ]
+
+
+class NrsAnisoConfig(C.Structure):
+    _fields_ = [("support", C.c_double), ("lam", C.c_double), ("k_r", C.c_double), ("k_n", C.c_double), ("n_eps", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class NrsEmitter(C.Structure):
@@ -203,6 +211,12 @@ def load_library(path=None):
     lib.nrs_surface_result.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(u64)]
     lib.nrs_surface_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
     lib.nrs_surface_release.argtypes = [vp]
+    lib.nrs_aniso_build.argtypes = [vp, C.POINTER(NrsAnisoConfig)]
+    lib.nrs_aniso_result.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(u64)]
+    lib.nrs_aniso_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
+    lib.nrs_aniso_release.argtypes = [vp]
+    lib.nrs_surface_extract_aniso.argtypes = [vp, C.POINTER(NrsLattice), C.c_double, C.c_uint32, C.POINTER(NrsAnisoConfig), C.POINTER(u64),
+                                              C.POINTER(u64)]
     lib.nrs_diffuse_configure.argtypes = [vp, C.POINTER(NrsDiffuseConfig)]
     lib.nrs_diffuse_step.argtypes = [vp, C.c_double]
     lib.nrs_diffuse_count.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
@@ -579,6 +593,51 @@ class Solver:
 
     def surface_release(self):
         self._chk(self.lib.nrs_surface_release(self.h))
+
+    # ---- anisotropic surface reconstruction ------------------------------------------------------------
+    @staticmethod
+    def _aniso_config(cfg):
+        """None (the library's defaults) or a dict with any of support, lam, k_r, k_n, n_eps, reserved over those defaults (support 0 = h)"""
+        if cfg is None:
+            return None
+        c = NrsAnisoConfig(0.0, 0.9, 4.0, 0.5, 25, 0)
+        for k, v in cfg.items():
+            if k not in ("support", "lam", "k_r", "k_n", "n_eps", "reserved"):
+                raise KeyError(k)
+            setattr(c, k, v)
+        return C.byref(c)
+
+    def aniso_build(self, cfg=None):
+        """the anisotropic kernel of every fluid particle, in the sampler's sorted order (nrs_aniso_build); does not wait for the device"""
+        self._chk(self.lib.nrs_aniso_build(self.h, self._aniso_config(cfg)))
+
+    def aniso_result(self, which):
+        """one result of the last aniso_build on the host: ANISO_CENTER (N, 4) centre + bound, ANISO_G (N, 8) G00 G01 G02 G11 G12 G22
+        weight 0, ANISO_COUNT / ANISO_INDEX (N,) uint32"""
+        nbytes = C.c_uint64(0)
+        self._chk(self.lib.nrs_aniso_result(self.h, int(which), None, 0, C.byref(nbytes)))
+        dt = np.uint32 if which in (ANISO_COUNT, ANISO_INDEX) else self.real
+        a = np.empty(nbytes.value // np.dtype(dt).itemsize, dtype=dt)
+        if nbytes.value:
+            self._chk(self.lib.nrs_aniso_result(self.h, int(which), _ptr(a), nbytes.value, None))
+        return a.reshape(-1, 4) if which == ANISO_CENTER else a.reshape(-1, 8) if which == ANISO_G else a
+
+    def aniso_device_ptr(self, which):
+        p, b = C.c_void_p(), C.c_uint64()
+        self._chk(self.lib.nrs_aniso_device_ptr(self.h, int(which), C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def aniso_release(self):
+        self._chk(self.lib.nrs_aniso_release(self.h))
+
+    def surface_extract_aniso(self, origin, spacing, dims, iso=0.5, flags=0, cfg=None):
+        """the iso-surface phi = iso of the anisotropic colour field on the lattice (nrs_surface_extract_aniso): builds the kernels, writes
+        phi (and the attributes) into the sampler's result arrays, meshes them, waits for the totals; -> (V, T); the mesh comes back through
+        surface_result"""
+        L = self._lattice(origin, spacing, dims)
+        v, t = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self.lib.nrs_surface_extract_aniso(self.h, C.byref(L), float(iso), int(flags), self._aniso_config(cfg), C.byref(v), C.byref(t)))
+        return int(v.value), int(t.value)
 
     # ---- diffuse particles ----------------------------------------------------------------------------
     def diffuse_configure(self, capacity, seed=0, tau_ta=(5.0, 20.0), tau_wc=(2.0, 8.0), tau_k=(5.0, 50.0), k_ta=4000.0, k_wc=50000.0,

@@ -471,6 +471,33 @@ int nrs_surface_release(nrs_ctx *ctx)
     CTX_GUARD(ctx);
     return ctx->impl->surface_release();
 }
+int nrs_aniso_build(nrs_ctx *ctx, const nrs_aniso_config *cfg)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->aniso_build(cfg);
+}
+int nrs_aniso_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_bytes, uint64_t *out_bytes)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->aniso_result(which, dst, dst_bytes, out_bytes);
+}
+int nrs_aniso_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes)
+{
+    CTX_GUARD(ctx);
+    if (!dptr || !bytes) return fail(NRS_E_INVALID, "NULL argument");
+    return ctx->impl->aniso_device_ptr(which, dptr, bytes);
+}
+int nrs_aniso_release(nrs_ctx *ctx)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->aniso_release();
+}
+int nrs_surface_extract_aniso(nrs_ctx *ctx, const nrs_lattice *lattice, double iso, uint32_t flags, const nrs_aniso_config *cfg, uint64_t *vertices,
+                              uint64_t *triangles)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->surface_extract_aniso(lattice, iso, flags, cfg, vertices, triangles);
+}
 int nrs_diffuse_configure(nrs_ctx *ctx, const nrs_diffuse_config *cfg)
 {
     CTX_GUARD(ctx);

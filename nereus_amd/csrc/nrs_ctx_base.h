@@ -145,6 +145,12 @@ struct CtxBase {
     virtual int surface_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) = 0;
     virtual int surface_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) = 0;
     virtual int surface_release() = 0;
+    virtual int aniso_build(const nrs_aniso_config *cfg) = 0;
+    virtual int aniso_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) = 0;
+    virtual int aniso_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) = 0;
+    virtual int aniso_release() = 0;
+    virtual int surface_extract_aniso(const nrs_lattice *lattice, double iso, uint32_t flags, const nrs_aniso_config *cfg, uint64_t *vertices,
+                                      uint64_t *triangles) = 0;
     // diffuse particles (nrs_kernels_diffuse.h; the host decisions: nrs_host_diffuse.h)
     virtual int diffuse_configure(const nrs_diffuse_config *cfg) = 0;
     virtual int diffuse_step(double dt) = 0;

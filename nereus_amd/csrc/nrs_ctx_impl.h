@@ -1572,6 +1572,17 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int surface_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override { return rd.surface_device_ptr(which, dptr, bytes); }
     int surface_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override { return rd.surface_result(which, dst, dstBytes, outBytes, stream); }
     int surface_release() override { return rd.release(rd.sf, stream); }
+    int aniso_build(const nrs_aniso_config *cfg) override { NRSCHK(validate("nrs_sample_*")); return rd.aniso_build(fluid_now(), cfg); }
+    int aniso_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override { return rd.aniso_result(which, dst, dstBytes, outBytes, stream); }
+    int aniso_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override { return rd.aniso_device_ptr(which, dptr, bytes); }
+    int aniso_release() override { return rd.release(rd.an, stream); }
+    int surface_extract_aniso(const nrs_lattice *lattice, double iso, uint32_t flags, const nrs_aniso_config *cfg, uint64_t *vertices,
+                              uint64_t *triangles) override
+    {
+        NRSCHK(aniso_check_extract(iso, flags)); // (its refusals come before the state check's)
+        NRSCHK(validate("nrs_sample_*"));
+        return rd.surface_extract_aniso(fluid_now(), lattice, iso, flags, cfg, vertices, triangles);
+    }
     int diffuse_configure(const nrs_diffuse_config *c) override { NRSCHK(validate("nrs_diffuse_configure")); return rd.diffuse_configure(fluid_now(), c); }
     int diffuse_step(double dt) override { NRSCHK(validate("nrs_diffuse_step")); return rd.diffuse_step(fluid_now(), dt); }
     int diffuse_count(uint64_t *alive, uint64_t *byKind, uint64_t *dropped) override

@@ -28,6 +28,7 @@ struct FieldSampler {
     const uint32_t *cell_start() const { return cellStart.as<uint32_t>(); }
     const uint32_t *cell_end() const { return cellEnd.as<uint32_t>(); }
     uint32_t *err_word() const { return err.as<uint32_t>(); }
+    const uint32_t *sorted_index() const { return valCur; } // slot -> the particle's index in the arrays the grid was built from
     template <typename T4> const T4 *query_points() const { return points.as<T4>(); }
     void *result(uint32_t field) const
     {
@@ -77,6 +78,7 @@ struct FieldSampler {
         NRSCHK(sortTmp.alloc(tmp));
         HIPCHK(sort_pairs_plain(sortTmp.p, tmp, kv, (size_t)N, bits, stream));
         keyCur = kv.key;
+        valCur = kv.val;
         hipLaunchKernelGGL((k_reorder<R>), dim3(nblocks(N)), dim3(BLOCK), 0, stream, (const uint32_t *)kv.key, (const uint32_t *)kv.val, pos, vel,
                            (const R *)nullptr, sPos.as<T4>(), sVel.as<T4>(), (R *)nullptr, cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(),
                            (uint32_t *)nullptr, N, (const uint32_t *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr, QuantCfg{},
@@ -123,7 +125,7 @@ struct FieldSampler {
         staged.release();
         stagedBytes = 0;
         stagedEvent.release();
-        keyCur = nullptr;
+        keyCur = valCur = nullptr;
         builtN = 0;
         tableCells = 0;
         cache.dropped();
@@ -133,6 +135,7 @@ struct FieldSampler {
 private:
     DevBuf key, keyAlt, val, valAlt, sortTmp; // the (hash, index) pairs of the last build and the sort's workspace
     uint32_t *keyCur = nullptr;               // whichever of key / keyAlt the sort left the sorted hashes in
+    uint32_t *valCur = nullptr;               // ... and of val / valAlt the sorted indices
     DevBuf sPos, sVel;                        // the fluid in sorted order
     DevBuf cellStart, cellEnd;                // the sampler's own fluid cell table
     uint32_t builtN = 0;                      // particles the table describes (0: the table is all-EMPTY)

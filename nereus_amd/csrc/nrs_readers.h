@@ -9,6 +9,7 @@
 #include <climits>
 #include <cstring>
 
+#include "nrs_aniso.h"
 #include "nrs_diffuse.h"
 #include "nrs_field_sampler.h"
 #include "nrs_surface_mesher.h"
@@ -33,6 +34,7 @@ template <typename R, int KSET> struct FluidReaders {
     FieldSampler sm;
     SurfaceMesher sf;
     DiffuseSystem df;
+    AnisoSurface an;
 
     // ---- shared -----------------------------------------------------------------------------------------------------------------------
     // The sampler's grid of f's particles, rebuilt if the cache rule asks for it, as the kernels see it; walls: with the boundary's tables
@@ -159,6 +161,68 @@ template <typename R, int KSET> struct FluidReaders {
         uint64_t sz = 0;
         NRSCHK(surface_route_result(sf.last, which, PRECISION, &sz));
         return copy_out(dst, dstBytes, sf.result(which), sz, outBytes, stream);
+    }
+
+    // ---- anisotropic surface reconstruction -----------------------------------------------------------------------------------------------
+    // The sampler's particle grid (its cache rule and build count), then pass A on its sorted particles into an's record buffers: recomputed
+    // on every call.  cfg has passed aniso_check_config.
+    int aniso_records(const FluidNow<R> &f, const AnisoConfig &cfg, GridView<R> &G)
+    {
+        an.last = AnisoLast();
+        NRSCHK(grid(f, false, G));
+        NRSCHK(an.template records<R>(f.P, G, cfg, sm.template sorted_pos<T4>(), sm.sorted_index(), sm.sorted_count(), f.stream));
+        an.last = AnisoLast{true, sm.sorted_count()};
+        return NRS_OK;
+    }
+    int aniso_build(const FluidNow<R> &f, const nrs_aniso_config *c)
+    {
+        AnisoConfig cfg;
+        NRSCHK(aniso_check_config(c, f.facts.h, &cfg));
+        NRSCHK(aniso_refusal(f.facts));
+        GridView<R> G;
+        return aniso_records(f, cfg, G);
+    }
+    int aniso_device_ptr(uint32_t which, void **dptr, uint64_t *bytes)
+    {
+        NRSCHK(aniso_route_result(an.last, which, PRECISION, bytes));
+        *dptr = *bytes ? an.result(which) : nullptr;
+        return NRS_OK;
+    }
+    int aniso_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes, hipStream_t stream)
+    {
+        uint64_t sz = 0;
+        NRSCHK(aniso_route_result(an.last, which, PRECISION, &sz));
+        return copy_out(dst, dstBytes, an.result(which), sz, outBytes, stream, sm.err_word(),
+                        "anisotropic kernels: a cell range of the sampler's table lies outside its sorted particles; the walks skipped it, the results are invalid");
+    }
+    // Pass A, pass B on the lattice into the sampler's result arrays (sm.last names them: nrs_sample_result afterwards returns the lattice the
+    // mesh was cut from), then the mesher as nrs_surface_extract runs it.  iso and flags have passed aniso_check_extract.
+    int surface_extract_aniso(const FluidNow<R> &f, const nrs_lattice *lattice, double iso, uint32_t flags, const nrs_aniso_config *c,
+                              uint64_t *vertices, uint64_t *triangles)
+    {
+        const uint32_t fields = aniso_sample_fields(flags);
+        AnisoConfig cfg;
+        NRSCHK(aniso_check_config(c, f.facts.h, &cfg));
+        NRSCHK(aniso_refusal(f.facts));
+        uint64_t m = 0;
+        NRSCHK(surface_check_lattice(lattice, &m));
+        const Lattice L = lattice_from(*lattice);
+        GridView<R> G;
+        NRSCHK(aniso_records(f, cfg, G));
+        sm.last = SampleLast();
+        NRSCHK(sm.ensure_results(fields, m, sizeof(R)));
+        void *grad = (flags & NRS_SURFACE_GRADIENT) ? sm.result(NRS_FIELD_GRADIENT) : nullptr;
+        void *vel = (flags & NRS_SURFACE_VELOCITY) ? sm.result(NRS_FIELD_VELOCITY) : nullptr;
+        NRSCHK(an.template lattice<R>(f.P, G, sm.template sorted_vel<T4>(), L, m, sm.result(NRS_FIELD_DENSITY), grad, vel, f.stream));
+        sm.last = SampleLast{true, fields, m};
+        const SurfaceInput in{L, m, iso, PRECISION, sm.result(NRS_FIELD_DENSITY), grad, vel};
+        sf.last = SurfaceLast();
+        uint64_t V = 0, T = 0;
+        NRSCHK(sf.extract(in, f.stream, &V, &T));
+        sf.last = SurfaceLast{true, flags, V, T};
+        if (vertices) *vertices = V;
+        if (triangles) *triangles = T;
+        return NRS_OK;
     }
 
     // ---- diffuse particles ------------------------------------------------------------------------------------------------------------

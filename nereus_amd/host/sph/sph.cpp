@@ -351,6 +351,67 @@ const std::vector<SVec4> &SPH::getSurfaceVelocity()
     return m_surfaceVelocity;
 }
 
+// ---- anisotropic surface reconstruction ---------------------------------------------------------------------------------------------
+void SPH::anisoKernels(const nrs_aniso_config *cfg)
+{
+    ensureContext();
+    pushHostToDevice();
+    if (nrs_aniso_build(m_ctx, cfg) != NRS_OK) fatal("nrs_aniso_build");
+}
+template <typename T> static const std::vector<T> &fetchAniso(nrs_ctx *ctx, SUint which, std::vector<T> &v, bool &ok)
+{
+    uint64_t bytes = 0;
+    ok = nrs_aniso_result(ctx, which, nullptr, 0, &bytes) == NRS_OK;
+    if (!ok) return v;
+    v.resize((size_t)(bytes / sizeof(T)));
+    if (bytes) ok = nrs_aniso_result(ctx, which, v.data(), bytes, nullptr) == NRS_OK;
+    return v;
+}
+const std::vector<SVec4> &SPH::getAnisoCenters()
+{
+    bool ok = false;
+    ensureContext();
+    fetchAniso(m_ctx, NRS_ANISO_CENTER, m_anisoCenters, ok);
+    if (!ok) fatal("nrs_aniso_result");
+    return m_anisoCenters;
+}
+const std::vector<SVec4> &SPH::getAnisoG()
+{
+    bool ok = false;
+    ensureContext();
+    fetchAniso(m_ctx, NRS_ANISO_G, m_anisoG, ok);
+    if (!ok) fatal("nrs_aniso_result");
+    return m_anisoG;
+}
+const std::vector<SUint> &SPH::getAnisoCount()
+{
+    bool ok = false;
+    ensureContext();
+    fetchAniso(m_ctx, NRS_ANISO_COUNT, m_anisoCount, ok);
+    if (!ok) fatal("nrs_aniso_result");
+    return m_anisoCount;
+}
+const std::vector<SUint> &SPH::getAnisoIndex()
+{
+    bool ok = false;
+    ensureContext();
+    fetchAniso(m_ctx, NRS_ANISO_INDEX, m_anisoIndex, ok);
+    if (!ok) fatal("nrs_aniso_result");
+    return m_anisoIndex;
+}
+void SPH::extractSurfaceAniso(const double origin[3], const double spacing[3], const SUint dims[3], double iso, SUint flags, const nrs_aniso_config *cfg)
+{
+    ensureContext();
+    pushHostToDevice();
+    nrs_lattice L;
+    std::memset(&L, 0, sizeof(L));
+    for (int a = 0; a < 3; ++a) { L.origin[a] = origin[a]; L.spacing[a] = spacing[a]; L.dims[a] = dims[a]; }
+    uint64_t V = 0, T = 0;
+    if (nrs_surface_extract_aniso(m_ctx, &L, iso, flags, cfg, &V, &T) != NRS_OK) fatal("nrs_surface_extract_aniso");
+    m_surfaceV = (SUint)V;
+    m_surfaceT = (SUint)T;
+}
+
 // ---- diffuse particles -----------------------------------------------------------------------------------------------------------------
 void SPH::configureDiffuse(const nrs_diffuse_config &cfg)
 {

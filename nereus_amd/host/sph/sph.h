@@ -28,6 +28,7 @@
 #define MAX_PARTICLE_NUMBER 150000
 
 struct nrs_ctx;
+struct nrs_aniso_config;
 struct nrs_diffuse_config;
 struct nrs_emitter;
 struct nrs_sink_config;
@@ -122,6 +123,19 @@ public:
     const std::vector<SUint> &getSurfaceTriangles();
     const std::vector<SVec4> &getSurfaceGradient();
     const std::vector<SVec4> &getSurfaceVelocity();
+    // Anisotropic surface reconstruction (nrs_aniso_* / nrs_surface_extract_aniso, DESIGN.md "Anisotropic kernels"; Yu & Turk 2013).
+    // anisoKernels builds one ellipsoidal kernel per fluid particle, in the sampler's sorted order (cfg null: the library's defaults), and
+    // returns without waiting; the getters wait and return one result of the LAST build in a host array the solver owns: centre + largest
+    // semi-axis; two SVec4 per particle (G00, G01, G02, G11), (G12, G22, weight, 0); the neighbour count; the particle's index in host order.
+    // extractSurfaceAniso builds the kernels, evaluates their colour field phi on the lattice INTO the sampled fields (getSampledDensity()
+    // afterwards is phi, the lattice the mesh was cut from) and meshes phi = iso; the mesh comes back through the getSurface* getters.
+    void anisoKernels(const nrs_aniso_config *cfg = nullptr);
+    const std::vector<SVec4> &getAnisoCenters();
+    const std::vector<SVec4> &getAnisoG();
+    const std::vector<SUint> &getAnisoCount();
+    const std::vector<SUint> &getAnisoIndex();
+    void extractSurfaceAniso(const double origin[3], const double spacing[3], const SUint dims[3], double iso, SUint flags,
+                             const nrs_aniso_config *cfg = nullptr);
     // Diffuse particles (nrs_diffuse_*, DESIGN.md "Diffuse particles"): spray, foam and bubbles born from the fluid's trapped air, wave
     // crests and kinetic energy, kept and advected on the device.  configureDiffuse stores the configuration (struct_size and reserved are
     // filled in); stepDiffuse advances the set on the current state (dt 0: the timestep) and returns without waiting — call it after
@@ -212,6 +226,8 @@ protected:
     std::vector<SVec4> m_surfaceVertices, m_surfaceGradient, m_surfaceVelocity; // ... and of the last surface extract
     std::vector<SUint> m_surfaceTriangles;
     SUint m_surfaceV = 0, m_surfaceT = 0;
+    std::vector<SVec4> m_anisoCenters, m_anisoG; // host copies of the results of the last anisoKernels
+    std::vector<SUint> m_anisoCount, m_anisoIndex;
     std::vector<SVec4> m_diffusePositions, m_diffuseVelocities; // ... and the living diffuse set of the last getDiffuse
     std::vector<SUint> m_diffuseKinds;
     bool m_inflow = false; // emitters or sinks were configured: the device's particle count leads

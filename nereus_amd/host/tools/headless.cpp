@@ -26,6 +26,8 @@
 //                                                               as run, then the surface density = iso on that lattice
 //                                                               (SPH::extractSurface) as a Wavefront OBJ: "v x y z" lines, then
 //                                                               "f a b c" lines with 1-based vertex numbers, wound outwards
+//   headless surface ... <iso> <out.obj> --aniso [support]      the same with the anisotropic kernels (SPH::extractSurfaceAniso): <iso> is a
+//                                                               value of the colour field (0.5); support: a length, default (and 0) h
 //   headless diffuse <solver> <in.bin> <steps> <out.dif>        as run with SPH::stepDiffuse after every update (capacity 2^20, seed 0,
 //                                                               the ranges below), then the living diffuse set (SPH::getDiffuse)
 //                                                               out.dif: u32 count, u32 precision (32 | 64), pos4[count] (w = lifetime),
@@ -233,13 +235,23 @@ int main(int argc, char **argv)
             const double h = std::strtod(argv[8], nullptr);
             const double origin[3] = {std::strtod(argv[5], nullptr), std::strtod(argv[6], nullptr), std::strtod(argv[7], nullptr)}, spacing[3] = {h, h, h};
             const SUint dims[3] = {(SUint)std::strtoul(argv[9], nullptr, 10), (SUint)std::strtoul(argv[10], nullptr, 10), (SUint)std::strtoul(argv[11], nullptr, 10)};
-            sim->extractSurface(origin, spacing, dims, std::strtod(argv[12], nullptr), 0);
+            const bool aniso = argc > 14 && std::string(argv[14]) == "--aniso";
+            if (argc > 14 && !aniso) die("surface: unknown option (--aniso [support])");
+            if (aniso) {
+                nrs_aniso_config ac;
+                std::memset(&ac, 0, sizeof(ac));
+                ac.support = argc > 15 ? std::strtod(argv[15], nullptr) : 0.0;
+                ac.lambda = 0.9; ac.k_r = 4.0; ac.k_n = 0.5; ac.n_eps = 25;
+                sim->extractSurfaceAniso(origin, spacing, dims, std::strtod(argv[12], nullptr), 0, &ac);
+            } else {
+                sim->extractSurface(origin, spacing, dims, std::strtod(argv[12], nullptr), 0);
+            }
             const std::vector<SVec4> &v = sim->getSurfaceVertices();
             const std::vector<SUint> &t = sim->getSurfaceTriangles();
             if (v.size() != sim->getSurfaceNumVertices() || t.size() != 3 * (size_t)sim->getSurfaceNumTriangles()) die("extractSurface: wrong sizes");
             FILE *o = std::fopen(argv[13], "w");
             if (!o) die("cannot open output");
-            std::fprintf(o, "# density = %s, %zu vertices, %zu triangles\n", argv[12], v.size(), t.size() / 3);
+            std::fprintf(o, "# %s = %s, %zu vertices, %zu triangles\n", aniso ? "anisotropic colour field" : "density", argv[12], v.size(), t.size() / 3);
             const int digits = sizeof(SReal) == 8 ? 17 : 9; // enough to read every coordinate back bit for bit
             for (size_t i = 0; i < v.size(); ++i) std::fprintf(o, "v %.*g %.*g %.*g\n", digits, (double)v[i].x, digits, (double)v[i].y, digits, (double)v[i].z);
             for (size_t i = 0; i + 2 < t.size(); i += 3) std::fprintf(o, "f %u %u %u\n", t[i] + 1, t[i + 1] + 1, t[i + 2] + 1);
