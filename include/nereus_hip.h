@@ -356,7 +356,9 @@ int nrs_set_surface_akinci(nrs_ctx *ctx, double gamma, double beta_adhesion);
  * launches.  stage_mask: bit s set = time NRS_STAGE_s (0 = off, 0xffffffff = every stage).  nrs_set_profiling also
  * resets the accumulated times.  nrs_stage_ms returns the time of that stage summed over all steps since the last
  * nrs_set_profiling call and how many launches of the stage that covers; it synchronizes the stream (nrs_step itself
- * does not: event pairs are resolved lazily). */
+ * does not: event pairs are resolved lazily).  `launches` counts the event brackets of the stage, not kernels: a stage's launches of a
+ * step share one bracket (a continuation later in the step adds time, not a count); a context that tracks its particles (nrs_track_*)
+ * records its gather in a bracket of its own in NRS_STAGE_REORDER, whose count is then one higher per step and whose time is the sum. */
 int nrs_set_profiling(nrs_ctx *ctx, uint32_t stage_mask);
 int nrs_stage_ms(nrs_ctx *ctx, int stage, float *ms, uint32_t *launches);
 
@@ -717,6 +719,74 @@ int nrs_aniso_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *by
 int nrs_aniso_release(nrs_ctx *ctx);
 int nrs_surface_extract_aniso(nrs_ctx *ctx, const nrs_lattice *lattice, double iso, uint32_t flags, const nrs_aniso_config *cfg,
                               uint64_t *vertices, uint64_t *triangles);
+
+/* ---- particle identity and attributes (DESIGN.md "Particle identity and attributes"; came without a version change) ------------------------
+ * Every step returns its arrays in that step's grid-hash order, emitters append and kill volumes remove: nothing else tells the caller
+ * which particle is which afterwards.  With tracking enabled the context keeps, per fluid particle and in the order of NRS_ARR_POS /
+ * nrs_download (the "current order"):
+ *   id      uint32_t, unique within the context's life (until the next nrs_track_enable); NRS_TRACK_NONE is never an id
+ *   birth   uint32_t, the number of completed steps at the moment the particle entered, saturating at 0xffffffff
+ *   record  one SVec4 of user data, only with NRS_TRACK_ATTR
+ * Opt-in: nothing is allocated before nrs_track_enable, and a context that never enables it launches what it always launched.  A
+ * tracked context steps bit-identically to an untracked one.  Every solver, both precisions, both kernel sets; not on a slab context.
+ *
+ * HOW THE STATE MOVES.  A step: one launch behind the reorder gathers new[s] = old[index[s]] (index: NRS_ARR_INDEX of that step) for
+ * id, birth and the record; the buffers swap at the end of the step, so a partial step (nrs_step_partial) leaves the tracked arrays of
+ * the last completed state in place.  Emission: the particle of a launch's site t gets id = first + t (emitters: layer-major, layers
+ * in schedule order, slots ascending; nrs_emit_block: the lattice's linear index), birth = completed steps, record = the slot's emit
+ * value.  Cull: survivors keep id, birth, record and their order.  nrs_upload_particles(first, count): slots below the old n keep
+ * id, birth and record (the same particle, moved); slots at or above the old n get fresh consecutive ids in slot order, birth =
+ * completed steps and the emit value of slot -1.  nrs_set_num_particles: shrinking drops the tail, growing makes the new slots fresh
+ * the same way.  Ids are never reused.  A call or step that would pass id 0xfffffffe fails with NRS_E_CAPACITY and changes nothing
+ * (nrs_track_enable renumbers).
+ *
+ * nrs_track_enable numbers the n particles now present 0 .. n-1 in the current order, birth 0, record zeros, next_id = n, emit values
+ * zeros; calling it again renumbers and resets (that is how flags are changed).  nrs_track_disable drains the stream and frees the
+ * buffers.  nrs_track_info never refuses (any pointer may be NULL).
+ * nrs_track_upload overwrites slots [first, first + count) of NRS_TRACK_ID, _BIRTH (uint32_t) or _ATTRIBUTE (SVec4) from host memory
+ * and waits; for ids next_id becomes the larger of itself and one plus the largest uploaded id.  UNIQUENESS OF UPLOADED IDS IS THE
+ * CALLER'S BUSINESS.  It is the call that carries identity across a context rebuild.
+ * nrs_track_result copies one array to the host and waits (dst NULL: only the size); nrs_track_device_ptr gives its device address.
+ * A consumer on the context's stream needs no wait; the pointers are valid until the next enable, disable or nrs_destroy, and have
+ * to be asked for again after every step, cull and nrs_track_diffuse (the buffers swap).  NRS_TRACK_SLOT_OF names the result of the
+ * last nrs_track_locate; its pointer is valid only until the next nrs_track_locate (a larger one reallocates).
+ * nrs_track_emit_value: slots 0 .. NRS_MAX_EMITTERS-1 hold the record given to each emitter's particles, slot -1 serves
+ * nrs_emit_block, appended uploads and count growth; the default is zeros (values are rounded to SReal).
+ * nrs_track_locate(first_id, count) answers "where is id k now": uint32_t slot_of[count], NRS_TRACK_NONE where id first_id + k does
+ * not live, else its slot in the current order; count <= 2^27, 0 gives an empty result.  Enqueues and returns.
+ *
+ * nrs_track_diffuse: one explicit Euler step of da/dt = kappa_c lap a on channel c of the record (dye mixing, heat conduction).
+ * Never part of nrs_step; it does not touch the simulation state.  dt == 0: the context's timestep.  A channel with kappa_c == 0 is
+ * copied.  It runs on the field sampler's particle grid (its refusals and cache rule apply, nrs_sample_builds counts a rebuild).  With
+ * h = interactionRadius, m = particleMass, rho0 = restDensity, R = SReal, rho the sampler's density at the particles (with
+ * NRS_FIELD_WALLS when the context has boundary particles), eta2 = (R)0.01 * (h * h), per particle i over the fluid particles j != i of
+ * its 27 cells (cells z, y, x ascending, sorted slots ascending, one accumulator per channel):
+ *   d = x_i - x_j; len = length(d) (float); skipped unless len < h; skipped if len == 0
+ *   g = grad W(d); dot = d.x g.x + d.y g.y + d.z g.z; r = (R)len; w = (m / (rho_i * rho_j)) * (dot / (r * r + eta2))
+ *   acc_c += (a_i[c] - a_j[c]) * w
+ *   a_new[c] = a_i[c] + ((((R)2 * (R)dt) * (R)kappa_c) * rho0) * acc_c
+ * (the Laplacian of Brookshaw / Cleary and Monaghan with a uniform coefficient; w_ij == w_ji bit for bit, so a pair exchanges equal
+ * and opposite amounts before the sums round).  A particle with a non-finite position keeps its record.  STABILITY IS NOT CHECKED:
+ * the step obeys a maximum principle only while lambda_i = 2 dt kappa_c rho0 sum_j |w_ij| <= 1 for every particle.
+ *
+ * NRS_E_STATE: everything but nrs_track_enable, _disable and _info before nrs_track_enable; a record call (nrs_track_emit_value,
+ * nrs_track_diffuse, NRS_TRACK_ATTRIBUTE) without NRS_TRACK_ATTR; a result, pointer, locate or diffuse mid-update after
+ * nrs_step_partial or while a host-driven IISPH step is in progress (then also nrs_track_enable and nrs_track_upload);
+ * NRS_TRACK_SLOT_OF before any locate.  NRS_E_INVALID: unknown flag bits; a slab context (and nrs_slab_configure on a tracking
+ * context); an unknown `which`; an upload outside [0, n) or with a NULL source; an uploaded id of NRS_TRACK_NONE; a slot outside
+ * -1 .. NRS_MAX_EMITTERS-1; count above 2^27; a negative or non-finite kappa or dt.  A refused call changes nothing. */
+enum { NRS_TRACK_ATTR = 1u };                                   /* flags of nrs_track_enable */
+enum { NRS_TRACK_ID = 0, NRS_TRACK_BIRTH = 1, NRS_TRACK_ATTRIBUTE = 2, NRS_TRACK_SLOT_OF = 3 };
+#define NRS_TRACK_NONE 0xffffffffu
+int nrs_track_enable(nrs_ctx *ctx, uint32_t flags);
+int nrs_track_disable(nrs_ctx *ctx);
+int nrs_track_info(nrs_ctx *ctx, int *on, uint32_t *flags, uint64_t *next_id);
+int nrs_track_upload(nrs_ctx *ctx, uint32_t which, const void *src, uint64_t first, uint64_t count);
+int nrs_track_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_bytes, uint64_t *out_bytes);
+int nrs_track_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes);
+int nrs_track_emit_value(nrs_ctx *ctx, int32_t slot, const double a[4]);
+int nrs_track_locate(nrs_ctx *ctx, uint64_t first_id, uint64_t count);
+int nrs_track_diffuse(nrs_ctx *ctx, const double kappa[4], double dt);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,10 @@ DIFFUSE_SPRAY, DIFFUSE_FOAM, DIFFUSE_BUBBLE = 0, 1, 2
 MAX_EMITTERS, MAX_SINK_BOXES = 16, 16
 EMITTER_RECT, EMITTER_DISC = 0, 1
 SINK_DOMAIN = 1
+# particle identity and attributes: the flag of track_enable, the NRS_TRACK_* arrays, the id that is none
+TRACK_ATTR = 1
+TRACK_ID, TRACK_BIRTH, TRACK_ATTRIBUTE, TRACK_SLOT_OF = 0, 1, 2, 3
+TRACK_NONE = 0xFFFFFFFF
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
@@ -85,6 +89,8 @@ EXPORTS = [
     "nrs_diffuse_configure", "nrs_diffuse_step", "nrs_diffuse_count", "nrs_diffuse_result", "nrs_diffuse_device_ptr",
     "nrs_diffuse_upload", "nrs_diffuse_release",
     "nrs_emitter_set", "nrs_emitter_get", "nrs_emit_block", "nrs_sinks_set", "nrs_cull", "nrs_sinks_count",
+    "nrs_track_enable", "nrs_track_disable", "nrs_track_info", "nrs_track_upload", "nrs_track_result", "nrs_track_device_ptr",
+    "nrs_track_emit_value", "nrs_track_locate", "nrs_track_diffuse",
 ]
 
 
@@ -230,6 +236,15 @@ def load_library(path=None):
     lib.nrs_sinks_set.argtypes = [vp, C.POINTER(NrsSinkConfig)]
     lib.nrs_cull.argtypes = [vp, C.POINTER(u64)]
     lib.nrs_sinks_count.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    lib.nrs_track_enable.argtypes = [vp, C.c_uint32]
+    lib.nrs_track_disable.argtypes = [vp]
+    lib.nrs_track_info.argtypes = [vp, C.POINTER(i32), C.POINTER(C.c_uint32), C.POINTER(u64)]
+    lib.nrs_track_upload.argtypes = [vp, C.c_uint32, vp, u64, u64]
+    lib.nrs_track_result.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(u64)]
+    lib.nrs_track_device_ptr.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64)]
+    lib.nrs_track_emit_value.argtypes = [vp, C.c_int32, dp]
+    lib.nrs_track_locate.argtypes = [vp, u64, u64]
+    lib.nrs_track_diffuse.argtypes = [vp, dp, C.c_double]
     _lib = lib
     return lib
 
@@ -750,6 +765,61 @@ class Solver:
         r, c = C.c_uint64(0), C.c_uint64(0)
         self._chk(self.lib.nrs_sinks_count(self.h, C.byref(r), C.byref(c)))
         return int(r.value), int(c.value)
+
+    # ---- particle identity and attributes -----------------------------------------------------------------
+    def track_enable(self, flags=0):
+        """number the particles now present 0 .. n-1 in the current order and start tracking (nrs_track_enable); TRACK_ATTR adds the
+        attribute record; calling it again renumbers and resets"""
+        self._chk(self.lib.nrs_track_enable(self.h, int(flags)))
+
+    def track_disable(self):
+        self._chk(self.lib.nrs_track_disable(self.h))
+
+    def track_info(self):
+        """(on, flags, next_id) (nrs_track_info)"""
+        on, fl, nx = C.c_int(0), C.c_uint32(0), C.c_uint64(0)
+        self._chk(self.lib.nrs_track_info(self.h, C.byref(on), C.byref(fl), C.byref(nx)))
+        return bool(on.value), int(fl.value), int(nx.value)
+
+    def track_upload(self, which, src, first=0):
+        """overwrite slots first .. first + len(src) of TRACK_ID / TRACK_BIRTH (uint32) or TRACK_ATTRIBUTE ((count, 4) SReal) (nrs_track_upload)"""
+        if which == TRACK_ATTRIBUTE:
+            a = np.ascontiguousarray(src, dtype=self.real).reshape(-1, 4)
+        else:
+            a = np.ascontiguousarray(src, dtype=np.uint32).reshape(-1)
+        self._chk(self.lib.nrs_track_upload(self.h, int(which), _ptr(a) if len(a) else None, int(first), len(a)))
+
+    def track_result(self, which):
+        """one tracked array on the host, in the order of download(): (n,) uint32 ids / births, (n, 4) SReal records, or the (count,)
+        uint32 slots of the last track_locate (nrs_track_result; waits)"""
+        nbytes = C.c_uint64(0)
+        self._chk(self.lib.nrs_track_result(self.h, int(which), None, 0, C.byref(nbytes)))
+        dt = self.real if which == TRACK_ATTRIBUTE else np.uint32
+        a = np.empty(nbytes.value // np.dtype(dt).itemsize, dtype=dt)
+        if nbytes.value:
+            self._chk(self.lib.nrs_track_result(self.h, int(which), _ptr(a), nbytes.value, None))
+        return a.reshape(-1, 4) if which == TRACK_ATTRIBUTE else a
+
+    def track_device_ptr(self, which):
+        p, b = C.c_void_p(), C.c_uint64()
+        self._chk(self.lib.nrs_track_device_ptr(self.h, int(which), C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def track_emit_value(self, slot, a):
+        """the record given to the particles of emitter `slot`, or, slot -1, of emit_block, appended uploads and count growth"""
+        v = (C.c_double * 4)(*[float(x) for x in a])
+        self._chk(self.lib.nrs_track_emit_value(self.h, int(slot), v))
+
+    def track_locate(self, first_id, count):
+        """the slot of ids first_id .. first_id + count - 1 in the current order, TRACK_NONE where an id does not live
+        (nrs_track_locate, then its result on the host)"""
+        self._chk(self.lib.nrs_track_locate(self.h, int(first_id), int(count)))
+        return self.track_result(TRACK_SLOT_OF)
+
+    def track_diffuse(self, kappa, dt=0.0):
+        """one explicit Euler step of da/dt = kappa_c lap a on the attribute record (nrs_track_diffuse; dt 0: the context's timestep)"""
+        k = (C.c_double * 4)(*[float(x) for x in np.broadcast_to(np.asarray(kappa, np.float64), (4,))])
+        self._chk(self.lib.nrs_track_diffuse(self.h, k, float(dt)))
 
     @property
     def n_owned(self):

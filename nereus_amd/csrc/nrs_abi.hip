@@ -564,6 +564,52 @@ int nrs_sinks_count(nrs_ctx *ctx, uint64_t *removed_total, uint64_t *culls)
     CTX_GUARD(ctx);
     return ctx->impl->sinks_count(removed_total, culls);
 }
+int nrs_track_enable(nrs_ctx *ctx, uint32_t flags)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->track_enable(flags);
+}
+int nrs_track_disable(nrs_ctx *ctx)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->track_disable();
+}
+int nrs_track_info(nrs_ctx *ctx, int *on, uint32_t *flags, uint64_t *next_id)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->track_info(on, flags, next_id);
+}
+int nrs_track_upload(nrs_ctx *ctx, uint32_t which, const void *src, uint64_t first, uint64_t count)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->track_upload(which, src, first, count);
+}
+int nrs_track_result(nrs_ctx *ctx, uint32_t which, void *dst, uint64_t dst_bytes, uint64_t *out_bytes)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->track_result(which, dst, dst_bytes, out_bytes);
+}
+int nrs_track_device_ptr(nrs_ctx *ctx, uint32_t which, void **dptr, uint64_t *bytes)
+{
+    CTX_GUARD(ctx);
+    if (!dptr || !bytes) return fail(NRS_E_INVALID, "NULL argument");
+    return ctx->impl->track_device_ptr(which, dptr, bytes);
+}
+int nrs_track_emit_value(nrs_ctx *ctx, int32_t slot, const double a[4])
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->track_emit_value(slot, a);
+}
+int nrs_track_locate(nrs_ctx *ctx, uint64_t first_id, uint64_t count)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->track_locate(first_id, count);
+}
+int nrs_track_diffuse(nrs_ctx *ctx, const double kappa[4], double dt)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->track_diffuse(kappa, dt);
+}
 uint64_t nrs_slab_message_bytes(uint64_t capacity, int precision) { return 16 + capacity * 2 * (precision == 64 ? 32 : 16); }
 
 int nrs_max_density(nrs_ctx *ctx, double *out)

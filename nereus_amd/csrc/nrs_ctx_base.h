@@ -166,6 +166,16 @@ struct CtxBase {
     virtual int sinks_set(const nrs_sink_config *cfg) = 0;
     virtual int cull(uint64_t *removed) = 0;
     virtual int sinks_count(uint64_t *removedTotal, uint64_t *culls) = 0;
+    // particle identity and attributes (nrs_kernels_track.h; the host decisions: nrs_host_track.h)
+    virtual int track_enable(uint32_t flags) = 0;
+    virtual int track_disable() = 0;
+    virtual int track_info(int *on, uint32_t *flags, uint64_t *nextId) = 0;
+    virtual int track_upload(uint32_t which, const void *src, uint64_t first, uint64_t count) = 0;
+    virtual int track_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) = 0;
+    virtual int track_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) = 0;
+    virtual int track_emit_value(int32_t slot, const double *a) = 0;
+    virtual int track_locate(uint64_t firstId, uint64_t count) = 0;
+    virtual int track_diffuse(const double *kappa, double dt) = 0;
     hipStream_t stream = nullptr;
     bool ownStream = false;
     int device = 0;

@@ -21,6 +21,8 @@
 // read the particle state — field sampling, surface extraction, diffuse particles — depend on the precision and the kernel set: rd
 // (FluidReaders<R, KSET>, nrs_readers.h) holds their buffers, launches on them and copies their results out; the context tells it per call
 // what the fluid is now (fluid_now).  The sources and sinks change n and the array state: their buffers are inflow's (InflowSystem, nrs_inflow.h).
+// Particle tracking follows the particle arrays — gathered where they are reordered, swapped where they swap, written where particles are
+// created: the ids, births and records, the id counter and the emit values are track's (TrackSystem, nrs_track.h).
 // Host bookkeeping that depends on none of them lives in plain structs the context holds as members, or in pure functions it calls:
 // the stage timer (nrs_host_profile.h), the snapshot ring (nrs_host_snapshot.h), the solver settings and their validation
 // (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
@@ -55,6 +57,7 @@
 #include "nrs_slab_exchange.h"
 #include "nrs_readers.h"
 #include "nrs_inflow.h"
+#include "nrs_track.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
 
@@ -332,6 +335,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         NRSCHK(validate("nrs_upload_particles"));
         if (first + count > cap) return fail(NRS_E_CAPACITY, "upload exceeds capacity");
+        if (track.on && count && !pos4) return fail(NRS_E_INVALID, "pos4 is NULL"); // (tracking: refused before the ids are handed out)
+        if (track.on) NRSCHK(track_new_slots(track_fresh_after_upload(n, first, count))); // slots at or above the old n are new particles
         NRSCHK(compact_holes());
         if (count) {
             if (!pos4) return fail(NRS_E_INVALID, "pos4 is NULL");
@@ -355,6 +360,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         NRSCHK(validate("nrs_set_num_particles"));
         if (nn > cap) return fail(NRS_E_CAPACITY, "n exceeds capacity");
+        if (track.on) NRSCHK(track_new_slots(track_fresh_after_set_n(n, nn))); // growing: fresh ids; shrinking drops the tail
         NRSCHK(compact_holes());
         if (nn != n) st.to_fresh();
         if (nn != n) ++particleGen;
@@ -502,6 +508,11 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             dfSt.kvValid = true;
         }
         NRSCHK(ev_end());
+        if (track.on) { // id, birth and the record into sorted order: one launch, an entry of its own in the reorder stage's count
+            NRSCHK(ev_begin(NRS_STAGE_REORDER));
+            track.template gather<R>(sort.index(), N, stream);
+            NRSCHK(ev_end());
+        }
         return NRS_OK;
     }
 
@@ -1270,6 +1281,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(refuse_mid_iisph("nrs_slab_configure"));
         NRSCHK(slab_refuse_configure(cfg.solver, bt.has_bodies(), lo, hi, halo));
         if (inflow.configured()) return inflow_refuse_slab();
+        if (track.on) return track_refuse_slab_configure();
         bool cutsChanged = false;
         exch.configure(lo, hi, halo, &cutsChanged);
         // the last force kernel classified (and marked dead keys) for the old cuts: partition the slow way once
@@ -1448,6 +1460,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         }
         if (pressure_swaps(cfg.solver)) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB, PBF its lambda, DFSPH K)
         if (dfsph()) std::swap(dfKvA.p, dfKvB.p);
+        if (track.on) track.swap();
         return NRS_OK;
     }
     int step(int nsteps, int stop) override
@@ -1614,7 +1627,21 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         ++particleGen;
         st.to_fresh();
     }
-    EmitOut<R> emit_out() { return EmitOut<R>{posA.as<T4>(), velA.as<T4>(), presA.as<R>(), dfsph() ? dfKvA.as<R>() : (R *)nullptr, (uint32_t)n}; }
+    // where the particles of emit value `slot` (-1: nrs_emit_block) go; tracking: their ids start at firstId
+    EmitOut<R> emit_out(int32_t slot, uint32_t firstId)
+    {
+        EmitOut<R> O{};
+        O.pos = posA.as<T4>(); O.vel = velA.as<T4>(); O.pres = presA.as<R>(); O.kv = dfsph() ? dfKvA.as<R>() : (R *)nullptr;
+        O.first = (uint32_t)n;
+        if (track.on) {
+            const TrackView<R> v = track.template cur<R>();
+            const double *a = track.emit_value(slot);
+            O.id = v.id; O.birth = v.birth; O.rec = v.rec;
+            O.firstId = firstId; O.birthNow = track_birth(stepsDone);
+            O.recValue.x = (R)a[0]; O.recValue.y = (R)a[1]; O.recValue.z = (R)a[2]; O.recValue.w = (R)a[3];
+        }
+        return O;
+    }
     int emitter_set(uint32_t slot, const nrs_emitter *e) override
     {
         NRSCHK(inflow_check_slot(slot));
@@ -1641,7 +1668,9 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         uint64_t m = 0;
         NRSCHK(inflow_check_block(lattice, vel, n, cap, &m));
         NRSCHK(inflow_refusal(false, midStep, iisphPhase != 0, true));
-        NRSCHK(inflow.template emit_block<R>(lattice_from(*lattice), vel, (uint32_t)m, emit_out(), stream));
+        uint32_t firstId = 0;
+        if (track.on) NRSCHK(track.ids.reserve(m, &firstId));
+        NRSCHK(inflow.template emit_block<R>(lattice_from(*lattice), vel, (uint32_t)m, emit_out(-1, firstId), stream));
         n += m;
         particles_changed();
         if (added) *added = m;
@@ -1661,30 +1690,47 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return NRS_OK;
     }
     // one cull with the current sinks: count, scan, read the survivor count back (the wait); only when something goes: compact and swap
-    int cull_now(uint64_t *removed)
+    // (in two halves: between them the top of a tracked step learns how much room its emitters get, and may still refuse)
+    CullBounds<R> cull_bounds() const { return inflow_bounds<R>(inflow.haveSinks ? &inflow.sinks : nullptr, PU.worldOrigin, PU.gridSize, PU.cellSize); }
+    int cull_count(uint32_t *keep)
+    {
+        *keep = (uint32_t)n;
+        if (!n) return NRS_OK;
+        NRSCHK(inflow.template count<R>(posA.as<T4>(), cull_bounds(), (uint32_t)n, stream, keep));
+        if (*keep > n) return fail(NRS_E_STATE, "cull: more survivors than particles");
+        return NRS_OK;
+    }
+    int cull_finish(uint32_t keep, uint64_t *removed)
     {
         *removed = 0;
-        if (n) {
-            const CullBounds<R> B = inflow_bounds<R>(inflow.haveSinks ? &inflow.sinks : nullptr, PU.worldOrigin, PU.gridSize, PU.cellSize);
-            const uint32_t N = (uint32_t)n;
-            uint32_t keep = 0;
-            NRSCHK(inflow.template count<R>(posA.as<T4>(), B, N, stream, &keep));
-            if (keep > N) return fail(NRS_E_STATE, "cull: more survivors than particles");
-            if (keep < N) {
-                const CullArrays<R> A{posA.as<T4>(), velA.as<T4>(), presA.as<R>(), dfsph() ? dfKvA.as<R>() : (const R *)nullptr,
-                                      posB.as<T4>(), velB.as<T4>(), presB.as<R>(), dfsph() ? dfKvB.as<R>() : (R *)nullptr};
-                NRSCHK(inflow.template compact<R>(A, B, N, stream));
-                std::swap(posA.p, posB.p);
-                std::swap(velA.p, velB.p);
-                std::swap(presA.p, presB.p);
-                if (dfsph()) std::swap(dfKvA.p, dfKvB.p);
-                *removed = N - keep;
-                n = keep;
-                particles_changed();
+        const uint32_t N = (uint32_t)n;
+        if (keep < N) {
+            CullArrays<R> A{posA.as<T4>(), velA.as<T4>(), presA.as<R>(), dfsph() ? dfKvA.as<R>() : (const R *)nullptr,
+                            posB.as<T4>(), velB.as<T4>(), presB.as<R>(), dfsph() ? dfKvB.as<R>() : (R *)nullptr};
+            if (track.on) {
+                const TrackView<R> from = track.template cur<R>(), to = track.template other<R>();
+                A.id = from.id; A.birth = from.birth; A.rec = from.rec;
+                A.idTo = to.id; A.birthTo = to.birth; A.recTo = to.rec;
             }
+            NRSCHK(inflow.template compact<R>(A, cull_bounds(), N, stream));
+            std::swap(posA.p, posB.p);
+            std::swap(velA.p, velB.p);
+            std::swap(presA.p, presB.p);
+            if (dfsph()) std::swap(dfKvA.p, dfKvB.p);
+            if (track.on) track.swap();
+            *removed = N - keep;
+            n = keep;
+            particles_changed();
         }
         inflow.culled(*removed);
         return NRS_OK;
+    }
+    int cull_now(uint64_t *removed)
+    {
+        uint32_t keep = 0;
+        *removed = 0;
+        NRSCHK(cull_count(&keep));
+        return cull_finish(keep, removed);
     }
     int cull(uint64_t *removed) override
     {
@@ -1698,9 +1744,16 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // the top of a step (step(), nrs_iisph_predict): the sinks, then the emitters' layers of this step, slots ascending
     int apply_inflow()
     {
-        if (inflow.cull_due()) {
+        const bool due = inflow.cull_due();
+        uint32_t keep = (uint32_t)n;
+        if (due) NRSCHK(cull_count(&keep));
+        if (track.on && track_ids_of_step(keep) != NRS_OK) { // refused before anything moved: this step does not count
+            inflow.step_not_taken();
+            return NRS_E_CAPACITY;
+        }
+        if (due) {
             uint64_t r = 0;
-            NRSCHK(cull_now(&r));
+            NRSCHK(cull_finish(keep, &r));
         }
         bool any = false;
         std::vector<double> offsets;
@@ -1710,12 +1763,105 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             offsets.clear();
             inflow_schedule(inflow.slots[si], (double)PU.timestep, room, offsets);
             if (offsets.empty()) continue;
-            NRSCHK(inflow.template emit<R>(si, offsets, emit_out(), stream));
+            uint32_t firstId = 0;
+            if (track.on) NRSCHK(track.ids.reserve(before - room, &firstId)); // (fits: track_ids_of_step)
+            NRSCHK(inflow.template emit<R>(si, offsets, emit_out((int32_t)si, firstId), stream));
             n += before - room;
             any = true;
         }
         if (any) particles_changed();
         return NRS_OK;
+    }
+    // the ids this step's layers need, with `living` particles behind the cull: the schedule counted without touching the slots (inflow_schedule_count); NRS_E_CAPACITY when
+    // they pass the last id, with nothing changed
+    int track_ids_of_step(uint32_t living) const
+    {
+        if (!inflow.emitter_enabled()) return NRS_OK;
+        uint64_t room = cap - living, need = 0;
+        for (const EmitterSlot &sl : inflow.slots) need += inflow_schedule_count(sl, (double)PU.timestep, room);
+        return track_ids_fit(track.ids.next, need);
+    }
+
+    // ---- particle identity and attributes (include/nereus_hip.h; DESIGN.md "Particle identity and attributes") ----------------------------------
+    // The tracked arrays, the id counter and the emit values are track's (nrs_track.h).  They follow the particle arrays: gathered behind a
+    // step's reorder (stage_prefix), swapped where those swap (end_of_step, cull_finish), written by emission, filled for the slots an
+    // upload or a count change makes new.  With tracking never enabled nothing here runs.
+    TrackSystem track;
+    TrackFacts track_facts() const { return TrackFacts{track.on, track.flags, midStep, iisphPhase != 0}; }
+    // the slots f of the current order are new particles: fresh ids, born now, the emit value of slot -1
+    int track_new_slots(const TrackFresh &f)
+    {
+        uint32_t firstId = 0;
+        NRSCHK(track.ids.reserve(f.count, &firstId));
+        return track.template fill<R>(f.first, f.count, firstId, track_birth(stepsDone), track.emit_value(-1), stream);
+    }
+    int track_enable(uint32_t flags) override
+    {
+        NRSCHK(track_check_flags(flags));
+        if (exch.on()) return track_refuse_slab();
+        NRSCHK(refuse_mid_iisph("nrs_track_enable"));
+        NRSCHK(validate("nrs_track_enable"));
+        return track.template enable<R>(flags, cap, n, stream);
+    }
+    int track_disable() override { return track.disable(stream); }
+    int track_info(int *on, uint32_t *flags, uint64_t *nextId) override
+    {
+        if (on) *on = track.on ? 1 : 0;
+        if (flags) *flags = track.flags;
+        if (nextId) *nextId = track.ids.next;
+        return NRS_OK;
+    }
+    int track_upload(uint32_t which, const void *src, uint64_t first, uint64_t count) override
+    {
+        NRSCHK(track_refusal(track_facts(), false, false));
+        NRSCHK(refuse_mid_iisph("nrs_track_upload"));
+        NRSCHK(track_check_upload(which, track.flags, src, first, count, n));
+        uint64_t next = track.ids.next;
+        if (which == NRS_TRACK_ID) NRSCHK(track_ids_uploaded((const uint32_t *)src, count, next, &next));
+        NRSCHK(track.template upload<R>(which, src, first, count, stream));
+        track.ids.next = next;
+        return NRS_OK;
+    }
+    int track_device_ptr(uint32_t which, void **dptr, uint64_t *bytes) override
+    {
+        NRSCHK(track_refusal(track_facts(), false, true));
+        NRSCHK(track_route_result(which, track.flags, track.haveLocate, n, track.located, FluidReaders<R, KSET>::PRECISION, bytes));
+        *dptr = *bytes ? track.result(which) : nullptr;
+        return NRS_OK;
+    }
+    int track_result(uint32_t which, void *dst, uint64_t dstBytes, uint64_t *outBytes) override
+    {
+        void *p = nullptr;
+        uint64_t sz = 0;
+        NRSCHK(track_device_ptr(which, &p, &sz));
+        return FluidReaders<R, KSET>::copy_out(dst, dstBytes, p, sz, outBytes, stream);
+    }
+    int track_emit_value(int32_t slot, const double *a) override
+    {
+        NRSCHK(track_refusal(track_facts(), true, false));
+        NRSCHK(track_check_emit_value(slot, a));
+        std::memcpy(track.emitValue[slot + 1], a, 4 * sizeof(double));
+        return NRS_OK;
+    }
+    int track_locate(uint64_t firstId, uint64_t count) override
+    {
+        NRSCHK(track_refusal(track_facts(), false, true));
+        NRSCHK(track_check_locate(firstId, count));
+        return track.locate(firstId, count, n, stream);
+    }
+    // on the sampler's particle grid (its refusals, its cache rule, nrs_sample_builds), as the diffuse particles read the fluid
+    int track_diffuse(const double *kappa, double dt) override
+    {
+        NRSCHK(track_refusal(track_facts(), true, true));
+        NRSCHK(track_check_diffuse(kappa, dt));
+        NRSCHK(validate("nrs_track_diffuse"));
+        const FluidNow<R> f = fluid_now();
+        NRSCHK(sample_refusal(f.facts));
+        const bool walls = bt.count() != 0;
+        GridView<R> G;
+        NRSCHK(rd.grid(f, walls, G));
+        return track.template diffuse<R, KSET>(P, G, walls, rd.sm.template sorted_pos<T4>(), rd.sm.template sorted_vel<T4>(), rd.sm.sorted_index(),
+                                               rd.sm.sorted_count(), kappa, dt == 0.0 ? (double)P.timestep : dt, stream);
     }
 };
 

@@ -185,6 +185,25 @@ static inline void inflow_schedule(EmitterSlot &sl, double dt, uint64_t &room, s
         }
     }
 }
+// the sites inflow_schedule would emit for this slot and step, with nothing changed but `room` (the same arithmetic on copies of the
+// accumulator and the count): a tracked step asks before it hands out ids (nrs_ctx_impl.h)
+static inline uint64_t inflow_schedule_count(const EmitterSlot &sl, double dt, uint64_t &room)
+{
+    if (!sl.used || !sl.e.enabled) return 0;
+    double acc = sl.acc;
+    acc += sl.e.speed * dt;
+    const uint64_t sites = sl.sites.sites;
+    uint64_t emitted = sl.emitted, total = 0;
+    while (acc >= sl.s) {
+        acc -= sl.s;
+        if (sites <= room && (!sl.e.max_particles || emitted + sites <= sl.e.max_particles)) {
+            room -= sites;
+            emitted += sites;
+            total += sites;
+        }
+    }
+    return total;
+}
 static inline void inflow_origin(const EmitterSlot &sl, double offset, double o[3])
 {
     for (int a = 0; a < 3; ++a) o[a] = sl.e.center[a] + offset * sl.f.d[a];

@@ -45,6 +45,9 @@ struct InflowSystem {
         return inflow_cull_due(stepsSeen, sinks.interval);
     }
 
+    // the step cull_due() counted was refused before anything moved (particle ids exhausted, nrs_track.h)
+    void step_not_taken() { if (haveSinks) --stepsSeen; }
+
     // Count the survivors among the n particles at pos (B: the bounds), wait, and report them.  Nothing is moved.
     template <typename R> int count(const typename Vec4T<R>::type *pos, const CullBounds<R> &B, uint32_t n, hipStream_t stream, uint32_t *survivors)
     {
@@ -94,6 +97,7 @@ struct InflowSystem {
             hipLaunchKernelGGL((k_inflow_emit<R>), dim3(nblocks((uint64_t)A.layers * A.sites)), dim3(BLOCK), 0, stream, A,
                                (const int32_t *)rowHalf[si].as<int32_t>(), (const uint32_t *)rowStart[si].as<uint32_t>(), O);
             O.first += A.layers * A.sites;
+            O.firstId += A.layers * A.sites;
         }
         HIPCHK(hipGetLastError());
         return NRS_OK;

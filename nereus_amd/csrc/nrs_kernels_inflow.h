@@ -24,12 +24,17 @@ struct EmitArgs {
     double v[3]; // speed * d
     uint32_t layers, sites, ku, kv, disc;
 };
-// the arrays a new particle is written to (kv: DFSPH only, else null), from slot `first` on
+// the arrays a new particle is written to (kv: DFSPH only, else null), from slot `first` on; with particle tracking (nrs_track.h) also its
+// id = firstId + t for the launch's site t, its birth stamp and (rec: null without the attribute record) the slot's emit value
 template <typename R> struct EmitOut {
     typedef typename Vec4T<R>::type T4;
     T4 *pos, *vel;
     R *pres, *kv;
     uint32_t first;
+    uint32_t *id, *birth; // null: the context does not track
+    T4 *rec;
+    uint32_t firstId, birthNow;
+    T4 recValue;
 };
 template <typename R> NRS_DEV void emit_store(const EmitOut<R> &O, uint32_t t, R x, R y, R z, R vx, R vy, R vz)
 {
@@ -38,6 +43,11 @@ template <typename R> NRS_DEV void emit_store(const EmitOut<R> &O, uint32_t t, R
     O.vel[to] = mk4<R>(vx, vy, vz, (R)0);
     O.pres[to] = (R)0;
     if (O.kv) O.kv[to] = (R)0;
+    if (O.id) {
+        O.id[to] = O.firstId + t;
+        O.birth[to] = O.birthNow;
+        if (O.rec) O.rec[to] = O.recValue;
+    }
 }
 // One thread per (layer, site), layer-major; which (i, j) site k is and where it lies: inflow_site, inflow_site_pos (nrs_host_inflow.h)
 template <typename R>
@@ -98,6 +108,11 @@ template <typename R> struct CullArrays {
     const R *pres, *kv; // kv: DFSPH only, else null
     T4 *posTo, *velTo;
     R *presTo, *kvTo;
+    // particle tracking (nrs_track.h): id null when the context does not track, rec null without the attribute record
+    const uint32_t *id, *birth;
+    const T4 *rec;
+    uint32_t *idTo, *birthTo;
+    T4 *recTo;
 };
 template <typename R>
 __global__ __launch_bounds__(BLOCK) void k_cull_compact(CullArrays<R> A, CullBounds<R> B, uint32_t n, const uint32_t *__restrict__ blockOff)
@@ -116,6 +131,11 @@ __global__ __launch_bounds__(BLOCK) void k_cull_compact(CullArrays<R> A, CullBou
     A.velTo[to] = A.vel[i];
     A.presTo[to] = A.pres[i];
     if (A.kv) A.kvTo[to] = A.kv[i];
+    if (A.id) {
+        A.idTo[to] = A.id[i];
+        A.birthTo[to] = A.birth[i];
+        if (A.rec) A.recTo[to] = A.rec[i];
+    }
 }
 
 } // namespace nrs

@@ -169,6 +169,7 @@ void SPH::reserveParticles(SUint capacity)
     growHost(capacity);
     if (m_ctx && capacity > m_ctxCapacity) {
         pullDeviceToHost();
+        trackSave();
         releaseContext();
         m_hostDirty = true;
     }
@@ -192,6 +193,7 @@ void SPH::ensureContext()
     if (m_ctx && m_ctxCapacity >= m_numParticles) return;
     if (m_ctx) { // capacity exceeded: save the state and rebuild a larger context
         pullDeviceToHost();
+        trackSave();
         releaseContext();
         m_hostDirty = true;
     }
@@ -207,6 +209,7 @@ void SPH::ensureContext()
     cfg.capacity = std::max<SUint>(m_hostCapacity, m_numParticles);
     if (nrs_create(&cfg, &m_params, &m_ctx) != NRS_OK) fatal("nrs_create");
     m_ctxCapacity = (SUint)cfg.capacity;
+    m_trackPending = m_tracking; // enabled behind the first upload (trackStart)
     configureContext();
     if (m_boundariesPending && m_bi && m_vbi && m_num_boundaries) {
         if (nrs_set_boundaries(m_ctx, m_bi, m_vbi, m_num_boundaries, 0) != NRS_OK) fatal("nrs_set_boundaries");
@@ -518,13 +521,134 @@ nrs_ctx *SPH::deviceContext()
 
 void SPH::pushHostToDevice()
 {
-    if (!m_hostDirty) return;
-    if (nrs_set_num_particles(m_ctx, 0) != NRS_OK) fatal("nrs_set_num_particles");
-    if (m_numParticles &&
-        nrs_upload_particles(m_ctx, m_pos, m_vel, m_pressure, 0, m_numParticles) != NRS_OK)
-        fatal("nrs_upload_particles");
-    m_hostDirty = false;
-    m_deviceNewer = false;
+    if (m_hostDirty) {
+        // a tracking context keeps identities: slots below the device's count are the same particles, rewritten; the rest are new
+        const bool keep = m_tracking && !m_trackPending;
+        const SUint onDevice = keep ? (SUint)nrs_num_particles(m_ctx) : 0;
+        if ((!keep || onDevice > m_numParticles) && nrs_set_num_particles(m_ctx, keep ? m_numParticles : 0) != NRS_OK) fatal("nrs_set_num_particles");
+        if (m_numParticles &&
+            nrs_upload_particles(m_ctx, m_pos, m_vel, m_pressure, 0, m_numParticles) != NRS_OK)
+            fatal("nrs_upload_particles");
+        m_hostDirty = false;
+        m_deviceNewer = false;
+        m_colDirty = keep; // (the host's colours go with the host's particles)
+    }
+    if (!m_tracking) return;
+    if (m_trackPending) {
+        trackStart();
+    } else if (m_colDirty) {
+        if (m_numParticles && nrs_track_upload(m_ctx, NRS_TRACK_ATTRIBUTE, m_colors, 0, m_numParticles) != NRS_OK) fatal("nrs_track_upload");
+        m_colDirty = false;
+    }
+}
+
+// ---- particle tracking ---------------------------------------------------------------------------------------------------------------------
+// the device's ids, births and colours into the host arrays, in the order of its positions
+void SPH::fetchTracked() const
+{
+    const size_t n = (size_t)nrs_num_particles(m_ctx);
+    m_ids.resize(n);
+    m_birth.resize(n);
+    if (!n) return;
+    if (nrs_track_result(m_ctx, NRS_TRACK_ID, m_ids.data(), 4 * n, nullptr) != NRS_OK) fatal("nrs_track_result");
+    if (nrs_track_result(m_ctx, NRS_TRACK_BIRTH, m_birth.data(), 4 * n, nullptr) != NRS_OK) fatal("nrs_track_result");
+    if (n <= m_hostCapacity && nrs_track_result(m_ctx, NRS_TRACK_ATTRIBUTE, m_colors, sizeof(SReal) * 4 * n, nullptr) != NRS_OK) fatal("nrs_track_result");
+}
+// before a context is released to grow: what identifies its particles (the colours are on the host already, pullDeviceToHost)
+void SPH::trackSave()
+{
+    if (!m_tracking || !m_ctx || m_trackPending) return;
+    const size_t n = (size_t)nrs_num_particles(m_ctx);
+    m_ids.resize(n);
+    m_birth.resize(n);
+    if (n && nrs_track_result(m_ctx, NRS_TRACK_ID, m_ids.data(), 4 * n, nullptr) != NRS_OK) fatal("nrs_track_result");
+    if (n && nrs_track_result(m_ctx, NRS_TRACK_BIRTH, m_birth.data(), 4 * n, nullptr) != NRS_OK) fatal("nrs_track_result");
+    uint64_t next = 0;
+    if (nrs_track_info(m_ctx, nullptr, nullptr, &next) != NRS_OK) fatal("nrs_track_info");
+    m_savedNextId = next;
+    m_haveSaved = true;
+}
+// behind the first upload into a context: enable, put back what a released context had, the colours as the record, the emit colours
+void SPH::trackStart()
+{
+    if (nrs_track_enable(m_ctx, NRS_TRACK_ATTR) != NRS_OK) fatal("nrs_track_enable");
+    const size_t n = m_numParticles;
+    if (m_haveSaved && n) {
+        const size_t k = std::min(m_ids.size(), n);
+        std::vector<SUint> ids(n), birth(n, 0);
+        for (size_t i = 0; i < n; ++i) ids[i] = i < k ? m_ids[i] : (SUint)(m_savedNextId + (i - k)); // (particles the old context never saw)
+        for (size_t i = 0; i < k; ++i) birth[i] = m_birth[i];
+        if (m_savedNextId) { // ids are never reused: the counter passes the old one even where the largest ids have left (slot 0 is rewritten below)
+            const SUint top = (SUint)(m_savedNextId - 1);
+            if (nrs_track_upload(m_ctx, NRS_TRACK_ID, &top, 0, 1) != NRS_OK) fatal("nrs_track_upload");
+        }
+        if (nrs_track_upload(m_ctx, NRS_TRACK_ID, ids.data(), 0, n) != NRS_OK) fatal("nrs_track_upload");
+        if (nrs_track_upload(m_ctx, NRS_TRACK_BIRTH, birth.data(), 0, n) != NRS_OK) fatal("nrs_track_upload");
+    }
+    m_haveSaved = false;
+    if (n && nrs_track_upload(m_ctx, NRS_TRACK_ATTRIBUTE, m_colors, 0, n) != NRS_OK) fatal("nrs_track_upload");
+    for (int s = 0; s < 17; ++s)
+        if (m_emitColorSet[s] && nrs_track_emit_value(m_ctx, s - 1, m_emitColors[s]) != NRS_OK) fatal("nrs_track_emit_value");
+    m_trackPending = false;
+    m_colDirty = false;
+    m_ids.clear();
+    m_birth.clear();
+}
+void SPH::setParticleTracking(bool on)
+{
+    if (on == m_tracking) return;
+    if (on) {
+        m_tracking = true;
+        m_trackPending = true;
+        if (m_ctx) pushHostToDevice();
+        return;
+    }
+    if (m_ctx && !m_trackPending) {
+        pullDeviceToHost(); // (the colours stay as the device had them)
+        if (nrs_track_disable(m_ctx) != NRS_OK) fatal("nrs_track_disable");
+    }
+    m_tracking = m_trackPending = m_colDirty = m_haveSaved = false;
+}
+const SUint *SPH::getHostIds()
+{
+    if (!m_tracking) return nullptr;
+    ensureContext();
+    pushHostToDevice();
+    pullDeviceToHost();
+    if (m_ids.size() != m_numParticles) fetchTracked();
+    return m_ids.data();
+}
+const SUint *SPH::getHostBirth()
+{
+    if (!getHostIds()) return nullptr;
+    return m_birth.data();
+}
+void SPH::setEmitterColor(int slot, SVec4 c)
+{
+    if (slot < -1 || slot > 15) { std::fprintf(stderr, "Nereus: setEmitterColor: slot must be -1 .. 15\n"); std::exit(EXIT_FAILURE); }
+    const double a[4] = {(double)c.x, (double)c.y, (double)c.z, (double)c.w};
+    std::memcpy(m_emitColors[slot + 1], a, sizeof(a));
+    m_emitColorSet[slot + 1] = true;
+    if (m_tracking && m_ctx && !m_trackPending && nrs_track_emit_value(m_ctx, slot, a) != NRS_OK) fatal("nrs_track_emit_value");
+}
+void SPH::diffuseColors(const double kappa[4], double dt)
+{
+    if (!m_tracking) { std::fprintf(stderr, "Nereus: diffuseColors needs setParticleTracking(true)\n"); std::exit(EXIT_FAILURE); }
+    ensureContext();
+    pushHostToDevice();
+    if (nrs_track_diffuse(m_ctx, kappa, dt) != NRS_OK) fatal("nrs_track_diffuse");
+    m_deviceNewer = true; // (the colours on the device are newer than the host's)
+    m_ids.clear();
+}
+const std::vector<SUint> &SPH::locateParticles(unsigned long long first, SUint count)
+{
+    if (!m_tracking) { std::fprintf(stderr, "Nereus: locateParticles needs setParticleTracking(true)\n"); std::exit(EXIT_FAILURE); }
+    ensureContext();
+    pushHostToDevice();
+    if (nrs_track_locate(m_ctx, first, count) != NRS_OK) fatal("nrs_track_locate");
+    m_slotOf.resize(count);
+    if (count && nrs_track_result(m_ctx, NRS_TRACK_SLOT_OF, m_slotOf.data(), 4 * (uint64_t)count, nullptr) != NRS_OK) fatal("nrs_track_result");
+    return m_slotOf;
 }
 
 void SPH::pullDeviceToHost() const
@@ -533,6 +657,7 @@ void SPH::pullDeviceToHost() const
     const bool wantPressure = solverKind() == NRS_SOLVER_IISPH || solverKind() == NRS_SOLVER_PCISPH || solverKind() == NRS_SOLVER_PBF ||
                               solverKind() == NRS_SOLVER_DFSPH;
     if (nrs_download(m_ctx, m_pos, m_vel, wantPressure ? m_pressure : nullptr) != NRS_OK) fatal("nrs_download");
+    if (m_tracking && !m_trackPending) fetchTracked(); // the colours, ids and births of the same order
     m_deviceNewer = false;
 }
 
@@ -605,7 +730,14 @@ const SReal *SPH::latestFrame(SUint *numParticles, unsigned long long *step)
 
 SReal *&SPH::getPos() { pullDeviceToHost(); m_hostDirty = true; return m_pos; }
 SReal *&SPH::getVel() { pullDeviceToHost(); m_hostDirty = true; return m_vel; }
-SReal *&SPH::getCol() { return m_colors; }
+SReal *&SPH::getCol()
+{
+    if (m_tracking) { // the colours in the order of the positions; the caller may write them
+        if (m_ctx && !m_trackPending) pullDeviceToHost();
+        m_colDirty = true;
+    }
+    return m_colors;
+}
 SReal *SPH::getHostPos() const
 {
     if (m_asyncReadback && m_ctx && m_deviceNewer && m_framesInFlight > 0) collectFrames(true);
@@ -615,7 +747,11 @@ SReal *SPH::getHostPos() const
 }
 SReal *SPH::getHostVel() const { pullDeviceToHost(); return m_vel; }
 SReal *SPH::getHostPressure() const { pullDeviceToHost(); return m_pressure; }
-SReal *SPH::getHostCol() const { return m_colors; }
+SReal *SPH::getHostCol() const
+{
+    if (m_tracking && m_ctx && !m_trackPending) pullDeviceToHost(); // tracking: in the order of getHostPos(); else as the caller filled it
+    return m_colors;
+}
 
 std::pair<SVec3, SVec3> SPH::computeGridMinMax() const
 {

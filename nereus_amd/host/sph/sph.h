@@ -157,6 +157,24 @@ public:
     void setSinks(const nrs_sink_config *sinks);
     SUint cull();
     void sinkCounts(unsigned long long *removedTotal, unsigned long long *culls);
+    // Particle tracking (nrs_track_*, DESIGN.md "Particle identity and attributes"), off by default; while it is off the colours behave
+    // as in the reference: getHostCol() is the array as the caller filled it, never permuted.  While it is on, the device context is
+    // enabled with NRS_TRACK_ATTR and the colours travel as the attribute record: getHostCol() / getCol() return them in the order of
+    // getHostPos(), getHostIds() and getHostBirth() give each particle's id (unique for the life of the solver, also across a context
+    // rebuilt to grow) and the update() count at its entry, in the same order.  Particles present when tracking starts are numbered
+    // 0 .. n-1 in host order; rewriting positions through getPos() keeps identities, appended particles get new ids.
+    // setEmitterColor(slot, c): the colour of emitter `slot`'s particles, slot -1 that of emitBlock's.  diffuseColors: one explicit
+    // diffusion step of the colours between neighbours (nrs_track_diffuse; dt 0: the timestep; stable while 2 dt kappa restDensity
+    // sum |w_ij| <= 1, not checked).  locateParticles(first, count): the index in getHostPos() order of ids first .. first + count - 1,
+    // 0xffffffff for an id that is gone, in a host array the solver owns.  A context rebuilt to grow keeps ids, births and colours (the
+    // class pulls them and puts them back with nrs_track_upload); emitter colours are applied again.
+    void setParticleTracking(bool on);
+    bool getParticleTracking() const { return m_tracking; }
+    const SUint *getHostIds();
+    const SUint *getHostBirth();
+    void setEmitterColor(int slot, SVec4 color);
+    void diffuseColors(const double kappa[4], double dt = 0.0);
+    const std::vector<SUint> &locateParticles(unsigned long long first, SUint count);
     void reserveParticles(SUint capacity);        // grow host+device storage up front
     void setEagerSync(bool on) { m_eagerSync = on; } // true: D2H at the end of every update() like the reference
     const SphSimParams &getParams() const { return m_params; }
@@ -168,7 +186,8 @@ public:
     // dt = lambda * h / max|v| (lambda = 0.4) from a device-side reduction; off by default as in the reference build
     void setAdaptiveTimestep(bool on, SReal lambda = 0.4f) { m_cfl = on; m_cflLambda = lambda; }
     // binary checkpoint of the particle state (parameters, positions, velocities, IISPH warm-start pressure);
-    // the reference has none.  A restored solver continues bit-identically.
+    // the reference has none.  A restored solver continues bit-identically.  The format does not hold particle ids, births
+    // or colours: a solver that tracks its particles numbers a loaded state afresh, as it does not hold poses, emitters or sinks.
     bool saveState(const char *path) const;
     bool loadState(const char *path);
     // Viewer hand-off that does not stall the solver (the reference copies pos+vel back synchronously at the end of every
@@ -232,6 +251,17 @@ protected:
     std::vector<SUint> m_diffuseKinds;
     bool m_inflow = false; // emitters or sinks were configured: the device's particle count leads
     void adoptDeviceCount();
+    // particle tracking: asked for / the context still has to be enabled (trackStart, at the next upload) / colours edited on the host
+    bool m_tracking = false, m_trackPending = false, m_colDirty = false;
+    mutable std::vector<SUint> m_ids, m_birth; // host copies, in getHostPos() order
+    std::vector<SUint> m_slotOf;               // the last locateParticles
+    bool m_haveSaved = false;                  // m_ids / m_birth hold what a released context had: trackStart puts them back
+    unsigned long long m_savedNextId = 0;
+    double m_emitColors[17][4] = {};           // [slot + 1]
+    bool m_emitColorSet[17] = {};
+    void trackStart();
+    void trackSave();
+    void fetchTracked() const;
 };
 
 NEREUS_NAMESPACE_END

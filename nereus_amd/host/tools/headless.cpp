@@ -37,6 +37,14 @@
 //                                                               rest spacings, 4 m/s) and a domain sink (SPH::setSinks); <steps> updates,
 //                                                               then out.bin: u32 n, u32 precision (32 | 64), u64 emitted, u64 dropped,
 //                                                               u64 removed, u64 culls, pos4[n], vel4[n]
+//   headless track <solver> <steps> <out.txt> [kappa]           the faucet scene with SPH::setParticleTracking(true) and two touching disc
+//                                                               emitters, red (slot 0, left) and blue (slot 1, right); SPH::diffuseColors
+//                                                               with kappa (default 0.05; 0: never) on r, g, b after every update;
+//                                                               out.txt: "id birth x y z r g b a" per living particle
+//   headless colours <solver> <steps> <track 0|1> <out.txt>     the shipped cube with colour.r = the particle's number, <steps> updates (tracking:
+//                                                               then a context rebuilt to grow and one more); out.txt per number k:
+//                                                               "k slot id r", slot from SPH::locateParticles (k without tracking), r =
+//                                                               getHostCol()[4 * slot]
 // in.bin : u32 n, u32 nb, then pos4[n], vel4[n], bi4[nb], vbi[nb] (SReal)
 // out.bin: u32 n, u32 nb, u32 iters, u32 sizeof(params), params, pos4[n], vel4[n], pressure[n], bi4[nb], vbi[nb]
 #include <cmath>
@@ -148,6 +156,68 @@ int main(int argc, char **argv)
         std::fwrite(sim->getHostVel(), sizeof(SReal) * 4, n, o);
         std::fclose(o);
         std::printf("faucet: %u particles after %d steps (%llu emitted, %llu removed)\n", n, steps, emitted, removed);
+    } else if (mode == "track") {
+        if (argc < 5) die("track needs <steps> <out.txt> [kappa]");
+        const int steps = std::atoi(argv[3]);
+        const double k = argc > 5 ? std::atof(argv[5]) : 0.05;
+        const SphSimParams &P = sim->getParams();
+        const double s0 = std::cbrt((double)P.particleMass / (double)P.restDensity);
+        sim->setParticleTracking(true);
+        nrs_sink_config sk;
+        std::memset(&sk, 0, sizeof(sk));
+        sk.flags = NRS_SINK_DOMAIN;
+        sim->setSinks(&sk);
+        for (int e = 0; e < 2; ++e) { // two touching jets: red on the left, blue on the right
+            nrs_emitter em;
+            std::memset(&em, 0, sizeof(em));
+            em.shape = NRS_EMITTER_DISC; em.enabled = 1;
+            em.center[0] = (e ? 2.5 : -2.5) * s0; em.center[1] = -0.9; em.direction[1] = -1.0;
+            em.half_extent[0] = 2.5 * s0;
+            em.speed = 4.0;
+            sim->setEmitter((SUint)e, &em);
+            sim->setEmitterColor(e, e ? make_SVec4(0, 0, 1, 1) : make_SVec4(1, 0, 0, 1));
+        }
+        const double kappa[4] = {k, k, k, 0.0};
+        for (int s = 0; s < steps; ++s) {
+            sim->update();
+            if (k > 0.0) sim->diffuseColors(kappa);
+        }
+        const unsigned n = sim->getNumParticles();
+        const SUint *ids = sim->getHostIds(), *birth = sim->getHostBirth();
+        const SReal *x = sim->getHostPos(), *c = sim->getHostCol();
+        FILE *o = std::fopen(argv[4], "w");
+        if (!o) die("cannot open output");
+        for (unsigned i = 0; i < n; ++i)
+            std::fprintf(o, "%u %u %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", ids[i], birth[i], (double)x[4 * i], (double)x[4 * i + 1], (double)x[4 * i + 2],
+                         (double)c[4 * i], (double)c[4 * i + 1], (double)c[4 * i + 2], (double)c[4 * i + 3]);
+        std::fclose(o);
+        std::printf("track: %u particles after %d steps\n", n, steps);
+    } else if (mode == "colours") {
+        if (argc < 6) die("colours needs <steps> <track 0|1> <out.txt>");
+        const int steps = std::atoi(argv[3]);
+        const bool track = std::atoi(argv[4]) != 0;
+        sim->generateParticleCube(make_SVec4(-0.4, 0.04, 0.5, 1.0), make_SVec4(0.5, 0.5, 0.5, 1.0), make_SVec4(0, 0, 0, 0));
+        const unsigned n = sim->getNumParticles();
+        sim->setParticleTracking(track);
+        SReal *col = sim->getCol();
+        for (unsigned i = 0; i < n; ++i) { col[4 * i] = (SReal)i; col[4 * i + 1] = (SReal)0.5; col[4 * i + 2] = (SReal)0; col[4 * i + 3] = (SReal)1; }
+        for (int s = 0; s < steps; ++s) sim->update();
+        if (track) sim->reserveParticles(2 * MAX_PARTICLE_NUMBER); // a context rebuilt to grow keeps ids, births and colours
+        if (track) sim->update();
+        FILE *o = std::fopen(argv[5], "w");
+        if (!o) die("cannot open output");
+        const SReal *c = sim->getHostCol();
+        std::vector<SUint> slotOf(n);
+        for (unsigned k = 0; k < n; ++k) slotOf[k] = k;
+        if (track) slotOf = sim->locateParticles(0, n);
+        for (unsigned k = 0; k < n && k < 16 && track; ++k) slotOf[k] = sim->locateParticles(k, 1)[0]; // (one id at a time gives the same)
+        const SUint *ids = track ? sim->getHostIds() : nullptr;
+        for (unsigned k = 0; k < n; ++k) {
+            const unsigned slot = slotOf[k];
+            const unsigned id = track ? ids[slot] : k;
+            std::fprintf(o, "%u %u %u %.9g\n", k, slot, id, (double)c[4 * slot]);
+        }
+        std::fclose(o);
     } else if (mode == "run" || mode == "frames" || mode == "lattice" || mode == "surface" || mode == "diffuse") {
         if (argc < 6) die("run needs <in.bin> <steps> <out.bin>");
         if (mode == "lattice" && argc < 13) die("lattice needs <in.bin> <steps> <ox> <oy> <oz> <spacing> <dx> <dy> <dz> <out.lat>");
