@@ -60,6 +60,34 @@ def check_cell_tables(cs_a, ce_a, cs_b, ce_b):
     np.testing.assert_array_equal(ce_a[m], ce_b[m])
 
 
+def next_sorted_keys(params, pos, real):
+    """The `hash` (sorted cell keys) and `index` (stable argsort: the slot each sorted particle had in `pos`) that the step taken from
+    the positions `pos` must show, whichever sort path the context takes: the coherent re-sort's merge and the full radix sort both
+    claim this order.  pos: the positions the step starts from, in the context's order (a download after the step before); params:
+    the context's; real: its SReal.  Built on diffuse_model's cells and sorted_order, whose power-of-two wrap is the reference's.  A cell
+    coordinate that is NaN or outside int32 converts as the device's (int) does (NaN -> 0, saturating), which numpy's cast
+    does not promise: those rows get their cells here and the stable sort is taken of the keys directly."""
+    from tests import diffuse_model as dm  # (imports the smoothing-kernel models; only this helper needs them)
+
+    gs = np.asarray(params["gridSize"]).reshape(-1)[:3].astype(np.int64)
+    wo = np.asarray(params["worldOrigin"]).reshape(-1)[:3].astype(real)
+    cs = np.asarray(params["cellSize"]).reshape(-1)[:3].astype(real)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = dm.cells(params, pos, real)
+        q = np.floor((np.asarray(pos)[:, :3].astype(real) - wo) / cs)
+    odd = ~(np.abs(q) < 2.0 ** 31)
+    if odd.any():
+        c[odd] = np.where(np.isnan(q[odd]), 0, np.where(q[odd] > 0, 2 ** 31 - 1, -2 ** 31))
+        c &= gs - 1
+        keys = (c[:, 2] * gs[1] + c[:, 1]) * gs[0] + c[:, 0]
+        index = np.argsort(keys, kind="stable")
+    else:
+        c &= gs - 1
+        keys = (c[:, 2] * gs[1] + c[:, 1]) * gs[0] + c[:, 0]
+        index = dm.sorted_order(params, pos, real)
+    return keys[index].astype(np.uint32), index.astype(np.uint32)
+
+
 def close_masked(got, want, tol, what=""):
     """NaN-aware comparison: the non-finite entries are the same element for element (NaN where NaN, inf of the same sign), the
     finite ones are within `tol` array-relative.  Returns the error of the finite entries."""
