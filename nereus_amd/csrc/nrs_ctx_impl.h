@@ -28,7 +28,9 @@
 // (nrs_host_settings.h), the grid a boundary box asks for (nrs_host_grid.h), the decisions of the slab exchange — window, partition
 // form, stream totals, unpack offsets — (nrs_host_slab.h), the state of the particle arrays with its transitions and the sort stage's
 // choice (nrs_host_state.h), the step plan and the exit rule of the solver loops (nrs_host_plan.h), what differs by solver — stages,
-// stale and derived constants, buffers, what an array or statistic id means — with one state struct per solver (nrs_host_solver.h).
+// stale and derived constants, buffers, what an array or statistic id means — with one state struct per solver (nrs_host_solver.h),
+// the geometry of the neighbour scan — the cell-table window that makes P of PU, the cut-offs of the exact test, the quantisation
+// set-up of the compact scan, the wall workgroups of a launch — (nrs_host_scan.h, which the kernels include too: nrs_math.h).
 // Every buffer, pinned landing and event frees itself (DevBuf, PinnedBuf, Event: nrs_ctx_base.h); ~Ctx only synchronises.
 #pragma once
 #include "nrs_ctx_base.h"
@@ -72,33 +74,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // rebases x: the sort order, and with it every per-particle result, is the one of the global grid.
     Params<R> PU, P;
     SlabExchange<R> exch; // the cuts, the window, the last pack and its totals, the exchange's buffers and launches (nrs_slab_exchange.h)
+    // geo: the scan's geometry for P — the quantisation set-up of the compact scan (and whether the grid allows it) and the two
+    // cut-offs of the exact test (nrs_host_scan.h).  Both follow P: derived here, wherever the parameters or the window change.
+    ScanGeometry geo{};
     void derive_kernel_params()
     {
-        P = PU;
-        P.numBodies = 0;
-        const SlabHost &w = exch.host();
-        if (w.winW && w.winW < PU.gridSize[0]) {
-            P.numBodies = (uint32_t)w.winBase;
-            P.gridSize[0] = w.winW;
-            P.numCells = w.winW * PU.gridSize[1] * PU.gridSize[2];
-        }
-        // compact scan candidates (nrs_math.h): quanta per metre, threshold of the superset test, and whether the geometry allows
-        // it at all (a pair inside the interaction radius must be less than two cells apart on every axis)
-        float hq = 0.0f;
-        qOk = P.gridSize[0] >= 4u; // (narrower grids alias the row's three cells: tags by position fail)
-        for (int a = 0; a < 3; ++a) {
-            qc.o[a] = (double)P.worldOrigin[a];
-            qc.s[a] = QP_PER_CELL / (float)P.cellSize[a];
-            const float r = (float)P.interactionRadius * qc.s[a];
-            qOk = qOk && P.cellSize[a] > (R)0 && std::isfinite(qc.s[a]) && (r + QP_MARGIN < QP_HALF);
-            hq = std::max(hq, r);
-        }
-        const double lim = (double)hq + (double)QP_MARGIN;
-        qT = qOk ? (uint32_t)std::ceil(lim * lim) + 1u : 0u;
+        P = window_params(PU, exch.host().winW, exch.host().winBase);
+        geo = scan_geometry(P);
     }
-    QuantCfg qc;
-    uint32_t qT = 0;
-    bool qOk = false;
     DevBuf gatherPos; // (x, y, z, p / rho^2), (vx, vy, vz, m / rho) side by side per sorted slot: density kernel -> force kernel of the same step (HitBuffer)
     DevBuf qpos; // one word per sorted slot (+ 4 slots of padding), written by the reorder kernels
     nrs_config cfg;
@@ -192,12 +175,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool sesph() const { return cfg.solver == NRS_SOLVER_SESPH; }
     bool pbf() const { return cfg.solver == NRS_SOLVER_PBF; }
     bool dfsph() const { return cfg.solver == NRS_SOLVER_DFSPH; }
-    bool pow2_grid() const { return is_pow2(P.gridSize[0]) && is_pow2(P.gridSize[1]) && is_pow2(P.gridSize[2]); }
+    bool pow2_grid() const { return nrs::pow2_grid(P.gridSize); }
 
     // ---- which kernels a step launches (nrs_host_plan.h) -----------------------------------------------------------------------
     PlanFacts plan_facts() const
     {
-        return PlanFacts{cfg.flags, cfg.solver, KSET == KS_MULLER, std::is_same<R, float>::value, cap, n, qOk, pow2_grid(), bt.near_bits_valid(), bt.count() != 0,
+        return PlanFacts{cfg.flags, cfg.solver, KSET == KS_MULLER, std::is_same<R, float>::value, cap, n, geo.q.ok, pow2_grid(), bt.near_bits_valid(), bt.count() != 0,
                          exch.on(), P.numCells};
     }
     Features features() const { return plan_features(plan_facts()); }
@@ -443,8 +426,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         G.nSorted = (uint32_t)n;
         G.err = errWord.as<uint32_t>();
         G.qpos = plan.quant ? qpos.as<qword_t>() : (const qword_t *)nullptr;
-        G.qT = qT;
-        G.qc = qc;
+        G.qT = geo.q.qT;
+        G.qc = geo.q.qc;
         return G;
     }
     IisphArrays<R> iisph_view() const
@@ -494,12 +477,12 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             hipLaunchKernelGGL((k_reorder_merged<R>), g, b, 0, stream, merged, sort.hash(), sort.index(), posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
                                cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
-                               nearB, wlist.tile_counts(), wlist.slot_masks(), qc, qp);
+                               nearB, wlist.tile_counts(), wlist.slot_masks(), geo.q.qc, qp);
         else
             hipLaunchKernelGGL((k_reorder<R>), g, b, 0, stream, sort.hash(), sort.index(), posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
                                cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
-                               nearB, wlist.tile_counts(), wlist.slot_masks(), qc, qp);
+                               nearB, wlist.tile_counts(), wlist.slot_masks(), geo.q.qc, qp);
         if (iisph() && (cfg.flags & NRS_FLAG_IISPH_SELF_BY_SLOT)) // Q5 off: the pressure kernels skip j == own slot
             hipLaunchKernelGGL(k_identity, g, b, 0, stream, inv.as<uint32_t>(), N);
         if (dfsph()) { // the warm-start inputs of the step, K_prev and Kv_prev, into sorted order
@@ -570,10 +553,10 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
         } else if (plan.staged) {
             if constexpr (std::is_same<R, float>::value)
-                launch_density_staged<KSET, HAS_B>(stream, P, G, share, plan.fast, posB.as<T4>(), dens.as<R>(), presB.as<R>(),
+                launch_density_staged<KSET, HAS_B>(stream, P, G, geo.thr, share, plan.fast, posB.as<T4>(), dens.as<R>(), presB.as<R>(),
                                                    plan.fast ? fastQ.as<FastPair>() : (FastPair *)nullptr, N);
         } else {
-            launch_density_tiled<R, KSET, HAS_B>(stream, P, G, share, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, walls);
+            launch_density_tiled<R, KSET, HAS_B>(stream, P, G, geo.thr, share, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N, walls);
         }
         if (exch.on()) { G.actLo = exch.cuts().lo; G.actHi = exch.cuts().hi; }
         NRSCHK(ev_end());
@@ -613,7 +596,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
                 launch_forces_fast<SURF, HAS_B>(stream, P, G, hb, posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(),
                                                 fastQ.as<FastPair>(), out, fused, N);
         } else {
-            launch_forces_tiled<R, KSET, SURF, HAS_B>(stream, P, G, share, posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), out,
+            launch_forces_tiled<R, KSET, SURF, HAS_B>(stream, P, G, geo.thr, share, posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), out,
                                                       fused, N, walls);
         }
         if (plan.keys) {
@@ -708,7 +691,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(ev_begin(stage));
         const WallList wv = wall_view();
         if (!plan.lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
-        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, hit_buffer(), posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
+        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, geo.thr, hit_buffer(), posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
         return NRS_OK;
     }
     // The last launch of an IISPH, PCISPH, PBF or DFSPH step, inside the stage the caller opened: like the fused SESPH force kernel it

@@ -17,7 +17,7 @@ struct PlanFacts {
     bool muller;    // KSET == KS_MULLER
     bool fp32;      // R is float
     uint64_t cap, n;
-    bool qOk;           // the geometry allows the compact scan candidates (derive_kernel_params)
+    bool qOk;           // the geometry allows the compact scan candidates (scan_quant, nrs_host_scan.h)
     bool pow2Grid;      // every extent of the grid is a power of two
     bool nearBitsValid; // the wall buffers exist and nearBits describes the current grid
     bool walls;         // nb != 0

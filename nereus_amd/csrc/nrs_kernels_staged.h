@@ -574,10 +574,9 @@ __global__ __launch_bounds__(BLOCK) void k_forces_fast(Params<float> P, GridView
 }
 
 template <int KSET, bool HAS_B>
-static inline void launch_density_staged(hipStream_t stream, const Params<float> &P, const GridView<float> &G, const HitBuffer *share,
+static inline void launch_density_staged(hipStream_t stream, const Params<float> &P, const GridView<float> &G, const CutThresholds &thr, const HitBuffer *share,
                                          bool fast, const float4 *sPos, float *dens, float *pres, FastPair *fq, uint32_t n)
 {
-    const CutThresholds thr = make_thresholds<float>(P);
     const dim3 g((n + STG_WAVE - 1) / STG_WAVE), b(STG_WAVE);
     const HitBuffer hb = share ? *share : HitBuffer{};
     constexpr unsigned pad = NRS_DBG_LDS_PAD; // occupancy experiment (compile-time, see nrs_kernels_tiled.h)

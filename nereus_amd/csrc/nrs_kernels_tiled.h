@@ -45,11 +45,8 @@ constexpr int HIT_CAP = 20; // hits kept per thread.  LDS = HIT_CAP*BLOCK*4 B = 
 constexpr uint32_t HIT_INDEX = (1u << 27) - 1;
 constexpr int HIT_TAG_SHIFT = 27;
 
-// Thresholds that turn the reference's two cut-off predicates into one float compare on the float dot
-// product d2 = dot(r,r)  (exact: sqrtf and the products are monotone, correctly rounded):
-//   lenLtIr : smallest float T with  sqrtf(T) >= ir          ⇒  (length(r) <  ir)        ⇔ d2 < T
-//   r2LeH2  : smallest float T with  fl(sqrtf(T)^2) > h*h    ⇒  !(length(r)^2 > h^2)     ⇔ d2 < T
-struct CutThresholds { float lenLtIr, r2LeH2; };
+// (CutThresholds — the reference's two cut-off predicates as one float compare on d2 = dot(r,r) — and the host's search for them,
+// the wall workgroups of a launch and the quantiser of the compact scan: nrs_host_scan.h, through nrs_math.h)
 
 // waves per SIMD the fp32 list-driven force kernel is compiled for: 7 caps it at 72 VGPRs (3 dwords spilled with
 // boundaries) and measured 0.487 -> 0.465 ms at 10 M particles; 8 (64 VGPRs) spills into the hit loop: 0.563 ms
@@ -276,7 +273,7 @@ template <typename R> struct Sweep {
         quantize_t<R>(G.qc, p, tx, ty, tz);
         // an owner too far from the grid origin for the error budget of the quanta (or with a NaN coordinate) is served by the
         // reference-order walk, like a list overflow
-        const bool far = !((fabsf(tx) < QP_FAR) & (fabsf(ty) < QP_FAR) & (fabsf(tz) < QP_FAR));
+        const bool far = !(quanta_near(tx) & quanta_near(ty) & quanta_near(tz));
         const uint32_t Qi = pack_quanta(tx, ty, tz) | QP_GUARD;
         const uint32_t qT = G.qT;
         const qword_t *__restrict__ qpos = G.qpos;
@@ -291,8 +288,8 @@ template <typename R> struct Sweep {
 #pragma unroll
             for (int u = 0; u < QSLOTS; ++u) {
                 if ((u & 1) == 0) cur = min(cur, capOff);
-                const uint32_t t = Qi - c.v[u];
-                const int dx = ((int)(t << 22)) >> 22, dy = ((int)(t << 11)) >> 22, dz = ((int)t) >> 22;
+                const QuantDelta d = quant_delta(Qi, c.v[u]);
+                const int dx = d.x, dy = d.y, dz = d.z;
                 const uint32_t d2 = (uint32_t)mad24(dz, dz, mad24(dy, dy, __mul24(dx, dx)));
                 const uint32_t q = base + (uint32_t)u;
                 const bool hit = (d2 < qT) & (q < nT);
@@ -1270,40 +1267,12 @@ __global__ __launch_bounds__(BLOCK) void k_mark_near_boundary(Params<R> P, const
             }
 }
 
-static inline bool is_pow2(uint32_t v) { return v && !(v & (v - 1)); }
-
-// host-side threshold search (IEEE float arithmetic on the host)
-template <typename R> static inline CutThresholds make_thresholds(const Params<R> &P)
-{
-    CutThresholds t;
-    const R ir = P.interactionRadius;
-    {
-        float T = (float)(ir * ir);
-        auto ge = [&](float x) { return !((R)sqrtf(x) < ir); }; // NOT (length < ir)
-        while (ge(T) && T > 0.0f) T = nextafterf(T, 0.0f);
-        while (!ge(T)) T = nextafterf(T, INFINITY);
-        t.lenLtIr = T;
-    }
-    {
-        const R h2 = ir * ir;
-        float T = (float)h2;
-        auto gt = [&](float x) { float l = sqrtf(x); R r2 = l * l; return r2 > h2; };
-        while (gt(T) && T > 0.0f) T = nextafterf(T, 0.0f);
-        while (!gt(T)) T = nextafterf(T, INFINITY);
-        t.r2LeH2 = T;
-    }
-    return t;
-}
-
-// wall workgroups of a gather launch (grid-stride over the wall list, whose length is only known on the device)
-static inline uint32_t wall_blocks(uint32_t interiorBlocks) { return std::min<uint32_t>(1024u, std::max<uint32_t>(1u, interiorBlocks / 16u)); }
-
+// thr: the context's cut-offs for P.interactionRadius (make_thresholds, nrs_host_scan.h)
 // wall: this step's wall list (tile counts of the reorder kernel / scan / k_wall_compact) — needs `share`; null = one kind of workgroup
 template <typename R, int KSET, bool HAS_B>
-static inline void launch_density_tiled(hipStream_t stream, const Params<R> &P, const GridView<R> &G, const HitBuffer *share,
+static inline void launch_density_tiled(hipStream_t stream, const Params<R> &P, const GridView<R> &G, const CutThresholds &thr, const HitBuffer *share,
                                         const typename Vec4T<R>::type *sPos, R *dens, R *pres, uint32_t n, const WallList *wall = nullptr)
 {
-    const CutThresholds thr = make_thresholds<R>(P);
     const dim3 g((n + BLOCK - 1) / BLOCK), b(BLOCK);
     const HitBuffer hb = share ? *share : HitBuffer{};
     // occupancy experiment (tools/occupancy_sweep.sh builds variants with -DNRS_DBG_LDS_PAD=bytes): extra dynamic LDS per
@@ -1322,10 +1291,9 @@ static inline void launch_density_tiled(hipStream_t stream, const Params<R> &P, 
     }
 }
 template <typename R, int KSET, bool HAS_B>
-static inline void launch_density_wide(hipStream_t stream, const Params<R> &P, const GridView<R> &G, const HitBuffer &hb,
+static inline void launch_density_wide(hipStream_t stream, const Params<R> &P, const GridView<R> &G, const CutThresholds &thr, const HitBuffer &hb,
                                        const typename Vec4T<R>::type *sPos, R *dens, uint32_t n, const WallList *wall = nullptr)
 {
-    const CutThresholds thr = make_thresholds<R>(P);
     const uint32_t g = (n + BLOCK - 1) / BLOCK;
     if (HAS_B && wall) { // wall workgroups (boundary code, exact positions) + interior workgroups (quantised scan), see k_density_tiled
         const uint32_t wb = wall_blocks(g);
@@ -1338,7 +1306,7 @@ static inline void launch_density_wide(hipStream_t stream, const Params<R> &P, c
 }
 // `lists`: hit lists published by launch_density_tiled of the same step (then no scan), or nullptr
 template <typename R, int KSET, bool SURF, bool HAS_B>
-static inline void launch_forces_tiled(hipStream_t stream, const Params<R> &P, const GridView<R> &G, const HitBuffer *lists,
+static inline void launch_forces_tiled(hipStream_t stream, const Params<R> &P, const GridView<R> &G, const CutThresholds &thr, const HitBuffer *lists,
                                        const typename Vec4T<R>::type *sPos, const typename Vec4T<R>::type *sVel, const R *dens,
                                        const R *pres, typename Vec4T<R>::type *forces, const FusedOut<R> *fused, uint32_t n,
                                        const WallList *wall = nullptr)
@@ -1355,7 +1323,6 @@ static inline void launch_forces_tiled(hipStream_t stream, const Params<R> &P, c
         if (fused) hipLaunchKernelGGL((k_forces_lists<R, KSET, SURF, HAS_B, true>), g, b, padF, stream, P, G, *lists, sPos, sVel, dens, pres, forces, fo, n, WallList{}, 0u);
         else hipLaunchKernelGGL((k_forces_lists<R, KSET, SURF, HAS_B, false>), g, b, 0, stream, P, G, *lists, sPos, sVel, dens, pres, forces, fo, n, WallList{}, 0u);
     } else {
-        const CutThresholds thr = make_thresholds<R>(P);
         if (fused) hipLaunchKernelGGL((k_forces_tiled<R, KSET, SURF, HAS_B, true>), g, b, 0, stream, P, G, thr, sPos, sVel, dens, pres, forces, fo, n);
         else hipLaunchKernelGGL((k_forces_tiled<R, KSET, SURF, HAS_B, false>), g, b, 0, stream, P, G, thr, sPos, sVel, dens, pres, forces, fo, n);
     }

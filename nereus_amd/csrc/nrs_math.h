@@ -9,10 +9,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace nrs {
-
 #define NRS_DEV __device__ __forceinline__
-#define NRS_HD __host__ __device__ __forceinline__
+#include "nrs_host_scan.h" // NRS_HD; the scan's geometry and its quantiser, one definition for the host and the device
+
+namespace nrs {
 
 template <typename R> struct V3 { R x, y, z; };
 
@@ -320,43 +320,20 @@ constexpr int BLOCK = 256;
 static inline uint32_t nblocks(uint64_t n) { return (uint32_t)((n + BLOCK - 1) / BLOCK); } // workgroups of BLOCK threads over n items
 
 // ---- compact scan candidates (the neighbour scan of the interior workgroups, nrs_kernels_tiled.h) -----------------------------
-// A quantised copy of every sorted position, written by the reorder kernels next to the exact one: the position modulo FOUR
-// cells per axis.  Differences of such coordinates wrap, so for two particles less than two cells apart on every axis — which
-// every pair inside the interaction radius is (host check: h < ~2 cellSize, else the context does not use the compact scan) —
-// the wrapped difference IS the coordinate difference in quanta, whatever cells the two sit in.  The scan keeps a candidate when
-// the integer squared distance is below (h / quantum + QP_MARGIN)^2: a SUPERSET of the exact hits; the process phase applies the
-// exact float test to the exact position, which it has to gather anyway, and compacts the list before it is published.
-struct QuantCfg { double o[3]; float s[3]; }; // grid origin, quanta per metre (host: QP_PER_CELL / cellSize)
+// What a quantised position is, the QP_* constants and the arithmetic per coordinate: nrs_host_scan.h (included above; the host
+// prepares QuantCfg and the scan's threshold from the same header).  Here: its forms on a V3.
 template <typename R> NRS_DEV void quantize_t(const QuantCfg &q, V3<R> p, float &tx, float &ty, float &tz)
 {
-    tx = (float)(p.x - (R)q.o[0]) * q.s[0];
-    ty = (float)(p.y - (R)q.o[1]) * q.s[1];
-    tz = (float)(p.z - (R)q.o[2]) * q.s[2];
-}
-// 4-byte quantised candidates: measured faster than a 16-bit-per-axis form and than exact positions, DESIGN.md §4 (what a candidate
-// costs is its bytes through the L1 path and its register, not the distance arithmetic).
-// 10 bits per axis at bits 0 / 11 / 22 (units of cellSize/256, modulo 4 cells); bits 10 and 21 are guard bits, left 0.  With the
-// guard bits SET in the owner's word, ONE 32-bit subtraction gives the three differences modulo 1024 (each guard absorbs its
-// field's borrow); three sign extensions, three 24-bit multiplies and an add give the squared distance (about 3 % false positives).
-typedef uint32_t qword_t;
-constexpr uint32_t QP_GUARD = (1u << 10) | (1u << 21);
-constexpr float QP_PER_CELL = 256.0f;
-// |k_i - k_j - (t_i - t_j)| < 1 (two floors) + 2 * 0.19 (relative error <= 3 * 2^-24 on |t| < 2^20 + 2^9) per axis, so
-// |dk| <= |dt| + 1.38 * sqrt(3) = |dt| + 2.39; + the float rounding of the exact test itself
-constexpr float QP_MARGIN = 2.5f;
-constexpr float QP_FAR = 1048576.0f; // 2^20 quanta = 4096 cells from the grid origin: an owner beyond that (or with a NaN coordinate) is scanned on exact positions (quant_far)
-constexpr float QP_HALF = 511.0f;
-NRS_DEV qword_t pack_quanta(float tx, float ty, float tz)
-{
-    const uint32_t kx = (uint32_t)(int)floorf(tx) & 1023u, ky = (uint32_t)(int)floorf(ty) & 1023u, kz = (uint32_t)(int)floorf(tz) & 1023u;
-    return kx | (ky << 11) | (kz << 22);
+    tx = quantize_axis<R>(p.x, q.o[0], q.s[0]);
+    ty = quantize_axis<R>(p.y, q.o[1], q.s[1]);
+    tz = quantize_axis<R>(p.z, q.o[2], q.s[2]);
 }
 // an owner too far from the grid origin for the error budget of the quanta, or with a NaN coordinate
 template <typename R> NRS_DEV bool quant_far(const QuantCfg &q, V3<R> p)
 {
     float tx, ty, tz;
     quantize_t<R>(q, p, tx, ty, tz);
-    return !((fabsf(tx) < QP_FAR) && (fabsf(ty) < QP_FAR) && (fabsf(tz) < QP_FAR));
+    return !(quanta_near(tx) && quanta_near(ty) && quanta_near(tz));
 }
 template <typename R> NRS_DEV qword_t quantize_pos(const QuantCfg &q, V3<R> p)
 {
