@@ -6,9 +6,13 @@
 // "unsorted" arrays of step t+1 are the integrated sorted arrays of step t (buffer swap), which is what
 // the reference obtains by copying sorted→host→device.
 //
-// Ctx<R, KSET, SURF> keeps what depends on the precision, the kernel set or the launches: the particle arrays, the solvers' buffers,
-// the cell table and the hit lists, the hash and reorder launches of the sort stage, the solver tails.  Everything else has one owner
-// outside it, held as one member, read through views and driven through named operations; no buffer of theirs is assigned here.
+// Ctx<R, KSET, SURF> keeps the particle arrays, the cell table and the hit lists, the hash and reorder launches of the sort stage, the
+// SESPH tail, and what frames every step: the step plan, the last launch that leaves the next step's keys, the end of the step.
+// Everything else has one owner outside it, held as one member, read through views and driven through named operations; no buffer of
+// theirs is assigned here.  The pressure solvers — IISPH, PCISPH, PBF, DFSPH, with Akinci's surface model — are one of them: ps
+// (PressureSolvers<R, KSET, SURF>, nrs_solvers.h) has their buffers, settings, derived constants and statistics and launches their
+// chains; the context tells it per chain what the step is now (solver_step) and lends it launch_last.  The reductions both use are
+// red's (Reductions<R>, nrs_solvers.h).
 // The boundary particles, their tables and bodies depend on the precision alone: bt (BoundaryTables<R>, nrs_boundary_tables.h), which
 // launches its own builds.  So does the slab exchange: exch (SlabExchange<R>, nrs_slab_exchange.h) has the cuts, the window, the last
 // pack, the ghost streams, block counts, totals and flags of the partition, the pinned landing and the pack's event, and launches the
@@ -50,11 +54,7 @@
 #include "nrs_kernels_tiled.h"
 #include "nrs_kernels_staged.h"
 #include <type_traits>
-#include "nrs_kernels_iisph.h"
-#include "nrs_kernels_pcisph.h"
-#include "nrs_kernels_pbf.h"
-#include "nrs_kernels_dfsph.h"
-#include "nrs_kernels_akinci.h"
+#include "nrs_solvers.h"
 #include "nrs_kernels_bodies.h"
 #include "nrs_slab_exchange.h"
 #include "nrs_readers.h"
@@ -89,49 +89,25 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     bool midStep = false; // a partial step left the state mid-update
     // particle state: A = current ("unsorted" input of the next step), B = sorted work arrays
     DevBuf posA, posB, velA, velB, presA, presB, dens, forces;
-    DevBuf inv;
     SortStage sort; // the (hash, index) pairs, the sort's workspace, the coherent re-sort and its statistics (nrs_sort.h)
     DevBuf cellStart, cellEnd;
     uint32_t cellsAllocated = 0;
     BoundaryTables<R> bt; // the boundary particles, their tables and bodies (nrs_boundary_tables.h)
-    // the solvers' buffers (BufName, nrs_host_solver.h: which solver allocates which, and what the shared ones hold on each)
-    DevBuf densAdv, densCorr, P_l, P_l2, aii, velAdv, forcesAdv, forcesP, diiF, diiB, sumDij, diiSum;
-    DevBuf redPartial, redOut;
-    DevBuf posPred, posPred2, pciErr;
-    DevBuf dfAlpha, dfKvA, dfKvB, dfErrV;
-    DevBuf pbfVort, akNormals; // allocated when confinement is first enabled / gamma is first set above 0
-    // per solver: settings, derived constants, what the last step left (nrs_host_solver.h).  PBF shares pciSt.xs and pciSt.lastErr.
-    PciState<R> pciSt;   // nrs_kernels_pcisph.h
-    PbfState<R> pbfSt;   // nrs_kernels_pbf.h
-    DfsphState<R> dfSt;  // nrs_kernels_dfsph.h; DESIGN.md "DFSPH"
-    AkinciState akSt;    // nrs_kernels_akinci.h; PCISPH, PBF, DFSPH
-    DevBuf *devbuf(BufName b)
-    {
-        switch (b) {
-        case BUF_POS_A: return &posA; case BUF_POS_B: return &posB; case BUF_VEL_A: return &velA; case BUF_VEL_B: return &velB;
-        case BUF_PRES_A: return &presA; case BUF_PRES_B: return &presB; case BUF_DENS: return &dens; case BUF_FORCES: return &forces;
-        case BUF_CELL_START: return &cellStart; case BUF_CELL_END: return &cellEnd;
-        case BUF_INV: return &inv; case BUF_DENS_ADV: return &densAdv; case BUF_P_L2: return &P_l2; case BUF_AII: return &aii;
-        case BUF_DII_F: return &diiF; case BUF_DII_B: return &diiB; case BUF_SUM_DIJ: return &sumDij; case BUF_DII_SUM: return &diiSum;
-        case BUF_VEL_ADV: return &velAdv; case BUF_FORCES_ADV: return &forcesAdv; case BUF_FORCES_P: return &forcesP;
-        case BUF_DENS_CORR: return &densCorr; case BUF_P_L: return &P_l; case BUF_POS_PRED: return &posPred; case BUF_POS_PRED2: return &posPred2;
-        case BUF_PCI_ERR: return &pciErr; case BUF_DF_ALPHA: return &dfAlpha; case BUF_DF_KV_A: return &dfKvA; case BUF_DF_KV_B: return &dfKvB;
-        case BUF_DF_ERR_V: return &dfErrV; case BUF_PBF_VORT: return &pbfVort; case BUF_AK_NORMALS: return &akNormals;
-        // no default: -Wswitch names a BufName that is missing here.  The sorted keys / values are pointers into a pair, the boundary's
-        // arrays live in bt (buf_ptr).
-        case BUF_NONE: case BUF_HASH_CUR: case BUF_INDEX_CUR: case BUF_COUNT: break;
-        case BUF_B_HASH_CUR: case BUF_B_INDEX_CUR: case BUF_B_CELL_START: case BUF_B_CELL_END: case BUF_B_SORTED: case BUF_BD_BODY_SORTED: break;
-        }
-        return nullptr;
-    }
+    Reductions<R> red;    // sums, maxima and the hit statistics (nrs_solvers.h)
+    PressureSolvers<R, KSET, SURF> ps{red}; // IISPH, PCISPH, PBF, DFSPH, Akinci: buffers, settings, chains (nrs_solvers.h)
+    // where a buffer of the given name lives: the boundary's are bt's, the solvers' ps's (whose switch has no default: -Wswitch names a
+    // BufName nobody answers for), the sorted keys / values are pointers into a pair
     void *buf_ptr(BufName b)
     {
         void *p = nullptr;
         size_t bytes = 0;
-        if (bt.buffer(b, &p, &bytes)) return p;
+        if (bt.buffer(b, &p, &bytes) || ps.buffer(b, &p, &bytes)) return p;
         switch (b) {
+        case BUF_POS_A: return posA.p; case BUF_POS_B: return posB.p; case BUF_VEL_A: return velA.p; case BUF_VEL_B: return velB.p;
+        case BUF_PRES_A: return presA.p; case BUF_PRES_B: return presB.p; case BUF_DENS: return dens.p; case BUF_FORCES: return forces.p;
+        case BUF_CELL_START: return cellStart.p; case BUF_CELL_END: return cellEnd.p;
         case BUF_HASH_CUR: return sort.hash(); case BUF_INDEX_CUR: return sort.index();
-        default: { DevBuf *d = devbuf(b); return d ? d->p : nullptr; }
+        default: return nullptr;
         }
     }
     DevBuf errWord; // set by the device-side consistency guard of the scans (GridView::err)
@@ -171,9 +147,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
 
     bool iisph() const { return cfg.solver == NRS_SOLVER_IISPH; }
-    bool pcisph() const { return cfg.solver == NRS_SOLVER_PCISPH; }
     bool sesph() const { return cfg.solver == NRS_SOLVER_SESPH; }
-    bool pbf() const { return cfg.solver == NRS_SOLVER_PBF; }
     bool dfsph() const { return cfg.solver == NRS_SOLVER_DFSPH; }
     bool pow2_grid() const { return nrs::pow2_grid(P.gridSize); }
 
@@ -185,7 +159,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     }
     Features features() const { return plan_features(plan_facts()); }
     // Chosen at the start of every step (step(), nrs_iisph_predict) and held until its end: a host-driven IISPH step spans three calls.
-    // iisph_tail replaces it with plan_step(stop, true) for the reference-order repeat of a diverged step.
+    // The reference-order repeat of a diverged IISPH step runs by plan_step(stop, true), which solver_step hands over beside it.
     StepPlan plan;
     StepPlan plan_step(int stop, bool ref = false) const { return nrs::plan_step(plan_facts(), stop, ref); }
 
@@ -220,26 +194,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (cap == 0 || cap > (uint64_t)HIT_INDEX) return fail(NRS_E_INVALID, "capacity must be in 1..2^27-1");
         std::memcpy(&PU, params, sizeof(PU));
         derive_kernel_params();
-        const size_t v = sizeof(T4) * cap, s = sizeof(R) * cap, u = 4 * cap;
+        const size_t v = sizeof(T4) * cap, s = sizeof(R) * cap;
         NRSCHK(posA.alloc(v)); NRSCHK(posB.alloc(v)); NRSCHK(velA.alloc(v)); NRSCHK(velB.alloc(v));
         NRSCHK(presA.alloc(s)); NRSCHK(presB.alloc(s)); NRSCHK(dens.alloc(s)); NRSCHK(forces.alloc(v));
         HIPCHK(hipMemsetAsync(presA.p, 0, s, stream));
         HIPCHK(hipMemsetAsync(presB.p, 0, s, stream));
         HIPCHK(hipMemsetAsync(dens.p, 0, s, stream));
         HIPCHK(hipMemsetAsync(forces.p, 0, v, stream));
-        const SolverBufferList own = solver_buffers(cfg.solver);
-        for (const SolverBuffer &b : own) {
-            size_t bytes = 0;
-            switch (b.unit) { // (the table's contract: per-particle units, sized by the capacity)
-            case UNIT_VEC4_N: bytes = v; break;
-            case UNIT_SCALAR_N: bytes = s; break;
-            case UNIT_U32_N: bytes = u; break;
-            case UNIT_U32_CELLS: case UNIT_VEC4_NB: case UNIT_U32_NB: return fail(NRS_E_STATE, "solver_buffers lists a buffer that is not per particle");
-            }
-            NRSCHK(devbuf(b.buf)->alloc(bytes));
-        }
-        for (const SolverBuffer &b : own)
-            if (b.zero) HIPCHK(hipMemsetAsync(devbuf(b.buf)->p, 0, devbuf(b.buf)->bytes, stream));
+        NRSCHK(ps.init(cfg.solver, cap, stream));
         const Features ft = features();
         if (ft.lists) {
             NRSCHK(hitBuf.alloc((size_t)HIT_CAP * cap * 4));
@@ -250,8 +212,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (ft.fast) NRSCHK(fastQ.alloc((size_t)cap * sizeof(FastPair)));
         NRSCHK(errWord.alloc(8)); // [0] run guard of the scans, [1] IISPH: a gathered value went non-finite (IisphArrays::nonFinite)
         HIPCHK(hipMemsetAsync(errWord.p, 0, 8, stream));
-        NRSCHK(redPartial.alloc(sizeof(double) * 1024));
-        NRSCHK(redOut.alloc(2 * sizeof(double)));
+        NRSCHK(red.init(stream));
         NRSCHK(sort.init(cap, ft.resort, stream));
         exch.init(cap, stream);
         NRSCHK(alloc_cells());
@@ -263,7 +224,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // by uploading particles)
     int refuse_mid_iisph(const char *what) const
     {
-        if (!iisphPhase) return NRS_OK;
+        if (!ps.host_step()) return NRS_OK;
         char buf[200];
         snprintf(buf, sizeof(buf), "%s while a host-driven IISPH step is in progress (nrs_iisph_finish first, or upload particles to abandon it)", what);
         return fail(NRS_E_STATE, buf);
@@ -281,9 +242,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!sameGrid) NRSCHK(invalidate_grid_state());
         const uint32_t cellsBefore = P.numCells;
         const StaleConstants stale = stale_after_params(params_key(PU), params_key(q)); // (the host classes set the parameters every step)
-        pciSt.params_changed(stale);
-        pbfSt.params_changed(stale);
-        dfSt.params_changed(stale);
+        ps.params_changed(stale);
         PU = q;
         if (!sameGrid && exch.on()) exch.choose_window(PU.gridSize, true);
         derive_kernel_params();
@@ -328,14 +287,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             else HIPCHK(hipMemsetAsync(velA.as<T4>() + first, 0, sizeof(T4) * count, stream));
             if (pres) HIPCHK(hipMemcpyAsync(presA.as<R>() + first, pres, sizeof(R) * count, hipMemcpyHostToDevice, stream));
             else HIPCHK(hipMemsetAsync(presA.as<R>() + first, 0, sizeof(R) * count, stream));
-            if (dfsph()) HIPCHK(hipMemsetAsync(dfKvA.as<R>() + first, 0, sizeof(R) * count, stream)); // (Kv restarts at zero; K is the pressure)
+            NRSCHK(ps.kv_zero(first, count, stream));
             HIPCHK(hipStreamSynchronize(stream)); // the caller may reuse its host buffers on return
         }
         if (first + count > n) n = first + count;
         ++particleGen;
         if (exch.on()) nOwned = n; // (until the next partition says otherwise)
         midStep = false;
-        iisphPhase = 0; iisphIter = 0; // new particles abandon a host-driven IISPH step that was in progress
+        ps.abandon_host_step(); // new particles abandon a host-driven IISPH step that was in progress
         st.to_fresh();
         return NRS_OK;
     }
@@ -347,7 +306,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         NRSCHK(compact_holes());
         if (nn != n) st.to_fresh();
         if (nn != n) ++particleGen;
-        if (nn != n) { iisphPhase = 0; iisphIter = 0; } // (the hit lists of a predicted step belong to the old particle set)
+        if (nn != n) ps.abandon_host_step(); // (the hit lists of a predicted step belong to the old particle set)
         n = nn;
         if (exch.on()) nOwned = n;
         return NRS_OK;
@@ -430,16 +389,14 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         G.qc = geo.q.qc;
         return G;
     }
-    IisphArrays<R> iisph_view() const
+    // what the step is now, for a chain of ps (nrs_solvers.h): built once per chain, from the plan of the step in progress
+    SolverStep<R> solver_step(int stop)
     {
-        IisphArrays<R> I;
-        I.densAdv = densAdv.as<R>(); I.densCorr = densCorr.as<R>(); I.P_l = P_l.as<R>(); I.P_l_next = P_l2.as<R>();
-        I.aii = aii.as<R>();
-        I.velAdv = velAdv.as<T4>(); I.forcesAdv = forcesAdv.as<T4>(); I.forcesP = forcesP.as<T4>();
-        I.diiF = diiF.as<T4>(); I.diiB = diiB.as<T4>(); I.sumDij = sumDij.as<T4>(); I.diiSum = diiSum.as<T4>();
-        I.inv = inv.as<uint32_t>();
-        I.nonFinite = plan.watch ? errWord.as<uint32_t>() + 1 : (uint32_t *)nullptr; // (second word of the error buffer)
-        return I;
+        const uint32_t N = (uint32_t)n;
+        return SolverStep<R>{P, plan, plan_step(stop, true), grid_view(), geo.thr, hit_buffer(), wall_view(),
+                             SortedArrays<R>{posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), N}, presA.as<R>(), sort.index(),
+                             errWord.as<uint32_t>() + 1 /* (second word of the error buffer) */, exch.on(), exch.max_iters(), bt.moving_step(),
+                             bt.wall_velocities(), maxIters, &lastIters, &timer, profMask, stream};
     }
 
     // hash → sort → cell ranges + reorder: common prefix of both solvers
@@ -476,19 +433,18 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (merged)
             hipLaunchKernelGGL((k_reorder_merged<R>), g, b, 0, stream, merged, sort.hash(), sort.index(), posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
-                               cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
+                               cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? ps.inverse_slots() : (uint32_t *)nullptr, N,
                                nearB, wlist.tile_counts(), wlist.slot_masks(), geo.q.qc, qp);
         else
             hipLaunchKernelGGL((k_reorder<R>), g, b, 0, stream, sort.hash(), sort.index(), posA.as<T4>(), velA.as<T4>(),
                                iisph() ? presA.as<R>() : (const R *)nullptr, posB.as<T4>(), velB.as<T4>(), presB.as<R>(),
-                               cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? inv.as<uint32_t>() : (uint32_t *)nullptr, N,
+                               cellStart.as<uint32_t>(), cellEnd.as<uint32_t>(), iisph() ? ps.inverse_slots() : (uint32_t *)nullptr, N,
                                nearB, wlist.tile_counts(), wlist.slot_masks(), geo.q.qc, qp);
         if (iisph() && (cfg.flags & NRS_FLAG_IISPH_SELF_BY_SLOT)) // Q5 off: the pressure kernels skip j == own slot
-            hipLaunchKernelGGL(k_identity, g, b, 0, stream, inv.as<uint32_t>(), N);
+            hipLaunchKernelGGL(k_identity, g, b, 0, stream, ps.inverse_slots(), N);
         if (dfsph()) { // the warm-start inputs of the step, K_prev and Kv_prev, into sorted order
             hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, presA.as<R>(), sort.index(), presB.as<R>(), N);
-            hipLaunchKernelGGL((k_gather_scalar<R>), g, b, 0, stream, dfKvA.as<R>(), sort.index(), dfKvB.as<R>(), N);
-            dfSt.kvValid = true;
+            ps.kv_gather(sort.index(), N, stream);
         }
         NRSCHK(ev_end());
         if (track.on) { // id, birth and the record into sorted order: one launch, an entry of its own in the reorder stage's count
@@ -613,602 +569,58 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         return NRS_OK;
     }
 
-    int reduce_sum(const R *a, uint32_t N, double *out)
-    {
-        const uint32_t nbk = std::min<uint32_t>(1024u, nblocks(N));
-        hipLaunchKernelGGL((k_sum_partial<R>), dim3(nbk), dim3(BLOCK), 0, stream, a, redPartial.as<double>(), N);
-        hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(BLOCK), 0, stream, redPartial.as<double>(), redOut.as<double>(), nbk);
-        HIPCHK(hipMemcpyAsync(out, redOut.p, sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return NRS_OK;
-    }
     int reduce_max(int which, double *out) override
     {
         if (!n) { *out = 0; return NRS_OK; }
         NRSCHK(compact_holes());
-        if (which == 0) return max_of<false>(dens.p, (uint32_t)n, out);
-        return max_of<true>(velA.p, (uint32_t)n, out);
-    }
-    // max over an SReal array (VEC: of |v| over a vec4 array), deterministic: per-block maxima on the device, their max on the host
-    template <bool VEC> int max_of(const void *a, uint32_t N, double *out)
-    {
-        const uint32_t nbk = std::min<uint32_t>(1024u, nblocks(N));
-        hipLaunchKernelGGL((k_max_partial<R, VEC>), dim3(nbk), dim3(BLOCK), 0, stream, a, redPartial.as<double>(), N);
-        std::vector<double> h(nbk);
-        HIPCHK(hipMemcpyAsync(h.data(), redPartial.p, sizeof(double) * nbk, hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        double m = h[0];
-        for (uint32_t i = 1; i < nbk; ++i) m = std::max(m, h[i]);
-        *out = m;
-        return NRS_OK;
+        if (which == 0) return red.template max_of<false>(dens.p, (uint32_t)n, out);
+        return red.template max_of<true>(velA.p, (uint32_t)n, out);
     }
 
-    // ---- IISPH step in three phases (the single-domain nrs_step runs them back to back; a slab run has the host decide after
-    //      every solver iteration, on the sum over ALL ranks: nrs_iisph_predict / _iterate / _finish) -----------------------------
-    uint32_t iisphIter = 0;  // solver iterations done in the current step
-    int iisphPhase = 0;      // 0 idle, 1 predicted (iterations may follow)
-    // An IISPH list kernel with wall workgroups over this step's wall list + interior workgroups without the boundary code, as the
-    // scan (grid + wall_blocks), or interior workgroups only.  The list kernels use the Muller gradient: they are instantiated, under
-    // `if constexpr`, for the Muller kernels only (plan.lists is never set for Monaghan IISPH, Features::listKernels).
-    template <typename... K, typename... A> void launch_listed(void (*walled)(K...), void (*plain)(K...), uint32_t blocks, A... args)
-    {
-        if (plan.walls) {
-            const uint32_t wb = wall_blocks(blocks);
-            hipLaunchKernelGGL(walled, dim3(blocks + wb), dim3(BLOCK), 0, stream, args..., wall_view(), wb);
-        } else {
-            hipLaunchKernelGGL(plain, dim3(blocks), dim3(BLOCK), 0, stream, args..., WallList{}, 0u);
-        }
-    }
-    // One neighbour pass of PCISPH, PBF, DFSPH or the Akinci normals (nrs_kernels_walk.h) over the sorted slots: the reference-order
-    // kernel or, with plan.lists (Muller kernels only), the list kernel — with wall workgroups where the pass has a boundary term,
-    // one plain launch where it walks fluid neighbours only.
-    template <bool HAS_B, typename Pass> void launch_pass(const Pass &pass)
-    {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        const T4 *sPos = posB.as<T4>();
-        if (!plan.lists) {
-            hipLaunchKernelGGL((k_walk_ref<Pass, HAS_B && Pass::WALLED>), g, b, 0, stream, pass, G, sPos, N);
-        } else if constexpr (KSET == KS_MULLER) {
-            if constexpr (Pass::WALLED) launch_listed(k_walk_lists<Pass, HAS_B, true>, k_walk_lists<Pass, HAS_B>, g.x, pass, G, hit_buffer(), sPos, N);
-            else hipLaunchKernelGGL((k_walk_lists<Pass, false>), g, b, 0, stream, pass, G, hit_buffer(), sPos, N, WallList{}, 0u);
-        }
-    }
-    // The head of an IISPH, PCISPH, PBF or DFSPH step: this step's wall list (timed with the reorder stage, whose tile counts it
-    // finishes), then the one neighbourhood scan of the step, whose hit lists drive the rest of the chain (nrs_kernels_iisph.h).  The
-    // scan opens `stage`; the caller ends it.
-    template <bool HAS_B> int begin_density_scan(int stage)
-    {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        if (plan.walls) {
-            NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
-            NRSCHK(build_wall_list(N));
-            NRSCHK(ev_end());
-        }
-        NRSCHK(ev_begin(stage));
-        const WallList wv = wall_view();
-        if (!plan.lists) hipLaunchKernelGGL((k_density_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, posB.as<T4>(), dens.as<R>(), (R *)nullptr, N);
-        else if constexpr (KSET == KS_MULLER) launch_density_wide<R, KSET, HAS_B>(stream, P, G, geo.thr, hit_buffer(), posB.as<T4>(), dens.as<R>(), N, plan.walls ? &wv : nullptr);
-        return NRS_OK;
-    }
+    // ---- the pressure solvers: ps (nrs_solvers.h) has the settings and the chains; here: the forwards, and what frames a chain --------
+    int pcisph_configure(double eta, uint32_t minIters, double spacing, double delta) override { return ps.pcisph_configure(eta, minIters, spacing, delta); }
+    int pbf_configure(double eta, uint32_t minIters, double relaxation, double xsph) override { return ps.pbf_configure(eta, minIters, relaxation, xsph); }
+    int pbf_set_tensile(double k, double dq) override { return ps.pbf_set_tensile(P, k, dq, stream); }
+    int pbf_set_vorticity(double epsV) override { return ps.pbf_set_vorticity(epsV); }
+    int dfsph_configure(double eta, uint32_t minIters, double etaV, uint32_t minItersV, int warm) override { return ps.dfsph_configure(eta, minIters, etaV, minItersV, warm); }
+    int set_surface_akinci(double gamma, double beta) override { return ps.set_surface_akinci(gamma, beta); }
+
+    // f(std::true_type) with boundary particles, f(std::false_type) without: the one place a launch chain learns HAS_B
+    template <typename F> int with_walls(F &&f) { return bt.count() ? f(std::true_type{}) : f(std::false_type{}); }
     // The last launch of an IISPH, PCISPH, PBF or DFSPH step, inside the stage the caller opened: like the fused SESPH force kernel it
-    // also writes the next step's sort keys (plan.keys) and counts the movers per tile (plan.resort).  launch(hash, index, prevHash,
-    // tileMovers) gets where those go, or nulls; the stage ends behind it, the keys are ready and the split is queued.
-    template <typename Launch> int launch_last(Launch &&launch)
+    // also writes the next step's sort keys (pl.keys) and counts the movers per tile (pl.resort).  launch(hash, index, prevHash,
+    // tileMovers) gets where those go, or nulls; the stage ends behind it, the keys are ready and the split is queued.  pl: the plan
+    // the chain runs by — the step's, or the one of IISPH's repeat in reference order, which leaves no keys.
+    template <typename Launch> int launch_last(const StepPlan &pl, Launch &&launch)
     {
-        const KeyPair next = plan.keys ? sort.next_keys() : KeyPair{nullptr, nullptr};
-        if (plan.resort) NRSCHK(sort.clean_tile_counts());
-        launch(next.hash, next.index, plan.resort ? (const uint32_t *)sort.hash() : (const uint32_t *)nullptr, plan.resort ? sort.tile_movers() : (uint32_t *)nullptr);
+        const KeyPair next = pl.keys ? sort.next_keys() : KeyPair{nullptr, nullptr};
+        if (pl.resort) NRSCHK(sort.clean_tile_counts());
+        launch(next.hash, next.index, pl.resort ? (const uint32_t *)sort.hash() : (const uint32_t *)nullptr, pl.resort ? sort.tile_movers() : (uint32_t *)nullptr);
         NRSCHK(ev_end());
-        if (plan.keys) keys_ready();
-        if (plan.resort) NRSCHK(queue_resort_split((uint32_t)n));
+        if (pl.keys) keys_ready();
+        if (pl.resort) NRSCHK(queue_resort_split((uint32_t)n));
         return NRS_OK;
     }
-
-    // predictAdvection (sph_cuda.cu:513-697)
-    template <bool HAS_B> int iisph_predict(int stop)
+    auto last_launch()
     {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        IisphArrays<R> I = iisph_view();
-        const HitBuffer hb = hit_buffer();
-        NRSCHK(begin_density_scan<HAS_B>(NRS_STAGE_I_DENSITY));
-        NRSCHK(ev_end());
-        if (stop == NRS_STAGE_I_DENSITY) return NRS_OK;
-        NRSCHK(ev_begin(NRS_STAGE_I_DISPLACEMENT));
-        if (!plan.lists)
-            hipLaunchKernelGGL((k_displacement_ref<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), velB.as<T4>(),
-                               dens.as<R>(), presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER)
-            launch_listed(k_displacement_lists<R, KSET, SURF, HAS_B, true>, k_displacement_lists<R, KSET, SURF, HAS_B>, g.x, P, G, I, hb,
-                          posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
-        NRSCHK(ev_end());
-        if (stop == NRS_STAGE_I_DISPLACEMENT) return NRS_OK;
-        NRSCHK(ev_begin(NRS_STAGE_I_ADVECTION));
-        if (!plan.lists)
-            hipLaunchKernelGGL((k_advection_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), velB.as<T4>(),
-                               dens.as<R>(), presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER)
-            launch_listed(k_advection_lists<R, KSET, HAS_B, true>, k_advection_lists<R, KSET, HAS_B>, g.x, P, G, I, hb, posB.as<T4>(),
-                          velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
-        NRSCHK(ev_end());
-        iisphIter = 0;
-        return NRS_OK;
+        return [this](const StepPlan &pl, auto &&launch) { return this->launch_last(pl, launch); };
     }
-    // one relaxed-Jacobi iteration of pressureSolve (sph_cuda.cu:736-823): sum d_ij p_j, pressure update (double-buffered P_l)
-    template <bool HAS_B> int iisph_iteration()
+    // The head of an IISPH, PCISPH, PBF or DFSPH chain: this step's wall list, timed with the reorder stage, whose tile counts it
+    // finishes.  The one neighbourhood scan of the step follows it (ps).
+    int wall_list_of_step()
     {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        IisphArrays<R> I = iisph_view();
-        const HitBuffer hb = hit_buffer();
-        if (!plan.lists) {
-            hipLaunchKernelGGL((k_sumdij_ref<R, KSET>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), N);
-            hipLaunchKernelGGL((k_pressure_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
-        } else if constexpr (KSET == KS_MULLER) {
-            hipLaunchKernelGGL((k_sumdij_lists<R, KSET>), g, b, 0, stream, P, G, I, hb, posB.as<T4>(), dens.as<R>(), N);
-            launch_listed(k_pressure_lists<R, KSET, HAS_B, true>, k_pressure_lists<R, KSET, HAS_B>, g.x, P, G, I, hb, posB.as<T4>(),
-                          dens.as<R>(), presB.as<R>(), N);
-        }
-        std::swap(P_l.p, P_l2.p);
-        ++iisphIter;
-        return NRS_OK;
+        if (!plan.walls) return NRS_OK;
+        NRSCHK(ev_begin(NRS_STAGE_REORDER, true));
+        NRSCHK(build_wall_list((uint32_t)n));
+        return ev_end();
     }
-    // computePressureForce + iisph_integrate (sph_cuda.cu:827-867)
-    template <bool HAS_B> int iisph_finish(int stop)
+    // everything behind the reorder of a step
+    template <bool HAS_B> int tail(int stop)
     {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        IisphArrays<R> I = iisph_view();
-        NRSCHK(ev_begin(NRS_STAGE_I_PFORCE));
-        if (!plan.lists)
-            hipLaunchKernelGGL((k_pforce_ref<R, KSET, HAS_B>), g, b, 0, stream, P, G, I, posB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER)
-            launch_listed(k_pforce_lists<R, KSET, HAS_B, true>, k_pforce_lists<R, KSET, HAS_B>, g.x, P, G, I, hit_buffer(), posB.as<T4>(),
-                          dens.as<R>(), presB.as<R>(), N);
-        NRSCHK(ev_end());
-        if (stop == NRS_STAGE_I_PFORCE) return NRS_OK;
-        return integrate_adv(NRS_STAGE_I_INTEGRATE);
-    }
-    // iisph_integrate (sph_cuda.cu:857-867) of velAdv + forcesP, timed as `stage`: the last launch of an IISPH or PCISPH step
-    int integrate_adv(int stage)
-    {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        NRSCHK(ev_begin(stage));
-        return launch_last([&](uint32_t *nh, uint32_t *ni, const uint32_t *prevHash, uint32_t *tileMovers) {
-            hipLaunchKernelGGL((k_iisph_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), velAdv.as<T4>(), forcesP.as<T4>(), N,
-                               nh, ni, prevHash, tileMovers, exch.on() ? 1 : 0);
-        });
-    }
-
-    // The list-driven chain is the reference-order chain only while every value a neighbour gathers is finite (IisphArrays::nonFinite).
-    // A solve that overflows raises the flag; the step is then repeated from the sorted input with the reference-order kernels,
-    // so that even a diverging run produces what the reference's loops produce (plan.watch).
-    template <bool HAS_B> int iisph_tail(int stop)
-    {
-        if (plan.watch) HIPCHK(hipMemsetAsync(errWord.as<uint32_t>() + 1, 0, 4, stream));
-        NRSCHK(iisph_tail_once<HAS_B>(stop));
-        if (!plan.watch || !iisphDiverged) return NRS_OK;
-        const StepPlan chosen = plan;
-        plan = plan_step(stop, true);
-        ++iisphRestarts;
-        hipLaunchKernelGGL((k_gather_scalar<R>), dim3(nblocks((uint32_t)n)), dim3(BLOCK), 0, stream, presA.as<R>(), sort.index(), presB.as<R>(), (uint32_t)n);
-        const int rc = iisph_tail_once<HAS_B>(stop);
-        plan = chosen;
-        return rc;
-    }
-    bool iisphDiverged = false;
-    uint64_t iisphRestarts = 0;
-    template <bool HAS_B> int iisph_tail_once(int stop)
-    {
-        const uint32_t N = (uint32_t)n;
-        const bool watch = plan.watch;
-        iisphDiverged = false;
-        uint32_t hflag = 0u;
-        uint32_t *flag = errWord.as<uint32_t>() + 1;
-        NRSCHK(iisph_predict<HAS_B>(stop));
-        if (stop && stop <= NRS_STAGE_I_ADVECTION) {
-            if (watch) {
-                HIPCHK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                iisphDiverged = hflag != 0u;
-            }
-            return NRS_OK;
-        }
-        // pressureSolve (sph_cuda.cu:702-899): while ((rho_avg - 1000) > 1 || l < 2)
-        NRSCHK(ev_begin(NRS_STAGE_I_SOLVE));
-        uint32_t l = 0;
-        R rho_avg = 0.f;
-        const R rd = 1000.f;
-        const R max_rho_err = 1.f;
-        bool flagRead = false;
-        while (((rho_avg - rd) > max_rho_err) || (l < 2)) {
-            NRSCHK(iisph_iteration<HAS_B>());
-            l++;
-            flagRead = false;
-            if (maxIters && l >= maxIters) break;
-            // the loop condition reads rho_avg only once l >= 2 (sph_cuda.cu:736: `|| l < 2`): the average of the first
-            // iteration is never looked at, so its reduction and host round trip are skipped
-            if (l >= 2) {
-                double acc = 0.0;
-                if (watch) HIPCHK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, stream)); // (rides in the reduction's round trip)
-                NRSCHK(reduce_sum(densCorr.as<R>(), N, &acc));
-                flagRead = true;
-                if (watch && hflag) break;
-                rho_avg = (R)acc;
-                rho_avg /= N;
-            }
-        }
-        if (watch && !flagRead) {
-            HIPCHK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-        }
-        lastIters = l;
-        NRSCHK(ev_end());
-        if (watch && hflag) { iisphDiverged = true; return NRS_OK; } // (the caller repeats the step in reference order)
-        if (stop == NRS_STAGE_I_SOLVE) return NRS_OK;
-        return iisph_finish<HAS_B>(stop);
-    }
-
-    // ---- PCISPH step (nrs_kernels_pcisph.h; DESIGN.md "PCISPH") -------------------------------------------------------------------
-    void *pci_xs_current() const { return pciSt.xs ? posPred2.p : posPred.p; }
-    PciArrays<R> pci_view(int in, int out) const
-    {
-        PciArrays<R> A;
-        A.velAdv = velAdv.as<T4>(); A.forcesAdv = forcesAdv.as<T4>(); A.forcesP = forcesP.as<T4>();
-        A.densPred = densCorr.as<R>(); A.pres = P_l.as<R>(); A.err = pciErr.as<R>();
-        A.xsIn = (in ? posPred2 : posPred).as<T4>();
-        A.xsOut = (out ? posPred2 : posPred).as<T4>();
-        A.delta = pciSt.delta();
-        return A;
-    }
-    int pcisph_configure(double eta, uint32_t minIters, double spacing, double delta) override
-    {
-        if (!pcisph()) return fail(NRS_E_STATE, "nrs_pcisph_configure on a context that is not PCISPH");
-        NRSCHK(pciSt.s.set(eta, minIters, spacing, delta));
-        pciSt.settings_changed();
-        return NRS_OK;
-    }
-    // delta from the prototype's sums (k_pci_prototype, the solver's own W_grad on the device; pci_delta) unless it was given; once per
-    // parameter or settings change
-    int pcisph_prepare()
-    {
-        if (pciSt.delta_valid()) return NRS_OK;
-        const double m = (double)PU.particleMass, rd = (double)PU.restDensity, given = pciSt.s.deltaGiven;
-        double o[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (!(given > 0.0))
-            NRSCHK(prototype_sums(true, pciSt.s.spacing > 0.0 ? pciSt.s.spacing : prototype_default_spacing(m, rd), "PCISPH", "pressure scale delta", o));
-        R d;
-        NRSCHK(pci_delta(given, o, (double)PU.timestep, m, rd, &d));
-        pciSt.set_delta(d);
-        return NRS_OK;
-    }
-    int set_surface_akinci(double gamma, double beta) override
-    {
-        if (!pcisph() && !pbf() && !dfsph()) return fail(NRS_E_STATE, "nrs_set_surface_akinci on a context that is not PCISPH, PBF or DFSPH");
-        AkinciSettings a;
-        NRSCHK(a.set(gamma, beta));
-        if (gamma > 0.0) NRSCHK(akNormals.alloc(sizeof(T4) * cap));
-        akSt.s = a;
-        return NRS_OK;
-    }
-    // the advection launch with the Akinci model on (nrs_kernels_akinci.h); SURF_EFF: the context's fsurf term, off while gamma > 0
-    template <bool HAS_B, bool SURF_EFF> void akinci_advect(const PciArrays<R> &A0, const AkinciView<R> &K)
-    {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        if (!plan.lists)
-            hipLaunchKernelGGL((k_akinci_advect_ref<R, KSET, SURF_EFF, HAS_B>), g, b, 0, stream, P, G, A0, K, posB.as<T4>(), velB.as<T4>(),
-                               dens.as<R>(), presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER)
-            launch_listed(k_akinci_advect_lists<R, KSET, SURF_EFF, HAS_B, true>, k_akinci_advect_lists<R, KSET, SURF_EFF, HAS_B>, g.x, P, G, A0, K,
-                          hit_buffer(), posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
-    }
-    // the density scan and the advection launch of a PCISPH or PBF step (x*0 into posPred); *more = false when the step stops here
-    template <bool HAS_B> int pci_prefix(int stop, bool *more)
-    {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        const GridView<R> G = grid_view();
-        const HitBuffer hb = hit_buffer();
-        *more = false;
-        NRSCHK(begin_density_scan<HAS_B>(NRS_STAGE_DENSITY));
-        if (dfsph()) dfsph_factor<HAS_B>();
-        NRSCHK(ev_end());
-        if (stop == NRS_STAGE_DENSITY) return NRS_OK;
-        NRSCHK(ev_begin(NRS_STAGE_P_ADVECT));
-        if (dfsph()) { // the divergence solve on the sorted velocities: the advection reads divergence-free ones
-            dfSt.divIters = 0;
-            if (dfSt.s.minItersV) NRSCHK((dfsph_solve<HAS_B, false>(velB.as<T4>(), dfKvB.as<R>(), dfErrV.as<R>(), dfSt.s.minItersV, dfSt.s.etaV, &dfSt.divIters)));
-            dfSt.divN = dfSt.s.minItersV ? N : 0u;
-        }
-        pciSt.xs = 0;
-        const PciArrays<R> A0 = pci_view(0, 0);
-        const bool cohesion = akSt.s.gamma > 0.0;
-        if (cohesion || (HAS_B && akSt.s.beta > 0.0)) { // the Akinci model: the normals launch, then the advection launch with its walk
-            const AkinciView<R> K{cohesion ? akNormals.as<T4>() : (T4 *)nullptr, (R)akSt.s.gamma, (R)akSt.s.beta};
-            if (cohesion) {
-                launch_pass<HAS_B>(AkinciNormalsPass<R, KSET>{P, dens.as<R>(), K.normals});
-                akSt.normalsValid = true;
-            }
-            if (SURF && !cohesion) akinci_advect<HAS_B, SURF>(A0, K);
-            else akinci_advect<HAS_B, false>(A0, K);
-        } else if (!plan.lists)
-            hipLaunchKernelGGL((k_pci_advect_ref<R, KSET, SURF, HAS_B>), g, b, 0, stream, P, G, A0, posB.as<T4>(), velB.as<T4>(), dens.as<R>(),
-                               presB.as<R>(), N);
-        else if constexpr (KSET == KS_MULLER)
-            launch_listed(k_pci_advect_lists<R, KSET, SURF, HAS_B, true>, k_pci_advect_lists<R, KSET, SURF, HAS_B>, g.x, P, G, A0, hb,
-                          posB.as<T4>(), velB.as<T4>(), dens.as<R>(), presB.as<R>(), N);
-        NRSCHK(ev_end());
-        *more = stop != NRS_STAGE_P_ADVECT;
-        return NRS_OK;
-    }
-    template <bool HAS_B> int pcisph_tail(int stop)
-    {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        bool more;
-        NRSCHK(pci_prefix<HAS_B>(stop, &more));
-        if (!more) return NRS_OK;
-        // the predictive-corrective loop: stop after the iteration l with l >= min_iters and max e <= eta, or at the cap; the max is
-        // not formed (nor read back) before min_iters
-        NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
-        uint32_t l = 0;
-        double err = -1.0;
-        NRSCHK(solve_loop(
-            false, pciSt.s.minIters, maxIters ? maxIters : 50u, pciSt.s.eta,
-            [&](uint32_t) {
-                const PciArrays<R> A = pci_view(pciSt.xs, pciSt.xs ^ 1);
-                launch_pass<HAS_B>(PciDensityPass<R, KSET>{P, A});
-                if (!plan.lists) // (hand-written, nrs_kernels_pcisph.h)
-                    hipLaunchKernelGGL((k_pci_pforce_ref<R, KSET, HAS_B>), g, b, 0, stream, P, grid_view(), A, posB.as<T4>(), N);
-                else if constexpr (KSET == KS_MULLER)
-                    launch_listed(k_pci_pforce_lists<R, KSET, HAS_B, true>, k_pci_pforce_lists<R, KSET, HAS_B>, g.x, P, grid_view(), A, hit_buffer(),
-                                  posB.as<T4>(), N);
-                pciSt.xs ^= 1;
-            },
-            [&](double *e) { return max_of<false>(pciErr.p, N, e); }, &l, &err));
-        lastIters = l;
-        pciSt.lastErr = err;
-        HIPCHK(hipMemcpyAsync(presB.p, P_l.p, sizeof(R) * N, hipMemcpyDeviceToDevice, stream)); // (the step's pressures, NRS_ARR_PRES)
-        NRSCHK(ev_end());
-        if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
-        return integrate_adv(NRS_STAGE_P_INTEGRATE);
-    }
-
-    // ---- PBF step (nrs_kernels_pbf.h; DESIGN.md "PBF") ---------------------------------------------------------------------------------
-    PbfArrays<R> pbf_view(int in, int out) const
-    {
-        PbfArrays<R> A;
-        A.densPred = densCorr.as<R>(); A.lambda = P_l.as<R>(); A.err = pciErr.as<R>();
-        A.dx = forcesP.as<T4>();
-        A.xsIn = (in ? posPred2 : posPred).as<T4>();
-        A.xsOut = (out ? posPred2 : posPred).as<T4>();
-        A.eps = pbfSt.eps();
-        return A;
-    }
-    int pbf_configure(double eta, uint32_t minIters, double relaxation, double xsph) override
-    {
-        if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_configure on a context that is not PBF");
-        NRSCHK(pbfSt.s.set(eta, minIters, relaxation, xsph));
-        pbfSt.settings_changed();
-        return NRS_OK;
-    }
-    // W_q = W((dq h, 0, 0)) on the device (k_pbf_wq), with the current parameters
-    int pbf_eval_wq(double dq, R *wq)
-    {
-        hipLaunchKernelGGL((k_pbf_wq<R, KSET>), dim3(1), dim3(64), 0, stream, P, (R)dq, redPartial.as<double>());
-        HIPCHK(hipGetLastError());
-        double o = 0.0;
-        HIPCHK(hipMemcpyAsync(&o, redPartial.p, sizeof(o), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (!(o > 0.0) || !std::isfinite(o)) return fail(NRS_E_INVALID, "PBF tensile correction: W((dq h, 0, 0)) is not positive");
-        *wq = (R)o;
-        return NRS_OK;
-    }
-    int pbf_set_tensile(double k, double dq) override
-    {
-        if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_set_tensile on a context that is not PBF");
-        PbfSettings t = pbfSt.s;
-        NRSCHK(t.set_tensile(k, dq));
-        R wq;
-        NRSCHK(pbf_eval_wq(dq, &wq));
-        pbfSt.s = t;
-        pbfSt.set_wq(wq);
-        return NRS_OK;
-    }
-    int pbf_set_vorticity(double epsV) override
-    {
-        if (!pbf()) return fail(NRS_E_STATE, "nrs_pbf_set_vorticity on a context that is not PBF");
-        PbfSettings t = pbfSt.s;
-        NRSCHK(t.set_vorticity(epsV));
-        if (epsV > 0.0) NRSCHK(pbfVort.alloc(sizeof(T4) * cap));
-        pbfSt.s = t;
-        return NRS_OK;
-    }
-    // The five prototype sums (nrs_host_solver.h "the derived constants") of a particle on the cubic lattice of the given spacing, by
-    // k_pci_prototype or k_pbf_prototype: the solver's own gradient on the device.  At least one neighbour, or an error.
-    int prototype_sums(bool pci, double spacing, const char *who, const char *what, double *o)
-    {
-        const double h = (double)PU.interactionRadius;
-        const R sp = (R)spacing;
-        int kmax;
-        NRSCHK(prototype_lattice((double)sp, h, who, &kmax));
-        if (pci) hipLaunchKernelGGL((k_pci_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
-        else hipLaunchKernelGGL((k_pbf_prototype<R, KSET>), dim3(1), dim3(64), 0, stream, P, sp, kmax, redPartial.as<double>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(o, redPartial.p, 5 * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        return prototype_has_neighbours(o, (double)sp, h, who, what);
-    }
-    // D of PBF's prototype on the default lattice (eps = relaxation * D, DFSPH's threshold = 1e-6 D)
-    int pbf_prototype_d(const char *who, const char *what, double *d)
-    {
-        double o[5];
-        NRSCHK(prototype_sums(false, prototype_default_spacing((double)PU.particleMass, (double)PU.restDensity), who, what, o));
-        *d = prototype_d(o);
-        return NRS_OK;
-    }
-    // W_q and eps, each once per change of the parameters or settings it depends on
-    int pbf_prepare()
-    {
-        if (pbfSt.s.tensK > 0.0 && !pbfSt.wq_valid()) {
-            R wq;
-            NRSCHK(pbf_eval_wq(pbfSt.s.tensDq, &wq));
-            pbfSt.set_wq(wq);
-        }
-        if (pbfSt.eps_valid()) return NRS_OK;
-        double d;
-        NRSCHK(pbf_prototype_d("PBF", "eps", &d));
-        R e;
-        NRSCHK(pbf_eps(pbfSt.s.relax, d, &e));
-        pbfSt.set_eps(e);
-        return NRS_OK;
-    }
-    template <bool HAS_B> int pbf_tail(int stop)
-    {
-        const uint32_t N = (uint32_t)n;
-        const dim3 g(nblocks(N)), b(BLOCK);
-        bool more;
-        NRSCHK(pci_prefix<HAS_B>(stop, &more));
-        if (!more) return NRS_OK;
-        // Jacobi projection: with eta > 0 stop after the iteration l with l >= min_iters and max e <= eta, or at the cap, the max not
-        // formed (nor read back) before min_iters; with eta = 0 exactly min_iters iterations and no read-back at all
-        NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
-        const bool fixed = pbfSt.s.eta == 0.0;
-        const uint32_t cap = fixed ? pbfSt.s.minIters : (maxIters ? maxIters : 50u);
-        const bool tens = pbfSt.s.tensK > 0.0;
-        const PbfTensile<R> T{(R)pbfSt.s.tensK, pbfSt.wq()};
-        uint32_t l = 0;
-        double err = -1.0;
-        NRSCHK(solve_loop(
-            fixed, pbfSt.s.minIters, cap, pbfSt.s.eta,
-            [&](uint32_t) {
-                const PbfArrays<R> A = pbf_view(pciSt.xs, pciSt.xs ^ 1);
-                launch_pass<HAS_B>(PbfLambdaPass<R, KSET>{P, A});
-                if (tens) launch_pass<HAS_B>(PbfCorrectPass<R, KSET, true>{P, A, T});
-                else launch_pass<HAS_B>(PbfCorrectPass<R, KSET, false>{P, A, {}});
-                pciSt.xs ^= 1;
-            },
-            [&](double *e) { return max_of<false>(pciErr.p, N, e); }, &l, &err));
-        lastIters = l;
-        pciSt.lastErr = err;
-        pbfSt.errPending = fixed ? N : 0u;
-        HIPCHK(hipMemcpyAsync(presB.p, P_l.p, sizeof(R) * N, hipMemcpyDeviceToDevice, stream)); // (lambda, NRS_ARR_PRES)
-        NRSCHK(ev_end());
-        if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
-        // v = (x* - x) / dt (+ XSPH), x = x*.  The XSPH launch reads x_j and x*_j of its neighbours, so it leaves the velocities in velB
-        // and k_pbf_integrate, which overwrites x, follows it.
-        NRSCHK(ev_begin(NRS_STAGE_P_INTEGRATE));
-        const T4 *xs = (const T4 *)pci_xs_current();
-        const bool xsph = pbfSt.s.xsph > 0.0, vort = pbfSt.s.vortEps > 0.0;
-        if (xsph) launch_pass<HAS_B>(PbfXsphPass<R, KSET>{{}, P, xs, velB.as<T4>(), (R)pbfSt.s.xsph});
-        // vorticity confinement: omega from u = (x* - x) / dt, then the confinement on the velocity XSPH left (or u); both read x_j
-        if (vort) {
-            T4 *om = pbfVort.as<T4>();
-            const int given = xsph ? 1 : 0;
-            launch_pass<HAS_B>(PbfVorticityPass<R, KSET>{{}, P, xs, om});
-            launch_pass<HAS_B>(PbfConfinePass<R, KSET>{{}, P, xs, (const T4 *)om, velB.as<T4>(), given, (R)pbfSt.s.vortEps});
-            pbfSt.vortValid = true;
-        }
-        return launch_last([&](uint32_t *nh, uint32_t *ni, const uint32_t *prevHash, uint32_t *tileMovers) {
-            hipLaunchKernelGGL((k_pbf_integrate<R>), g, b, 0, stream, P, posB.as<T4>(), velB.as<T4>(), xs, (xsph || vort) ? 1 : 0, N, nh, ni,
-                               prevHash, tileMovers);
-        });
-    }
-
-    // ---- DFSPH step (nrs_kernels_dfsph.h; DESIGN.md "DFSPH") -------------------------------------------------------------------------
-    // HASH .. DENSITY as PCISPH (then the factor launch), P_ADVECT = the divergence solve + PCISPH's advection launch, P_SOLVE = the
-    // density solve on vel_adv, P_INTEGRATE = integrate_adv (Fp = 0: v = vel_adv, x += dt v)
-    DfsphArrays<R> dfsph_view(T4 *u, R *K, R *err) const
-    {
-        DfsphArrays<R> A;
-        A.u = u; A.dens = dens.as<R>(); A.alpha = dfAlpha.as<R>(); A.kappa = P_l.as<R>(); A.K = K; A.err = err;
-        A.rhoAdv = densCorr.as<R>(); A.thr = dfSt.threshold();
-        return A;
-    }
-    int dfsph_configure(double eta, uint32_t minIters, double etaV, uint32_t minItersV, int warm) override
-    {
-        if (!dfsph()) return fail(NRS_E_STATE, "nrs_dfsph_configure on a context that is not DFSPH");
-        NRSCHK(dfSt.s.set(eta, minIters, etaV, minItersV, warm));
-        return NRS_OK;
-    }
-    // thr = 1e-6 D_proto, D_proto = |sum g|^2 + sum |g|^2 of PBF's prototype (k_pbf_prototype); once per parameter change
-    int dfsph_prepare()
-    {
-        if (dfSt.threshold_valid()) return NRS_OK;
-        double d;
-        NRSCHK(pbf_prototype_d("DFSPH", "D_proto", &d));
-        R thr;
-        NRSCHK(dfsph_threshold(d, &thr));
-        dfSt.set_threshold(thr);
-        return NRS_OK;
-    }
-    template <bool HAS_B> void dfsph_factor()
-    {
-        launch_pass<HAS_B>(DfsphFactorPass<R, KSET>{{P, dfsph_view(nullptr, nullptr, nullptr)}});
-        dfSt.alphaValid = true;
-    }
-    // one A/B pair on u
-    template <bool HAS_B, bool DENS> void dfsph_pair(const DfsphArrays<R> &A, int phase)
-    {
-        const DfsphPassBase<R, KSET> base{P, A};
-        const bool moving = HAS_B && bt.moving_step(); // A with the wall velocities (DfsphDivPass's MOVING); B is unchanged
-        if constexpr (HAS_B) {
-            if (moving) launch_pass<HAS_B>(DfsphDivPass<R, KSET, DENS, true>{base, bt.wall_velocities(), phase});
-        }
-        if (!moving) launch_pass<HAS_B>(DfsphDivPass<R, KSET, DENS>{base, {}, phase});
-        const uint32_t N = (uint32_t)n; // B: hand-written (nrs_kernels_dfsph.h)
-        const dim3 g(nblocks(N)), b(BLOCK);
-        if (!plan.lists)
-            hipLaunchKernelGGL((k_dfsph_vupdate_ref<R, KSET, HAS_B>), g, b, 0, stream, P, grid_view(), A, posB.as<T4>(), N);
-        else if constexpr (KSET == KS_MULLER)
-            launch_listed(k_dfsph_vupdate_lists<R, KSET, HAS_B, true>, k_dfsph_vupdate_lists<R, KSET, HAS_B>, g.x, P, grid_view(), A, hit_buffer(),
-                          posB.as<T4>(), N);
-    }
-    // one solve (DENS: the density solve) in place on u, K in place on K (the sorted K_prev on entry).  eta > 0: stop after the iteration
-    // l with l >= min_iters and avg e <= eta, or at the cap (nrs_set_max_iterations, 0 = 100), the average not formed (nor read back)
-    // before min_iters; eta = 0: exactly min_iters iterations and no read-back.  The warm-start pair counts as no iteration.
-    template <bool HAS_B, bool DENS> int dfsph_solve(T4 *u, R *K, R *err, uint32_t minIters, double eta, uint32_t *iters)
-    {
-        const uint32_t N = (uint32_t)n;
-        const DfsphArrays<R> A = dfsph_view(u, K, err);
-        const bool fixed = eta == 0.0;
-        const uint32_t cap = fixed ? minIters : (maxIters ? maxIters : 100u);
-        if (dfSt.s.warm) dfsph_pair<HAS_B, DENS>(A, DFSPH_PHASE_WARM);
-        double avg = 0.0;
-        return solve_loop(
-            fixed, minIters, cap, eta, [&](uint32_t l) { dfsph_pair<HAS_B, DENS>(A, (l || dfSt.s.warm) ? DFSPH_PHASE_MORE : DFSPH_PHASE_FIRST); },
-            [&](double *e) {
-                double acc = 0.0;
-                NRSCHK(reduce_sum(err, N, &acc));
-                *e = acc / (double)N;
-                return (int)NRS_OK;
-            },
-            iters, &avg);
-    }
-    template <bool HAS_B> int dfsph_tail(int stop)
-    {
-        const uint32_t N = (uint32_t)n;
-        bool more;
-        NRSCHK(pci_prefix<HAS_B>(stop, &more));
-        if (!more) return NRS_OK;
-        NRSCHK(ev_begin(NRS_STAGE_P_SOLVE));
-        uint32_t l = 0;
-        NRSCHK((dfsph_solve<HAS_B, true>(velAdv.as<T4>(), presB.as<R>(), pciErr.as<R>(), dfSt.s.minIters, dfSt.s.eta, &l)));
-        lastIters = l;
-        dfSt.denN = N;
-        NRSCHK(ev_end());
-        if (stop == NRS_STAGE_P_SOLVE) return NRS_OK;
-        return integrate_adv(NRS_STAGE_P_INTEGRATE);
+        if (sesph()) return sesph_tail<HAS_B>(stop);
+        if (plan.watch) HIPCHK(hipMemsetAsync(errWord.as<uint32_t>() + 1, 0, 4, stream)); // (IISPH: SolverStep::nonFinite)
+        NRSCHK(wall_list_of_step());
+        return ps.template tail<HAS_B>(solver_step(stop), stop, last_launch());
     }
 
     // ---- host-driven IISPH step (multi-GPU: the loop exit needs the average over ALL ranks) ---------------------------------
@@ -1217,44 +629,23 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (!iisph()) return fail(NRS_E_STATE, "not an IISPH context");
         NRSCHK(validate("nrs_iisph_*"));
         if (phase == 0) { // predict
-            if (midStep || iisphPhase) return fail(NRS_E_STATE, "a step is already in progress");
+            if (midStep || ps.host_step()) return fail(NRS_E_STATE, "a step is already in progress");
             if (inflow.active()) NRSCHK(apply_inflow());
             if (n == 0) return NRS_OK;
             fusedThisStep = false; splitClearedCells = false;
             plan = plan_step(0);
             NRSCHK(advance_bodies_and_rebuild());
             NRSCHK(stage_prefix(0));
-            if (bt.count()) NRSCHK(iisph_predict<true>(0)); else NRSCHK(iisph_predict<false>(0));
-            iisphPhase = 1;
-            return NRS_OK;
+            NRSCHK(wall_list_of_step());
+            return with_walls([&](auto hasB) { return ps.template host_predict<hasB>(solver_step(0)); });
         }
-        if (!iisphPhase) return fail(NRS_E_STATE, "nrs_iisph_predict first");
-        if (phase == 1) { // one iteration + the density-error sum over the particles this rank owns
-            if (exch.on() && (int)iisphIter >= exch.max_iters())
-                return fail(NRS_E_STATE, "IISPH slab run: more solver iterations than the halo width supports (halo >= 2 * iterations + 4 cells)");
-            if (bt.count()) NRSCHK(iisph_iteration<true>()); else NRSCHK(iisph_iteration<false>());
-            const uint32_t N = (uint32_t)n, nbk = std::min<uint32_t>(1024u, nblocks(N));
-            unsigned long long *cnt = (unsigned long long *)((char *)redOut.p); // redOut: [double sum][u64 count]
-            HIPCHK(hipMemsetAsync(redOut.p, 0, 16, stream));
-            hipLaunchKernelGGL((k_sum_partial<R>), dim3(nbk), dim3(BLOCK), 0, stream, densCorr.as<R>(), redPartial.as<double>(), N,
-                               exch.on() ? posB.as<T4>() : (const T4 *)nullptr, cnt + 1);
-            hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(BLOCK), 0, stream, redPartial.as<double>(), redOut.as<double>(), nbk);
-            double h[2] = {0, 0};
-            HIPCHK(hipMemcpyAsync(h, redOut.p, 16, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            unsigned long long c;
-            std::memcpy(&c, &h[1], 8);
-            if (sum) *sum = h[0];
-            if (count) *count = exch.on() ? (uint64_t)c : (uint64_t)N;
-            lastIters = iisphIter;
-            return NRS_OK;
-        }
+        if (!ps.host_step()) return fail(NRS_E_STATE, "nrs_iisph_predict first");
+        if (phase == 1) return with_walls([&](auto hasB) { return ps.template host_iterate<hasB>(solver_step(0), sum, count); });
         // finish
-        if (iisphIter == 0) return fail(NRS_E_STATE, "nrs_iisph_iterate at least once before nrs_iisph_finish");
-        if (bt.count()) NRSCHK(iisph_finish<true>(0)); else NRSCHK(iisph_finish<false>(0));
+        NRSCHK(with_walls([&](auto hasB) { return ps.template host_finish<hasB>(solver_step(0), last_launch()); }));
         HIPCHK(hipGetLastError());
         NRSCHK(end_of_step());
-        iisphPhase = 0;
+        ps.host_step_ended();
         return NRS_OK;
     }
     // ---- slab decomposition: the exchange itself lives in exch (nrs_slab_exchange.h; its kernels: nrs_kernels_slab.h; the host
@@ -1299,7 +690,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (mcap == 0 || mcap > (uint64_t)HIT_INDEX) return fail(NRS_E_INVALID, "bad message capacity");
         NRSCHK(finish_pack());   // (a pack right behind a pack whose totals nobody has looked at yet)
         NRSCHK(compact_holes()); // (a pack right after a pack/unpack without a step in between)
-        if (iisphPhase) return fail(NRS_E_STATE, "a host-driven IISPH step is in progress");
+        if (ps.host_step()) return fail(NRS_E_STATE, "a host-driven IISPH step is in progress");
         if (iisph() && n) // the warm-start pressure travels in vel.w (k_pressure_to_velw)
             hipLaunchKernelGGL((k_pressure_to_velw<R>), dim3(nblocks(n)), dim3(BLOCK), 0, stream, velA.as<T4>(), presA.as<R>(), (uint32_t)n);
         const uint32_t N = (uint32_t)n;
@@ -1382,47 +773,38 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (steps) *steps = sort.stats().steps;
         if (fallbacks) *fallbacks = sort.stats().fallbacks;
     }
-    // which statistic an id means on this context, or its refusal: route_stat (nrs_host_solver.h); the device work is here
+    // which statistic an id means on this context, or its refusal: route_stat (nrs_host_solver.h); the device work on a solver's buffer
+    // is ps's, on the hit lists red's
     StatFacts stat_facts() const
     {
-        return StatFacts{cfg.solver, exch.host().packed, pbfSt.errPending != 0, !(pciSt.lastErr < 0.0), dfSt.denN, dfSt.divN, hitCounts.p != nullptr, n != 0, midStep};
+        return StatFacts{cfg.solver, exch.host().packed, ps.pbfSt.errPending != 0, !(ps.pciSt.lastErr < 0.0), ps.dfSt.denN, ps.dfSt.divN, hitCounts.p != nullptr, n != 0, midStep};
     }
     int get_stat(int which, double *out) override
     {
         StatRoute r;
         NRSCHK(route_stat(which, stat_facts(), r));
         if (r.formMaxFirst) {
-            NRSCHK(max_of<false>(pciErr.p, pbfSt.errPending, &pciSt.lastErr));
-            pbfSt.errPending = 0;
+            NRSCHK(ps.form_pending_max());
             NRSCHK(route_stat(which, stat_facts(), r)); // again, on the maximum just formed: "no PBF solve yet" is tested on that value
         }
         switch (r.kind) {
         case STAT_MOVER_COUNT: *out = sort.stats().lastMovers; return NRS_OK;
         case STAT_SLAB_FORM: *out = (int)exch.host().form; return NRS_OK;
         case STAT_PBF_ERROR:
-        case STAT_PCI_ERROR: *out = pciSt.lastErr; return NRS_OK;
-        case STAT_PBF_EPS: *out = (double)pbfSt.eps(); return NRS_OK;
-        case STAT_PCI_DELTA: *out = (double)pciSt.delta(); return NRS_OK;
-        case STAT_DFSPH_DIV_ITERS: *out = (double)dfSt.divIters; return NRS_OK;
-        case STAT_DFSPH_MAX: return max_of<false>(r.divergence ? dfErrV.p : pciErr.p, r.count, out);
-        case STAT_DFSPH_AVG: {
-            double acc = 0.0;
-            NRSCHK(reduce_sum((const R *)(r.divergence ? dfErrV.p : pciErr.p), r.count, &acc));
-            *out = acc / (double)r.count;
-            return NRS_OK;
-        }
+        case STAT_PCI_ERROR: *out = ps.pciSt.lastErr; return NRS_OK;
+        case STAT_PBF_EPS: *out = (double)ps.pbfSt.eps(); return NRS_OK;
+        case STAT_PCI_DELTA: *out = (double)ps.pciSt.delta(); return NRS_OK;
+        case STAT_DFSPH_DIV_ITERS: *out = (double)ps.dfSt.divIters; return NRS_OK;
+        case STAT_DFSPH_MAX: return ps.dfsph_error(r.divergence, false, r.count, out);
+        case STAT_DFSPH_AVG: return ps.dfsph_error(r.divergence, true, r.count, out);
         case STAT_HIT_OVERFLOW:
         case STAT_HIT_MEAN:
         case STAT_HIT_MAX:
         case STAT_HIT_UNSTAGED: break;
         }
         const uint32_t N = (uint32_t)n;
-        HIPCHK(hipMemsetAsync(redPartial.p, 0, 4 * sizeof(unsigned long long), stream));
-        hipLaunchKernelGGL(k_hit_stats, dim3(std::min<uint32_t>(1024u, nblocks(N))), dim3(BLOCK), 0, stream, hitCounts.as<uint32_t>(),
-                           (unsigned long long *)redPartial.p, N);
         unsigned long long h[4] = {0, 0, 0, 0};
-        HIPCHK(hipMemcpyAsync(h, redPartial.p, sizeof(h), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
+        NRSCHK(red.hit_stats(hitCounts.as<uint32_t>(), N, h));
         *out = r.kind == STAT_HIT_OVERFLOW ? (double)h[0] : (r.kind == STAT_HIT_MEAN ? (double)h[1] / (double)N : (r.kind == STAT_HIT_MAX ? (double)h[2] : (double)h[3]));
         return NRS_OK;
     }
@@ -1442,21 +824,19 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             std::swap(velA.p, velB.p);
         }
         if (pressure_swaps(cfg.solver)) std::swap(presA.p, presB.p); // (PCISPH: the solve left its final pressures in presB, PBF its lambda, DFSPH K)
-        if (dfsph()) std::swap(dfKvA.p, dfKvB.p);
+        ps.kv_swap(); // (DFSPH's Kv follows the particles)
         if (track.on) track.swap();
         return NRS_OK;
     }
     int step(int nsteps, int stop) override
     {
-        if (iisphPhase) return fail(NRS_E_STATE, "a host-driven IISPH step is in progress (nrs_iisph_finish first)");
+        if (ps.host_step()) return fail(NRS_E_STATE, "a host-driven IISPH step is in progress (nrs_iisph_finish first)");
         NRSCHK(validate("nrs_step"));
         if (midStep) return fail(NRS_E_STATE, "state is mid-update after nrs_step_partial; upload particles first");
         NRSCHK(stage_allowed(cfg.solver, stop));
         const bool sources = inflow.active(); // sinks, then emitters, at the top of every step; an enabled emitter steps from empty
         if (n == 0 && !(sources && inflow.emitter_enabled())) return NRS_OK;
-        if (pcisph()) NRSCHK(pcisph_prepare());
-        if (pbf()) NRSCHK(pbf_prepare());
-        if (dfsph()) NRSCHK(dfsph_prepare());
+        NRSCHK(ps.prepare(P, stream));
         for (int s = 0; s < nsteps; ++s) {
             if (sources) {
                 NRSCHK(apply_inflow());
@@ -1468,11 +848,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             NRSCHK(advance_bodies_and_rebuild());
             NRSCHK(stage_prefix(stop));
             if (stop && stop <= NRS_STAGE_REORDER) { midStep = true; break; }
-            if (iisph()) { if (bt.count()) NRSCHK(iisph_tail<true>(stop)); else NRSCHK(iisph_tail<false>(stop)); }
-            else if (pcisph()) { if (bt.count()) NRSCHK(pcisph_tail<true>(stop)); else NRSCHK(pcisph_tail<false>(stop)); }
-            else if (pbf()) { if (bt.count()) NRSCHK(pbf_tail<true>(stop)); else NRSCHK(pbf_tail<false>(stop)); }
-            else if (dfsph()) { if (bt.count()) NRSCHK(dfsph_tail<true>(stop)); else NRSCHK(dfsph_tail<false>(stop)); }
-            else { if (bt.count()) NRSCHK(sesph_tail<true>(stop)); else NRSCHK(sesph_tail<false>(stop)); }
+            NRSCHK(with_walls([&](auto hasB) { return tail<hasB>(stop); }));
             HIPCHK(hipGetLastError());
             if (stop) { midStep = true; break; }
             NRSCHK(end_of_step());
@@ -1527,8 +903,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     {
         if (which == NRS_ARR_POS || which == NRS_ARR_VEL) NRSCHK(compact_holes());
         ArrayRoute r;
-        NRSCHK(route_array(which, ArrayRouteFacts{cfg.solver, midStep, bt.count() != 0, bt.has_bodies(), pbfSt.vortValid, akSt.normalsValid, dfSt.alphaValid,
-                                                  dfSt.kvValid, pciSt.xs}, r));
+        NRSCHK(route_array(which, ArrayRouteFacts{cfg.solver, midStep, bt.count() != 0, bt.has_bodies(), ps.pbfSt.vortValid, ps.akSt.normalsValid,
+                                                  ps.dfSt.alphaValid, ps.dfSt.kvValid, ps.pciSt.xs}, r));
         const uint64_t count = (r.unit == UNIT_U32_CELLS) ? P.numCells : (r.unit == UNIT_VEC4_NB || r.unit == UNIT_U32_NB) ? bt.count() : n;
         const uint64_t elem = (r.unit == UNIT_VEC4_N || r.unit == UNIT_VEC4_NB) ? sizeof(T4) : r.unit == UNIT_SCALAR_N ? sizeof(R) : 4;
         *dptr = buf_ptr(r.buf);
@@ -1544,7 +920,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint64_t particleGen = 0, gridGen = 0, boundaryGen = 0; // uploads / nrs_set_num_particles, grid changes, boundary sets / body assignments
     FluidNow<R> fluid_now() const
     {
-        const SampleFacts facts{midStep, iisphPhase != 0, exch.on(), {P.gridSize[0], P.gridSize[1], P.gridSize[2]},
+        const SampleFacts facts{midStep, ps.host_step(), exch.on(), {P.gridSize[0], P.gridSize[1], P.gridSize[2]},
                                 {(double)P.cellSize[0], (double)P.cellSize[1], (double)P.cellSize[2]}, (double)P.interactionRadius};
         return FluidNow<R>{P, posA.as<T4>(), velA.as<T4>(), n, SampleKey{stepsDone, particleGen, gridGen, boundaryGen}, facts,
                            bt.cell_start(), bt.cell_end(), bt.sorted(), bt.count(), stream};
@@ -1603,7 +979,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int inflow_begin(const char *where, bool driven) const
     {
         NRSCHK(validate(where));
-        return inflow_refusal(exch.on(), midStep, iisphPhase != 0, driven);
+        return inflow_refusal(exch.on(), midStep, ps.host_step(), driven);
     }
     void particles_changed()
     {
@@ -1614,7 +990,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     EmitOut<R> emit_out(int32_t slot, uint32_t firstId)
     {
         EmitOut<R> O{};
-        O.pos = posA.as<T4>(); O.vel = velA.as<T4>(); O.pres = presA.as<R>(); O.kv = dfsph() ? dfKvA.as<R>() : (R *)nullptr;
+        O.pos = posA.as<T4>(); O.vel = velA.as<T4>(); O.pres = presA.as<R>(); O.kv = ps.kv_current();
         O.first = (uint32_t)n;
         if (track.on) {
             const TrackView<R> v = track.template cur<R>();
@@ -1650,7 +1026,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         if (exch.on()) return inflow_refusal(true, false, false, true);
         uint64_t m = 0;
         NRSCHK(inflow_check_block(lattice, vel, n, cap, &m));
-        NRSCHK(inflow_refusal(false, midStep, iisphPhase != 0, true));
+        NRSCHK(inflow_refusal(false, midStep, ps.host_step(), true));
         uint32_t firstId = 0;
         if (track.on) NRSCHK(track.ids.reserve(m, &firstId));
         NRSCHK(inflow.template emit_block<R>(lattice_from(*lattice), vel, (uint32_t)m, emit_out(-1, firstId), stream));
@@ -1688,8 +1064,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         *removed = 0;
         const uint32_t N = (uint32_t)n;
         if (keep < N) {
-            CullArrays<R> A{posA.as<T4>(), velA.as<T4>(), presA.as<R>(), dfsph() ? dfKvA.as<R>() : (const R *)nullptr,
-                            posB.as<T4>(), velB.as<T4>(), presB.as<R>(), dfsph() ? dfKvB.as<R>() : (R *)nullptr};
+            CullArrays<R> A{posA.as<T4>(), velA.as<T4>(), presA.as<R>(), ps.kv_current(), posB.as<T4>(), velB.as<T4>(), presB.as<R>(), ps.kv_other()};
             if (track.on) {
                 const TrackView<R> from = track.template cur<R>(), to = track.template other<R>();
                 A.id = from.id; A.birth = from.birth; A.rec = from.rec;
@@ -1699,7 +1074,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
             std::swap(posA.p, posB.p);
             std::swap(velA.p, velB.p);
             std::swap(presA.p, presB.p);
-            if (dfsph()) std::swap(dfKvA.p, dfKvB.p);
+            ps.kv_swap();
             if (track.on) track.swap();
             *removed = N - keep;
             n = keep;
@@ -1770,7 +1145,7 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     // step's reorder (stage_prefix), swapped where those swap (end_of_step, cull_finish), written by emission, filled for the slots an
     // upload or a count change makes new.  With tracking never enabled nothing here runs.
     TrackSystem track;
-    TrackFacts track_facts() const { return TrackFacts{track.on, track.flags, midStep, iisphPhase != 0}; }
+    TrackFacts track_facts() const { return TrackFacts{track.on, track.flags, midStep, ps.host_step()}; }
     // the slots f of the current order are new particles: fresh ids, born now, the emit value of slot -1
     int track_new_slots(const TrackFresh &f)
     {

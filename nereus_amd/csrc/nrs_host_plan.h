@@ -1,6 +1,6 @@
-// nrs_host_plan.h — which kernels a step launches, and the exit rule of the solver loops.  No HIP: the flags, the solver, the build's
+// nrs_host_plan.h — which kernels a step launches, and the exit rules of the solver loops.  No HIP: the flags, the solver, the build's
 // precision and kernel set and a few grid facts in, a plan out.  The context (nrs_ctx_impl.h) fills PlanFacts, keeps the plan of the
-// step in progress and launches by it.
+// step in progress and launches by it, as do the solver chains it hands the plan to (nrs_solvers.h), which run the loops.
 #pragma once
 #include <cstdint>
 
@@ -111,6 +111,41 @@ int solve_loop(bool fixed, uint32_t minIters, uint32_t cap, double eta, Iterate 
         }
     }
     *iters = l;
+    return NRS_OK;
+}
+
+// IISPH's exit rule, the reference's (pressureSolve, sph_cuda.cu:702-899): while ((rho_avg - 1000) > 1 || l < 2), evaluated in the
+// solver's precision R, or until maxIters (0: no cap) iterations.  iterate() queues one iteration.  The loop condition reads rho_avg
+// only once l >= 2 (sph_cuda.cu:736: `|| l < 2`): the average of the first iteration is never looked at, so nothing is reduced or read
+// back after it.  measure(&acc, flag) forms the sum of the N density errors (rho_avg = (R)acc / N, in R) and waits for it; flag, unless
+// null, gets the word the list-driven chain raises on a non-finite gather (watch; StepPlan::watch), which rides in the same round
+// trip and ends the loop when set.  measure(nullptr, flag) reads the word alone: once, behind the loop, when the last iteration did no
+// reduction.  *flagged: the word was set; the caller repeats the step in reference order.
+template <typename R, typename Iterate, typename Measure>
+int iisph_loop(uint32_t N, uint32_t maxIters, bool watch, Iterate &&iterate, Measure &&measure, uint32_t *iters, bool *flagged)
+{
+    uint32_t l = 0, hflag = 0u;
+    R rho_avg = 0.f;
+    const R rd = 1000.f;
+    const R max_rho_err = 1.f;
+    bool flagRead = false;
+    while (((rho_avg - rd) > max_rho_err) || (l < 2)) {
+        NRSCHK(iterate());
+        l++;
+        flagRead = false;
+        if (maxIters && l >= maxIters) break;
+        if (l >= 2) {
+            double acc = 0.0;
+            NRSCHK(measure(&acc, watch ? &hflag : (uint32_t *)nullptr));
+            flagRead = true;
+            if (watch && hflag) break;
+            rho_avg = (R)acc;
+            rho_avg /= N;
+        }
+    }
+    if (watch && !flagRead) NRSCHK(measure((double *)nullptr, &hflag));
+    *iters = l;
+    *flagged = watch && hflag != 0u;
     return NRS_OK;
 }
 

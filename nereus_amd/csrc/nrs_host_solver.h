@@ -1,8 +1,9 @@
 // nrs_host_solver.h — what differs by solver on the host: which stages a partial step may stop at, which derived constant a parameter
 // change makes stale, the constants themselves (PCISPH's delta, PBF's eps, DFSPH's threshold) from the prototype sums, which of the
 // shared buffers a solver allocates, and which buffer an array id or which computation a statistic id means on a context — or with
-// which text it is refused.  No HIP: solver ids, bools and doubles in, a code and a plain struct out.  The context (nrs_ctx_impl.h)
-// holds one state struct per solver (below), launches the prototype kernels and the reductions, and maps buffer names to pointers.
+// which text it is refused.  No HIP: solver ids, bools and doubles in, a code and a plain struct out.  The solvers' owner
+// (PressureSolvers, nrs_solvers.h) holds one state struct per solver (below), launches the prototype kernels and the reductions and
+// maps its buffer names to pointers; the context (nrs_ctx_impl.h) routes arrays and statistics.
 #pragma once
 #include <cmath>
 #include <cstdint>

@@ -417,7 +417,7 @@ template <typename R> struct IisphArrays {
     // that a product or difference of two such values could overflow.  The list walks visit only neighbours inside the kernel
     // support; the reference's 27-cell walks also multiply the zero gradient of a particle beyond it with expressions of those
     // values (0 * inf = NaN): identical only while everything stays finite.  The context then repeats the step with the
-    // reference-order kernels (Ctx::iisph_tail).  null: not watched.
+    // reference-order kernels (PressureSolvers::iisph_tail, nrs_solvers.h).  null: not watched.
     uint32_t *nonFinite;
 };
 // (1e12: the cube of it is still a finite float — fp64 builds pass scalars through float as well, SURVEY Q11 —; a fluid step has no

@@ -3,6 +3,7 @@
 // and tests/test_host_solver_cpu.py: one command per line on stdin, one answer per line on stdout (the commands that enumerate a cross
 // product themselves answer with one word or line per case, in the order stated at the command).  Doubles travel as C99 hex floats (or
 // nan / inf), so nothing is rounded on the way.  Built by the test with the host compiler, plain and under the sanitizers.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -116,6 +117,29 @@ template <typename R> static void grid(const std::vector<double> &a)
     AabbGrid<R> g = {{(R)7, (R)7, (R)7}, {7u, 7u, 7u}, 7u};
     answer(grid_from_aabb(mn, mx, (R)a[1], g));
     printf("grid %a %a %a %u %u %u %u\n", (double)g.origin[0], (double)g.origin[1], (double)g.origin[2], g.size[0], g.size[1], g.size[2], g.numCells);
+}
+
+// iloop prec N maxIters watch flagFrom acc0 acc1 ...: IISPH's exit rule in the context's precision.  The k-th reduction answers acc_k
+// (the last one again once they run out); the watch word reads 1 from iteration flagFrom on (0: never).  Answers rc, then iterate
+// calls, iters, whether the loop reports the word set, and every measure call: r = the sum, f = the word, then the iterations done
+template <typename R> static void iloop(const std::vector<double> &a)
+{
+    const uint32_t N = (uint32_t)a[1], maxIters = (uint32_t)a[2], flagFrom = (uint32_t)a[4];
+    uint32_t iterates = 0, iters = 12345u;
+    size_t k = 5;
+    bool flagged = false;
+    std::string calls;
+    const int rc = iisph_loop<R>(
+        N, maxIters, a[3] != 0.0, [&] { ++iterates; return (int)NRS_OK; },
+        [&](double *acc, uint32_t *flag) {
+            calls += std::string(" ") + (acc ? "r" : "") + (flag ? "f" : "") + std::to_string(iterates);
+            if (flag) *flag = (flagFrom && iterates >= flagFrom) ? 1u : 0u;
+            if (acc) *acc = a[std::min(k++, a.size() - 1)];
+            return (int)NRS_OK;
+        },
+        &iters, &flagged);
+    answer(rc);
+    printf("iloop %u %u %d%s\n", iterates, iters, flagged ? 1 : 0, calls.c_str());
 }
 
 int main()
@@ -362,6 +386,10 @@ int main()
             printf("loop %u %u %a %d", iterates, iters, err, ordered ? 1 : 0);
             for (uint32_t l : measured) printf(" %u", l);
             printf("\n");
+        } else if (cmd == "iloop") {
+            if (a.size() < 6) { fprintf(stderr, "host_parts_main: 'iloop' takes at least 6 numbers\n"); exit(2); }
+            if (a[0] == 64.0) iloop<double>(a);
+            else iloop<float>(a);
         } else if (cmd == "stage") { // stage solver stop
             need(2);
             answer(stage_allowed((int)a[0], (int)a[1]));

@@ -448,8 +448,100 @@ def test_stat_routing(plain):
     check_stat(plain)
 
 
+# ---- IISPH's exit rule ---------------------------------------------------------------------------------------------------------------
+def iisph_loop_model(prec, n, max_iters, watch, flag_from, accs):
+    """The loop of Ctx::iisph_tail_once of the commit before (pressureSolve, sph_cuda.cu:702-899), in the context's precision:
+    (iterations, word seen set, the measure calls).  A call is "r" (the sum) and / or "f" (the watch word, 1 from iteration flag_from
+    on) followed by the iterations done when it was made."""
+    real = np.float32 if prec == 32 else np.float64
+    l, k, hflag, flag_read, calls = 0, 0, 0, False, []
+    rho_avg, rd, max_rho_err = real(0.0), real(1000.0), real(1.0)
+    while (real(rho_avg - rd) > max_rho_err) or l < 2:
+        l += 1                                   # one iteration
+        flag_read = False
+        if max_iters and l >= max_iters:
+            break
+        if l >= 2:                               # (the average of the first iteration is never looked at: nothing is reduced)
+            if watch:                            # (the word rides in the reduction's round trip)
+                hflag = int(bool(flag_from) and l >= flag_from)
+            calls.append(("rf" if watch else "r") + str(l))
+            acc = accs[min(k, len(accs) - 1)]
+            k += 1
+            flag_read = True
+            if watch and hflag:
+                break
+            rho_avg = real(acc)                  # (R)acc, then / N in R
+            rho_avg = real(rho_avg / real(n))
+    if watch and not flag_read:                  # the last iteration did no reduction: the word alone
+        hflag = int(bool(flag_from) and l >= flag_from)
+        calls.append("f" + str(l))
+    return l, int(bool(watch and hflag)), calls
+
+
+def iisph_loop_cases():
+    n = 1000
+    slow = [n * v for v in (1010.0, 1005.0, 1001.5, 1000.9)]          # the error bound is met by the fourth reduction: l = 5
+    never = [n * 1500.0]
+    cases = []
+    for prec in (32, 64):
+        for watch in (0, 1):
+            cases.append((prec, n, 0, watch, 0, [n * 1000.5]))        # exit at l = 2
+            cases.append((prec, n, 0, watch, 0, [n * 1001.0]))        # (rho_avg - 1000 == 1 is not > 1)
+            cases.append((prec, n, 0, watch, 0, slow))                # exit on the error bound
+            cases.append((prec, n, 9, watch, 0, slow))                # ... before the cap
+            for cap in (1, 2, 3, 5, 7):                               # exit at maxIters = 1, 2, n: no reduction behind the last iteration
+                cases.append((prec, n, cap, watch, 0, never))
+            for flag_from in (1, 2, 3, 4):                            # the word set in a reduction round
+                cases.append((prec, n, 0 if watch else 8, watch, flag_from, never))   # (unwatched, only the cap ends it)
+                cases.append((prec, n, 6, watch, flag_from, slow))
+            for cap, flag_from in ((1, 1), (2, 1), (2, 2), (4, 4), (3, 4)):   # ... and where no reduction ran (or not yet: (3, 4))
+                cases.append((prec, n, cap, watch, flag_from, never))
+        # rounding of the average: (R)acc / N in R.  Sums whose average straddles 1001 in double and rounds onto it in float
+        for big_n in (3, 1000, 16777217, 100000007):
+            for eps in (-3e-7, -1e-9, 0.0, 1e-9, 3e-7, 1e-4):
+                cases.append((prec, big_n, 0, 0, 0, [big_n * 1001.0 * (1.0 + eps), big_n * 1000.0]))
+    return cases
+
+
+def check_iisph_loop(exe):
+    cases = iisph_loop_cases()
+    ans = run(exe, [cmd("iloop", prec, n, cap, watch, flag_from, accs) for prec, n, cap, watch, flag_from, accs in cases])
+    assert len(ans) == 2 * len(cases)
+    by_prec, seen = {}, set()
+    for k, c in enumerate(cases):
+        prec, n, cap, watch, flag_from, accs = c
+        iters, flagged, calls = iisph_loop_model(prec, n, cap, watch, flag_from, accs)
+        v = ans[2 * k + 1][1].split()
+        assert refusal(ans[2 * k]) == (0, "") and ans[2 * k + 1][0] == "iloop", (c, ans[2 * k])
+        assert (int(v[0]), int(v[1]), int(v[2]), v[3:]) == (iters, iters, flagged, calls), (c, v, iters, flagged, calls)
+        assert not any(t.lstrip("rf") == "1" and "r" in t for t in calls)           # no reduction before l >= 2
+        assert sum(t.startswith("f") for t in calls) <= 1 and (not watch) == (not any("f" in t for t in calls))
+        by_prec.setdefault((n, cap, watch, flag_from, tuple(accs)), {})[prec] = iters
+        seen.add((iters == 2, bool(cap) and iters == cap, flagged, bool(calls) and calls[-1].startswith("f")))
+    assert any(len(set(d.values())) == 2 for d in by_prec.values())                  # float and double round the average apart
+    assert {s[0] for s in seen} == {s[1] for s in seen} == {s[3] for s in seen} == {False, True} and {s[2] for s in seen} == {0, 1}
+    assert any(s[2] and s[3] for s in seen) and any(s[2] and not s[3] for s in seen)  # the word found late, and in a reduction round
+
+
+def test_iisph_loop(plain):
+    check_iisph_loop(plain)
+
+
+def test_iisph_loop_model_examples():
+    """the rule on the model itself: the cases the exit rule is known by"""
+    n = 1000
+    assert iisph_loop_model(32, n, 0, 0, 0, [n * 1000.5]) == (2, 0, ["r2"])
+    assert iisph_loop_model(64, n, 0, 1, 0, [n * 1010.0, n * 1005.0, n * 1001.5, n * 1000.9]) == (5, 0, ["rf2", "rf3", "rf4", "rf5"])
+    assert iisph_loop_model(32, n, 1, 1, 1, [0.0]) == (1, 1, ["f1"])
+    assert iisph_loop_model(32, n, 2, 1, 0, [0.0]) == (2, 0, ["f2"])
+    assert iisph_loop_model(64, n, 5, 1, 0, [n * 1500.0]) == (5, 0, ["rf2", "rf3", "rf4", "f5"])
+    assert iisph_loop_model(64, n, 0, 1, 3, [n * 1500.0]) == (3, 1, ["rf2", "rf3"])
+    assert iisph_loop_model(64, n, 0, 0, 3, [n * 1500.0, n * 1500.0, n * 1000.0]) == (4, 0, ["r2", "r3", "r4"])
+
+
 # ---- everything once more under the sanitizers ---------------------------------------------------------------------------------------
 def test_sanitized(sanitized):
+    check_iisph_loop(sanitized)
     check_stage(sanitized)
     check_stale(sanitized)
     check_derived(sanitized)

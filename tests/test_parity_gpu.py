@@ -681,6 +681,44 @@ def test_iisph_list_kernels_equal_reference_order_bitwise(hip_lib):
             np.testing.assert_array_equal(a, b, err_msg=nm)
 
 
+def test_iisph_diverged_list_step_repeats_in_reference_order(hip_lib):
+    """A list-driven IISPH step whose gathers go non-finite is repeated from the sorted input with the reference-order kernels
+    (StepPlan::watch; PressureSolvers::iisph_tail): one full step on a default context equals one on a reference_order context bit
+    for bit, NaNs at the same places — in every stage array, the positions, velocities, pressures and the iteration count.
+    The scene: the smallest compressed block (7^3 particles, fp32 Muller), its two innermost particles coincident and carrying an
+    overflowed warm-start pressure.  The coincident pair alone makes velAdv, densAdv and the new positions NaN but leaves sumDij and
+    the pressures finite (the pressure gradient is poly6's, zero at r = 0, and the clamp at zero swallows a NaN pressure); with
+    P_l = 0.5 * 3e38 the products d_ij p_j overflow, and the reference's loops without a cut-off multiply the infinities with the
+    zero gradients beyond the support (0 * inf = NaN), which the list kernels never visit: only the repeat makes the two
+    contexts agree.  The scene counts because the oracle, run here, shows non-finite entries in sumDij or the pressure of the step."""
+    p, pos, vel = compressed_block(lattice=(7, 7, 7))
+    inner = np.argsort(((pos[:, :3] - pos[:, :3].mean(0)) ** 2).sum(1))[:2]
+    pos = pos.copy()
+    pos[inner[1]] = pos[inner[0]]
+    pres = np.zeros(len(pos), np.float32)
+    pres[inner] = 3e38
+    o = Oracle(p, solver=IISPH)
+    o.set_particles(pos, vel, pres)
+    o.set_boundaries(None, None, update_grid=True)
+    o.step(1)
+    assert not (np.isfinite(o.get("sumDij")).all() and np.isfinite(o.get("pressure")).all())
+    names = ["dens", "velAdv", "forcesAdv", "diiFluid", "diiBoundary", "densAdv", "aii", "sumDij", "densCorr", "P_l", "pres", "forcesP"]
+    outs = []
+    for ref in (False, True):
+        s = capi.Solver(p, len(pos), solver=capi.IISPH, reference_order=ref)
+        s.set_particles(pos, vel, pres)
+        s.set_boundaries(None, None, update_grid=True)
+        s.step(1)
+        outs.append([s.get(nm) for nm in names] + list(s.download(pressure=True)) + [np.array([s.last_iterations], np.float32)])
+        s.close()
+    assert not all(np.isfinite(a).all() for a in outs[1])   # the reference order itself went non-finite
+    for nm, a, b in zip(names + ["pos", "vel", "pressure", "iters"], *outs):
+        a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+        nan = np.isnan(a)
+        np.testing.assert_array_equal(nan, np.isnan(b), err_msg=nm)
+        np.testing.assert_array_equal(a.view(np.uint32)[~nan], b.view(np.uint32)[~nan], err_msg=nm)
+
+
 def test_iisph_self_by_slot_flag(hip_lib):
     """NRS_FLAG_IISPH_SELF_BY_SLOT (SURVEY Q5 off): against the oracle in the same mode, both kernel paths; and the point of the
     flag — the result no longer depends on the order of the input arrays (with the default flags it does, by centimetres)."""
