@@ -788,6 +788,73 @@ int nrs_track_emit_value(nrs_ctx *ctx, int32_t slot, const double a[4]);
 int nrs_track_locate(nrs_ctx *ctx, uint64_t first_id, uint64_t count);
 int nrs_track_diffuse(nrs_ctx *ctx, const double kappa[4], double dt);
 
+/* ---- mesh sampling (DESIGN.md "Mesh sampling"; came after nrs_version() 0.3 without a version change) ------------------------------------
+ * The inverse of the surface extraction: a triangle mesh in, a signed-distance classification on a lattice and the selected lattice
+ * nodes as particles out.  nrs_mesh_field and nrs_mesh_particles need no context (like nrs_boundary_volumes; device < 0 = the current
+ * device); nrs_emit_mesh is nrs_emit_block restricted to the selected nodes.  Brute force: every node against every triangle, no
+ * acceleration structure.  Deterministic: no atomics, every output is bit-reproducible.
+ *
+ * INPUT.  vertices: 3 nv doubles; triangles: 3 nt indices, wound counter-clockwise seen from outside; both HOST arrays.  Node
+ * (i, j, k) of the lattice has the linear index (k * dims[1] + j) * dims[0] + i and the position P[a] = origin[a] + (double)i_a *
+ * spacing[a] (the lattice rule of nrs_sample_lattice, kept in double).
+ *
+ * ARITHMETIC.  All of it is double, in the order written, without contraction; u.v = u.x v.x + u.y v.y + u.z v.z left to right;
+ * u x v = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x).  Per node P the triangles t = 0 .. nt-1 ascending, (A, B, C) its
+ * corners:
+ *   WINDING (the generalised winding number, van Oosterom and Strackee's solid angle).  a = A - P, b = B - P, c = C - P;
+ *     la = sqrt(a.a), lb = sqrt(b.b), lc = sqrt(c.c);  num = a . (b x c);
+ *     den = la * lb * lc + (a.b) * lc + (b.c) * la + (c.a) * lb  (summed left to right);  acc += 2 * atan2(num, den), one accumulator;
+ *     at the end w = acc / (4.0 * M_PI).  About 1 inside a closed mesh, about 0 outside, in between near holes.
+ *   CLOSEST POINT (Ericson, Real-Time Collision Detection 5.1.5).  ab = B - A, ac = C - A, ap = P - A, bp = P - B, cp = P - C;
+ *     d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp;
+ *     vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4.  The first matching region wins:
+ *       1. d1 <= 0 && d2 <= 0:                        q = A
+ *       2. d3 >= 0 && d4 <= d3:                       q = B
+ *       3. vc <= 0 && d1 >= 0 && d3 <= 0:             q = A + (d1 / (d1 - d3)) * ab
+ *       4. d6 >= 0 && d5 <= d6:                       q = C
+ *       5. vb <= 0 && d2 >= 0 && d6 <= 0:             q = A + (d2 / (d2 - d6)) * ac
+ *       6. va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0:   q = B + ((d4 - d3) / ((d4 - d3) + (d5 - d6))) * (C - B)
+ *       7. otherwise dn = 1 / (va + vb + vc):         q = A + ab * (vb * dn) + ac * (vc * dn)   (left to right, per component)
+ *     r = P - q, dd = r.r.  The candidate replaces the best only if dd < best (strict): ties keep the lower triangle index and a NaN
+ *     (a triangle without area can produce one) never wins.  best starts at +inf with index 0xffffffff.
+ * Only atan2 is not an IEEE-exact operation: dist2, nearest and closest3 are the same bits wherever these formulas are evaluated,
+ * winding is bit-reproducible from run to run on one library.  A node's result does not depend on how the nodes are batched.
+ *
+ * nrs_mesh_field writes, for every node in linear index order, to the HOST arrays that are not NULL: winding (w), dist2 (best),
+ * nearest (its triangle) and closest3 (its q, 3 doubles).  With winding NULL no atan2 is evaluated, with the other three NULL no
+ * closest point.  All four NULL: the arguments are checked, nothing runs.
+ *
+ * SELECTION.  A node is selected iff its side is selected (NRS_MESH_INSIDE: w > 0.5; NRS_MESH_OUTSIDE: w <= 0.5; both: every node) and
+ * dmin * dmin <= dist2 <= dmax * dmax (dmax may be +inf).  Fill with clearance: INSIDE, dmin = clearance, dmax = inf.  Wall shell:
+ * INSIDE | OUTSIDE, 0, thickness.  NRS_MESH_SNAP emits the closest point q instead of the node: a smooth single layer on the surface
+ * instead of a staircase.  SNAPPED POINTS MAY COINCIDE along sharp edges and at corners (several nodes share one closest point); Akinci
+ * volumes (nrs_boundary_volumes) share the volume between coincident samples, so such a shell is a valid wall.  The selected nodes
+ * keep the linear index order (a scan, no atomics).  A particle's component is (SReal)P[a], or (SReal)q[a] with SNAP, rounded once;
+ * its w is 1.
+ * nrs_mesh_particles: pos4 is a HOST array of `capacity` SVec4 of the given precision; *count is always set; pos4 NULL: count only;
+ * count > capacity: nothing is written, NRS_E_CAPACITY.
+ * nrs_emit_mesh appends the selected nodes behind the context's n exactly as nrs_emit_block appends all nodes (velocity (SReal)vel[a],
+ * pressure 0, DFSPH Kv 0; tracking: consecutive ids in selection order, the emit value of slot -1): all of them or, with
+ * NRS_E_CAPACITY (more than capacity - n selected), none.  The selection stays on the device; the call reads one number back, the
+ * count, and frees its scratch buffers before it returns (it waits for the append).
+ *
+ * NRS_E_INVALID: a NULL mesh, vertices or triangles; nv == 0; nt == 0 or nt >= 2^31; an index >= nv; a non-finite vertex; a bad
+ * lattice (as nrs_sample_lattice); a NULL rule, flags without a side or with unknown bits, reserved != 0, dmin < 0 or NaN, dmax NaN or
+ * below dmin; a precision that is not 32 or 64; for nrs_emit_mesh also SNAP and everything nrs_emit_block refuses (NRS_E_STATE
+ * likewise).  A refused call changes nothing. */
+typedef struct nrs_mesh { const double *vertices; uint64_t nv; const uint32_t *triangles; uint64_t nt; } nrs_mesh;
+/* flags of nrs_mesh_rule (macros: the NRS_MESH_* enumerators are the results of the surface extraction) */
+#define NRS_MESH_INSIDE 1u
+#define NRS_MESH_OUTSIDE 2u
+#define NRS_MESH_SNAP 4u
+typedef struct nrs_mesh_rule { uint32_t flags, reserved; double dmin, dmax; } nrs_mesh_rule;
+int nrs_mesh_field(int device, const nrs_mesh *mesh, const nrs_lattice *lattice, double *winding, double *dist2, uint32_t *nearest,
+                   double *closest3);
+int nrs_mesh_particles(int device, int precision, const nrs_mesh *mesh, const nrs_lattice *lattice, const nrs_mesh_rule *rule, void *pos4,
+                       uint64_t capacity, uint64_t *count);
+int nrs_emit_mesh(nrs_ctx *ctx, const nrs_mesh *mesh, const nrs_lattice *lattice, const nrs_mesh_rule *rule, const double vel[3],
+                  uint64_t *added);
+
 #ifdef __cplusplus
 }
 #endif

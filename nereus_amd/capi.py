@@ -48,6 +48,8 @@ SINK_DOMAIN = 1
 TRACK_ATTR = 1
 TRACK_ID, TRACK_BIRTH, TRACK_ATTRIBUTE, TRACK_SLOT_OF = 0, 1, 2, 3
 TRACK_NONE = 0xFFFFFFFF
+# mesh sampling: the flags of a selection rule (NRS_MESH_INSIDE, _OUTSIDE, _SNAP)
+MESH_INSIDE, MESH_OUTSIDE, MESH_SNAP = 1, 2, 4
 
 # NRS_STAGE_*
 STAGE_HASH, STAGE_SORT, STAGE_REORDER, STAGE_DENSITY, STAGE_FORCES, STAGE_INTEGRATE = 1, 2, 3, 4, 5, 6
@@ -91,6 +93,7 @@ EXPORTS = [
     "nrs_emitter_set", "nrs_emitter_get", "nrs_emit_block", "nrs_sinks_set", "nrs_cull", "nrs_sinks_count",
     "nrs_track_enable", "nrs_track_disable", "nrs_track_info", "nrs_track_upload", "nrs_track_result", "nrs_track_device_ptr",
     "nrs_track_emit_value", "nrs_track_locate", "nrs_track_diffuse",
+    "nrs_mesh_field", "nrs_mesh_particles", "nrs_emit_mesh",
 ]
 
 
@@ -133,6 +136,14 @@ class NrsConfig(C.Structure):
 
 class NrsLattice(C.Structure):
     _fields_ = [("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("dims", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+class NrsMesh(C.Structure):
+    _fields_ = [("vertices", C.c_void_p), ("nv", C.c_uint64), ("triangles", C.c_void_p), ("nt", C.c_uint64)]
+
+
+class NrsMeshRule(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("dmin", C.c_double), ("dmax", C.c_double)]
 
 
 class NereusError(RuntimeError):
@@ -245,6 +256,9 @@ def load_library(path=None):
     lib.nrs_track_emit_value.argtypes = [vp, C.c_int32, dp]
     lib.nrs_track_locate.argtypes = [vp, u64, u64]
     lib.nrs_track_diffuse.argtypes = [vp, dp, C.c_double]
+    lib.nrs_mesh_field.argtypes = [i32, C.POINTER(NrsMesh), C.POINTER(NrsLattice), vp, vp, vp, vp]
+    lib.nrs_mesh_particles.argtypes = [i32, i32, C.POINTER(NrsMesh), C.POINTER(NrsLattice), C.POINTER(NrsMeshRule), vp, u64, C.POINTER(u64)]
+    lib.nrs_emit_mesh.argtypes = [vp, C.POINTER(NrsMesh), C.POINTER(NrsLattice), C.POINTER(NrsMeshRule), dp, C.POINTER(u64)]
     _lib = lib
     return lib
 
@@ -263,6 +277,75 @@ def boundary_volumes(bi4, h, double=False, device=-1):
     if rc != 0:
         raise NereusError("libnereus_hip error %d: %s" % (rc, lib.nrs_last_error().decode()))
     return out
+
+
+def _lattice(origin, spacing, dims):
+    L = NrsLattice()
+    sp = np.broadcast_to(np.asarray(spacing, np.float64), (3,))
+    for a in range(3):
+        L.origin[a], L.spacing[a], L.dims[a] = float(origin[a]), float(sp[a]), int(dims[a])
+    return L
+
+
+def _mesh(vertices, triangles):
+    """an nrs_mesh over vertices (nv, 3) double and triangles (nt, 3) uint32; returns (struct, the arrays it points into)"""
+    v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+    m = NrsMesh(v.ctypes.data if v.size else None, v.shape[0], t.ctypes.data if t.size else None, t.shape[0])
+    return m, (v, t)
+
+
+def _mesh_rule(flags, dmin, dmax, reserved=0):
+    return NrsMeshRule(int(flags), int(reserved), float(dmin), float(dmax))
+
+
+def mesh_field(vertices, triangles, origin, spacing, dims, winding=True, dist2=True, nearest=True, closest=True, device=-1):
+    """winding number, squared distance, nearest triangle and closest point of a triangle mesh at the nodes of a lattice
+    (nrs_mesh_field); returns a dict with the outputs asked for: "winding" (m,), "dist2" (m,), "nearest" (m,) uint32,
+    "closest" (m, 3), m the nodes in linear index order"""
+    lib = load_library()
+    M, keep = _mesh(vertices, triangles)
+    L = _lattice(origin, spacing, dims)
+    m = int(dims[0]) * int(dims[1]) * int(dims[2])
+    out = {}
+    if winding:
+        out["winding"] = np.empty(m, np.float64)
+    if dist2:
+        out["dist2"] = np.empty(m, np.float64)
+    if nearest:
+        out["nearest"] = np.empty(m, np.uint32)
+    if closest:
+        out["closest"] = np.empty((m, 3), np.float64)
+    rc = lib.nrs_mesh_field(int(device), C.byref(M), C.byref(L), _ptr(out.get("winding")), _ptr(out.get("dist2")),
+                            _ptr(out.get("nearest")), _ptr(out.get("closest")))
+    if rc != 0:
+        raise NereusError("libnereus_hip error %d: %s" % (rc, lib.nrs_last_error().decode()))
+    return out
+
+
+def mesh_particles(vertices, triangles, origin, spacing, dims, flags=MESH_INSIDE, dmin=0.0, dmax=float("inf"), double=False,
+                   count_only=False, capacity=None, device=-1):
+    """the lattice nodes a rule selects as particles (nrs_mesh_particles): (count, 4) SReal, w = 1, in linear index order; with
+    MESH_SNAP the closest points on the mesh.  Two calls: the count, then the particles.  count_only: just the count.  capacity: the room offered (default: what is needed;
+    less raises NereusError with NRS_E_CAPACITY)"""
+    lib = load_library()
+    M, keep = _mesh(vertices, triangles)
+    L = _lattice(origin, spacing, dims)
+    R = _mesh_rule(flags, dmin, dmax)
+    real = np.float64 if double else np.float32
+    count = C.c_uint64(0)
+    rc = lib.nrs_mesh_particles(int(device), 64 if double else 32, C.byref(M), C.byref(L), C.byref(R), None, 0, C.byref(count))
+    if rc != 0:
+        raise NereusError("libnereus_hip error %d: %s" % (rc, lib.nrs_last_error().decode()))
+    if count_only:
+        return int(count.value)
+    cap = int(count.value) if capacity is None else int(capacity)
+    out = np.empty((cap, 4), real)
+    rc = lib.nrs_mesh_particles(int(device), 64 if double else 32, C.byref(M), C.byref(L), C.byref(R), _ptr(out) if cap else None, cap,
+                                C.byref(count))
+    if rc != 0:
+        raise NereusError("libnereus_hip error %d: %s" % (rc, lib.nrs_last_error().decode()))
+    return out[:int(count.value)]
 
 
 def eval_smoothing(which, r, s, h, c0, c1, double=False):
@@ -544,13 +627,7 @@ class Solver:
         pts = np.ascontiguousarray(points4, dtype=self.real).reshape(-1, 4)
         self._chk(self.lib.nrs_sample_points(self.h, _ptr(pts) if len(pts) else None, pts.shape[0], int(fields)))
 
-    @staticmethod
-    def _lattice(origin, spacing, dims):
-        L = NrsLattice()
-        sp = np.broadcast_to(np.asarray(spacing, np.float64), (3,))
-        for a in range(3):
-            L.origin[a], L.spacing[a], L.dims[a] = float(origin[a]), float(sp[a]), int(dims[a])
-        return L
+    _lattice = staticmethod(_lattice)
 
     def sample_lattice(self, origin, spacing, dims, fields):
         """evaluate `fields` on the dims[0] x dims[1] x dims[2] nodes origin + idx * spacing (nrs_sample_lattice); spacing: a number
@@ -738,6 +815,17 @@ class Solver:
         L = self._lattice(origin, spacing, dims)
         v, added = (C.c_double * 3)(*[float(a) for a in vel]), C.c_uint64(0)
         self._chk(self.lib.nrs_emit_block(self.h, C.byref(L), v, C.byref(added)))
+        return int(added.value)
+
+    def emit_mesh(self, vertices, triangles, origin, spacing, dims, flags=MESH_INSIDE, dmin=0.0, dmax=float("inf"),
+                  vel=(0.0, 0.0, 0.0)):
+        """append the lattice nodes a rule selects against a triangle mesh (see mesh_particles) as fluid particles with velocity
+        `vel` (nrs_emit_mesh): all or, above the capacity, none; returns how many were added"""
+        M, keep = _mesh(vertices, triangles)
+        L = self._lattice(origin, spacing, dims)
+        R = _mesh_rule(flags, dmin, dmax)
+        v, added = (C.c_double * 3)(*[float(a) for a in vel]), C.c_uint64(0)
+        self._chk(self.lib.nrs_emit_mesh(self.h, C.byref(M), C.byref(L), C.byref(R), v, C.byref(added)))
         return int(added.value)
 
     def sinks_set(self, boxes=(), domain=False, interval=1, flags=None, nboxes=None, reserved=0):

@@ -549,6 +549,11 @@ int nrs_emit_block(nrs_ctx *ctx, const nrs_lattice *sites, const double vel[3], 
     CTX_GUARD(ctx);
     return ctx->impl->emit_block(sites, vel, added);
 }
+int nrs_emit_mesh(nrs_ctx *ctx, const nrs_mesh *mesh, const nrs_lattice *lattice, const nrs_mesh_rule *rule, const double vel[3], uint64_t *added)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->emit_mesh(mesh, lattice, rule, vel, added);
+}
 int nrs_sinks_set(nrs_ctx *ctx, const nrs_sink_config *cfg)
 {
     CTX_GUARD(ctx);

@@ -163,6 +163,7 @@ struct CtxBase {
     virtual int emitter_set(uint32_t slot, const nrs_emitter *e) = 0;
     virtual int emitter_get(uint32_t slot, nrs_emitter *e, uint64_t *emitted, uint64_t *dropped) = 0;
     virtual int emit_block(const nrs_lattice *lattice, const double *vel, uint64_t *added) = 0;
+    virtual int emit_mesh(const nrs_mesh *mesh, const nrs_lattice *lattice, const nrs_mesh_rule *rule, const double *vel, uint64_t *added) = 0;
     virtual int sinks_set(const nrs_sink_config *cfg) = 0;
     virtual int cull(uint64_t *removed) = 0;
     virtual int sinks_count(uint64_t *removedTotal, uint64_t *culls) = 0;

@@ -59,6 +59,7 @@
 #include "nrs_slab_exchange.h"
 #include "nrs_readers.h"
 #include "nrs_inflow.h"
+#include "nrs_mesh.h"
 #include "nrs_track.h"
 #include "nrs_kernels_resort.h"
 #include <climits>
@@ -1030,6 +1031,41 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
         uint32_t firstId = 0;
         if (track.on) NRSCHK(track.ids.reserve(m, &firstId));
         NRSCHK(inflow.template emit_block<R>(lattice_from(*lattice), vel, (uint32_t)m, emit_out(-1, firstId), stream));
+        n += m;
+        particles_changed();
+        if (added) *added = m;
+        return NRS_OK;
+    }
+    // nrs_emit_mesh: the selection runs on the device (MeshSampler, nrs_mesh.h: at most capacity - n node indices are kept), the count is
+    // read back (the one wait), then the append; the sampler's buffers go before the call returns
+    MeshSampler meshSampler;
+    int emit_mesh(const nrs_mesh *mesh, const nrs_lattice *lattice, const nrs_mesh_rule *rule, const double *vel, uint64_t *added) override
+    {
+        if (added) *added = 0;
+        NRSCHK(validate("nrs_emit_mesh"));
+        if (exch.on()) return inflow_refusal(true, false, false, true);
+        uint64_t nodes = 0;
+        NRSCHK(inflow_check_sites(lattice, vel, &nodes));
+        NRSCHK(mesh_check_mesh(mesh));
+        NRSCHK(mesh_check_rule(rule));
+        if (rule->flags & NRS_MESH_SNAP) return mesh_refuse_snap();
+        NRSCHK(inflow_refusal(false, midStep, ps.host_step(), true));
+        const int rc = emit_mesh_checked(*mesh, lattice_from(*lattice), nodes, *rule, vel, added);
+        (void)hipStreamSynchronize(stream); // (the append reads the selection)
+        meshSampler.release();
+        return rc;
+    }
+    int emit_mesh_checked(const nrs_mesh &mesh, const Lattice &L, uint64_t nodes, const nrs_mesh_rule &rule, const double *vel, uint64_t *added)
+    {
+        const uint64_t room = cap - n;
+        uint64_t m = 0;
+        NRSCHK(meshSampler.upload(mesh, stream));
+        NRSCHK(meshSampler.select(L, nodes, rule, room, stream, &m));
+        if (m > room) return fail(NRS_E_CAPACITY, "emit mesh: more nodes selected than capacity - n");
+        if (!m) return NRS_OK;
+        uint32_t firstId = 0;
+        if (track.on) NRSCHK(track.ids.reserve(m, &firstId));
+        NRSCHK(inflow.template emit_sites<R>(L, meshSampler.selected(), vel, (uint32_t)m, emit_out(-1, firstId), stream));
         n += m;
         particles_changed();
         if (added) *added = m;

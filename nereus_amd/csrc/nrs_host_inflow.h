@@ -210,12 +210,18 @@ static inline void inflow_origin(const EmitterSlot &sl, double offset, double o[
 }
 
 // ---- nrs_emit_block --------------------------------------------------------------------------------------------------------------------------
-static inline int inflow_check_block(const nrs_lattice *L, const double *vel, uint64_t n, uint64_t cap, uint64_t *nodes)
+// the lattice and the velocity of nrs_emit_block and nrs_emit_mesh
+static inline int inflow_check_sites(const nrs_lattice *L, const double *vel, uint64_t *nodes)
 {
     NRSCHK(sample_check_lattice(L, nodes));
     if (!vel) return fail(NRS_E_INVALID, "emit block: vel is NULL");
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(vel[a])) return fail(NRS_E_INVALID, "emit block: vel is not finite");
+    return NRS_OK;
+}
+static inline int inflow_check_block(const nrs_lattice *L, const double *vel, uint64_t n, uint64_t cap, uint64_t *nodes)
+{
+    NRSCHK(inflow_check_sites(L, vel, nodes));
     if (*nodes > cap - n) return fail(NRS_E_CAPACITY, "emit block: the lattice has more nodes than capacity - n");
     return NRS_OK;
 }

@@ -109,6 +109,14 @@ struct InflowSystem {
         HIPCHK(hipGetLastError());
         return NRS_OK;
     }
+    // nrs_emit_mesh: the m selected nodes sel[0 .. m) of L (device, linear indices) behind O.first; enqueues
+    template <typename R> int emit_sites(const Lattice &L, const uint32_t *sel, const double vel[3], uint32_t m, EmitOut<R> O, hipStream_t stream)
+    {
+        if (!m) return NRS_OK;
+        hipLaunchKernelGGL((k_inflow_sites<R>), dim3(nblocks(m)), dim3(BLOCK), 0, stream, L, sel, vel[0], vel[1], vel[2], m, O);
+        HIPCHK(hipGetLastError());
+        return NRS_OK;
+    }
 
 private:
     DevBuf blockTot, hdr;                                     // survivors per workgroup, scanned in place; InflowHeader

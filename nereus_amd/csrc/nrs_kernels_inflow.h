@@ -1,6 +1,6 @@
 // nrs_kernels_inflow.h — the device side of the sources and sinks (include/nereus_hip.h "sources and sinks"; DESIGN.md "Sources and
-// sinks"): the sites of emitted layers and of a lattice block written behind the living particles, and the cull — survivors counted
-// per workgroup, the totals scanned by one workgroup, the arrays compacted in order.  The rules (frame, sites, predicate) are
+// sinks"): the sites of emitted layers, of a lattice block and of a mesh selection (nrs_emit_mesh) written behind the living
+// particles, and the cull — survivors counted per workgroup, the totals scanned by one workgroup, the arrays compacted in order.  The rules (frame, sites, predicate) are
 // nrs_host_inflow.h's; the host schedules, so no kernel here decides how many particles there are.  No atomics, no waiting between
 // workgroups: every offset comes from a scan, every output is bit-reproducible.
 #pragma once
@@ -70,6 +70,17 @@ template <typename R> __global__ __launch_bounds__(BLOCK) void k_inflow_block(La
     const uint32_t i = q % L.dims[0], t = q / L.dims[0];
     const V3<R> x = lattice_node<R>(L, i, t % L.dims[1], t / L.dims[1]);
     emit_store<R>(O, q, x.x, x.y, x.z, (R)vx, (R)vy, (R)vz);
+}
+// nrs_emit_mesh: one thread per selected node; sel[t] is its linear index in L (ascending: the selection keeps the lattice's order)
+template <typename R>
+__global__ __launch_bounds__(BLOCK) void k_inflow_sites(Lattice L, const uint32_t *__restrict__ sel, double vx, double vy, double vz, uint32_t m, EmitOut<R> O)
+{
+    const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= m) return;
+    const uint32_t q = sel[s];
+    const uint32_t i = q % L.dims[0], t = q / L.dims[0];
+    const V3<R> x = lattice_node<R>(L, i, t % L.dims[1], t / L.dims[1]);
+    emit_store<R>(O, s, x.x, x.y, x.z, (R)vx, (R)vy, (R)vz);
 }
 
 // ---- the cull ----------------------------------------------------------------------------------------------------------------------------------

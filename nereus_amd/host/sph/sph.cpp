@@ -489,6 +489,23 @@ SUint SPH::emitBlock(const double origin[3], const double spacing[3], const SUin
     adoptDeviceCount();
     return (SUint)added;
 }
+SUint SPH::emitMesh(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const double origin[3], const double spacing[3],
+                    const SUint dims[3], double clearance, const double vel[3])
+{
+    ensureContext();
+    pushHostToDevice();
+    nrs_lattice L;
+    std::memset(&L, 0, sizeof(L));
+    for (int a = 0; a < 3; ++a) { L.origin[a] = origin[a]; L.spacing[a] = spacing[a]; L.dims[a] = dims[a]; }
+    const nrs_mesh mesh = {vertices.data(), (uint64_t)(vertices.size() / 3), triangles.data(), (uint64_t)(triangles.size() / 3)};
+    const nrs_mesh_rule rule = {NRS_MESH_INSIDE, 0u, clearance, INFINITY};
+    uint64_t added = 0;
+    const int rc = nrs_emit_mesh(m_ctx, &mesh, &L, &rule, vel, &added);
+    if (rc == NRS_E_CAPACITY) return 0;
+    if (rc != NRS_OK) fatal("nrs_emit_mesh");
+    adoptDeviceCount();
+    return (SUint)added;
+}
 void SPH::setSinks(const nrs_sink_config *sinks)
 {
     ensureContext();

@@ -7,6 +7,7 @@
 #ifndef SPH_H
 #define SPH_H
 
+#include <cstdint>
 #include <utility>
 #include <vector>
 
@@ -154,6 +155,11 @@ public:
     void setEmitter(SUint slot, const nrs_emitter *emitter);
     void getEmitter(SUint slot, nrs_emitter *emitter, unsigned long long *emitted, unsigned long long *dropped);
     SUint emitBlock(const double origin[3], const double spacing[3], const SUint dims[3], const double vel[3]);
+    // emitMesh: emitBlock restricted to the nodes inside a triangle mesh (vertices: 3 doubles each; triangles: 3 indices each, wound
+    // counter-clockwise seen from outside) and at least `clearance` away from it (nrs_emit_mesh with NRS_MESH_INSIDE, dmin = clearance,
+    // dmax = infinity: "fill this shape with fluid"); sample_spheres::ss::meshLattice gives the lattice that walls sampled from meshes use.
+    SUint emitMesh(const std::vector<double> &vertices, const std::vector<uint32_t> &triangles, const double origin[3], const double spacing[3],
+                   const SUint dims[3], double clearance, const double vel[3]);
     void setSinks(const nrs_sink_config *sinks);
     SUint cull();
     void sinkCounts(unsigned long long *removedTotal, unsigned long long *culls);

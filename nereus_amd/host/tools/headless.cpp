@@ -45,6 +45,12 @@
 //                                                               then a context rebuilt to grow and one more); out.txt per number k:
 //                                                               "k slot id r", slot from SPH::locateParticles (k without tracking), r =
 //                                                               getHostCol()[4 * slot]
+//   headless mesh <in.obj> <spacing> <fill|shell> <out.bin>     no solver kind: the "v" and "f" lines of a Wavefront OBJ (polygons fanned from their
+//                                                               first corner, "a/b/c" corners by their first number, negative numbers
+//                                                               from the end; wound outwards) sampled on ss::meshLattice(vertices, spacing);
+//                                                               shell: ss::sampleMesh (one layer on the surface); fill: SPH::emitMesh with
+//                                                               clearance spacing / 2 and no velocity into an empty solver.
+//                                                               out.bin: u32 n, u32 precision (32 | 64), pos4[n]
 // in.bin : u32 n, u32 nb, then pos4[n], vel4[n], bi4[nb], vbi[nb] (SReal)
 // out.bin: u32 n, u32 nb, u32 iters, u32 sizeof(params), params, pos4[n], vel4[n], pressure[n], bi4[nb], vbi[nb]
 #include <cmath>
@@ -81,6 +87,45 @@ static void dump(const char *path, Nereus::SPH *s, unsigned iters, const std::ve
     std::fclose(f);
 }
 
+// the triangle mesh of a Wavefront OBJ: every "v x y z" line a vertex, every "f ..." line a polygon, fanned
+static void read_obj(const char *path, std::vector<double> &vertices, std::vector<uint32_t> &triangles)
+{
+    FILE *f = std::fopen(path, "r");
+    if (!f) die("cannot open input");
+    std::vector<char> line(1 << 16);
+    while (std::fgets(line.data(), (int)line.size(), f)) {
+        char *p = line.data();
+        while (*p == ' ' || *p == '\t') ++p;
+        if (p[0] == 'v' && (p[1] == ' ' || p[1] == '\t')) {
+            ++p;
+            for (int a = 0; a < 3; ++a) {
+                char *end = nullptr;
+                vertices.push_back(std::strtod(p, &end));
+                if (end == p) die("obj: a vertex line with fewer than three numbers");
+                p = end;
+            }
+        } else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
+            ++p;
+            std::vector<uint32_t> corner;
+            for (;;) {
+                char *end = nullptr;
+                const long long k = std::strtoll(p, &end, 10);
+                if (end == p) break;
+                const long long nv = (long long)(vertices.size() / 3), idx = k > 0 ? k - 1 : nv + k;
+                if (k == 0 || idx < 0 || idx >= nv) die("obj: a face names a vertex that is not there (yet)");
+                corner.push_back((uint32_t)idx);
+                p = end;
+                while (*p && *p != ' ' && *p != '\t' && *p != '\n' && *p != '\r') ++p; // (the /vt/vn part)
+            }
+            if (corner.size() < 3) die("obj: a face with fewer than three corners");
+            for (size_t c = 1; c + 1 < corner.size(); ++c) {
+                triangles.push_back(corner[0]); triangles.push_back(corner[c]); triangles.push_back(corner[c + 1]);
+            }
+        }
+    }
+    std::fclose(f);
+}
+
 int main(int argc, char **argv)
 {
     if (argc < 4) die("usage: see source header");
@@ -104,6 +149,43 @@ int main(int argc, char **argv)
         std::fwrite(dev.data(), sizeof(SReal), nb, o);
         std::fwrite(host.data(), sizeof(SReal), nb, o);
         std::fclose(o);
+        return 0;
+    }
+    if (mode == "mesh") {
+        if (argc < 6) die("mesh needs <in.obj> <spacing> <fill|shell> <out.bin>");
+        std::vector<double> vertices;
+        std::vector<uint32_t> triangles;
+        read_obj(argv[2], vertices, triangles);
+        const double spacing = std::strtod(argv[3], nullptr);
+        const std::string what = argv[4];
+        std::vector<SVec4> out;
+        if (what == "shell") {
+            sample_spheres::ss::sampleMesh(out, vertices, triangles, spacing);
+        } else if (what == "fill") {
+            const nrs_lattice L = sample_spheres::ss::meshLattice(vertices, spacing);
+            const nrs_mesh mesh = {vertices.data(), (uint64_t)(vertices.size() / 3), triangles.data(), (uint64_t)(triangles.size() / 3)};
+            const nrs_mesh_rule rule = {NRS_MESH_INSIDE, 0u, spacing / 2, INFINITY};
+            uint64_t count = 0; // (how much room the solver needs)
+            if (nrs_mesh_particles(-1, (int)(8 * sizeof(SReal)), &mesh, &L, &rule, nullptr, 0, &count) != 0) die(nrs_last_error());
+            Nereus::SPH fluid;
+            fluid._initialize();
+            if (count) fluid.reserveParticles((SUint)count);
+            const double vel[3] = {0.0, 0.0, 0.0};
+            const SUint dims[3] = {L.dims[0], L.dims[1], L.dims[2]};
+            const SUint added = fluid.emitMesh(vertices, triangles, L.origin, L.spacing, dims, spacing / 2, vel);
+            if (added != count || fluid.getNumParticles() != added) die("emitMesh: not the count nrs_mesh_particles gives");
+            const SVec4 *hp = (const SVec4 *)fluid.getHostPos();
+            out.assign(hp, hp + added);
+        } else {
+            die("mesh: fill or shell");
+        }
+        FILE *o = std::fopen(argv[5], "wb");
+        if (!o) die("cannot open output");
+        const unsigned head[2] = {(unsigned)out.size(), (unsigned)(8 * sizeof(SReal))};
+        std::fwrite(head, sizeof(unsigned), 2, o);
+        if (!out.empty()) std::fwrite(out.data(), sizeof(SVec4), out.size(), o);
+        std::fclose(o);
+        std::printf("mesh: %zu vertices, %zu triangles, %zu particles (%s)\n", vertices.size() / 3, triangles.size() / 3, out.size(), what.c_str());
         return 0;
     }
     const bool iisph = kind == "iisph", pcisphSolve = kind == "pcisph-solve", pcisph = kind == "pcisph" || pcisphSolve;
