@@ -150,6 +150,8 @@ __global__ __launch_bounds__(STG_WAVE, STG_MIN_WAVES) void k_density_staged(Para
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) staged = staged && (len[3 * pl] + len[3 * pl + 1] + len[3 * pl + 2] <= (uint32_t)STG_POOL);
         if (FAST) {
+            // (always true where `staged` still is: the pool test above bounds every hull of a staged wave by STG_POOL = 320 — the runs
+            // are monotone across the lanes, so no length wraps.  Kept as the statement of what the 16-bit hits need)
 #pragma unroll
             for (int r = 0; r < STG_ROWS; ++r) staged = staged && len[r] < 4096u; // 12-bit offsets in the 16-bit hits
         }
@@ -324,7 +326,9 @@ __global__ __launch_bounds__(STG_WAVE, STG_MIN_WAVES) void k_density_staged(Para
                 }
             }
         }
-        // (an owner with a NaN / inf coordinate takes the reference-order walk: see Sweep::scan)
+        // (an owner with a NaN / inf coordinate takes the reference-order walk: see Sweep::scan.  In a single-domain context this is
+        // always true here: such a coordinate converts to cell 0 or to the last cell, a grid-edge cell, so its wave never stages.  Under
+        // a slab window the x cell is taken relative to the window's first column and need not be an edge)
         const bool finiteOwner = (fabsf(p.x) < INFINITY) & (fabsf(p.y) < INFINITY) & (fabsf(p.z) < INFINITY);
         hc.nf = nf; hc.nb = nb; hc.over = (nf + nb > HIT_CAP) | !finiteOwner;
     } else {

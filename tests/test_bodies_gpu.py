@@ -125,6 +125,8 @@ def test_list_kernels_equal_reference_order_with_moving_walls(hip_lib, solver):
     ref = make(sc, solver, reference_order=True)
     # (1,080 particles never re-sort coherently, so the FLAG_FULL_SORT run is the default run here: tests/test_resort_features_gpu.py has the tank-scale one)
     runs = [make(sc, solver), make(sc, solver, flags=capi.FLAG_NO_WALL_WORKGROUPS), make(sc, solver, flags=capi.FLAG_FULL_SORT)]
+    if solver == capi.SESPH:   # the LDS-staged density launch while the plate crosses cell faces and the boundary tables are rebuilt
+        runs.append(make(sc, solver, flags=capi.FLAG_STAGED_SCAN))
     h, ox = float(p["interactionRadius"][0]), float(ref.params["worldOrigin"][0][0])
     cells, reach = set(), 0
     for step in range(steps):

@@ -29,13 +29,16 @@ TOL = 1e-5
 VEL_TOL = {10: 1e-5, 50: 5e-4, 150: 5e-3}
 
 
-def record_drift(scene_name, steps, ep, ev):
+def record_drift(scene_name, steps, ep, ev, file=None, entry=None):
+    """file, entry: another record of this mode kept in the same directory (entry stored under scene_name as it is)"""
     import json
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "fast_arith_drift.json")
+    if file:
+        path = os.path.join(os.path.dirname(path), file)
     try:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         doc = json.load(open(path)) if os.path.exists(path) else {}
-        doc["%s@%d" % (scene_name, steps)] = {"pos_rel": ep, "vel_rel": ev}
+        doc[scene_name if file else "%s@%d" % (scene_name, steps)] = entry if file else {"pos_rel": ep, "vel_rel": ev}
         json.dump(doc, open(path, "w"), indent=1)
     except OSError:
         pass

@@ -141,3 +141,80 @@ def test_random_scenes_against_oracle(hip_lib):
     assert not failures, failures[:3]
     skipped = [sd for sd, r in results.items() if r == "not comparable"]
     assert len(skipped) <= len(seeds) // 10, skipped
+
+
+# ---- the launches selected by NRS_FLAG_STAGED_SCAN / NRS_FLAG_FAST_ARITH on the soak's scenes (tools/fuzz_parity.py one_flags) -------
+FLAG_SEEDS = range(9300, 9348)
+_flags_shared = {}   # per seed: the scene, the reference-order context's run and the oracle's, shared by the five flag sets
+
+
+def _flag_classes():
+    from fuzz_parity import FLAGS_CONFIG, make_scene
+    c = dict(narrow_x=0, far=0, nonfinite=0, resort=0, walls=0, wrap=0, below_h=0, modes=[0, 0, 0])
+    for sd in FLAG_SEEDS:
+        sc = make_scene(sd, config=FLAGS_CONFIG)
+        assert sc["solver"] == 0 and not sc["double"] and sc["kset"] == 1
+        pos = sc["pos"][np.all(np.isfinite(sc["pos"]), axis=1), :3]
+        lo = sc["p"]["worldOrigin"][0]
+        hi = lo + np.array(sc["gs"]) * sc["p"]["cellSize"][0]
+        c["narrow_x"] += sc["gs"][0] < 4
+        c["far"] += sd % 17 == 16
+        c["nonfinite"] += not np.all(np.isfinite(sc["pos"]))
+        c["resort"] += sc["n"] >= 40000
+        c["walls"] += sc["bi"] is not None
+        c["wrap"] += bool(np.any((pos < lo) | (pos >= hi)))
+        c["below_h"] += bool(np.any(sc["cs"] < sc["h"]))
+        c["modes"][sc["dens_mode"]] += 1
+    assert (c["narrow_x"] >= 3 and c["far"] >= 2 and c["nonfinite"] >= 2 and c["resort"] >= 3 and c["walls"] >= 25 and c["wrap"] >= 8
+            and c["below_h"] >= 15), c
+    return c
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flag_set", ["staged", "staged+nofusion", "staged+fullsort"])
+def test_random_scenes_staged_scan_equals_reference_order(hip_lib, flag_set):
+    """The soak's scenes as fp32 Muller SESPH with NRS_FLAG_STAGED_SCAN (alone, unfused, with the full sort): density and pressure of
+    the launches without shared lists (STAGE_DENSITY), density / pressure / forces at STAGE_FORCES, and the state after 3 steps (6 on
+    the coherent-re-sort seeds) equal the reference-order context's bit for bit, NaN-aware.  Seeds 9300-9347: clumps, cells below h,
+    grids the cloud wraps through, far origins, NaN / inf coordinates, wall sheets; on the narrow-x grids the plan ignores the flag,
+    which must then change nothing."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from fuzz_parity import EXACT_FLAG_SETS, one_flags
+
+    _flag_classes()
+    failures = [r for r in (one_flags(sd, EXACT_FLAG_SETS[flag_set], shared=_flags_shared) for sd in FLAG_SEEDS) if r]
+    assert not failures, failures[:3]
+
+
+def _record_fast_fuzz(flag_set, errors):
+    from tests.test_fast_arith_gpu import record_drift   # (fast_arith_fuzz.json, next to its drift record)
+
+    record_drift(flag_set, 1, None, None, file="fast_arith_fuzz.json", entry={"%d mode%d %s" % k: e for k, e in sorted(errors.items())})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flag_set", ["fast", "fast+staged"])
+def test_random_scenes_fast_arith_against_oracle(hip_lib, flag_set):
+    """The same scenes with NRS_FLAG_FAST_ARITH (alone: k_forces_fast behind the default density launch; with NRS_FLAG_STAGED_SCAN: the
+    FAST instantiations of the staged density launch too): hash, index and the cell tables equal the reference-order context's bit for
+    bit; density and forces of one STAGE_FORCES against the CPU oracle (fp32, tait = double7), non-finite entries element for element,
+    finite ones within 1e-5 array-relative: the density and the forces on every seed — the clump seeds (dens_mode 1, where large pair
+    forces cancel) stayed within the bar when first measured (7.0e-7 at most), so fuzz_parity.FAST_FORCE_MODES names all three modes.
+    The largest error of each quantity is printed per seed and per density mode and recorded next to the drift record of
+    tests/test_fast_arith_gpu.py; DESIGN.md section 3 quotes the maxima."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from fuzz_parity import FAST_FLAG_SETS, FAST_FORCE_MODES, one_flags
+
+    c = _flag_classes()
+    assert c["modes"][1] >= 12 and sum(c["modes"][m] for m in FAST_FORCE_MODES) == len(FLAG_SEEDS), c   # every seed carries the force assertion
+    errors, failures = {}, []
+    for sd in FLAG_SEEDS:
+        r = one_flags(sd, FAST_FLAG_SETS[flag_set], shared=_flags_shared, errors=errors)
+        if r:
+            failures.append(r)
+    _record_fast_fuzz(flag_set, errors)
+    for mode in (0, 1, 2):
+        for nm in ("dens", "forces"):
+            e = [v for (sd, m, q), v in errors.items() if m == mode and q == nm]
+            print("%s dens_mode %d %s: max %.3g over %d seeds" % (flag_set, mode, nm, max(e) if e else 0.0, len(e)))
+    assert not failures, failures[:3]

@@ -7,7 +7,10 @@ With a solver named (pcisph / pbf / dfsph), the same scenes run that solver inst
 settings, DFSPH with random settings of both loops and the warm start), production against reference order at the advection stage, at
 the solve stage and after 3 (6) steps; pcisph-model / pbf-model / dfsph-model compare the device with the float64 models of tests/ on
 pieces of those scenes, of the geometry where both find the same pairs (one_vs_model).
-usage: python tools/fuzz_parity.py [seeds=100] [first=0] [oracle | pcisph | pbf | dfsph | pcisph-model | pbf-model | dfsph-model]
+With a flag set named (staged, staged+nofusion, staged+fullsort, fast, fast+staged), the same scenes run as fp32 Muller SESPH with
+NRS_FLAG_STAGED_SCAN / NRS_FLAG_FAST_ARITH (one_flags): the exact sets against the reference order bit for bit, the FAST sets against
+the CPU oracle within the mode's bar.
+usage: python tools/fuzz_parity.py [seeds=100] [first=0] [oracle | pcisph | pbf | dfsph | pcisph-model | pbf-model | dfsph-model | <flag set>]
   (oracle: compare with the CPU oracle instead (one_vs_oracle): keys bit-exact, floats within the precision's parity bars, NaN-aware)"""
 import os, sys
 import numpy as np
@@ -83,7 +86,8 @@ def make_scene(seed, solver=None, config=None):
     elif solver == capi.DFSPH:   # (likewise)
         cfg = dict(eta=float(rng.choice([0.0, 10 ** rng.uniform(-4, -2)])), min_iters=int(rng.integers(1, 5)),
                    eta_v=float(rng.choice([0.0, 10 ** rng.uniform(-4, -2)])), min_v=int(rng.integers(0, 4)), warm=int(rng.integers(0, 2)))
-    return dict(p=p, n=n, pos=pos, vel=vel, bi=bi, vbi=vbi, solver=solver, double=double, kset=kset, gs=gs, cs=cs, h=h, cfg=cfg)
+    return dict(p=p, n=n, pos=pos, vel=vel, bi=bi, vbi=vbi, solver=solver, double=double, kset=kset, gs=gs, cs=cs, h=h, cfg=cfg,
+                dens_mode=int(dens_mode))
 
 
 def _configure(s, sc):
@@ -214,6 +218,113 @@ def one_vs_oracle(seed, config=None, errors=None):
         return None
     finally:
         s.close()
+
+
+# ---- the SESPH launches selected by flags (NRS_FLAG_STAGED_SCAN, NRS_FLAG_FAST_ARITH) on the soak's scenes -------------------------
+FLAGS_CONFIG = dict(solver=capi.SESPH, double=False, kset=1)   # the only solver, precision and kernel set whose plan honours either flag
+EXACT_FLAG_SETS = {"staged": capi.FLAG_STAGED_SCAN, "staged+nofusion": capi.FLAG_STAGED_SCAN | capi.FLAG_NO_FUSION,
+                   "staged+fullsort": capi.FLAG_STAGED_SCAN | capi.FLAG_FULL_SORT}
+FAST_FLAG_SETS = {"fast": capi.FLAG_FAST_ARITH, "fast+staged": capi.FLAG_FAST_ARITH | capi.FLAG_STAGED_SCAN}
+FAST_TOL = 1e-5           # the FAST mode's bar, array-relative (tests/test_fast_arith_gpu.py, north-star)
+# FAST forces are asserted in every density mode: on the uniform clouds and the jittered lattices (dens_mode 0 and 2) by the mode's
+# definition; on the clump scenes (dens_mode 1), where large pair forces cancel, because the measured errors stay within the bar as
+# well (largest 7.0e-7 over seeds 9300-9347)
+FAST_FORCE_MODES = (0, 1, 2)
+FLAGS_TABLES = ("hash", "index", "cellStart", "cellEnd")
+
+
+def _flags_context(sc, **kw):
+    s = capi.Solver(sc["p"], max(sc["n"], 1), solver=capi.SESPH, double=False, kernel_set=1, **kw)
+    s.set_particles(sc["pos"], sc["vel"])
+    s.set_boundaries(sc["bi"], sc["vbi"], update_grid=False)
+    return s
+
+
+def _flags_exact_run(sc, **kw):
+    """dens / pres at STAGE_DENSITY (the launches without shared lists), the tables and dens / pres / forces at STAGE_FORCES, positions
+    and velocities after 3 steps (6 from 40,000 particles: the coherent re-sort runs)"""
+    s = _flags_context(sc, **kw)
+    s.step_partial(capi.STAGE_DENSITY)
+    out = {"density " + k: s.get(k) for k in ("dens", "pres")}
+    s.set_particles(sc["pos"], sc["vel"])
+    s.step_partial(capi.STAGE_FORCES)
+    out.update({k: s.get(k) for k in FLAGS_TABLES + ("dens", "pres", "forces")})
+    s.set_particles(sc["pos"], sc["vel"])
+    s.step(6 if sc["n"] >= 40000 else 3)
+    out["pos"], out["vel"] = s.download()
+    s.close()
+    return out
+
+
+def flags_reference(seed, shared=None, oracle=False):
+    """What one_flags compares with, computed once per seed when the caller keeps `shared` (a dict): the scene under FLAGS_CONFIG, the
+    reference-order context's run of it and, with oracle=True, the CPU oracle's density and forces (fp32, tait="double7", as
+    one_vs_oracle runs it)."""
+    shared = {} if shared is None else shared
+    ent = shared.setdefault(seed, {})
+    if "sc" not in ent:
+        ent["sc"] = make_scene(seed, config=FLAGS_CONFIG)
+        ent["ref"] = _flags_exact_run(ent["sc"], reference_order=True)
+        # (the cell tables of 48 cached seeds, up to 2^27 cells each, would not fit: the non-empty cells only)
+        cs, ce = ent["ref"].pop("cellStart"), ent["ref"].pop("cellEnd")
+        full = np.flatnonzero(cs != 0xFFFFFFFF)
+        ent["cells"] = (len(cs), full, cs[full], ce[full])
+    if oracle and "oracle" not in ent:
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from tests.oracle_lib import SESPH as O_SESPH, STOP_FORCES, Oracle
+        sc = ent["sc"]
+        o = Oracle(sc["p"], False, 1, O_SESPH, threads=min(16, os.cpu_count() or 1), tait="double7")
+        o.set_particles(sc["pos"], sc["vel"]); o.set_boundaries(sc["bi"], sc["vbi"], update_grid=False)
+        o.step(1, stop=STOP_FORCES)
+        ent["oracle"] = {k: o.get(k) for k in ("dens", "forces")}
+    return ent
+
+
+def one_flags(seed, flags, shared=None, errors=None):
+    """The seed's scene as fp32 Muller SESPH (FLAGS_CONFIG; every other draw is the seed's own) in a context with `flags`.
+    Without NRS_FLAG_FAST_ARITH: everything _flags_exact_run reads equals the reference-order context's bit for bit (NaN-aware).
+    With it: hash, index and the cell tables equal the reference-order context's bit for bit; after one STAGE_FORCES (NRS_FLAG_NO_FUSION
+    added) density and forces against the CPU ORACLE through close_masked — the non-finite entries element for element, the finite
+    ones within FAST_TOL: density on every seed, forces where the scene's dens_mode is in FAST_FORCE_MODES (all three).  One step
+    only: afterwards the output order of the two arithmetics diverges (tests/test_fast_arith_gpu.py).  Returns None or a failure
+    message; `errors`, a dict, collects the error of each quantity as errors[(seed, dens_mode, "dens" | "forces")]."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tests.common import check_cell_tables, close_masked
+    fast = bool(flags & capi.FLAG_FAST_ARITH)
+    ent = flags_reference(seed, shared, oracle=fast)
+    sc, ref = ent["sc"], ent["ref"]
+    ncells, full, cs_full, ce_full = ent["cells"]
+    ref_cs, ref_ce = np.full(ncells, 0xFFFFFFFF, np.uint32), np.zeros(ncells, np.uint32)
+    ref_cs[full], ref_ce[full] = cs_full, ce_full
+    tag = "seed %d flags %d (n=%d grid=%s cs/h=%s walls=%s dens_mode=%d)" % (seed, flags, sc["n"], sc["gs"], sc["cs"] / sc["h"],
+                                                                             sc["bi"] is not None, sc["dens_mode"])
+    if not fast:
+        got = _flags_exact_run(sc, flags=flags)
+        for k in ref:
+            if not np.array_equal(got[k], ref[k], equal_nan=True):
+                bad = np.argwhere(~((got[k] == ref[k]) | (np.isnan(got[k]) & np.isnan(ref[k]))))
+                return "%s: %s differs at %d places, first %s" % (tag, k, len(bad), bad[0])
+        try:
+            check_cell_tables(got["cellStart"], got["cellEnd"], ref_cs, ref_ce)
+        except AssertionError as e:
+            return "%s: cell tables differ: %s" % (tag, str(e)[:200])
+        return None
+    s = _flags_context(sc, flags=flags | capi.FLAG_NO_FUSION)
+    s.step_partial(capi.STAGE_FORCES)
+    got = {k: s.get(k) for k in FLAGS_TABLES + ("dens", "forces")}
+    s.close()
+    try:
+        np.testing.assert_array_equal(got["hash"], ref["hash"], err_msg="hash")
+        np.testing.assert_array_equal(got["index"], ref["index"], err_msg="index")
+        check_cell_tables(got["cellStart"], got["cellEnd"], ref_cs, ref_ce)
+        for nm in ("dens", "forces"):
+            asserted = nm == "dens" or sc["dens_mode"] in FAST_FORCE_MODES
+            e = close_masked(got[nm], ent["oracle"][nm], FAST_TOL if asserted else np.inf, "%s %s" % (tag, nm))
+            if errors is not None:
+                errors[(seed, sc["dens_mode"], nm)] = e
+    except AssertionError as e:
+        return "%s: %s" % (tag, str(e)[:300])
+    return None
 
 
 MODEL_DENSITY = (1.2, 1.5)
@@ -383,6 +494,8 @@ if __name__ == "__main__":
     mode = sys.argv[3] if len(sys.argv) > 3 else ""
     if mode == "oracle":
         one = one_vs_oracle
+    elif mode in EXACT_FLAG_SETS or mode in FAST_FLAG_SETS:
+        one = (lambda sd, _f=dict(EXACT_FLAG_SETS, **FAST_FLAG_SETS)[mode]: one_flags(sd, _f))
     elif mode in SOLVERS:
         one = (lambda sd, _s=SOLVERS[mode]: one_pci(sd, _s))
     elif mode.endswith("-model") and mode[:-6] in SOLVERS:
