@@ -76,9 +76,42 @@ def _grid(params, real):
 
 
 def cells(params, x, real):
-    """calcGridPos: floor((p - worldOrigin) / cellSize), the quotient in `real`"""
+    """calcGridPos: floor((p - worldOrigin) / cellSize), the quotient in `real`, converted to a 32-bit int the way the device converts
+    (saturating; 0 for a NaN): the cell of a coordinate beyond +-2^31 cells or of a non-finite one is what the sampler's sort sees"""
     wo, cs, _ = _grid(params, real)
-    return np.floor((np.asarray(x)[:, :3].astype(real) - wo) / cs).astype(np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        f = np.floor((np.asarray(x)[:, :3].astype(real) - wo) / cs).astype(np.float64)
+    f = np.where(np.isnan(f), 0.0, np.clip(f, -2.0 ** 31, 2.0 ** 31 - 1))
+    return f.astype(np.int64)
+
+
+def dropped_pairs(params, owners, candidates, real, radius=None, reach=1, squared=False, same=False):
+    """The number of pairs (owner i, candidate j) within `radius` (default h) whose cells lie more than `reach` apart on some axis: pairs
+    that a model finding its pairs by distance alone counts and the device's walk over (2 reach + 1)^3 cells never meets.  The distance
+    is the float length() of the difference in `real` (the sampler's test), or with squared the anisotropic pass's
+    (dx dx + dy dy) + dz dz < radius^2 in `real`.  same: i != j.  The models that find pairs by brute force are the device's only on
+    inputs where this is 0 (tests/test_readers_fuzz_cpu.py asserts it for every committed seed)."""
+    r = real(pm._p(params, "interactionRadius") if radius is None else radius)
+    x, y = np.asarray(owners)[:, :3].astype(real), np.asarray(candidates)[:, :3].astype(real)
+    if not len(x) or not len(y):
+        return 0
+    cx, cy = cells(params, x, real), cells(params, y, real)
+    rows = max(1, 2_000_000 // len(y))
+    n = 0
+    for a in range(0, len(x), rows):
+        with np.errstate(invalid="ignore", over="ignore"):
+            d = x[a:a + rows, None, :] - y[None, :, :]
+            if squared:
+                near = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2] < r * r
+            else:
+                near = pm._len(d).astype(np.float64) < float(r)
+        i, j = np.nonzero(near)
+        i = i + a
+        far = (np.abs(cy[j] - cx[i]) > reach).any(axis=1)
+        if same:
+            far &= i != j
+        n += int(far.sum())
+    return n
 
 
 def sorted_order(params, pos, real):

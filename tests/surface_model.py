@@ -64,9 +64,11 @@ def lattice_axes(origin, spacing, dims, real):
     return [(np.float64(origin[a]) + np.arange(dims[a], dtype=np.float64) * np.float64(sp[a])).astype(real) for a in range(3)]
 
 
-def extract(dens, origin, spacing, dims, iso, real, attrs=None):
+def extract(dens, origin, spacing, dims, iso, real, attrs=None, tet_cases=False):
     """dens: (nodes,) in `real`, linear index (k * dims[1] + j) * dims[0] + i; attrs: {name: (nodes, 4) array} interpolated per vertex.
-    Returns a dict: V, T, vertices (V, 4), triangles (T, 3) uint32, cell_counts (triangles of every cell, cells ascending), attrs."""
+    Returns a dict: V, T, vertices (V, 4), triangles (T, 3) uint32, cell_counts (triangles of every cell, cells ascending), attrs; with
+    tet_cases also tet_cases, a (6, 16) histogram: how many cells have Kuhn tetrahedron t (PERMS order) in sign case m (bit c: local
+    corner c inside), taken from the inside mask alone."""
     nx, ny, nz = (int(d) for d in dims)
     f = np.ascontiguousarray(dens, dtype=real).reshape(nz, ny, nx)
     assert f.dtype == np.dtype(real)
@@ -106,6 +108,7 @@ def extract(dens, origin, spacing, dims, iso, real, attrs=None):
     ncell = cx * cy * cz
     tris = np.full((ncell, 6, 2, 3), -1, np.int64)
     vid3 = vid.reshape(nz, ny, nx, 7)
+    hist = np.zeros((6, 16), np.int64)
     corner = lambda c: (slice(c[2], c[2] + cz), slice(c[1], c[1] + cy), slice(c[0], c[0] + cx))
     for ti, perm in enumerate(PERMS):
         cc = tet_corners(perm)
@@ -113,6 +116,7 @@ def extract(dens, origin, spacing, dims, iso, real, attrs=None):
         for c in range(4):
             m |= inside[corner(cc[c])].astype(np.int64) << c
         m = m.ravel()
+        hist[ti] = np.bincount(m, minlength=16)
         for case in range(1, 15):
             sel = np.nonzero(m == case)[0]
             if not len(sel):
@@ -126,7 +130,10 @@ def extract(dens, origin, spacing, dims, iso, real, attrs=None):
     counts = (tris[..., 0] >= 0).sum((1, 2))
     flat = tris.reshape(-1, 3)
     flat = flat[flat[:, 0] >= 0]
-    return {"V": V, "T": len(flat), "vertices": vert, "triangles": flat.astype(np.uint32), "cell_counts": counts, "attrs": out_attrs}
+    out = {"V": V, "T": len(flat), "vertices": vert, "triangles": flat.astype(np.uint32), "cell_counts": counts, "attrs": out_attrs}
+    if tet_cases:
+        out["tet_cases"] = hist
+    return out
 
 
 def normalised(tri):

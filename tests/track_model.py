@@ -196,6 +196,8 @@ def diffuse(params, pos, rec, kappa, dt, ks=pm.MULLER, walls=None, info=None):
         with np.errstate(invalid="ignore", over="ignore"):
             acc = dm.seq_sum(n, i, (a[i, c] - a[j, c]) * w, real)
             new[:, c] = a[:, c] + (((real(2) * real(dt)) * real(kappa[c])) * rho0) * acc
+    fin = np.isfinite(np.asarray(pos)[order, :3].astype(np.float64)).all(axis=1)
+    new[~fin] = a[~fin]   # "a particle with a non-finite position keeps its record": its bytes, not a + 0
     out = rec.copy()
     out[order] = new
     if info is not None:

@@ -10,7 +10,11 @@ pieces of those scenes, of the geometry where both find the same pairs (one_vs_m
 With a flag set named (staged, staged+nofusion, staged+fullsort, fast, fast+staged), the same scenes run as fp32 Muller SESPH with
 NRS_FLAG_STAGED_SCAN / NRS_FLAG_FAST_ARITH (one_flags): the exact sets against the reference order bit for bit, the FAST sets against
 the CPU oracle within the mode's bar.
-usage: python tools/fuzz_parity.py [seeds=100] [first=0] [oracle | pcisph | pbf | dfsph | pcisph-model | pbf-model | dfsph-model | <flag set>]
+With a reader named (sample, surface, aniso, diffuse, track), unscaled pieces of the same scenes (make_reader_scene: cell edges >= h,
+grid axes >= 4 cells, the clumps, far origins, wrap and NaN / inf rows kept; no step is taken) are read out by the field sampler, the
+surface mesher, the anisotropic passes, the diffuse step and nrs_track_diffuse and compared with the models of tests/ (one_sample,
+one_surface, one_aniso, one_diffuse, one_track_diffuse).
+usage: python tools/fuzz_parity.py [seeds=100] [first=0] [oracle | pcisph | pbf | dfsph | pcisph-model | pbf-model | dfsph-model | <flag set> | <reader>]
   (oracle: compare with the CPU oracle instead (one_vs_oracle): keys bit-exact, floats within the precision's parity bars, NaN-aware)"""
 import os, sys
 import numpy as np
@@ -490,6 +494,413 @@ def one_vs_model(seed, solver):
     return None
 
 
+# ---- the read-out side (sampler, surface, anisotropic passes, diffuse particles, attribute diffusion) on pieces of the soak's scenes ----
+READER_MODES = ("sample", "surface", "aniso", "diffuse", "track")
+READER_MAX_NODES = 16384
+
+
+def make_reader_scene(seed, min_axis=4, max_particles=None):
+    """make_scene(seed, SESPH) cut down for the models of the readers (brute-force pairs), as make_model_scene cuts it, with draws of
+    its own (default_rng(seed + 2_000_003)): the K in 300..1500 particles nearest to one finite particle of the cloud (stable argsort)
+    with their velocities, the at most 1,500 wall particles nearest to it, cellSize = max(cs, h) per axis and every grid axis
+    max(min_axis, g) — the geometry sample_refusal accepts (8 cells for the anisotropic passes).  The origin stays, far ones included,
+    and so does the wrap.  Unlike make_model_scene the piece is NOT rescaled (the readers solve nothing: a clump at 60 x rest density
+    is what they should meet), and on the seed % 19 == 18 scenes the scene's NaN / inf rows are put back behind the piece.
+    max_particles: a cap on the whole piece (the anisotropic model holds N x N arrays)."""
+    sc = make_scene(seed, capi.SESPH)
+    rng = np.random.default_rng(seed + 2_000_003)
+    real = np.float64 if sc["double"] else np.float32
+    p, h = sc["p"], sc["h"]
+    fin = np.all(np.isfinite(sc["pos"]), axis=1)
+    good, bad = np.flatnonzero(fin), np.flatnonzero(~fin)
+    c = sc["pos"][good[int(rng.integers(0, len(good)))], :3]
+    k = int(rng.integers(300, 1501))
+    if max_particles:
+        k = min(k, max_particles - len(bad))
+    near = good[np.argsort(np.linalg.norm(sc["pos"][good, :3] - c, axis=1), kind="stable")[:k]]
+    keep = np.concatenate([near, bad])
+    pos, vel = sc["pos"][keep].copy(), sc["vel"][keep].copy()
+    cs = np.maximum(sc["cs"], h)
+    p["cellSize"][0] = cs.astype(real)
+    gs = [max(min_axis, g) for g in sc["gs"]]
+    while gs[0] * gs[1] * gs[2] > 2 ** 27: gs[int(np.argmax(gs))] //= 2
+    p["gridSize"][0] = gs; p["numCells"][0] = gs[0] * gs[1] * gs[2]
+    bi, vbi = sc["bi"], sc["vbi"]
+    if bi is not None and len(bi) > 1500:
+        kb = np.argsort(np.linalg.norm(bi[:, :3] - c, axis=1), kind="stable")[:1500]
+        bi, vbi = bi[kb], vbi[kb]
+    return dict(sc, seed=seed, p=p, n=len(pos), pos=pos, vel=vel, bi=bi, vbi=vbi, gs=gs, cs=cs, nonfinite=len(bad), real=real)
+
+
+def reader_box(sc):
+    """the bounding box of the piece's finite particles, float64"""
+    x = sc["pos"][np.all(np.isfinite(sc["pos"]), axis=1), :3].astype(np.float64)
+    return x.min(0), x.max(0)
+
+
+def reader_lattice(sc, pad=2.0):
+    """(origin, spacing, dims): the piece's box inflated by pad * h at the smallest spacing from h / 2 up (steps of 10 %) that keeps the
+    lattice at or below READER_MAX_NODES nodes; with pad >= 2 every border node is farther than h from every particle"""
+    lo, hi = reader_box(sc)
+    lo, hi = lo - pad * sc["h"], hi + pad * sc["h"]
+    sp = sc["h"] / 2
+    while True:
+        dims = tuple(int(np.ceil((hi[a] - lo[a]) / sp)) + 1 for a in range(3))
+        if dims[0] * dims[1] * dims[2] <= READER_MAX_NODES:
+            return tuple(float(v) for v in lo), float(sp), dims
+        sp *= 1.1
+
+
+def reader_queries(sc, attempt=0, m=700):
+    """The query set of one_sample, (m, 4) in the scene's precision, m no multiple of 64: rows 0-39 particle positions bit for bit,
+    40-79 points near particles moved by whole grid extents to beyond the grid's box (their cells wrap; the axis cycles x, y, z, the
+    side alternates every three), 80 / 81 at +-1e30 (saturated cell coordinates), 82 with a NaN, 83 with an inf coordinate, 84-143
+    near wall particles where the scene has walls, the rest uniform in the piece's box +- 2 h.  attempt: another draw, for a set with
+    a dropped pair (reader_queries_checked).
+    Rows 40-79 show only that a wrapped cell yields no false hit: the particles their cells alias to are whole grid extents away, so
+    the count is 0 on both sides.  Sums ACROSS the wrap come from the scenes whose particles lie outside the grid box, through the
+    uniform rows and rows 0-39."""
+    rng = np.random.default_rng([sc["seed"], 3_000_017, attempt])
+    real, h, p = sc["real"], sc["h"], sc["p"]
+    fin = sc["pos"][np.all(np.isfinite(sc["pos"]), axis=1)]
+    lo, hi = reader_box(sc)
+    q = np.ones((m, 4), real)
+    q[:, :3] = rng.uniform(lo - 2 * h, hi + 2 * h, (m, 3)).astype(real)
+    q[:40] = fin[rng.integers(0, len(fin), 40)]
+    q[:40, 3] = 1
+    wo = np.asarray(p["worldOrigin"][0], np.float64)
+    ext = np.asarray(sc["gs"], np.float64) * np.asarray(p["cellSize"][0], np.float64)
+    base = fin[rng.integers(0, len(fin), 40), :3].astype(np.float64) + rng.uniform(-0.3 * h, 0.3 * h, (40, 3))
+    for t in range(40):
+        a, up = t % 3, (t // 3) % 2
+        x = base[t].copy()
+        if up:
+            x[a] += ext[a] * max(np.floor((wo[a] + ext[a] - x[a]) / ext[a]) + 1, 0)
+        else:
+            x[a] -= ext[a] * max(np.floor((x[a] - wo[a]) / ext[a]) + 1, 0)
+        q[40 + t, :3] = x.astype(real)
+    q[80, :3], q[81, :3] = 1e30, -1e30
+    q[82, 1], q[83, 0] = np.nan, np.inf
+    if sc["bi"] is not None:   # the nearest wall particles of most pieces lie outside the piece's box: 60 queries within 0.6 h of some
+        q[84:144, :3] = (sc["bi"][rng.integers(0, len(sc["bi"]), 60), :3].astype(np.float64) + rng.uniform(-0.6 * h, 0.6 * h, (60, 3))).astype(real)
+    assert m % 64 != 0
+    return q
+
+
+def reader_dropped(sc, owners, reach=1, radius=None, squared=False, same=False, walls=True):
+    """diffuse_model.dropped_pairs of `owners` against the piece's particles and (walls) its wall particles"""
+    from tests import diffuse_model as dm
+    n = dm.dropped_pairs(sc["p"], owners, sc["pos"], sc["real"], radius, reach, squared, same)
+    if walls and sc["bi"] is not None:
+        n += dm.dropped_pairs(sc["p"], owners, sc["bi"], sc["real"], radius, reach, squared)
+    return n
+
+
+def reader_queries_checked(sc, attempts=8):
+    """(queries, attempt): the first draw of reader_queries without a dropped pair (a set with one is replaced, not skipped)"""
+    for attempt in range(attempts):
+        q = reader_queries(sc, attempt)
+        if reader_dropped(sc, q[np.all(np.isfinite(q[:, :3]), axis=1)]) == 0:
+            return q, attempt
+    raise AssertionError("seed %d: every one of %d query sets has a pair beyond the walk's reach" % (sc["seed"], attempts))
+
+
+def reader_diffuse_config(sc, capacity=1 << 20):
+    """the diffuse settings of a piece: SETTINGS of tests/test_diffuse_model_cpu.py with spray_below / bubble_above at the 33 % and 66 %
+    quantiles of the piece's neighbour counts (the particle included, as the kinds count): with the dam's 5 / 6 a dense piece gives
+    only bubbles"""
+    from tests import diffuse_model as dm
+    from tests.test_diffuse_model_cpu import SETTINGS
+    i, _, _ = dm.walk_pairs(sc["p"], sc["pos"], sc["pos"], sc["real"], same=True)
+    cnt = 1 + np.bincount(i, minlength=sc["n"])[np.all(np.isfinite(sc["pos"]), axis=1)]
+    lo_, hi_ = int(np.quantile(cnt, 0.33)), int(np.quantile(cnt, 0.66))
+    return dm.config(**dict(SETTINGS, capacity=capacity, spray_below=lo_, bubble_above=max(hi_, lo_)))
+
+
+READER_DIFFUSE_STEPS = 3
+
+
+def reader_moved(params, pos, vel, real):
+    """pos + dt * vel in the build's precision, dt the parameters' timestep: the fluid one upload on"""
+    out = pos.copy()
+    with np.errstate(invalid="ignore"):
+        out[:, :3] = pos[:, :3] + real(params["timestep"][0]) * vel[:, :3]
+    return out
+
+
+def reader_diffuse_run(sc, params=None, pos=None, vel=None):
+    """The model's run of one_diffuse: READER_DIFFUSE_STEPS diffuse steps of tests/diffuse_model.py from an empty set, the fluid moved
+    by pos + dt * vel between them.  Odd seeds run with a capacity of half the total of the model's own unbounded run (where that is
+    above 1).  Returns (cfg, capacity or None, fluid states, step results)."""
+    from tests import diffuse_model as dm
+    params = sc["p"] if params is None else params
+    pos, vel = (sc["pos"] if pos is None else pos), (sc["vel"] if vel is None else vel)
+    real = sc["real"]
+    cfg = reader_diffuse_config(sc)
+    states = [pos]
+    for _ in range(READER_DIFFUSE_STEPS - 1):
+        states.append(reader_moved(params, states[-1], vel, real))
+
+    def run(cap):
+        dpos, dvel, out = np.zeros((0, 4), real), np.zeros((0, 4), real), []
+        for k in range(READER_DIFFUSE_STEPS):
+            r = dm.step(params, cfg, states[k], vel, dpos, dvel, k, 0.0, sc["kset"], cap)
+            dpos, dvel = r["pos"], r["vel"]
+            out.append(r)
+        return out
+    res, cap = run(None), None
+    if sc["seed"] % 2 == 1 and res[-1]["total"] // 2 >= 1:
+        cap = res[-1]["total"] // 2
+        res = run(cap)
+    return cfg, cap, states, res
+
+
+def _reader_context(sc):
+    s = capi.Solver(sc["p"], max(sc["n"], 1), solver=capi.SESPH, double=sc["double"], kernel_set=sc["kset"])
+    s.set_particles(sc["pos"], sc["vel"])
+    if sc["bi"] is not None:
+        s.set_boundaries(sc["bi"], sc["vbi"], update_grid=False)
+    return s
+
+
+def _reader_tag(sc, what):
+    return "seed %d %s (n=%d grid=%s cs/h=%s walls=%s double=%s kset=%d nonfinite=%d)" % (
+        sc["seed"], what, sc["n"], sc["gs"], sc["cs"] / sc["h"], sc["bi"] is not None, sc["double"], sc["kset"], sc["nonfinite"])
+
+
+def _reader_guard(fn):
+    """(seed, errors=None) -> None | failure text: an AssertionError or a refusal of the library becomes the text"""
+    def run(seed, errors=None):
+        try:
+            return fn(seed, {} if errors is None else errors)
+        except (AssertionError, capi.NereusError) as e:
+            return "seed %d %s: %s" % (seed, fn.__name__, str(e)[:400])
+    run.__name__, run.__doc__ = fn.__name__, fn.__doc__
+    return run
+
+
+def _ratio(err, bound, sel=None):
+    sel = (bound > 0) if sel is None else (sel & (bound > 0))
+    return float((err[sel] / bound[sel]).max()) if sel.any() else 0.0
+
+
+@_reader_guard
+def one_sample(seed, errors):
+    """nrs_sample_points on reader_queries, all four outputs, without and with FIELD_WALLS, against tests/sample_model.py through its
+    compare (counts exact, the rest within the derived bound); the +-1e30 and non-finite queries give zeros; nrs_sample_lattice on
+    reader_lattice byte-equal to nrs_sample_points on its nodes.  errors[seed]: max(error / bound) per field."""
+    from tests import sample_model as sm
+    sc = make_reader_scene(seed)
+    q, attempt = reader_queries_checked(sc)
+    tag = _reader_tag(sc, "sample")
+    out = [capi.FIELD_DENSITY, capi.FIELD_GRADIENT, capi.FIELD_VELOCITY, capi.FIELD_COUNT]
+    s = _reader_context(sc)
+    try:
+        pos, vel = s.download()
+        assert pos.tobytes() == sc["pos"].tobytes() and vel.tobytes() == sc["vel"].tobytes(), tag + ": the upload came back changed"
+        bs = s.get("bSorted") if sc["bi"] is not None else None
+        worst = {}
+        for walls in (0, capi.FIELD_WALLS):
+            s.sample_points(q, sum(out) | walls)
+            got = {f: s.sample_result(f) for f in out}
+            want = sm.sample(s.params, pos, vel, q, sc["kset"], bs if walls else None)
+            for k, v in sm.compare(got, want, "%s walls=%d" % (tag, walls)).items():
+                worst[k] = max(worst.get(k, 0.0), v)
+            for f in out:   # saturated cell coordinates, NaN, inf: zeros, count 0
+                assert not got[f][80:84].any(), (tag, "a query at +-1e30 or a non-finite one has a result", f)
+        origin, sp, dims = reader_lattice(sc)
+        nodes = sm.lattice_points(origin, sp, dims, sc["real"])
+        for walls in (0, capi.FIELD_WALLS):
+            s.sample_lattice(origin, sp, dims, sum(out) | walls)
+            a = {f: s.sample_result(f) for f in out}
+            s.sample_points(nodes, sum(out) | walls)
+            for f in out:
+                assert a[f].tobytes() == s.sample_result(f).tobytes(), (tag, "lattice and points differ in field %d, walls=%d" % (f, walls))
+        errors[seed] = dict(worst, query_attempt=attempt)
+    finally:
+        s.close()
+    return None
+
+
+def reader_surface_walls(seed):
+    """whether one_surface sets SURFACE_WALLS: every second seed, the EVEN ones — 9416 and 9422, the two scenes of the committed slice
+    whose wall sheet reaches the piece's lattice, are among them (tests/test_readers_fuzz_cpu.py asserts that the wall term changes
+    the inside mask there)"""
+    return seed % 2 == 0
+
+
+def reader_wall_nodes(sc, origin, sp, dims):
+    """bool per lattice node: some wall particle lies within h (float length of the difference in the scene's precision)"""
+    from tests import pcisph_model as pm
+    from tests.sample_model import lattice_points
+    sees = np.zeros(dims[0] * dims[1] * dims[2], bool)
+    if sc["bi"] is not None:
+        with np.errstate(invalid="ignore", over="ignore"):
+            i, _ = pm.pairs_within(lattice_points(origin, sp, dims, sc["real"])[:, :3], sc["bi"][:, :3].astype(sc["real"]), sc["h"], real=sc["real"])
+        sees[i] = True
+    return sees
+
+
+@_reader_guard
+def one_surface(seed, errors):
+    """nrs_surface_extract on reader_lattice at iso = 0.5 rho0 with both attributes, every second seed (reader_surface_walls) with
+    SURFACE_WALLS, through tests/test_surface_gpu.py extract_and_check: bit for bit surface_model.extract on the sampler's arrays, and
+    mesh_checks — closed unless the wall term reaches a border node of the lattice.  With the flag, the meshed density equals the
+    wall-less one at the nodes that see no wall particle and exceeds it at most of those that do.  errors[seed]: V, T, nodes that see a wall."""
+    from tests.test_surface_gpu import ATTRS, extract_and_check
+    sc = make_reader_scene(seed)
+    walls = reader_surface_walls(seed)
+    origin, sp, dims = reader_lattice(sc)
+    sees = reader_wall_nodes(sc, origin, sp, dims) if walls else np.zeros(int(np.prod(dims)), bool)
+    border = np.ones(dims[::-1], bool)
+    border[1:-1, 1:-1, 1:-1] = False
+    s = _reader_context(sc)
+    try:
+        flags = ATTRS | (capi.SURFACE_WALLS if walls else 0)
+        tag = _reader_tag(sc, "surface")
+        m, want, dens = extract_and_check(s, origin, sp, dims, 0.5 * float(sc["p"]["restDensity"][0]), flags, not sees[border.ravel()].any(), tag)
+        if walls:
+            s.sample_lattice(origin, sp, dims, capi.FIELD_DENSITY)
+            plain = s.sample_result(capi.FIELD_DENSITY)
+            assert np.array_equal(dens[~sees], plain[~sees]) and np.all(dens[sees] >= plain[sees]), tag + ": the wall term away from the walls"
+            # (a wall particle at almost h adds a term that may round away: most of the nodes that see one, not all)
+            assert sees.sum() < 10 or (dens > plain).sum() > sees.sum() // 2, tag + ": the wall term is missing from the meshed density"
+        errors[seed] = dict(V=int(want["V"]), T=int(want["T"]), nodes=int(np.prod(dims)), wall_nodes=int(sees.sum()),
+                            wall_changed=int((dens > plain).sum()) if walls else 0)
+    finally:
+        s.close()
+    return None
+
+
+ANISO_MAX_PARTICLES = 1200
+
+
+@_reader_guard
+def one_aniso(seed, errors):
+    """The anisotropic passes on make_reader_scene(seed, min_axis=8) of at most ANISO_MAX_PARTICLES particles.  Pass A against
+    aniso_model.records: count, index and the liveness masks exact, centre / weight / G / bound within RECORD_CAP of
+    tests/test_aniso_gpu.py (the cap that marks a defect; the dam's measured maxima do not transfer to clumps).  The extract bit for
+    bit surface_model.extract on sample_result(DENSITY), closed; pass B on that lattice against aniso_model.field from the device's own
+    records within its a-priori bound.  errors[seed]: the record errors and max(error / bound) of phi, gradient, velocity."""
+    from tests import aniso_model as am
+    from tests.test_aniso_gpu import ATTRS, RECORD_CAP, compare_field, extract_and_check, records
+    sc = make_reader_scene(seed, min_axis=8, max_particles=ANISO_MAX_PARTICLES)
+    tag = _reader_tag(sc, "aniso")
+    real, h = sc["real"], float(sc["p"]["interactionRadius"][0])
+    r2h = float(real(2) * real(h))
+    assert reader_dropped(sc, sc["pos"], reach=2, radius=r2h, squared=True, same=True, walls=False) == 0, tag + ": a pair within 2 h beyond the walk's reach"
+    origin, sp, dims = reader_lattice(sc, pad=2.5)
+    from tests.sample_model import lattice_points
+    assert reader_dropped(sc, lattice_points(origin, sp, dims, real), reach=2, radius=2.0001 * h, walls=False) == 0, tag + ": a node within 2 h beyond the walk's reach"
+    s = _reader_context(sc)
+    try:
+        pos, vel = s.download()
+        s.aniso_build(None)
+        c, b, g, w, count, index = records(s)
+        n = len(pos)
+        assert len(count) == n and np.array_equal(np.sort(index), np.arange(n)), tag + " index"
+        want = am.records(pos, h, real)
+        np.testing.assert_array_equal(count, want["count"][index], err_msg=tag + " count")
+        live = want["weight"][index] > 0
+        assert np.array_equal(w > 0, live) and np.array_equal(b > 0, live), tag + " liveness"
+        support = am.config(h)["support"]
+        e = dict(center=0.0, weight=0.0, bound=0.0, G=float(np.linalg.norm(g - want["G"][index], axis=(1, 2)).max() * support))
+        if live.any():
+            e.update(center=float(np.abs(c[live] - want["center"][index][live]).max() / h),
+                     weight=float(np.abs(w[live] / want["weight"][index][live] - 1).max()),
+                     bound=float(np.abs(b[live] / want["bound"][index][live] - 1).max()))
+        print("%s: centre / h %.3g, weight (relative) %.3g, bound (relative) %.3g, |G - G_model|_F support %.3g" % (tag, e["center"], e["weight"], e["bound"], e["G"]))
+        errors[seed] = dict(e)
+        cap = RECORD_CAP[64 if sc["double"] else 32]
+        for k, v in e.items():
+            assert v <= cap, (tag, k, v, "above the cap: a defect, not a tolerance")
+        extract_and_check(s, origin, sp, dims, 0.5, ATTRS, True, tag)
+        index = s.aniso_result(capi.ANISO_INDEX)
+        fw, fg = compare_field(s, origin, sp, dims, vel[index], tag)
+        errors[seed].update(phi=_ratio(np.abs(fg["phi"] - fw["phi"]), fw["phi_bound"]),
+                            grad=_ratio(np.abs(fg["grad"][:, :3] - fw["grad"]), fw["grad_bound"]),
+                            vel=_ratio(np.abs(fg["vel"] - fw["vel"]), fw["vel_bound"], fw["vel_checked"][:, None] & np.ones((1, 4), bool)))
+    finally:
+        s.close()
+    return None
+
+
+@_reader_guard
+def one_diffuse(seed, errors):
+    """READER_DIFFUSE_STEPS nrs_diffuse_steps in lockstep with tests/diffuse_model.py (reader_diffuse_run) through
+    tests/test_diffuse_gpu.py check_step: normals, potentials, births, kinds, positions, lifetimes, velocities, counts and `dropped`
+    byte for byte; the fluid is moved by upload between the steps.  errors[seed]: the totals of the run."""
+    from tests.test_diffuse_gpu import check_step
+    sc = make_reader_scene(seed)
+    tag = _reader_tag(sc, "diffuse")
+    s = _reader_context(sc)
+    try:
+        pos, vel = s.download()
+        cfg, cap, states, res = reader_diffuse_run(sc, s.params, pos, vel)
+        s.diffuse_configure(**dict(cfg, capacity=cap or (1 << 15)))
+        assert res[-1]["total"] <= (1 << 15) or cap, tag
+        dropped = 0
+        for k, r in enumerate(res):
+            if k:
+                s.set_particles(states[k], vel)
+            s.diffuse_step()
+            dropped += r["dropped"]
+            check_step(s, r, "%s step %d" % (tag, k), cap=cap, dropped=dropped)
+        errors[seed] = dict(alive=int(res[-1]["alive"]), by_kind=res[-1]["by_kind"], dropped=int(dropped), capacity=cap,
+                            spray_below=cfg["spray_below"], bubble_above=cfg["bubble_above"])
+    finally:
+        s.close()
+    return None
+
+
+@_reader_guard
+def one_track_diffuse(seed, errors):
+    """Two nrs_track_diffuse calls on record_for(pos) of tests/test_track_model_cpu.py at dt = 0.5 / track_model.stability, the fluid
+    moved by upload between them (an upload through set_particles makes every slot new, so the record goes up again behind it), byte
+    for byte against track_model.diffuse, walls included where the scene has them; channel 3 (kappa 0) unchanged bit for bit."""
+    from tests import track_model as tm
+    from tests.test_track_model_cpu import KAPPA, record_for
+    sc = make_reader_scene(seed)
+    tag = _reader_tag(sc, "track")
+    s = _reader_context(sc)
+    try:
+        pos, vel = s.download()
+        p = s.params
+        walls = s.get("bSorted") if sc["bi"] is not None else None
+        s.track_enable(capi.TRACK_ATTR)
+        rec = record_for(np.where(np.isfinite(pos), pos, 0), s.real)
+        bad_rows = np.flatnonzero(~np.isfinite(pos[:, :3]).all(axis=1))
+        if len(bad_rows):   # "keeps its record" is its bytes: a + 0 would turn this -0.0 into +0.0
+            rec[bad_rows[0], 0] = -0.0
+        bits = np.uint64 if sc["double"] else np.uint32
+        changed = 0
+        for k in range(2):
+            s.track_upload(capi.TRACK_ATTRIBUTE, rec)
+            lam = tm.stability(p, pos, KAPPA, 1.0, sc["kset"], walls)
+            dt = 0.5 / lam if lam > 0 and np.isfinite(lam) else float(p["timestep"][0])
+            s.track_diffuse(KAPPA, dt)
+            want = tm.diffuse(p, pos, rec, KAPPA, dt, sc["kset"], walls)
+            got = s.track_result(capi.TRACK_ATTRIBUTE)
+            if got.tobytes() != want.tobytes():
+                bad = np.nonzero((got.view(bits) != want.view(bits)).any(axis=1))[0]
+                return "%s call %d: %d of %d records differ, first %d: device %r model %r" % (tag, k, len(bad), len(got), bad[0], got[bad[0]], want[bad[0]])
+            assert got[:, 3].tobytes() == rec[:, 3].tobytes(), tag + ": channel 3 (kappa 0) changed"
+            assert got[bad_rows].tobytes() == rec[bad_rows].tobytes(), tag + ": the record of a non-finite particle changed"
+            changed += int(np.count_nonzero(got[:, 0] != rec[:, 0]))
+            rec = got
+            if k == 0:
+                pos = reader_moved(p, pos, vel, s.real)
+                s.set_particles(pos, vel)
+        assert changed > sc["n"] // 2, (tag, "the diffusion changed %d records in two calls" % changed)
+        errors[seed] = dict(changed=changed, n=sc["n"])
+    finally:
+        s.close()
+    return None
+
+
+READERS = dict(sample=one_sample, surface=one_surface, aniso=one_aniso, diffuse=one_diffuse, track=one_track_diffuse)
+
+
 if __name__ == "__main__":
     mode = sys.argv[3] if len(sys.argv) > 3 else ""
     if mode == "oracle":
@@ -500,6 +911,8 @@ if __name__ == "__main__":
         one = (lambda sd, _s=SOLVERS[mode]: one_pci(sd, _s))
     elif mode.endswith("-model") and mode[:-6] in SOLVERS:
         one = (lambda sd, _s=SOLVERS[mode[:-6]]: one_vs_model(sd, _s))
+    elif mode in READERS:
+        one = READERS[mode]
     seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     fails = div = 0
