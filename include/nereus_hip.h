@@ -342,6 +342,26 @@ int nrs_pbf_set_vorticity(nrs_ctx *ctx, double eps_v);
  * min_iters == 0 or warm_start outside {0, 1}.  Came after nrs_version() 0.3 without a version change. */
 int nrs_dfsph_configure(nrs_ctx *ctx, double max_density_error, uint32_t min_iters, double max_divergence_error,
                         uint32_t min_divergence_iters, int warm_start);
+/* Implicit viscosity on a DFSPH context (NRS_E_STATE on any other), DESIGN.md "Implicit viscosity" (Weiler et al. 2018): behind the
+ * advection launch the step solves (I - dt nu L) u = v* for the velocity and replaces vel_adv by u; the density solve, the integration
+ * and everything after them are unchanged.  With x the step's start positions, DFSPH's neighbour rule and gradients g, rho of the
+ * step's scan and x_ij = x_i - x_j,
+ *   (A u)_i = u_i - dt nu          (rho0 / rho_i) 10 sum_j (rho0 / rho_j) ((u_i - u_j) . x_ij) / (|x_ij|^2 + 0.01 h^2) g_ij
+ *                 - dt nu_boundary (rho0 / rho_i) 10 sum_b                ( u_i        . x_ib) / (|x_ib|^2 + 0.01 h^2) g_ib.
+ * nu is the kinematic viscosity in m^2/s; nu_boundary the wall friction against walls at rest (0 = slip).  The solve is plain
+ * conjugate gradients from u0 = v*, every sum in a fixed order.  It stops after the iteration l >= min_iters with
+ * |r|^2 <= tolerance^2 |v*|^2, or at max_iters (0 = 100); |r|^2 is not read back before min_iters, and tolerance = 0 runs exactly
+ * min_iters iterations and reads nothing back during the step.  nu = 0 (the default) switches the solve off and frees its buffers: the
+ * step, its launches and its bits are then those of a context that never called this.  The explicit viscous term of the advection
+ * launch keeps obeying params.viscosity: for the implicit term alone set params.viscosity to 0.
+ * NRS_E_INVALID for a NaN, infinite or negative nu or nu_boundary, a tolerance outside [0, 1), tolerance = 0 with min_iters = 0, or
+ * max_iters not 0 and below min_iters.  nu_boundary > 0 on a context whose boundary particles are grouped into moving bodies, and
+ * nrs_set_boundary_bodies on a context with nu_boundary > 0, are NRS_E_STATE.  Came after nrs_version() 0.3 without a version change. */
+int nrs_dfsph_set_viscosity(nrs_ctx *ctx, double nu, double nu_boundary, double tolerance, uint32_t min_iters, uint32_t max_iters);
+/* What the last step's solve left: on (also filled when the call fails), the iterations that began with a nonzero residual,
+ * residual = |r| of the last iteration and rhs_norm = |v*|, read from the device on request (the call waits for the stream).  Any
+ * pointer may be NULL.  NRS_E_STATE before a step with the solve on. */
+int nrs_dfsph_viscosity_info(nrs_ctx *ctx, int *on, uint32_t *iterations, double *residual, double *rhs_norm);
 
 /* Surface tension and wall adhesion of Akinci, Akinci and Teschner (2013) on a PCISPH, PBF or DFSPH context (NRS_E_STATE on SESPH and
  * IISPH contexts, whose steps are the reference's), DESIGN.md "Akinci surface tension and adhesion": the advection stage's force_adv

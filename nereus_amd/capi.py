@@ -83,6 +83,7 @@ EXPORTS = [
     "nrs_get_stat", "nrs_boundary_volumes", "nrs_eval_smoothing", "nrs_iisph_predict", "nrs_iisph_iterate", "nrs_iisph_finish",
     "nrs_slab_last_counts", "nrs_pcisph_configure", "nrs_pbf_configure", "nrs_pbf_set_tensile",
     "nrs_pbf_set_vorticity", "nrs_dfsph_configure", "nrs_set_surface_akinci",
+    "nrs_dfsph_set_viscosity", "nrs_dfsph_viscosity_info",
     "nrs_set_boundary_bodies", "nrs_set_body_velocity", "nrs_set_body_pose", "nrs_get_body_pose",
     "nrs_sample_points", "nrs_sample_lattice", "nrs_sample_result", "nrs_sample_device_ptr", "nrs_sample_release",
     "nrs_sample_builds",
@@ -196,6 +197,8 @@ def load_library(path=None):
     lib.nrs_pbf_set_vorticity.argtypes = [vp, C.c_double]
     lib.nrs_dfsph_configure.argtypes = [vp, C.c_double, C.c_uint32, C.c_double, C.c_uint32, i32]
     lib.nrs_set_surface_akinci.argtypes = [vp, C.c_double, C.c_double]
+    lib.nrs_dfsph_set_viscosity.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32]
+    lib.nrs_dfsph_viscosity_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.nrs_set_profiling.argtypes = [vp, C.c_uint32]
     lib.nrs_stage_ms.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]
     lib.nrs_max_density.argtypes = [vp, C.POINTER(C.c_double)]
@@ -528,6 +531,18 @@ class Solver:
     def surface_akinci(self, gamma=0.0, beta=0.0):
         """Akinci surface tension gamma and wall adhesion beta_a on a PCISPH / PBF / DFSPH context (nrs_set_surface_akinci; 0, 0 = off)"""
         self._chk(self.lib.nrs_set_surface_akinci(self.h, float(gamma), float(beta)))
+
+    def dfsph_set_viscosity(self, nu=0.0, nu_boundary=0.0, tolerance=1e-3, min_iters=1, max_iters=0):
+        """the implicit viscosity solve of the DFSPH step (nrs_dfsph_set_viscosity): (I - dt nu L) u = vel_adv by conjugate gradients
+        behind the advection launch; nu = 0 = off, nu_boundary = wall friction (0 = slip), tolerance = 0 = exactly min_iters iterations
+        and nothing read back, max_iters = 0 = 100"""
+        self._chk(self.lib.nrs_dfsph_set_viscosity(self.h, float(nu), float(nu_boundary), float(tolerance), int(min_iters), int(max_iters)))
+
+    def dfsph_viscosity_info(self):
+        """dict(on, iterations, residual, rhs_norm) of the last step's implicit viscosity solve (nrs_dfsph_viscosity_info); waits"""
+        on, it, res, rhs = C.c_int(0), C.c_uint32(0), C.c_double(0), C.c_double(0)
+        self._chk(self.lib.nrs_dfsph_viscosity_info(self.h, C.byref(on), C.byref(it), C.byref(res), C.byref(rhs)))
+        return dict(on=bool(on.value), iterations=it.value, residual=res.value, rhs_norm=rhs.value)
 
     def set_profiling(self, stages=True):
         """stages: True = all, False = off, or an iterable of stage ids."""

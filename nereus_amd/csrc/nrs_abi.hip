@@ -346,6 +346,16 @@ int nrs_set_surface_akinci(nrs_ctx *ctx, double gamma, double beta_adhesion)
     CTX_GUARD(ctx);
     return ctx->impl->set_surface_akinci(gamma, beta_adhesion);
 }
+int nrs_dfsph_set_viscosity(nrs_ctx *ctx, double nu, double nu_boundary, double tolerance, uint32_t min_iters, uint32_t max_iters)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->dfsph_set_viscosity(nu, nu_boundary, tolerance, min_iters, max_iters);
+}
+int nrs_dfsph_viscosity_info(nrs_ctx *ctx, int *on, uint32_t *iterations, double *residual, double *rhs_norm)
+{
+    CTX_GUARD(ctx);
+    return ctx->impl->dfsph_viscosity_info(on, iterations, residual, rhs_norm);
+}
 int nrs_set_profiling(nrs_ctx *ctx, uint32_t stage_mask)
 {
     CTX_GUARD(ctx);

@@ -130,6 +130,8 @@ struct CtxBase {
     virtual int pbf_set_vorticity(double epsV) = 0;
     virtual int dfsph_configure(double eta, uint32_t minIters, double etaV, uint32_t minItersV, int warm) = 0;
     virtual int set_surface_akinci(double gamma, double beta) = 0;
+    virtual int dfsph_set_viscosity(double nu, double nuB, double tol, uint32_t minIters, uint32_t maxIters) = 0;
+    virtual int dfsph_viscosity_info(int *on, uint32_t *iterations, double *residual, double *rhsNorm) = 0;
     virtual int settle() = 0;                           // finish host bookkeeping a previous call deferred (nrs_slab_pack's totals)
     virtual int slab_last_counts(uint32_t *counts) = 0; // stream populations of the last nrs_slab_pack
     virtual int set_profiling(uint32_t mask) = 0;

@@ -95,7 +95,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     uint32_t cellsAllocated = 0;
     BoundaryTables<R> bt; // the boundary particles, their tables and bodies (nrs_boundary_tables.h)
     Reductions<R> red;    // sums, maxima and the hit statistics (nrs_solvers.h)
-    PressureSolvers<R, KSET, SURF> ps{red}; // IISPH, PCISPH, PBF, DFSPH, Akinci: buffers, settings, chains (nrs_solvers.h)
+    ViscositySolver<R> visc; // DFSPH's implicit viscosity solve: settings, buffers, the CG loop (nrs_viscosity.h)
+    PressureSolvers<R, KSET, SURF> ps{red, visc}; // IISPH, PCISPH, PBF, DFSPH, Akinci: buffers, settings, chains (nrs_solvers.h)
     // where a buffer of the given name lives: the boundary's are bt's, the solvers' ps's (whose switch has no default: -Wswitch names a
     // BufName nobody answers for), the sorted keys / values are pointers into a pair
     void *buf_ptr(BufName b)
@@ -330,6 +331,8 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int set_boundary_bodies(const uint32_t *bodyOf, uint64_t nbGiven, uint32_t nbodies) override
     {
         NRSCHK(refuse_mid_iisph("nrs_set_boundary_bodies"));
+        if (nbodies && visc.wall_friction())
+            return fail(NRS_E_STATE, "nrs_set_boundary_bodies on a context with implicit wall friction (nrs_dfsph_set_viscosity, nu_boundary > 0)");
         ++boundaryGen;
         return bt.set_bodies(bodyOf, nbGiven, nbodies, exch.on(), boundary_grid());
     }
@@ -585,6 +588,15 @@ template <typename R, int KSET, bool SURF> struct Ctx : CtxBase {
     int pbf_set_vorticity(double epsV) override { return ps.pbf_set_vorticity(epsV); }
     int dfsph_configure(double eta, uint32_t minIters, double etaV, uint32_t minItersV, int warm) override { return ps.dfsph_configure(eta, minIters, etaV, minItersV, warm); }
     int set_surface_akinci(double gamma, double beta) override { return ps.set_surface_akinci(gamma, beta); }
+    int dfsph_set_viscosity(double nu, double nuB, double tol, uint32_t minIters, uint32_t maxIters) override
+    {
+        return ps.dfsph_set_viscosity(nu, nuB, tol, minIters, maxIters, bt.has_bodies());
+    }
+    int dfsph_viscosity_info(int *on, uint32_t *iterations, double *residual, double *rhsNorm) override
+    {
+        if (!dfsph()) return fail(NRS_E_STATE, "nrs_dfsph_viscosity_info on a context that is not DFSPH");
+        return visc.info(stream, on, iterations, residual, rhsNorm);
+    }
 
     // f(std::true_type) with boundary particles, f(std::false_type) without: the one place a launch chain learns HAS_B
     template <typename F> int with_walls(F &&f) { return bt.count() ? f(std::true_type{}) : f(std::false_type{}); }

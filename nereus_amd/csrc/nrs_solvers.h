@@ -23,6 +23,7 @@
 #include "nrs_kernels_pbf.h"
 #include "nrs_kernels_dfsph.h"
 #include "nrs_kernels_akinci.h"
+#include "nrs_viscosity.h"
 
 namespace nrs {
 
@@ -45,12 +46,17 @@ template <typename R> struct Reductions {
     }
     int sum(const R *a, uint32_t N, double *o)
     {
-        const uint32_t nbk = std::min<uint32_t>(1024u, nblocks(N));
-        hipLaunchKernelGGL((k_sum_partial<R>), dim3(nbk), dim3(BLOCK), 0, stream, a, scratch(), N);
-        hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(BLOCK), 0, stream, scratch(), out.as<double>(), nbk);
+        sum_to(a, N, out.as<double>());
         HIPCHK(hipMemcpyAsync(o, out.p, sizeof(double), hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         return NRS_OK;
+    }
+    // the sum left in a device slot, nothing read back and nothing waited for (sum's two launches; the CG sums of nrs_viscosity.h)
+    void sum_to(const R *a, uint32_t N, double *slot)
+    {
+        const uint32_t nbk = std::min<uint32_t>(1024u, nblocks(N));
+        hipLaunchKernelGGL((k_sum_partial<R>), dim3(nbk), dim3(BLOCK), 0, stream, a, scratch(), N);
+        hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(BLOCK), 0, stream, scratch(), slot, nbk);
     }
     // the sum, and how many of the N particles a slab rank owns (ownedPos: their sorted positions; null: no count is formed)
     int sum_and_count(const R *a, uint32_t N, const T4 *ownedPos, double *o, uint64_t *owned)
@@ -137,7 +143,7 @@ template <typename R> struct SolverStep {
 template <typename R, int KSET, bool SURF> struct PressureSolvers {
     typedef typename Vec4T<R>::type T4;
     typedef SolverStep<R> Step;
-    explicit PressureSolvers(Reductions<R> &r) : red(r) {}
+    PressureSolvers(Reductions<R> &r, ViscositySolver<R> &v) : red(r), visc(v) {}
 
     // per solver: settings, derived constants, what the last step left (nrs_host_solver.h).  PBF shares pciSt.xs and pciSt.lastErr.
     PciState<R> pciSt;   // nrs_kernels_pcisph.h
@@ -242,6 +248,11 @@ template <typename R, int KSET, bool SURF> struct PressureSolvers {
         NRSCHK(dfSt.s.set(eta, minIters, etaV, minItersV, warm));
         return NRS_OK;
     }
+    int dfsph_set_viscosity(double nu, double nuB, double tol, uint32_t minIters, uint32_t maxIters, bool movingBodies)
+    {
+        if (!dfsph()) return fail(NRS_E_STATE, "nrs_dfsph_set_viscosity on a context that is not DFSPH");
+        return visc.configure(cap, nu, nuB, tol, minIters, maxIters, movingBodies);
+    }
     int set_surface_akinci(double gamma, double beta)
     {
         if (solver != NRS_SOLVER_PCISPH && solver != NRS_SOLVER_PBF && !dfsph())
@@ -325,6 +336,7 @@ template <typename R, int KSET, bool SURF> struct PressureSolvers {
 
 private:
     Reductions<R> &red;
+    ViscositySolver<R> &visc; // DFSPH's implicit viscosity solve (nrs_viscosity.h): the context's, run behind the advection launch
     int solver = NRS_SOLVER_SESPH;
     uint64_t cap = 0;
     // the solvers' buffers (BufName, nrs_host_solver.h: which solver allocates which, and what the shared ones hold on each)
@@ -585,6 +597,10 @@ private:
             gather<WALL_GROUPS>(s, k_pci_advect_ref<R, KSET, SURF, HAS_B>, [](auto ks, auto w) { return k_pci_advect_lists<R, ks, SURF, HAS_B, w>; },
                                 std::tie(s.P, s.G, A0), s.sorted.pvdp());
         }
+        if (dfsph() && visc.on()) // the implicit viscosity solve on vel_adv (DESIGN.md "Implicit viscosity")
+            NRSCHK(visc.solve(red, s.P, velAdv.as<T4>(), s.sorted.dens, s.sorted.N, s.stream, [&](auto start, const ViscArrays<R> &A) {
+                launch_pass<HAS_B>(s, ViscMatvecPass<R, KSET, decltype(start)::value>{s.P, A});
+            }));
         NRSCHK(ev_end(s));
         *more = stop != NRS_STAGE_P_ADVECT;
         return NRS_OK;

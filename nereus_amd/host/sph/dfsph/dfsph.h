@@ -26,6 +26,14 @@ public:
     // Surface tension gamma and wall adhesion beta of Akinci et al. 2013 (nrs_set_surface_akinci; 0, 0: off).  Same rule as
     // setSolverSettings: before the context exists.
     void setAkinciSurface(SReal gamma, SReal beta);
+    // The implicit viscosity solve (nrs_dfsph_set_viscosity, DESIGN.md "Implicit viscosity"): behind the advection launch the step solves
+    // (I - dt nu L) u = v* by conjugate gradients.  nu: the kinematic viscosity in m^2/s (0: off, the default), nuBoundary: the friction
+    // against walls at rest (0: slip; not together with moving boundary bodies), tol: the relative residual the solve stops at (0: exactly
+    // minIters iterations, nothing read back), maxIters: the cap (0 = 100).  The explicit viscous term keeps obeying the parameters'
+    // viscosity: set that to 0 for the implicit term alone.  May be called at any time; a context that exists takes the settings at once.
+    void setImplicitViscosity(double nu, double nuBoundary, double tol, SUint minIters, SUint maxIters);
+    // What the last step's solve left (nrs_dfsph_viscosity_info): false while the solve is off or before its first step
+    bool implicitViscosityInfo(SUint *iterations, double *residual, double *rhsNorm);
     SUint getLastIterations(); // density-solve iterations of the last step
     int solverKind() const override;
 
@@ -35,6 +43,8 @@ protected:
     SReal m_akinciGamma, m_akinciBeta;
     SUint m_minIters, m_minItersV;
     bool m_warmStart;
+    double m_viscNu, m_viscNuBoundary, m_viscTol; // (as given: the ABI takes doubles)
+    SUint m_viscMinIters, m_viscMaxIters;
 };
 
 NEREUS_NAMESPACE_END

@@ -51,6 +51,9 @@
 //                                                               shell: ss::sampleMesh (one layer on the surface); fill: SPH::emitMesh with
 //                                                               clearance spacing / 2 and no velocity into an empty solver.
 //                                                               out.bin: u32 n, u32 precision (32 | 64), pos4[n]
+//   headless viscous <nu> <nu_b> <steps> <out.bin>              no solver kind: Nereus::DFSPH with setImplicitViscosity(nu, nu_b, 1e-3, 1, 0) on the
+//                                                               mainscene dam break (the cube in the sampled box); out.bin as run's, iters =
+//                                                               the density solve's
 // in.bin : u32 n, u32 nb, then pos4[n], vel4[n], bi4[nb], vbi[nb] (SReal)
 // out.bin: u32 n, u32 nb, u32 iters, u32 sizeof(params), params, pos4[n], vel4[n], pressure[n], bi4[nb], vbi[nb]
 #include <cmath>
@@ -186,6 +189,30 @@ int main(int argc, char **argv)
         if (!out.empty()) std::fwrite(out.data(), sizeof(SVec4), out.size(), o);
         std::fclose(o);
         std::printf("mesh: %zu vertices, %zu triangles, %zu particles (%s)\n", vertices.size() / 3, triangles.size() / 3, out.size(), what.c_str());
+        return 0;
+    }
+    if (mode == "viscous") {
+        if (argc < 6) die("viscous needs <nu> <nu_b> <steps> <out.bin>");
+        Nereus::DFSPH fluid;
+        fluid.setImplicitViscosity(std::atof(argv[2]), std::atof(argv[3]), 1e-3, 1, 0);
+        fluid._initialize();
+        fluid.generateParticleCube(make_SVec4(-0.4f, 0.04f, 0.5f, 1.f), make_SVec4(0.5f, 0.5f, 0.5f, 1.f), make_SVec4(0, 0, 0, 0));
+        std::vector<SVec4> walls;
+        std::vector<SReal> volumes;
+        sample_spheres::ss::sampleBox(walls, make_SVec3(-1, -1, -1), make_SVec3(3.f, 3.f, 3.f), 0.02);
+        sample_spheres::boundary_forces::getVbi(volumes, walls, fluid.getInteractionRadius());
+        fluid.setNumBoundaries(walls.size());
+        fluid.setBi((SReal *)walls.data());
+        fluid.setVbi(volumes.data());
+        fluid.updateGpuBoundaries(walls.size());
+        const int steps = std::atoi(argv[4]);
+        for (int s = 0; s < steps; ++s) fluid.update();
+        SUint cg = 0;
+        double residual = 0.0, rhs = 0.0;
+        const bool on = fluid.implicitViscosityInfo(&cg, &residual, &rhs);
+        std::printf("viscous: %s, %u CG iterations in the last step, |r| / |b| = %.3g\n", on ? "on" : "off", cg, rhs > 0.0 ? residual / rhs : 0.0);
+        dump(argv[5], &fluid, fluid.getLastIterations(), walls, volumes);
+        fluid._finalize();
         return 0;
     }
     const bool iisph = kind == "iisph", pcisphSolve = kind == "pcisph-solve", pcisph = kind == "pcisph" || pcisphSolve;
